@@ -13,6 +13,9 @@ Scaling (--scaling): the default is STRONG -- the global batch of 1M spectra is 
 (spart_amd.sharding.shard_bounds; 8 x 125k + gather = config 4 as BASELINE states it); `weak` gives every rank its own
 1M-spectrum shard.  Rank 0 prints ONE JSON line; at N = 1 it also carries driver-timed sub-records: "fp64" (the
 reference's own arithmetic) and "configs" (BASELINE configs 2, 3, 5 on one GPU).
+
+--dump-outputs DIR writes what the last timed step computed (R_TOC / R_TOA / L_TOA as rank 0 holds them) to DIR/<name>.npy:
+the inputs are the same for the same arguments, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -586,6 +589,30 @@ def lut_records_multi_rank(torch, dist, args, dev, eng, rank, world, lut_local, 
     return rec
 
 
+DUMP_BYTES = 48_000_000     # --dump-outputs: at most this many bytes of column data (the .npy headers add a few hundred)
+DUMP_SEED = 0
+
+
+def dump_outputs(torch, path, cols):
+    """--dump-outputs: the (3, B, nb) columns a caller of the timed path receives (R_TOC, R_TOA, L_TOA; on N > 1 ranks
+    rank 0's gathered global batch) -> path/<name>.npy in the step's dtype.  When all B rows exceed DUMP_BYTES, a fixed
+    sample of rows is written instead: sorted(numpy default_rng(DUMP_SEED).choice(B, k, replace=False)), the same rows
+    for the same arguments in every run and every build."""
+    import numpy as np
+    _, B, nb = cols.shape
+    k = min(B, DUMP_BYTES // (3 * nb * cols.element_size()))
+    if k < B:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+        cols = cols.index_select(1, torch.as_tensor(idx, device=cols.device))
+    host = cols.cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    for i, name in enumerate(("R_TOC", "R_TOA", "L_TOA")):
+        np.save(os.path.join(path, name + ".npy"), host[i])
+    return {"dir": path, "names": ["R_TOC", "R_TOA", "L_TOA"], "rows": int(k), "of_rows": int(B),
+            "sample": None if k == B else f"sorted numpy default_rng({DUMP_SEED}).choice({B}, {k}, replace=False)",
+            "dtype": str(host.dtype)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -598,7 +625,11 @@ def main():
     ap.add_argument("--sensor", default="Sentinel2A-MSI")
     ap.add_argument("--cpu-rows", type=int, default=8192, help="rows PER HOST CORE for the CPU baseline (0 = skip)")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp64 / configs sub-records (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the columns of the last timed step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -688,6 +719,16 @@ def main():
         step()
     fence()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = (counter[0] - 1) % nbuf                 # the buffer the last timed step wrote (and, for N > 1, gathered)
+        if world > 1:
+            rows = [hi_r - lo_r for lo_r, hi_r in (sharding.shard_bounds(Bg, world, r) for r in range(world))] \
+                if scaling == "strong" else [args.batch] * world
+            cols = torch.cat([g[:, :n] for g, n in zip(gather_lists[last], rows)], dim=1)
+        else:
+            cols = res[last][:, :B]
+        dumped = dump_outputs(torch, args.dump_outputs, cols)
     stage, ncalls = eng.profile_read_stages()
     eng.profile(0)
     own_dt = dt
@@ -799,6 +840,8 @@ def main():
                                             "bit_identical_to_full_evaluation": pr["columns_bit_identical_to_full_evaluation"],
                                             "traffic": (pr.get("roofline") or {}).get("traffic"),
                                             "workload": pr["workload"]}
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -274,3 +274,33 @@ def test_bench_under_the_drivers_multi_rank_invocation():
         assert li["winners_equal_to_single_device_search"] == li["checked"] == li["costs_bit_equal"] == 65536
         assert lg["ranks_seen"] == world and sum(lg["rows_per_rank"]) == 8 * 200000 and lg["finite_on_every_rank"] is True
         assert lg["value"] > 0 and li["value"] > 0
+
+
+def test_bench_dump_outputs_are_the_timed_columns(tmp_path):
+    """bench.py --dump-outputs DIR: --steps sets the timed steps, ms_per_step is in the line, and DIR/<name>.npy hold the
+    columns the timed path computed -- bit for bit what Engine.run returns for the same synthetic batch, and for two ranks
+    (gloo, one GPU) the gathered global batch equal to the single-rank dump."""
+    import json
+    import subprocess
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "spart-python_amd"))
+    from spart_amd import get_engine, workloads
+    env = dict(os.environ, SPART_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    common = ["--batch", "20000", "--steps", "3", "--warmup", "1", "--cpu-rows", "0", "--no-extras"]
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *common,
+                          "--dump-outputs", str(tmp_path / "one")], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert one.returncode == 0, one.stderr[-2000:]
+    a = [json.loads(l) for l in one.stdout.splitlines() if l.startswith("{")][0]
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["dumped_outputs"]["rows"] == 20000
+    P = torch.as_tensor(workloads.lhs_params(20000, "full", seed=workloads.LHS_SEED).T.copy(), device="cuda:0")
+    ref = get_engine("Sentinel2A-MSI", 0).run(P, "float32")
+    torch.cuda.synchronize()
+    for k in ("R_TOC", "R_TOA", "L_TOA"):
+        d = np.load(tmp_path / "one" / (k + ".npy"))
+        assert d.dtype == np.float32 and np.array_equal(d, ref[k].cpu().numpy()), k
+    two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+                          "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", *common,
+                          "--dump-outputs", str(tmp_path / "two")], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert two.returncode == 0, two.stderr[-2000:]
+    for k in ("R_TOC", "R_TOA", "L_TOA"):
+        assert np.array_equal(np.load(tmp_path / "two" / (k + ".npy")), np.load(tmp_path / "one" / (k + ".npy"))), k

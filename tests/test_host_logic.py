@@ -162,6 +162,37 @@ def test_bench_finds_its_committed_profile_numbers():
     assert bench.algorithmic_bytes(13, "float32") == 27 * 8 + 3 * 13 * 4
 
 
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every row while the columns fit in DUMP_BYTES; above it the same seeded, sorted sample of
+    rows in every run, within the byte bound, in the step's own dtype."""
+    import importlib.util
+    import os
+    root = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    names = ("R_TOC", "R_TOA", "L_TOA")
+    cols = torch.arange(3 * 5000 * 13, dtype=torch.float64).reshape(3, 5000, 13)
+    r = bench.dump_outputs(torch, str(tmp_path / "all"), cols)
+    assert r["rows"] == r["of_rows"] == 5000 and r["sample"] is None and r["dtype"] == "float64"
+    for i, n in enumerate(names):
+        a = np.load(tmp_path / "all" / (n + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, cols[i].numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 13 * 4 * 1000 + 7)
+    c32 = cols.float()
+    for d in ("s1", "s2"):
+        r = bench.dump_outputs(torch, str(tmp_path / d), c32)
+        assert r["rows"] == 1000 and r["of_rows"] == 5000 and r["dtype"] == "float32"
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(5000, 1000, replace=False))
+    total = 0
+    for i, n in enumerate(names):
+        a, b = np.load(tmp_path / "s1" / (n + ".npy")), np.load(tmp_path / "s2" / (n + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (1000, 13) and np.array_equal(a, b)
+        assert np.array_equal(a, c32[i].numpy()[idx])
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES
+
+
 def test_lut_parquet_export(golden, tmp_path):
     """lut_to_parquet on a LUT directory in the documented layout (spart_amd/lut.py: meta.json, params.npy, one .npy per
     column) holding the reference's golden rows: one wide table, parameters + <column>_<band centre>, like the
