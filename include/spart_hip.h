@@ -55,8 +55,9 @@ extern "C" {
 /* Version of THIS interface (struct layouts, argument lists, stage count): spart_abi_version() of a loaded library must
  * equal the header's a binding was written against (the Python loader checks, so that a library built from another
  * round's header -- e.g. through SPART_HIP_LIB -- is refused instead of being called with shifted arguments).
- *   6: spart_materialize.lidf_in / .nlayers, spart_sailh_batch(lidf_in, nlayers), spart_abi_version itself */
-#define SPART_ABI_VERSION 6
+ *   6: spart_materialize.lidf_in / .nlayers, spart_sailh_batch(lidf_in, nlayers), spart_abi_version itself
+ *   7: spart_workspace_bandsum */
+#define SPART_ABI_VERSION 7
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -174,6 +175,15 @@ int spart_calculate_tav(double alpha_deg, const double *nr, int64_t n, double *o
  * sample, + the band sums of the full-band kernel).  The same buffer may be reused by successive calls
  * on one stream.  spart_smac_batch sizes its workspace with dtype = SPART_F64. */
 size_t spart_workspace_bytes(const spart_ctx *ctx, int dtype, int64_t B);
+
+/* Where a spart_run_batch(dtype, B) call that ran the full-band kernel unpruned (prune_unused_bands = 0) leaves its per-chunk
+ * band sums in the workspace it was given: *nchunk rows of *row_stride elements starting *offset bytes into the workspace;
+ * row c, element b (b < SPART_NWL + 1, b = SPART_NWL the thermal evaluation) = the sum over the samples of chunk c of
+ * rso + rdo + rsd + rdd at band b.  With spart_materialize.band_mean the four terms are kept apart instead: four
+ * consecutive elements per band (rso, rdo, rsd, rdd), rows of 4 * row_stride.  Elements are of the full-band kernel's type:
+ * float for SPART_F32 and with spart_materialize.f32_bands, double otherwise.  The chunks partition the batch in order, so
+ * the sum over the rows is the batch total.  A read-only query: it launches nothing and reads no device memory. */
+int spart_workspace_bandsum(const spart_ctx *ctx, int dtype, int64_t B, size_t *offset, int64_t *nchunk, int *row_stride);
 
 /* PROSPECT_5D (prospect_5d.py:117-246).  leaf[9] = Cab, Cdm, Cw, Cs, Cca, Cant, N, PROT, CBC.
  * Outputs (B,2001): refl, tran, kChlrel (any may be NULL). */

@@ -269,14 +269,6 @@ Workspace carve(int dtype, int64_t B) {
   return w;
 }
 
-// np.interp(x, wlS, .) support points (SPART.py:220-223) on the 2162-point grid
-void wl_solar(std::vector<double>& wl) {
-  wl.clear();
-  for (int i = 400; i <= 2400; ++i) wl.push_back(i);
-  for (int i = 2500; i <= 15000; i += 100) wl.push_back(i);
-  for (int i = 16000; i <= 50000; i += 1000) wl.push_back(i);
-}
-
 template <typename T> int upload(const spart_ctx* ctx, T** dst, const std::vector<T>& src) {
   HIP_TRY(ctx, hipMalloc((void**)dst, src.size() * sizeof(T)));
   HIP_TRY(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -764,24 +756,9 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
   // --- sensor block
   ctx->nb = t->nb;
   if (t->nb > 0) {
-    std::vector<double> wl;
-    wl_solar(wl);
     std::vector<int> e0(t->nb), e1(t->nb);
     std::vector<double> fr(t->nb);
-    auto eval_of = [](int grid_idx) { return grid_idx < NWL ? grid_idx : NWL; };   // every thermal grid point holds the same value
-    for (int j = 0; j < t->nb; ++j) {
-      double x = t->wl_smac[j];
-      // i0 = last grid point <= x, clipped to [0, n-2]; np.interp clamps outside the grid
-      int i0 = 0;
-      while (i0 + 1 < (int)wl.size() - 1 && wl[i0 + 1] <= x) ++i0;
-      int i1 = i0 + 1;
-      double f = (x - wl[i0]) / (wl[i1] - wl[i0]);
-      if (!(f > 0.0)) f = 0.0;
-      if (f > 1.0) f = 1.0;
-      e0[j] = eval_of(i0);
-      e1[j] = f > 0.0 ? eval_of(i1) : e0[j];
-      fr[j] = f;
-    }
+    for (int j = 0; j < t->nb; ++j) interp_support(t->wl_smac[j], e0[j], e1[j], fr[j]);
     std::vector<double> coef(t->coef, t->coef + (size_t)NCOEF * t->nb);
     std::vector<double> wsrf(t->wl_srf, t->wl_srf + (size_t)t->nsrf * t->nb), psrf(t->p_srf, t->p_srf + (size_t)t->nsrf * t->nb);
     double *d_w = nullptr, *d_p = nullptr;
@@ -875,6 +852,17 @@ int spart_calculate_tav(double alpha_deg, const double* nr, int64_t n, double* o
 size_t spart_workspace_bytes(const spart_ctx* ctx, int dtype, int64_t B) {
   if (!ctx || B <= 0) return 0;
   return carve(dtype, B).total;
+}
+
+int spart_workspace_bandsum(const spart_ctx* ctx, int dtype, int64_t B, size_t* offset, int64_t* nchunk, int* row_stride) {
+  if (!ctx || !offset || !nchunk || !row_stride) return fail(nullptr, SPART_ERR_INVALID, "spart_workspace_bandsum: null argument");
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(ctx, SPART_ERR_INVALID, "spart_workspace_bandsum: bad dtype %d", dtype);
+  if (B <= 0 || B > SPART_MAX_BATCH) return fail(ctx, SPART_ERR_INVALID, "spart_workspace_bandsum: batch %lld", (long long)B);
+  const int chunk = pick_chunk(B);                 // (the layout of run_impl: one row per workgroup column of k_bands)
+  *offset = carve(dtype, B).bs_off;
+  *nchunk = (B + chunk - 1) / chunk;
+  *row_stride = NTILE * TILE;
+  return SPART_OK;
 }
 
 #define CHECK_COMMON(name)                                                                                  \

@@ -550,6 +550,28 @@ inline double calculate_tav(double alpha, double nr) {
 }
 
 // ------------------------------------------------------------------------------------------
+// np.interp(x, wlS, .) of a sensor band centre (SPART.py:219-223), host only, once per context: the grid wlS (SPART.py:303-310)
+// and the evaluation indices of the two support points with the weight of the second.  Every thermal grid point holds the
+// same value (the padding of SPART.py:427-470), so grid indices >= NWL map to the one thermal evaluation, index NWL.
+inline double wl_solar_at(int i) {
+  return i < NWL ? 400.0 + i : (i < NWL + 126 ? 2500.0 + 100.0 * (i - NWL) : 16000.0 + 1000.0 * (i - NWL - 126));
+}
+
+inline void interp_support(double x, int& e0, int& e1, double& frac) {
+  auto eval_of = [](int grid_idx) { return grid_idx < NWL ? grid_idx : NWL; };
+  // i0 = last grid point <= x, clipped to [0, n-2]; np.interp clamps outside the grid
+  int i0 = 0;
+  while (i0 + 1 < NWLS - 1 && wl_solar_at(i0 + 1) <= x) ++i0;
+  int i1 = i0 + 1;
+  double f = (x - wl_solar_at(i0)) / (wl_solar_at(i1) - wl_solar_at(i0));
+  if (!(f > 0.0)) f = 0.0;
+  if (f > 1.0) f = 1.0;
+  e0 = eval_of(i0);
+  e1 = f > 0.0 ? eval_of(i1) : e0;
+  frac = f;
+}
+
+// ------------------------------------------------------------------------------------------
 // per-band table slice (lives in registers for the whole sample loop)
 // row order of the device table block ctx->tab[NTAB][NWL]
 enum TabRow {

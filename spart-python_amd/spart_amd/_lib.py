@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 6         # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 7         # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -43,6 +43,8 @@ SIGNATURES = {
     "spart_ctx_set_row_pitch": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64]),
     "spart_calculate_tav": (ctypes.c_int, [ctypes.c_double, c_dp, ctypes.c_int64, c_dp]),
     "spart_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int64]),
+    "spart_workspace_bandsum": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t),
+                                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),
     "spart_prospect_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(vp), vp, vp, vp, vp,
                                             ctypes.c_size_t, vp]),
     "spart_bsm_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(vp), vp, vp, vp, vp,

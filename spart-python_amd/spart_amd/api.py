@@ -624,7 +624,7 @@ class SPART:
             if materialize:
                 fields += _SPECTRA
             # the (B, nb) results share ONE device block, so that they come back in one device-to-host copy
-            B = max([int(np.size(c)) if not torch.is_tensor(c) else c.numel() for c in cols if c is not None] + [1])
+            B = max([int(np.size(c)) if not torch.is_tensor(c) else c.numel() for c in (*cols, *th) if c is not None] + [1])
             if rdry is not None:
                 r0 = rdry if torch.is_tensor(rdry) else np.asarray(rdry)
                 B = max(B, 1 if (r0.ndim == 1 or (r0.ndim == 2 and r0.shape[1] == 1)) else r0.shape[0])

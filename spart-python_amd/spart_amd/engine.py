@@ -244,6 +244,14 @@ class Engine:
             buf = self._ws_buf[key] = self.torch.empty(max(n, 256), dtype=self.torch.uint8, device=self.device)
         return ctypes.c_void_p(buf.data_ptr()), ctypes.c_size_t(buf.numel())
 
+    def bandsum_layout(self, dtype, B):
+        """(byte offset, chunks, row stride in elements) of the per-chunk band sums an unpruned run(dtype, B) leaves in its
+        workspace (spart_workspace_bandsum)"""
+        off, nchunk, stride = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int()
+        rc = self.lib.spart_workspace_bandsum(self.ctx, DTYPES[dtype], B, ctypes.byref(off), ctypes.byref(nchunk), ctypes.byref(stride))
+        _lib.check(self.lib, self.ctx, rc)
+        return int(off.value), int(nchunk.value), int(stride.value)
+
     def release_workspace(self):
         """Drop the scratch buffers the engine keeps between calls (one per stream used; each grows to the largest batch
         seen: ~0.9 KB per sample); the next call allocates what it needs."""
@@ -497,6 +505,11 @@ class Engine:
                 if nrow > B:
                     B = nrow
                     cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
+            nth = max([1] + [int(x.numel()) if torch.is_tensor(x) else int(np.size(x)) for x in (rho_thermal, tau_thermal)
+                             if x is not None])
+            if nth > B:                                     # LeafBiology.rho_thermal / tau_thermal given per sample
+                B = nth
+                cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
         nl = self._nlayers(nlayers)
         li = self._lidf_rows(canopy_lidf, B) if canopy_lidf is not None else None
         th = [None if x is None else self.to_f64(x, B) for x in (rho_thermal, tau_thermal)]

@@ -40,6 +40,13 @@ Files
                  through PROSPECT_5D: leaf (32,9) + refl / tran / kChlrel (32,2001)   (prospect_5d.py:117-246)
   surface.json   the SHAPE of the reference's public surface (surface_probe.py: return types, attribute names, array shapes and dtypes of
                  every public callable on the hot path, S2A + MODIS), for the drop-in audit of tests/test_surface.py
+  thermal.npz    the thermal leaf optics LeafBiology.rho_thermal / tau_thermal (prospect_5d.py:82-83, padded over bands 2001..2161 by
+                 set_leaf_refl_trans_assumptions, SPART.py:445-470): `run/<pair>/<sensor>/` SPART(...).run(debug=True) for defaults +
+                 8 LHS rows per (rho, tau) pair, one fresh object per row (`mixed/` gives every row its own pair), Sentinel2A (float64
+                 coefficients) and TerraAqua-MODIS: the columns + rsoil, SAILH rso/rdo/rsd/rdd and the padded leafopt at
+                 THERMAL_PROBES, the full padded leafopt of one row; `centres/<pair>/`: MODIS with band centres moved outside
+                 400-2400 nm (390 ... 60000 nm, SPART.py:219-223 np.interp over the 2162-point grid): the columns + rsoil
+                 (python tests/golden/make_golden.py thermal)
   edge.npz       128 rows of tools/edge_sweep.py's widened ranges with edge values (LAI 0 / 1e-4 / 10, dry soil, N = 1,
                  zero pigments, exact hot spot, grazing angles, PRO leaves), Sentinel2A: P + R_TOC / R_TOA / L_TOA
 """
@@ -614,8 +621,74 @@ def gen_grids():
                         canopy_means=np.array([r[1] for r in rc]))
 
 
+THERMAL_PAIRS = [(0.03, 0.02), (0.0, 0.0), (0.2, 0.05), (0.45, 0.45)]     # (rho_thermal, tau_thermal); 0.45 + 0.45: absorption ~0.1
+THERMAL_PROBES = [0, 150, 400, 1000, 1600, 2000, 2001, 2002, 2100, 2161]   # 400 ... 2400 nm, the first / second / a middle / last thermal band
+# MODIS band centres (its wl_smac is float; Sentinel-2's is uint16) moved to every branch of np.interp over wlS: below the grid,
+# the first point, between points, the last solar point, the solar-thermal lerp, thermal points, between them, the last point, beyond
+EDITED_CENTRES = [390.0, 400.0, 2399.5, 2400.0, 2450.0, 2500.0, 2550.0, 3000.0, 20000.0, 50000.0, 60000.0]
+
+
+def edited_centres(wl_smac):
+    """wl_smac (nb, 1) with its first len(EDITED_CENTRES) entries replaced (a new array)"""
+    w = np.array(wl_smac, dtype=np.float64, copy=True)
+    w[:len(EDITED_CENTRES), 0] = EDITED_CENTRES
+    return w
+
+
+def _thermal_row(args):
+    import table_edits
+    row, sensor, rho_th, tau_th, centres = args
+    leaf, soil, can, ang, atm, doy = row[0:9], row[9:15], row[15:19], row[19:22], row[22:26], row[26]
+    with redirect_stdout(io.StringIO()):
+        sp = SPART.SPART(SoilParameters(*soil), LeafBiology(*leaf[:7], PROT=leaf[7], CBC=leaf[8], rho_thermal=float(rho_th),
+                                                            tau_thermal=float(tau_th)),
+                         CanopyStructure(*can), AtmosphericProperties(atm[0], atm[1], atm[2], Pa=atm[3]), Angles(*ang), sensor, int(doy))
+        table_edits.upcast_coefs(sp.sensorinfo)
+        if centres:
+            sp.sensorinfo["wl_smac"] = edited_centres(sp.sensorinfo["wl_smac"])
+        df = sp.run(debug=True)
+    cols = tuple(df[c].to_numpy() for c in ("R_TOC", "R_TOA", "L_TOA", "rsoil"))
+    if centres:
+        return cols
+    spec = tuple(np.asarray(getattr(sp.canopyopt, k), dtype=np.float64)[:, 0] for k in ("rso", "rdo", "rsd", "rdd"))
+    leafopt = (np.asarray(sp.leafopt.refl, dtype=np.float64)[:, 0], np.asarray(sp.leafopt.tran, dtype=np.float64)[:, 0])
+    assert all(x.shape == (2162,) for x in spec + leafopt)
+    return cols + tuple(x[THERMAL_PROBES] for x in spec + leafopt) + (leafopt,)
+
+
+def gen_thermal():
+    import warnings
+    warnings.filterwarnings("ignore")
+    P = np.concatenate([workloads.default_row(), workloads.lhs_params(1000, "full", seed=37)[sample_rows(1000, 8)]])
+    out = {"P": P, "pairs": np.array(THERMAL_PAIRS), "probe_index": np.array(THERMAL_PROBES),
+           "edited_centres": np.array(EDITED_CENTRES)}
+    groups = [(f"{i}", np.full(len(P), r), np.full(len(P), t)) for i, (r, t) in enumerate(THERMAL_PAIRS)]
+    mix = np.arange(len(P)) % len(THERMAL_PAIRS)
+    groups.append(("mixed", np.array(THERMAL_PAIRS)[mix, 0], np.array(THERMAL_PAIRS)[mix, 1]))
+    names = ["R_TOC", "R_TOA", "L_TOA", "rsoil", "rso", "rdo", "rsd", "rdd", "leaf_refl", "leaf_tran"]
+    with np.errstate(all="ignore"), Pool(8) as pool:
+        for tag, rho, tau in groups:
+            for sensor in ("Sentinel2A-MSI", "TerraAqua-MODIS"):
+                res = pool.map(_thermal_row, [(r, sensor, a, b, False) for r, a, b in zip(P, rho, tau)], chunksize=1)
+                name = f"run/{tag}/{sensor}"
+                out[name + "/rho_thermal"], out[name + "/tau_thermal"] = rho, tau
+                for j, k in enumerate(names):
+                    out[f"{name}/{k}"] = np.array([r[j] for r in res])
+                out[name + "/leafopt_refl_row1"], out[name + "/leafopt_tran_row1"] = res[1][-1]
+                print(name, P.shape, flush=True)
+        wl = None
+        for tag, (rho, tau) in (("default", (0.01, 0.01)), ("2", THERMAL_PAIRS[2])):
+            res = pool.map(_thermal_row, [(r, "TerraAqua-MODIS", rho, tau, True) for r in P[:5]], chunksize=1)
+            name = f"centres/{tag}"
+            out[name + "/rho_thermal"], out[name + "/tau_thermal"] = np.full(5, rho), np.full(5, tau)
+            for j, k in enumerate(names[:4]):
+                out[f"{name}/{k}"] = np.array([r[j] for r in res])
+            print(name, "5 rows", flush=True)
+    out["centres/wl_smac"] = edited_centres(SPART.load_sensor_info("TerraAqua-MODIS")["wl_smac"])
+    np.savez_compressed(os.path.join(HERE, "thermal.npz"), **out)
+
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["prospect", "bsm", "sailh", "smac", "e2e", "rdry", "jpl", "edge", "s2f64", "tables"]
+    which = sys.argv[1:] or ["prospect", "bsm", "sailh", "smac", "e2e", "rdry", "jpl", "edge", "s2f64", "tables", "thermal"]
     for w in which:
         globals()["gen_" + w]()

@@ -148,4 +148,13 @@ void hm_plate_tau(int dtype, int64_t n, const double* K, double* tau, double* u)
     else { double t, uu; plate_tau<double>(K[i], t, uu); tau[i] = t; u[i] = uu; }
   }
 }
+
+// the band-centre support points spart_ctx_create builds from sensorinfo['wl_smac'] (interp_support), and the grid they index
+void hm_interp_support(int64_t n, const double* x, int* e0, int* e1, double* frac) {
+  for (int64_t i = 0; i < n; ++i) interp_support(x[i], e0[i], e1[i], frac[i]);
+}
+
+void hm_wl_solar(double* wl /* (NWLS,) */) {
+  for (int i = 0; i < NWLS; ++i) wl[i] = wl_solar_at(i);
+}
 }

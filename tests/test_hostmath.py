@@ -204,3 +204,31 @@ def test_lidf_jump_reproduces_the_literal_iteration(hm, oracle):
     ref = oracle.calculate_leafangles(a[:200], b[:200])        # (n, 13) class weights of the oracle (pinned to the reference)
     got = np.diff(np.concatenate([np.zeros((200, 1)), F[2][:200], np.ones((200, 1))], axis=1), axis=1)
     assert np.max(np.abs(got - ref)) < 1e-13
+
+
+def test_band_centre_support_points_equal_np_interp(hm, oracle):
+    """interp_support (csrc/spart_math.h), which spart_ctx_create runs on every sensorinfo['wl_smac'] entry, against
+    oracle.interp_weights (np.interp over wlS, SPART.py:219-223): the grid itself, then every branch -- below the grid, grid
+    points, between points, the last solar point, the solar-thermal lerp, thermal points, between them, the last point and
+    beyond.  Grid indices map to evaluation indices with eval_of (>= 2001 -> 2001: the thermal pad is one value); with a zero
+    weight the C side uses the first support point twice."""
+    wl = np.zeros(2162)
+    hm.hm_wl_solar(dp(wl))
+    assert np.array_equal(wl, oracle.wl_solar())
+    x = np.array([390.0, 400.0, 2399.5, 2400.0, 2450.0, 2500.0, 2550.0, 3000.0, 20000.0, 50000.0, 60000.0, -1.0, 0.0, 399.999,
+                  400.5, 401.0, 1234.25, 2000.0, 2400.0001, 2499.999, 15000.0, 15500.0, 16000.0, 49999.5, 1e9])
+    x = np.concatenate([x, oracle.wl_solar(), np.sort(np.random.default_rng(5).uniform(300, 60000, 500))])
+    n = x.size
+    e0, e1 = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    fr = np.zeros(n)
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))  # noqa: E731
+    hm.hm_interp_support(ctypes.c_int64(n), dp(x), ip(e0), ip(e1), dp(fr))
+    i0, i1, f = oracle.interp_weights(x)
+    ev = lambda i: np.minimum(i, 2001)  # noqa: E731
+    assert np.array_equal(fr, f)
+    assert np.array_equal(e0, ev(i0))
+    assert np.array_equal(e1, np.where(f > 0, ev(i1), ev(i0)))
+    # what the evaluation indices stand for: the value np.interp returns for a spectrum that is constant over the thermal pad
+    y = np.random.default_rng(6).uniform(0, 1, 2162)
+    y[2001:] = y[2001]
+    assert np.allclose(y[e0] + (y[e1] - y[e0]) * fr, np.interp(x, oracle.wl_solar(), y), rtol=1e-14, atol=1e-15)
