@@ -270,24 +270,8 @@ int spart_profile_read_stages(spart_ctx *ctx, double stage_ms[SPART_NSTAGE], int
  *     SPART_HIP_LIB=<path>   load another build of this ABI (A/B timing, tools/ab_bench.py)
  *     SPART_FAST_MATH=0      build with IEEE division / libm transcendentals instead of v_rcp / v_exp / v_log + Newton steps
  *                            (CHANGES results at the 1e-15 (float64) / 1e-7 (float32) level; parity is tested with the default)
- *   compile-time macros (A/B variants built through build.py's `extra` flags, which are hashed into spart_build_id):
- *     SPART_PRELUDE_WAVES (3)   occupancy the prelude kernel is compiled for
- *     SPART_HOIST_FILM          hoist the water-film transmittance out of the sample loop (default: float64 kernels only)
- *     SPART_FRESH_COEF (1)      re-materialise the plate-model polynomial coefficients per use instead of holding them in VGPRs
- *     SPART_LIDF_JUMP (1)       skip ahead in the LIDF fixed-point iteration by its contraction rate (same iterate sequence end)
- *     SPART_LIDF_ROTATE (1)     sin / cos of an LIDF iterate by rotating the previous iterate's pair through the (small) step
- *     SPART_LIDF_KJUMP (2e-2), SPART_LIDF_GATE (1e-2)   how early that skip takes over from the literal passes (expansion parameter, step size)
- *     SPART_HOTSPOT_SERIES (1)  closed-form series for the hot-spot integrals where it converges, panels elsewhere
- *     SPART_LUT_TO (8)          observation blocks per wave of the float32 LUT scan
- *     SPART_BANDS_PINGPONG      double-buffered constant staging in the full-band kernel (default: float32 columns-only kernel)
- *     SPART_BANDS_SUB (32)      samples per staged copy of that kernel (64 needs the double buffer)
- *     SPART_PRELUDE_SORT (1)    deal a workgroup's 256 samples to its waves in the order of |LIDFa| + |LIDFb|
- *     SPART_COLUMNS_WAVES (4)   occupancy the column kernel is compiled for
- *     SPART_COLUMNS_DIRECT (1)  column kernel stores its results directly (0: through an LDS transpose)
- *     SPART_SMAC_LIBM (1)       library exp / sqrt in the SMAC arithmetic (0: the table-driven float64 exp of the band kernels)
- *     SPART_SMAC_SHARE_EXP (1)  SMAC's three aerosol exponentials as products of exponentials it needs anyway
- *     SPART_EXPERIMENT          1 / 2: arithmetic-only / store-only measurement variants of k_prospect (tools/prospect_split.sh).
- *                               NOT a product configuration: variant 2 does not compute leaf spectra.  Never defined by build.py.
+ *   A/B of a tuning constant (a constexpr in csrc/, next to its measurement): edit it on a branch, build each tree with
+ *   build.build(out=...) and time the two libraries with tools/ab_bench.py.
  */
 
 #ifdef __cplusplus

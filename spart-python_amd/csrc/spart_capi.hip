@@ -403,7 +403,6 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
   mp.pf = ctx->pf; mp.po = ctx->po;
   const bool nt = nt_ok(ctx->pf, sizeof(T)) && nt_ok(ctx->po, sizeof(T));     // both row grids on the 128-byte lines
   bool mat = false;
-  const bool want_rsoil = opt && opt->rsoil;
   if (opt) {
     mp.leaf_refl = (T*)opt->leaf_refl; mp.leaf_tran = (T*)opt->leaf_tran; mp.leaf_kchl = (T*)opt->leaf_kchl;
     mp.soil_refl = (T*)opt->soil_refl; mp.soil_dry = (T*)opt->soil_refl_dry;
@@ -416,10 +415,6 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
   const bool full = !(opt && opt->prune_unused_bands);
   if (opt && opt->band_mean && !full)
     return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: band_mean needs prune_unused_bands = 0");
-  const int narr = 3 + (want_rsoil ? 1 : 0) + ((opt && opt->La) ? 1 : 0);
-  // LDS staging of the results: only the (measurement) variant of k_columns that transposes through LDS
-  const size_t lds = SPART_COLUMNS_DIRECT ? 0 : (size_t)narr * 64 * ctx->nb * sizeof(TO);     // <= 5 * 64 * 64 * 8 = 160 KiB only for nb = 64 fp64
-  if (lds > 64 * 1024) return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: %d sensor bands need %zu B of LDS staging", ctx->nb, lds);
   int rc;
   // optional per-stage timing: four events per call (before the prelude, after the prelude, after the full-band kernel,
   // after the column kernel)
@@ -448,7 +443,7 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
   const bool fork = lane != nullptr;
   hipStream_t s2 = fork ? lane->side : st;
   auto columns = [&]() -> int {                // the column kernel, on s2
-    hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), lds, s2, tabG, cstG,
+    hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, s2, tabG, cstG,
                        (const double*)atm, Bp, (const int*)ctx->band0, (const int*)ctx->band1, (const double*)ctx->frac,
                        (const double*)ctx->coef, (const double*)ctx->econv, ctx->nb,
                        (const TO*)(opt ? opt->rdry_in : nullptr), ctx->po, B, (TO*)R_TOC,

@@ -118,9 +118,7 @@ struct PreludeStore {            // sample_prelude_to's sink: straight to the st
   __device__ __forceinline__ void l(int, double) const {}
 };
 
-#ifndef SPART_PRELUDE_WAVES
-#define SPART_PRELUDE_WAVES 3     // waves per SIMD the prelude is compiled for (168 VGPRs, a handful of spilled values)
-#endif
+constexpr int PRELUDE_SIMD_WAVES = 3;   // waves per SIMD the prelude is compiled for (168 VGPRs, a handful of spilled values)
 // Which lane takes which sample of the workgroup's 256: the literal LIDF iteration (sailh.py:378-382) runs 12 fixed-point
 // solves per sample whose pass counts differ from sample to sample -- 6 passes on average, 15 for the slowest of 64 lanes,
 // and a wave pays its slowest lane.  The pass count grows with |LIDFa| + |LIDFb| (the contraction rate of the iteration), so
@@ -129,17 +127,14 @@ struct PreludeStore {            // sample_prelude_to's sink: straight to the st
 // the benchmark's distribution; 1024-sample groups would give 9.9).  A sample's arithmetic does not depend on the lane that
 // runs it: results are bit-identical with and without the permutation.  Rows stay coalesced at the cache-line level (a
 // workgroup still reads / writes one 2 KB segment of every row).
-#ifndef SPART_PRELUDE_SORT
-#define SPART_PRELUDE_SORT 1
-#endif
 // USER: the call carries canopy state of its own -- pp.lidf (the 12 fixed-point solves are then skipped: no sort either)
 // and / or pp.nlayers; the default instantiation does not look at either.
 template <bool FAST, bool USER = false>
-__global__ __launch_bounds__(256, SPART_PRELUDE_WAVES) void k_prelude(ParamPtrs pp, int mask, int64_t B, int64_t Bp, float* __restrict__ cstF,
+__global__ __launch_bounds__(256, PRELUDE_SIMD_WAVES) void k_prelude(ParamPtrs pp, int mask, int64_t B, int64_t Bp, float* __restrict__ cstF,
                                                  double* __restrict__ cstD, double* __restrict__ atm) {
   const int64_t base = (int64_t)blockIdx.x * blockDim.x;
   int64_t s = base + threadIdx.x;
-  if (SPART_PRELUDE_SORT && !FAST && (mask & PRE_CANOPY) && !(USER && pp.lidf)) {      // (block-uniform condition)
+  if (!FAST && (mask & PRE_CANOPY) && !(USER && pp.lidf)) {      // (block-uniform condition)
     constexpr int NB = 32;
     __shared__ int cnt[NB], start[NB];
     __shared__ unsigned char perm[256];
@@ -300,23 +295,13 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
   // land in VGPRs: on gfx950 a VALU op with an SGPR source issues ~1.6x slower than with VGPR / literal sources
   // (profiles/r1_ubench_valu_issue.txt), and ~60 ops per band use these constants -- the same kernel with
   // scalar loads (s_load_dwordx8 -> SGPR operands) is 6 % slower.
-#ifndef SPART_BANDS_SUB
-#define SPART_BANDS_SUB 32
-#endif
-  constexpr int SUB = SPART_BANDS_SUB;                 // (64 needs PINGPONG: the single-buffer copy is written for 32)
-#ifndef SPART_HOIST_FILM
-#define SPART_HOIST_FILM (sizeof(T) == 8)
-#endif
-  constexpr bool HOIST_FILM = SPART_HOIST_FILM;
+  constexpr int SUB = 32;
+  constexpr bool HOIST_FILM = sizeof(T) == 8;
   // Double-buffered staging (PINGPONG): the global loads of the next 32 samples' constants are issued BEFORE the sample loop
   // and land in LDS after it, so a workgroup meets ONE barrier per 32 samples and never waits for memory on its critical
   // path (single buffer: barrier, load, wait, barrier).  Five more VGPRs per lane (float32) while the loop runs.
-#ifndef SPART_BANDS_PINGPONG
-#define SPART_BANDS_PINGPONG (sizeof(T) == 4 && MAT == 0)
-#endif
-  constexpr bool PINGPONG = SPART_BANDS_PINGPONG;
+  constexpr bool PINGPONG = sizeof(T) == 4 && MAT == 0;
   __shared__ __attribute__((aligned(16))) T lds_all[(PINGPONG ? 2 : 1) * SUB * NCONST];
-  static_assert(PINGPONG || SUB == 32, "stage_constants copies 32 samples");
   T stg[NCONST * SUB / TILE];
   int cur = 0;
   if (PINGPONG) {
@@ -479,29 +464,21 @@ template <typename T> struct LdsCol {
 // tables are separate __restrict__ arguments (a pointer inside a by-value struct cannot be declared noalias).
 
 constexpr int COL_WAVES = 4;   // (more waves per 64-sample workgroup measured slower for both former kernels)
-#ifndef SPART_COLUMNS_WAVES
-#define SPART_COLUMNS_WAVES 4  // waves per SIMD the column kernel is compiled for (128 VGPRs)
-#endif
+constexpr int COLUMNS_SIMD_WAVES = 4;   // waves per SIMD the column kernel is compiled for (128 VGPRs)
 // Results leave straight from the lane that computed them (stride nb between lanes: the (64 x nb) block of a workgroup is
 // completed by its four waves within a few hundred cycles and merges in L2) instead of through an LDS transpose: the 10 KB
 // of staging were what limited the kernel to three workgroups per CU.
-#ifndef SPART_COLUMNS_DIRECT
-#define SPART_COLUMNS_DIRECT 1
-#endif
 
 template <typename TG, typename TO, typename TR>
-__global__ __launch_bounds__(64 * COL_WAVES, SPART_COLUMNS_WAVES) void k_columns(
+__global__ __launch_bounds__(64 * COL_WAVES, COLUMNS_SIMD_WAVES) void k_columns(
     const TG* __restrict__ tab, const TG* __restrict__ cst, const double* __restrict__ atm, int64_t Bp,
     const int* __restrict__ band0, const int* __restrict__ band1, const double* __restrict__ frac,
     const double* __restrict__ coef, const double* __restrict__ econv, int nb, const TR* __restrict__ rdry_in, int po, int64_t B,
     TO* __restrict__ R_TOC, TO* __restrict__ R_TOA, TO* __restrict__ L_TOA, TO* __restrict__ o_rsoil, TO* __restrict__ o_La) {
-  constexpr bool DIRECT = SPART_COLUMNS_DIRECT != 0;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  TO* stage = reinterpret_cast<TO*>(smem_raw);          // [narr][64 * nb]  (not used with DIRECT)
   __shared__ TG lds_c[NCONST_USED * 64];
   __shared__ double lds_a[NATM_USED * 64];
   __shared__ double lds_k[COL_WAVES * 64];              // per wave: the 48 SMAC coefficients of the band it is working on
-  if (sizeof(TG) == 8 || !SPART_SMAC_LIBM) stage_f64_tables();   // exp / log tables of the float64 arithmetic
+  if (sizeof(TG) == 8) stage_f64_tables();   // exp / log tables of the float64 arithmetic
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t s0 = (int64_t)blockIdx.x * 64;
@@ -513,7 +490,6 @@ __global__ __launch_bounds__(64 * COL_WAVES, SPART_COLUMNS_WAVES) void k_columns
   __syncthreads();
   const LdsCol<TG> c{lds_c + lane};
   const LdsCol<double> a{lds_a + lane};
-  const int tile = 64 * nb;
   const bool want_soil = o_rsoil != nullptr;
   // (starting wave w at band (w + workgroup) mod 4, so that the four-band wave of a 13-band sensor moves from SIMD to SIMD,
   //  changed nothing: 0.464 / 0.466 ms, profiles/r5_ab_columns.txt)
@@ -567,43 +543,14 @@ __global__ __launch_bounds__(64 * COL_WAVES, SPART_COLUMNS_WAVES) void k_columns
     const double La = a[A_LAF] * econv[j];               // SPART.py:353, 394
     double rtoc, rtoa, ltoa;
     toc_to_toa(so, v[0], v[1], v[3], v[2], La, rtoc, rtoa, ltoa);
-    if (DIRECT) {
-      if (ok) {
-        const int64_t o = s * nb + j;
-        R_TOC[o] = (TO)rtoc;
-        R_TOA[o] = (TO)rtoa;
-        L_TOA[o] = (TO)ltoa;
-        if (want_soil) o_rsoil[o] = (TO)v[4];           // SPART.py:262-267
-        if (o_La) o_La[o] = (TO)La;
-      }
-    } else {
-      const int o = lane * nb + j;
-      stage[o] = (TO)rtoc;
-      stage[tile + o] = (TO)rtoa;
-      stage[2 * tile + o] = (TO)ltoa;
-      int na = 3;
-      if (want_soil) {
-        stage[na * tile + o] = (TO)v[4];
-        ++na;
-      }
-      if (o_La) stage[na * tile + o] = (TO)La;
+    if (ok) {
+      const int64_t o = s * nb + j;
+      R_TOC[o] = (TO)rtoc;
+      R_TOA[o] = (TO)rtoa;
+      L_TOA[o] = (TO)ltoa;
+      if (want_soil) o_rsoil[o] = (TO)v[4];             // SPART.py:262-267
+      if (o_La) o_La[o] = (TO)La;
     }
-  }
-  if (DIRECT) return;
-  __syncthreads();
-  const int64_t rem = B - s0;
-  const int n = (int)((rem < 64 ? rem : 64) * nb);
-  const int64_t base = s0 * nb;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    R_TOC[base + i] = stage[i];
-    R_TOA[base + i] = stage[tile + i];
-    L_TOA[base + i] = stage[2 * tile + i];
-    int na = 3;
-    if (want_soil) {
-      o_rsoil[base + i] = stage[na * tile + i];
-      ++na;
-    }
-    if (o_La) o_La[base + i] = stage[na * tile + i];
   }
 }
 
@@ -669,23 +616,9 @@ __global__ __launch_bounds__(TILE) void k_prospect(const T* __restrict__ tab, co
   if (o_kchl) o_kchl += s0 * po;
   for_samples_staged<T, sizeof(T) == 4>(cst, Bp, s0, s1, [&](int64_t, auto c) {
     T refl, tran, absb, K;
-#ifndef SPART_EXPERIMENT
     leaf_band<T>(tb, c[C_CAB], c[C_CCA], c[C_CDM], c[C_CW], c[C_CS], c[C_CANT], c[C_CBC], c[C_PROT], c[C_NM1], refl,
                  tran, absb, K);
     if (active) {
-#else
-    // MEASUREMENT VARIANTS, never part of a product build (tools/prospect_split.sh builds them with
-    // build.py's `extra` flags, which are hashed into spart_build_id; nothing else defines the macro):
-    // SPART_EXPERIMENT = 1 arithmetic only (the stores sit behind a test no value passes), = 2 stores only (placeholder
-    // arithmetic -- NOT leaf spectra).  profiles/r4_prospect_split.txt is what they measured.
-#if SPART_EXPERIMENT == 2
-    refl = c[C_CAB] * tb.kab; tran = c[C_CW] * tb.kw; K = c[C_CDM] + tb.kdm; absb = 0;
-#else
-    leaf_band<T>(tb, c[C_CAB], c[C_CCA], c[C_CDM], c[C_CW], c[C_CS], c[C_CANT], c[C_CBC], c[C_PROT], c[C_NM1], refl,
-                 tran, absb, K);
-#endif
-    if (active && (SPART_EXPERIMENT != 1 || refl + tran + K == T(-12345.678))) {
-#endif
       if (o_refl) store_row<NT>(o_refl, off, refl);
       if (o_tran) store_row<NT>(o_tran, off, tran);
       if (o_kchl) store_row<NT>(o_kchl, off, (K > T(0)) ? divx(c[C_CAB] * tb.kab, K) : T(0));
@@ -763,7 +696,6 @@ struct Out9 {
 };
 static __global__ __launch_bounds__(256) void k_smac(const double* __restrict__ coef, int nb, const double* __restrict__ atm,
                                               int64_t Bp, int64_t B, Out9 out) {
-  if (!SPART_SMAC_LIBM) stage_f64_tables();             // smac_band's table exp
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * nb) return;
   int64_t s = i / nb;

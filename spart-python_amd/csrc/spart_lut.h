@@ -81,10 +81,7 @@ constexpr int LUT_FB_BLOCKS = 2048;        // workgroups (x 4 waves) of the brut
 // and 33.9 ns with four (tools/ubench/mfma_f32_rate2.hip) -- and every LUT tile loaded is used for twice the observations.
 // Measured 1M x 65 536, nb = 13: 4 / 6 / 7 / 8 / 10 / 12 / 16 blocks: 15.25 / 15.24 / 15.11 / 14.45 / 15.46 / 15.71 / 14.97 ms
 // (profiles/r4_lut_to_sweep2.txt); nb = 6: 9.25 -> 9.10 ms, nb = 21: unchanged.
-#ifndef SPART_LUT_TO
-#define SPART_LUT_TO 8
-#endif
-constexpr int LUT_TO = SPART_LUT_TO;
+constexpr int LUT_TO = 8;
 
 // column means of a strided sample (finite entries only) -> centre[nb]; also resets the control words
 template <typename T>

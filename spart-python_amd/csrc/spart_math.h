@@ -147,13 +147,10 @@ template <> struct Mx<float> {
 // (Device tables in this header are `static`: the library is built from more than one translation unit -- the float32
 // full-band kernels are compiled on their own, spart_bands_f32.hip -- and each unit carries its own copy.)
 // Coefficient tables in constant memory are read through a pointer the optimiser cannot prove loop-invariant
-// (SPART_FRESH): left alone, hipcc hoists all 48 float64 coefficients of the band path (96 SGPRs) out of the sample
+// (spart_fresh): left alone, hipcc hoists all 48 float64 coefficients of the band path (96 SGPRs) out of the sample
 // loop, runs out of SGPRs and parks them in VGPR lanes -- 32 v_readlane / v_writelane per band and sample in
 // k_prospect<double>, 16 % of its VALU instructions.  Reloaded per use they cost a few wide scalar loads (scalar
 // cache) and no VALU slot.
-#ifndef SPART_FRESH_COEF
-#define SPART_FRESH_COEF 1
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const double __attribute__((address_space(4))) * spart_cdp;   // constant address space: uniform loads stay scalar
 #else
@@ -161,7 +158,7 @@ typedef const double* spart_cdp;
 #endif
 __device__ __forceinline__ spart_cdp spart_fresh(const double* p) {
   spart_cdp q = (spart_cdp)p;
-#if SPART_FRESH_COEF && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+s"(q));
 #endif
   return q;
@@ -170,7 +167,7 @@ __device__ __forceinline__ spart_cdp spart_fresh(const double* p) {
 // v_fma_f64.  Written as C++, hipcc selects the two-address v_fmac_f64 (which overwrites its addend) and first copies
 // every coefficient into a VGPR pair: two v_mov_b32 per step, 138 of 467 VALU instructions in k_prospect<double>.
 __device__ __forceinline__ double spart_horner(double p, double x, double c_uniform) {
-#if defined(__HIP_DEVICE_COMPILE__) && SPART_FRESH_COEF
+#if defined(__HIP_DEVICE_COMPILE__)
   double d;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(p), "v"(x), "s"(c_uniform));
   return d;
@@ -250,15 +247,6 @@ template <> struct Mx<double> {
     r = __builtin_fma(-k, 2.9064910585985925e-13, r);                    // low part
     return exp_finish(k, r);
   }
-  // the same for callers that rely on exp(NaN) = NaN (smac_band: a NaN gas column reaches the result only through exp);
-  // a compare + select instead of the one v_max
-  static SPART_HD double exp_keepnan(double x) {
-    x = (x < -800.0) ? -800.0 : x;
-    const double k = __builtin_rint(x * 369.32993046757463);
-    double r = __builtin_fma(-k, 0.0027076061737716373, x);
-    r = __builtin_fma(-k, 2.9064910585985925e-13, r);
-    return exp_finish(k, r);
-  }
   static SPART_HD double exp2(double x) {                  // 2^x = 2^(k/256) e^((256 x - k) ln2 / 256)
     const double t = x * 256.0;
     const double k = __builtin_rint(t);
@@ -282,7 +270,6 @@ template <> struct Mx<double> {
 #else
   static SPART_HD double exp_poly(double x) { return ::exp(x); }
   static SPART_HD double exp(double x) { return ::exp(x); }
-  static SPART_HD double exp_keepnan(double x) { return ::exp(x); }
   static SPART_HD double exp2(double x) { return ::exp2(x); }
   static SPART_HD double log(double x) { return ::log(x); }
 #endif
@@ -909,9 +896,6 @@ SPART_HD void lidf_rotate(double d, double& sn, double& cs) {
   sn = s0 + (c0 * sd - s0 * cm);
   cs = c0 - (s0 * sd + c0 * cm);
 }
-#ifndef SPART_LIDF_ROTATE
-#define SPART_LIDF_ROTATE 1
-#endif
 constexpr double LIDF_ROT_MAX = 0.25;
 // (sn, cs) at the iterate u_new = u_old + d: by rotation when `rot` (this lane's own decision), by lidf_sincos otherwise.
 // Each form is issued only when some lane of the wave takes it; a lane's result never depends on its neighbours' choices.
@@ -950,10 +934,9 @@ template <bool JUMP> SPART_HD double lidf_dcum_lit_impl(double a, double b, int 
   const double rd = PI / 180.0;
   const double theta2 = 2.0 * rd * lidf_theta(i);
   const double s2 = lidf_sin_2theta(i), c2 = lidf_cos_2theta(i);
-#ifndef SPART_LIDF_KJUMP
-#define SPART_LIDF_KJUMP 2e-2   // (5e-3 until round 5: same iterates -- 0 mismatches in 5.4M solves against the literal loop -- two passes fewer)
-#endif
-  const double kjump = SPART_LIDF_KJUMP / (0.25 * (::fabs(a) + 2.0 * ::fabs(b)) + 0.02);   // 5e-3 / (bound of |y''| / 4, + margin)
+  constexpr double LIDF_KJUMP = 2e-2;      // (5e-3 until round 5: same iterates -- 0 mismatches in 5.4M solves against the literal loop -- two passes fewer)
+  constexpr double LIDF_GATE = 1e-2;       // (4e-3 until round 5)
+  const double kjump = LIDF_KJUMP / (0.25 * (::fabs(a) + 2.0 * ::fabs(b)) + 0.02);   // 5e-3 / (bound of |y''| / 4, + margin)
   double u = 0.0, y, dx = 0.0, dprev;
   double sn = s2, cs = c2;                 // (sin, cos)(2 theta + u), carried from pass to pass
   bool more, ready = false;
@@ -967,14 +950,11 @@ template <bool JUMP> SPART_HD double lidf_dcum_lit_impl(double a, double b, int 
     // scratch otherwise and every eighth pass.  The choice is the lane's own (a sample's result must not depend on the samples
     // it shares a wave with); the wave only skips a form that none of its lanes takes.
     // (pass 0 has u = 0 and dx = 0: the rotation through 0 returns the tabulated pair unchanged)
-    lidf_sincos_step(SPART_LIDF_ROTATE && (it & 7) != 7 && ::fabs(dx) < LIDF_ROT_MAX, dx, u, s2, c2, sn, cs);
+    lidf_sincos_step((it & 7) != 7 && ::fabs(dx) < LIDF_ROT_MAX, dx, u, s2, c2, sn, cs);
     y = sn * (a + b * cs);
     dx = 0.5 * (y - u);
     more = ::fabs(dx) > 1e-8;              // sailh.py:382 -- y belongs to the iterate BEFORE the update
-#ifndef SPART_LIDF_GATE
-#define SPART_LIDF_GATE 1e-2    // (4e-3 until round 5)
-#endif
-    if (JUMP && ::fabs(dx) < SPART_LIDF_GATE) {
+    if (JUMP && ::fabs(dx) < LIDF_GATE) {
       // rho = dx / dprev estimates r; ready when 0.3 < rho < 0.98 and |dx| < 5e-3 rho (1 - rho)^2 / c2max, written
       // without the division: |dprev|^3 < K (|dprev| - |dx|)^2
       const double ad = ::fabs(dx), ap = ::fabs(dprev), df = ap - ad;
@@ -989,13 +969,13 @@ template <bool JUMP> SPART_HD double lidf_dcum_lit_impl(double a, double b, int 
     double nstep = 1.0;
     // (sn, cs) belong to the iterate u: the first Newton point is a small step away (|d0| <~ 0.06 by the readiness test), every
     // later one a tiny one
-    lidf_sincos_step(SPART_LIDF_ROTATE && ::fabs(d0) < LIDF_ROT_MAX, d0, us, s2, c2, sn, cs);
+    lidf_sincos_step(::fabs(d0) < LIDF_ROT_MAX, d0, us, s2, c2, sn, cs);
     for (int k = 0; k < 3; ++k) {          // Newton on g(u) = 0: 1e-5 -> 1e-9 -> 1e-17
       const double f = sn * (a + b * cs) - us;                            // 2 g
       const double fp = a * cs + b * (2.0 * cs * cs - 1.0) - 1.0;         // 2 g'
       nstep = f * Md::rcp(fp);
       us -= nstep;
-      lidf_sincos_step(SPART_LIDF_ROTATE && ::fabs(nstep) < LIDF_ROT_MAX, -nstep, us, s2, c2, sn, cs);
+      lidf_sincos_step(::fabs(nstep) < LIDF_ROT_MAX, -nstep, us, s2, c2, sn, cs);
     }
     const double s2x = 2.0 * sn * cs, c2x = 2.0 * cs * cs - 1.0;          // sin 2x, cos 2x at the fixed point
     const double y1 = a * cs + b * c2x, y2 = -a * sn - 2.0 * b * s2x, y3 = -a * cs - 4.0 * b * c2x, y4 = a * sn + 8.0 * b * s2x;
@@ -1047,10 +1027,7 @@ template <bool JUMP> SPART_HD double lidf_dcum_lit_impl(double a, double b, int 
   }
   return (2.0 * y + theta2) / PI;
 }
-#ifndef SPART_LIDF_JUMP
-#define SPART_LIDF_JUMP 1
-#endif
-SPART_HD double lidf_dcum_lit(double a, double b, int i) { return lidf_dcum_lit_impl<(SPART_LIDF_JUMP != 0)>(a, b, i); }
+SPART_HD double lidf_dcum_lit(double a, double b, int i) { return lidf_dcum_lit_impl<true>(a, b, i); }
 
 // sin / cos of the 13 class-centre inclinations litab(i) and of twice the 12 class boundaries theta(i): constants of
 // the model (sailh.py:49, 388-394), tabulated (math.sin / math.cos of the same double arguments) so that no sample
@@ -1226,10 +1203,7 @@ SPART_HD void hotspot_integrals(double K, double k, double LAI, double q, double
     f.A = (K + k) * LAI;
     f.C = ::sqrt(K * k) * LAI / f.alpha;
     rate = ::fmax(f.alpha, f.A + ::sqrt(K * k) * LAI);
-#ifndef SPART_HOTSPOT_SERIES
-#define SPART_HOTSPOT_SERIES 1
-#endif
-    if (SPART_HOTSPOT_SERIES && hotspot_series(f.A, f.C, f.alpha, int_canopy, pso2w, nl)) return;
+    if (hotspot_series(f.A, f.C, f.alpha, int_canopy, pso2w, nl)) return;
   } else {
     f.hot = true;
     f.alpha = 0.0;
@@ -1445,18 +1419,9 @@ enum CoefRow {
 // C(r): coefficient row r (CoefRow) of this band
 template <typename A, typename CF> SPART_HD SmacOut smac_band_c(const A& atm, const CF& C) {
   using Md = Mx<double>;
-  // exp / sqrt: the library's (default), or with SPART_SMAC_LIBM=0 the float64 band arithmetic's own table-driven exp (LDS
-  // tables staged by the calling kernel: stage_f64_tables) and Newton-refined rsq: 17 % fewer instructions, more registers
-#ifndef SPART_SMAC_LIBM
-#define SPART_SMAC_LIBM 1     // measured: the table exp needs 168 VGPRs here (three waves per SIMD: 0.51 ms per 1M spectra, spilling at
-#endif                        // 128: 0.95 ms) against 0.47 ms with the library's exp at 128 (profiles/r5_ab_smac_exp.txt)
-#if SPART_SMAC_LIBM
-  auto EXP = [](double x) { return ::exp(x); };
-  auto SQRT = [](double x) { return ::sqrt(x); };
-#else
-  auto EXP = [](double x) { return Md::exp_keepnan(x); };
-  auto SQRT = [](double x) { return Md::sqrt(x); };
-#endif
+  // exp / sqrt: the library's.  The float64 band arithmetic's table-driven exp and Newton-refined rsq have 17 % fewer
+  // instructions but need 168 VGPRs here (three waves per SIMD: 0.51 ms per 1M spectra, spilling at 128: 0.95 ms) against
+  // 0.47 ms with the library's exp at 128 (profiles/r5_ab_smac_exp.txt)
   double us = atm[A_US], uv = atm[A_UV], m = atm[A_M], Peq = atm[A_PEQ], Pa = atm[A_PA];
   double taup550 = atm[A_AOT], cksi = atm[A_CKSI], ksiD = atm[A_KSID];
   double lpeq = atm[A_LOGPEQ], lm = atm[A_LOGM];
@@ -1468,11 +1433,11 @@ template <typename A, typename CF> SPART_HD SmacOut smac_band_c(const A& atm, co
   // bands): it is skipped, which leaves the product below bit-identical.
   auto gas = [&](int ka, int kn, double lum) -> double {
     double av = C(ka);
-    return (av != 0.0) ? EXP(av * EXP(C(kn) * lum)) : 1.0;
+    return (av != 0.0) ? ::exp(av * ::exp(C(kn) * lum)) : 1.0;
   };
   auto pgas = [&](int ka, int kn, int kp) -> double {
     double av = C(ka);
-    return (av != 0.0) ? EXP(av * EXP(C(kn) * (C(kp) * lpeq + lm))) : 1.0;
+    return (av != 0.0) ? ::exp(av * ::exp(C(kn) * (C(kp) * lpeq + lm))) : 1.0;
   };
   double to3 = gas(K_AO3, K_NO3, atm[A_LOGO3M]);
   double th2o = gas(K_AH2O, K_NH2O, atm[A_LOGH2OM]);
@@ -1499,20 +1464,20 @@ template <typename A, typename CF> SPART_HD SmacOut smac_band_c(const A& atm, co
   double g3 = 3.0 - wo * 3.0 * gc;
   double ig3 = Md::rcp(g3);
   double ak2 = (1.0 - wo) * g3;  // :149-150
-  double ak = SQRT(ak2);
+  double ak = ::sqrt(ak2);
   double idus = Md::rcp(1.0 - ak2 * us * us);
   double e = -3.0 * us * us * wo * 0.25 * idus;  // :153-157
   double f = -(1.0 - wo) * 3.0 * gc * us * us * wo * 0.25 * idus;
   double dp = e * ius * (1.0 / 3.0) + us * f;
   double d = e + f;
   double b = 2.0 * ak * ig3;
-  double eak = EXP(ak * taup), emak = Md::rcp(eak);
+  double eak = ::exp(ak * taup), emak = Md::rcp(eak);
   double delta = eak * (1.0 + b) * (1.0 + b) - emak * (1.0 - b) * (1.0 - b);  // :158
   double ww = wo * 0.25;
   double ss = us * idus;
   double q1 = 2.0 + 3.0 * us + (1.0 - wo) * 3.0 * gc * us * (1.0 + 2.0 * us);
   double q2 = 2.0 - 3.0 * us - (1.0 - wo) * 3.0 * gc * us * (1.0 - 2.0 * us);
-  const double e_us = EXP(-taup * ius);      // e^(-taup / us)
+  const double e_us = ::exp(-taup * ius);    // e^(-taup / us)
   double q3 = q2 * e_us;
   double wsd = ww * ss * Md::rcp(delta);
   double c1 = wsd * (q1 * eak * (1.0 + b) + q3 * (1.0 - b));    // :164
@@ -1528,16 +1493,10 @@ template <typename A, typename CF> SPART_HD SmacOut smac_band_c(const A& atm, co
   // taup n1 / uv = taup / uv + ak taup, taup n2 / uv = taup / uv - ak taup, taup n3 / (us uv) = taup / uv + taup / us: the three
   // exponentials of :175-179 are products of e^(-taup / uv) with e^(-+ ak taup) and e^(-taup / us), which :158 and :163 need
   // anyway -- one exp instead of three, each product within 2 ulp of the direct exponential
-#if defined(SPART_SMAC_SHARE_EXP) && !SPART_SMAC_SHARE_EXP
-  double aer_ref1 = x * aa1 * (1.0 - EXP(-taup * n1 * iuv));  // :175-179
-  double aer_ref2 = y * aa2 * (1.0 - EXP(-taup * n2 * iuv));
-  double aer_ref3 = z * aa3 * (1.0 - EXP(-taup * n3 * iusuv));
-#else
-  const double e_uv = EXP(-taup * iuv);
+  const double e_uv = ::exp(-taup * iuv);
   double aer_ref1 = x * aa1 * (1.0 - e_uv * emak);  // :175-179
   double aer_ref2 = y * aa2 * (1.0 - e_uv * eak);
   double aer_ref3 = z * aa3 * (1.0 - e_uv * e_us);
-#endif
   double aer_ref = (aer_ref1 + aer_ref2 + aer_ref3) * iusuv;
   double rr = taur * ray_phase * iusuv;
   double Res_ray = C(K_RESR1) + C(K_RESR2) * rr + C(K_RESR3) * (rr * rr);  // :182-186
@@ -1547,8 +1506,8 @@ template <typename A, typename CF> SPART_HD SmacOut smac_band_c(const A& atm, co
   double tt = tautot * m * cksi;
   double Res_6s = (C(K_REST1) + C(K_REST2) * tt + C(K_REST3) * (tt * tt)) + C(K_REST4) * (tt * tt * tt);  // :196-198
   o.Ra_so = ray_ref - Res_ray + aer_ref - Res_aer + Res_6s;  // :201
-  o.Ta_ss = EXP(-tautot * ius);                            // :204-207
-  o.Ta_oo = EXP(-tautot * iuv);
+  o.Ta_ss = ::exp(-tautot * ius);                          // :204-207
+  o.Ta_oo = ::exp(-tautot * iuv);
   o.Ta_sd = o.Ta_s - o.Ta_ss;
   o.Ta_do = o.Ta_o - o.Ta_oo;
   return o;
