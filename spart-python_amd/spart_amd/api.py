@@ -10,6 +10,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _lib
 from . import engine as _engine
 from . import tables as _tables
 from .tables import load_ET_parameters, load_optical_parameters, load_sensor_info  # noqa: F401 (re-exported)
@@ -24,6 +25,15 @@ def _is_scalar(*vals):
 
 def _np(t):
     return t.detach().cpu().numpy()
+
+
+def _snapshot(v):
+    """a parameter value as it is now: arrays, lists and tuples copied, tensors cloned, scalars (immutable) and None as they are"""
+    if v is None or type(v) in _PLAIN:                  # (first: a scalar SPART.run() snapshots ~40 of these per call)
+        return v
+    if isinstance(v, (np.ndarray, list, tuple)):
+        return np.array(v, copy=True)
+    return v.clone() if hasattr(v, "clone") else v
 
 
 def _colvec(t, scalar):
@@ -76,7 +86,6 @@ def calculate_tav(alpha, nr):
     """prospect_5d.py:249-311, float64 on the host through the library's own routine (spart_calculate_tav: the one the
     context derives its interface tables from); ``nr`` scalar or array, result of the same shape."""
     import ctypes
-    from . import _lib
     shape = np.shape(nr)
     a = np.ascontiguousarray(np.asarray(nr, dtype=np.float64).reshape(-1))
     out = np.empty_like(a)
@@ -277,8 +286,7 @@ class CanopyStructure:
         self.nlayers = 60
         self.nlincl = 13
         self.nlazi = 36
-        snap = lambda v: np.array(v, dtype=np.float64, copy=True) if isinstance(v, (np.ndarray, list, tuple)) else v  # noqa: E731
-        self._lidf_ab = (snap(LIDFa), snap(LIDFb))      # what sailh.py:348 evaluated lidf from
+        self._lidf_ab = (_snapshot(LIDFa), _snapshot(LIDFb))      # what sailh.py:348 evaluated lidf from
         self._lidf = None
 
     @property
@@ -549,20 +557,19 @@ class SPART:
         lidf values), ONE pinned (ncol, nb) block down, both preallocated per object (no per-call tensor allocation), and between
         them one spart_run_batch whose arguments were marshalled once (Engine.prepare)."""
         import torch
-        key = (id(eng), self.dtype, len(ncol))
+        key = (self.dtype, len(ncol))
         io = self.__dict__.setdefault("_scalar_io", {})
         b = io.get(key)
-        if b is None:
+        if b is None or b["eng"] is not eng:
             td = torch.float32 if _engine.DTYPES[self.dtype] == 0 else torch.float64
             hin = torch.empty((42, 1), dtype=torch.float64).pin_memory()
             hout = torch.empty((len(ncol), 1, eng.nb), dtype=td).pin_memory()
             io.clear()                                          # (one staging pair per object: the last configuration's)
-            b = io[key] = dict(hin=hin, hin_np=hin.numpy()[:, 0], hout=hout, hout_np=hout.numpy()[:, 0, :],
+            b = io[key] = dict(eng=eng, hin=hin, hin_np=hin.numpy()[:, 0], hout=hout, hout_np=hout.numpy()[:, 0, :],
                                din=torch.empty((42, 1), dtype=torch.float64, device=eng.device),
                                dout=torch.empty((len(ncol), 1, eng.nb), dtype=td, device=eng.device), calls={})
         vals = b["hin_np"]
-        for i, c in enumerate(cols):
-            vals[i] = 0.0 if c is None else c                   # (None: LIDFa / LIDFb with a given lidf, B / lat / lon with rdry)
+        vals[:27] = _engine.fill_nulls(cols, canopy_lidf=clidf)
         vals[27], vals[28] = th
         if clidf is not None:
             vals[29:42] = np.asarray(clidf, dtype=np.float64).reshape(13)
@@ -624,12 +631,7 @@ class SPART:
             if materialize:
                 fields += _SPECTRA
             # the (B, nb) results share ONE device block, so that they come back in one device-to-host copy
-            B = max([int(np.size(c)) if not torch.is_tensor(c) else c.numel() for c in (*cols, *th) if c is not None] + [1])
-            if rdry is not None:
-                r0 = rdry if torch.is_tensor(rdry) else np.asarray(rdry)
-                B = max(B, 1 if (r0.ndim == 1 or (r0.ndim == 2 and r0.shape[1] == 1)) else r0.shape[0])
-            if clidf is not None and np.ndim(clidf) == 2 and np.shape(clidf)[1] != 1:
-                B = max(B, int(np.shape(clidf)[0]))
+            B = _engine.batch_size(cols + list(th), [(rdry, _lib.NWL), (clidf, _lib.NLINCL)])
             td = torch.float32 if _engine.DTYPES[self.dtype] == 0 else torch.float64
             blk = torch.empty((len(ncol), B, eng.nb), dtype=td, device=eng.device)
             res = eng.run(cols, self.dtype, rho_thermal=th[0], tau_thermal=th[1], materialize=fields, rdry=rdry,
@@ -642,7 +644,7 @@ class SPART:
         self._La = out["La"][0] if scalar else out["La"]                                   # (nb,) for scalars (SPART.py:183)
         # what the lazy attributes are evaluated from: COPIES of the parameters and the dtype of THIS run (the reference sets the
         # attributes eagerly in run(): mutating an input array in place or changing sp.dtype afterwards must not change them)
-        snap = lambda c: None if c is None else (np.array(c, copy=True) if isinstance(c, np.ndarray) else (c.clone() if hasattr(c, "clone") else c))  # noqa: E731
+        snap = _snapshot
         self.__dict__["_last"] = dict(eng=eng, dtype=self.dtype, cols=[snap(c) for c in cols], th=tuple(snap(t) for t in th),
                                       rdry=snap(rdry), scalar=scalar, clidf=snap(clidf), nlayers=nlay,
                                       angles=[snap(c) for c in self.angles.columns()], atm=[snap(c) for c in self.atm.columns()])

@@ -3,6 +3,7 @@
 compute call goes through the C ABI (include/spart_hip.h)."""
 import collections
 import ctypes
+import math
 import threading
 
 import numpy as np
@@ -27,6 +28,54 @@ def _require_gpu():
 
 def _dp(a):
     return a.ctypes.data_as(_lib.c_dp)
+
+
+def _on_rows(t, row_stride):
+    """a 2-D tensor steps ``row_stride`` elements from row to row and 1 along a row (a dimension of size 1 is never stepped:
+    the kernels index element [b, j] at b * row_stride + j)"""
+    return all(n == 1 or s == want for n, s, want in zip(t.shape, t.stride(), (row_stride, 1)))
+
+
+def _nrows(x, width):
+    """the row count of a row-set: (width,) and the reference's (width, 1) column are one row, (..., width) are rows"""
+    s = tuple(np.shape(x))
+    if s == (width, 1):
+        return 1
+    if not s or s[-1] != width:
+        raise ValueError(f"an input of shape {s}: expected ({width},), ({width}, 1) or (B, {width})")
+    return math.prod(s[:-1])
+
+
+def batch_size(cols=(), rows=(), B=None):
+    """The batch size of one call, from shapes alone.  ``cols``: per-sample values, each a scalar or B values (None = not
+    given); ``rows``: (x, width) pairs of row-sets -- spectra (width 2001 / 2162) or lidf (13) -- each (width,),
+    (width, 1) or (B, width) (x None = not given); ``B``: fixed by a (27, B) params block, else the largest count.
+    Every input broadcasts: its count is 1 or B, anything else is a ValueError."""
+    counts = [math.prod(np.shape(c)) for c in cols if c is not None] + [_nrows(x, w) for x, w in rows if x is not None]
+    if B is None:
+        B = max(counts, default=1)
+    for n in counts:
+        if n != 1 and n != B:
+            raise ValueError(f"an input of {n} samples does not broadcast to a batch of {B}")
+    return B
+
+
+# the params rows (workloads.PARAM_NAMES) the C ABI lets be NULL, and the input that must then be given: soil B / lat / lon
+# with user dry-soil spectra (spart_materialize.rdry_in), LIDFa / LIDFb with a given lidf (lidf_in)
+NULLABLE = {9: "rdry", 10: "rdry", 11: "rdry", 16: "canopy_lidf", 17: "canopy_lidf"}
+
+
+def fill_nulls(vals, first=0, **given):
+    """``vals`` = params[first:first + len(vals)] with each None that NULLABLE allows for the inputs ``given`` (rdry=...,
+    canopy_lidf=...) replaced by 0.0; any other None is a ValueError."""
+    out = list(vals)
+    for k, v in enumerate(out):
+        if v is None:
+            if given.get(NULLABLE.get(first + k)) is None:
+                raise ValueError(f"params[{first + k}] is None (only B / lat / lon with rdry= and LIDFa / LIDFb with "
+                                 "canopy_lidf= may be)")
+            out[k] = 0.0
+    return out
 
 
 # Row pitch (elements) of the (B,2162) / (B,2001) spectrum arrays: rows padded to a multiple of 64 elements start
@@ -257,34 +306,26 @@ class Engine:
         seen: ~0.9 KB per sample); the next call allocates what it needs."""
         self._ws_buf = {}
 
-    def to_f64(self, x, B=None):
-        """scalar / sequence / numpy / tensor -> contiguous float64 device tensor of length B."""
+    def to_f64(self, x, B):
+        """scalar / sequence / numpy / tensor of 1 or B values (batch_size) -> contiguous float64 device tensor of length B."""
         torch = self.torch
         if not torch.is_tensor(x):
             x = torch.as_tensor(np.asarray(x, dtype=np.float64))
-        x = x.to(device=self.device, dtype=torch.float64).reshape(-1)
-        if B is not None and x.numel() != B:
-            if x.numel() != 1:
-                raise ValueError(f"parameter of length {x.numel()} does not broadcast to batch {B}")
-            x = x.expand(B)
-        return x.contiguous()
+        return x.to(device=self.device, dtype=torch.float64).reshape(-1).expand(B).contiguous()
 
-    def columns(self, cols):
-        """list of per-parameter values -> (list of (B,) tensors, B).  Host values (scalars, sequences, numpy arrays) travel in
-        ONE host-to-device copy of an (n, B) block (a scalar SPART.run() used to issue 29 one-element copies: half its
-        0.9 ms); device tensors are used where they are."""
+    def columns(self, cols, B=None):
+        """list of per-parameter values -> (list of (B,) tensors, B); B = batch_size(cols) unless given.  Host values (scalars,
+        sequences, numpy arrays) travel in ONE host-to-device copy of an (n, B) block (a scalar SPART.run() used to issue 29
+        one-element copies: half its 0.9 ms); device tensors are used where they are."""
         torch = self.torch
-        sizes = [int(np.size(c)) if not torch.is_tensor(c) else c.numel() for c in cols]
-        B = max(sizes) if sizes else 1
+        if B is None:
+            B = batch_size(cols)
         host = [i for i, c in enumerate(cols) if not torch.is_tensor(c)]
         out = [None] * len(cols)
         if host:
             blk = np.empty((len(host), B), dtype=np.float64)
             for k, i in enumerate(host):
-                a = np.asarray(cols[i], dtype=np.float64).reshape(-1)
-                if a.size != B and a.size != 1:
-                    raise ValueError(f"parameter of length {a.size} does not broadcast to batch {B}")
-                blk[k] = a
+                blk[k] = np.asarray(cols[i], dtype=np.float64).reshape(-1)
             dev = torch.as_tensor(blk).to(self.device)
             for k, i in enumerate(host):
                 out[i] = dev[k]
@@ -292,23 +333,6 @@ class Engine:
             if out[i] is None:
                 out[i] = self.to_f64(c, B)
         return out, B
-
-    def _lidf_rows(self, lidf, B):
-        """canopy.lidf as the caller set it -> (B, 13) contiguous float64 device tensor, B possibly raised to its row count.
-        Accepted: (13,), the reference's (13, 1) column (sailh.py:396), or (B, 13) rows."""
-        torch = self.torch
-        x = lidf if torch.is_tensor(lidf) else torch.as_tensor(np.asarray(lidf, dtype=np.float64))
-        x = x.to(device=self.device, dtype=torch.float64)
-        if x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1 and x.shape[0] == _lib.NLINCL):
-            x = x.reshape(1, -1)
-        if x.dim() != 2 or x.shape[1] != _lib.NLINCL:
-            raise ValueError(f"canopy.lidf of shape {tuple(np.shape(lidf))}: expected ({_lib.NLINCL},), ({_lib.NLINCL}, 1) or (B, {_lib.NLINCL})")
-        if x.shape[0] != B:
-            if x.shape[0] == 1:
-                x = x.expand(B, _lib.NLINCL)
-            elif B != 1:
-                raise ValueError(f"canopy.lidf has {x.shape[0]} rows for a batch of {B}")
-        return x.contiguous()
 
     @staticmethod
     def _nlayers(n):
@@ -333,28 +357,20 @@ class Engine:
         return self.torch.float32 if dt == _lib.SPART_F32 else self.torch.float64
 
     def _alloc_spec(self, B, width, td):
-        """(B, width) spectrum array on this context's row pitch (a view of padded storage when pitch > width)."""
-        pitch = self.row_pitch[width]
+        """(B, width) array on this context's row pitch (a view of padded storage when pitch > width; lidf rows are dense)."""
+        pitch = self.row_pitch.get(width, width)
         return self.torch.empty((B, pitch), dtype=td, device=self.device)[:, :width]
 
-    def _spec(self, x, B, width, dt):
-        """input spectra -> (B, width) device tensor of dtype dt on this context's row pitch."""
+    def _rows(self, x, B, width, td):
+        """an input row-set (spectra, or canopy.lidf as the caller set it) whose row count batch_size() has checked against B
+        -> (B, width) device tensor of dtype td laid out as _alloc_spec lays it out (the input itself when it already is)"""
         torch = self.torch
         if not torch.is_tensor(x):
             x = torch.as_tensor(np.asarray(x))
-        x = x.to(device=self.device, dtype=self._tdtype(dt))
-        if x.dim() == 2 and x.shape[1] == 1 and x.shape[0] == width:     # reference style (n,1) column
-            x = x.reshape(1, width)
-        x = x.reshape(-1, x.shape[-1])
-        if x.shape[1] != width:
-            raise ValueError(f"spectrum of length {x.shape[1]}, expected {width}")
-        if x.shape[0] != B:
-            if x.shape[0] != 1:
-                raise ValueError("spectra do not broadcast to the batch")
-            x = x.expand(B, width)
-        if x.stride() == (self.row_pitch[width], 1):
+        x = x.to(device=self.device, dtype=td).reshape(-1, width).expand(B, width)
+        if _on_rows(x, self.row_pitch.get(width, width)):
             return x
-        buf = self._alloc_spec(B, width, x.dtype)
+        buf = self._alloc_spec(B, width, td)
         buf.copy_(x)
         return buf
 
@@ -376,17 +392,10 @@ class Engine:
     def bsm(self, soil6, dtype="float64", rdry=None):
         """BSM (bsm.py:17-128): soil6 = [B,lat,lon,SMp,SMC,film]; rdry = optional (B,2001) dry spectra."""
         dt = DTYPES[dtype]
-        if rdry is not None:
-            soil6 = [0.0 if c is None else c for c in soil6]
-        cols, B = self.columns(soil6)
-        rd = None
-        if rdry is not None:
-            rd0 = rdry if self.torch.is_tensor(rdry) else np.asarray(rdry)
-            nrow = 1 if rd0.ndim == 1 or (rd0.ndim == 2 and rd0.shape[1] == 1) else rd0.shape[0]
-            B = max(B, nrow)
-            cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
-            rd = self._spec(rdry, B, _lib.NWL, dt)
+        soil6 = fill_nulls(soil6, 9, rdry=rdry)
+        cols, B = self.columns(soil6, batch_size(soil6, [(rdry, _lib.NWL)]))
         td = self._tdtype(dt)
+        rd = self._rows(rdry, B, _lib.NWL, td) if rdry is not None else None
         out = [self._alloc_spec(B, _lib.NWL, td) for _ in range(2)]
         ws, wsn = self._workspace(dt, B)
         self.calls["spart_bsm_batch"] += 1
@@ -410,22 +419,12 @@ class Engine:
         LIDFa / LIDFb, 60."""
         dt = DTYPES[dtype]
         nl = self._nlayers(nlayers)
-        canopy4 = list(canopy4)
-        if canopy_lidf is not None:
-            canopy4[1] = 0.0 if canopy4[1] is None else canopy4[1]
-            canopy4[2] = 0.0 if canopy4[2] is None else canopy4[2]
-        cols, B = self.columns(canopy4 + list(angles3))
-        for x in (rho, tau, rs):
-            n = x.shape[0] if (hasattr(x, "ndim") and x.ndim == 2 and x.shape[1] != 1) else 1
-            B = max(B, n)
-        li = None
-        if canopy_lidf is not None:
-            nrow = 1 if (np.ndim(canopy_lidf) == 1 or np.shape(canopy_lidf)[-1] == 1) else np.shape(canopy_lidf)[0]
-            B = max(B, nrow)
-            li = self._lidf_rows(canopy_lidf, B)
-        cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
-        rho, tau, rs = (self._spec(x, B, _lib.NWLS, dt) for x in (rho, tau, rs))
+        vals = fill_nulls(list(canopy4) + list(angles3), 15, canopy_lidf=canopy_lidf)
+        B = batch_size(vals, [(rho, _lib.NWLS), (tau, _lib.NWLS), (rs, _lib.NWLS), (canopy_lidf, _lib.NLINCL)])
+        cols, _ = self.columns(vals, B)
         td = self._tdtype(dt)
+        li = self._rows(canopy_lidf, B, _lib.NLINCL, self.torch.float64) if canopy_lidf is not None else None
+        rho, tau, rs = (self._rows(x, B, _lib.NWLS, td) for x in (rho, tau, rs))
         out = [self._alloc_spec(B, _lib.NWLS, td) for _ in range(4)]
         ws, wsn = self._workspace(dt, B)
         self.calls["spart_sailh_batch"] += 1
@@ -476,49 +475,30 @@ class Engine:
         torch = self.torch
         dt = DTYPES[dtype]
         td = self._tdtype(dt)
-        col_ptrs = None
+        rows = [(rdry, _lib.NWL), (canopy_lidf, _lib.NLINCL)]
+        col_ptrs = cols = None
         if torch.is_tensor(params) and params.dim() == 2:
             if params.shape[0] != _lib.NPARAM:
                 raise ValueError("params must be (27, B)")
             P = params.to(device=self.device, dtype=torch.float64).contiguous()
-            B = P.shape[1]
-            cols = None
+            B = batch_size((rho_thermal, tau_thermal), rows, P.shape[1])
             base = P.data_ptr()                     # row i of the contiguous block: no 27 tensor views, no 27 data_ptr() calls
             col_ptrs = (_lib.vp * _lib.NPARAM)(*[base + 8 * B * i for i in range(_lib.NPARAM)])
         else:
-            plist = [0.0 if (p is None and (rdry is not None or (canopy_lidf is not None and i in (16, 17)))) else p
-                     for i, p in enumerate(params)]
-            if len(plist) != _lib.NPARAM:
-                raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(plist)}")
-            for i, p in enumerate(plist):
-                if p is None:
-                    raise ValueError(f"params[{i}] is None (only B / lat / lon with rdry= and LIDFa / LIDFb with canopy_lidf= may be)")
-            cols, B = self.columns(plist)
-            if rdry is not None:
-                r0 = rdry if torch.is_tensor(rdry) else np.asarray(rdry)
-                nrow = 1 if (r0.ndim == 1 or (r0.ndim == 2 and r0.shape[1] == 1)) else r0.shape[0]
-                if nrow > B:
-                    B = nrow
-                    cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
-            if canopy_lidf is not None:
-                nrow = 1 if (np.ndim(canopy_lidf) == 1 or np.shape(canopy_lidf)[-1] == 1) else np.shape(canopy_lidf)[0]
-                if nrow > B:
-                    B = nrow
-                    cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
-            nth = max([1] + [int(x.numel()) if torch.is_tensor(x) else int(np.size(x)) for x in (rho_thermal, tau_thermal)
-                             if x is not None])
-            if nth > B:                                     # LeafBiology.rho_thermal / tau_thermal given per sample
-                B = nth
-                cols = [c.expand(B).contiguous() if c.numel() == 1 else c for c in cols]
+            if len(params) != _lib.NPARAM:
+                raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+            plist = fill_nulls(params, rdry=rdry, canopy_lidf=canopy_lidf)
+            B = batch_size(plist + [rho_thermal, tau_thermal], rows)
+            cols, _ = self.columns(plist, B)
         nl = self._nlayers(nlayers)
-        li = self._lidf_rows(canopy_lidf, B) if canopy_lidf is not None else None
+        li = self._rows(canopy_lidf, B, _lib.NLINCL, torch.float64) if canopy_lidf is not None else None
         th = [None if x is None else self.to_f64(x, B) for x in (rho_thermal, tau_thermal)]
         res = dict(out) if out is not None else {}       # (the caller's dict is not modified)
         for k in ("R_TOC", "R_TOA", "L_TOA"):
             if k not in res:
                 res[k] = torch.empty((B, self.nb), dtype=td, device=self.device)
             else:
-                self._check_out(k, res[k], (B, self.nb), td)
+                self._check_out(k, res[k], (B, self.nb), td, self.nb)
         mat = None
         rd = None
         if lidf not in ("literal", "newton"):
@@ -532,23 +512,19 @@ class Engine:
             mat.f32_columns = 1 if f32_columns else 0
             mat.f32_bands = 1 if f32_bands else 0
             if rdry is not None:
-                rd = self._spec(rdry, B, _lib.NWL, dt)
+                rd = self._rows(rdry, B, _lib.NWL, td)
                 mat.rdry_in = rd.data_ptr()
             for name in materialize:
                 if name not in MATERIALIZE_FIELDS:
                     raise ValueError(f"unknown materialize field {name}")
+                w = _MAT_WIDTH.get(name)
+                shape = (B, w) if w else ((4, _lib.NWLS) if name == "band_mean" else (B, self.nb))
                 if name in res:                     # caller-owned buffer (out=): must already have this context's layout
-                    shape = (B, _MAT_WIDTH[name]) if name in _MAT_WIDTH else ((4, _lib.NWLS) if name == "band_mean" else (B, self.nb))
-                    pitch = self.row_pitch[_MAT_WIDTH[name]] if name in _MAT_WIDTH else shape[1]
-                    t = res[name]
-                    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != td or t.device != self.device \
-                            or (B > 1 and t.stride() != (pitch, 1)) or t.stride(-1) != 1:
-                        raise ValueError(f"out[{name!r}] must be a {shape} {td} tensor with row stride {pitch} on {self.device}")
-                elif name in _MAT_WIDTH:
-                    res[name] = self._alloc_spec(B, _MAT_WIDTH[name], td)
+                    self._check_out(name, res[name], shape, td, self.row_pitch[w] if w else shape[1])
+                elif w:
+                    res[name] = self._alloc_spec(B, w, td)
                 else:
-                    res[name] = torch.empty((4, _lib.NWLS) if name == "band_mean" else (B, self.nb), dtype=td,
-                                            device=self.device)
+                    res[name] = torch.empty(shape, dtype=td, device=self.device)
                 setattr(mat, name, res[name].data_ptr())
         if _defer and _workspace is None:                  # a prepared call owns its scratch (other calls on the engine do not disturb it)
             n = int(self.lib.spart_workspace_bytes(self.ctx, dt, B))
@@ -566,7 +542,8 @@ class Engine:
             rc = self.lib.spart_run_batch(*args, self._stream())
             _lib.check(self.lib, self.ctx, rc)
             return res
-        keep = (params, cols, th, li, rd, mat, res, _workspace)        # everything the argument pointers point into
+        # everything the argument pointers point into, and the engine: its __del__ destroys the context the call uses
+        keep = (params, cols, th, li, rd, mat, res, _workspace, self)
         lib, ctx, calls, stream_of, device = self.lib, self.ctx, self.calls, self.torch.cuda.current_stream, self.device
 
         def call():
@@ -583,11 +560,7 @@ class Engine:
         thermal / lidf tensors), with nothing but the ctypes call on the hot path -- what a loop over small batches wants when
         a HIP-graph capture is too rigid (the stream may change from call to call).  The call owns its workspace."""
         torch = self.torch
-        if not (torch.is_tensor(params) and params.dim() == 2 and params.dtype == torch.float64 and params.is_contiguous()
-                and params.device == self.device):
-            raise ValueError("prepare() needs a contiguous (27, B) float64 tensor on the engine's device")
-        if out is None or any(k not in out for k in ("R_TOC", "R_TOA", "L_TOA")):
-            raise ValueError("prepare() needs preallocated out['R_TOC'|'R_TOA'|'L_TOA']")
+        self._check_resident("prepare", params, out)
         if kw.get("rdry") is not None:
             raise ValueError("prepare(): user dry-soil spectra are re-laid out per call (row pitch): use run()")
         for k in ("rho_thermal", "tau_thermal", "canopy_lidf"):
@@ -596,13 +569,25 @@ class Engine:
                 raise ValueError(f"prepare(): {k} must be a tensor on the engine's device (its storage is reused by every call)")
         return self.run(params, dtype, out=out, _defer=True, **kw)
 
-    def _check_out(self, name, t, shape, td):
-        """a caller-supplied output must be exactly what the kernels write: they get its data_ptr() and nothing else"""
-        if not self.torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != td or t.device != self.device \
-                or not t.is_contiguous():
-            raise ValueError(f"out[{name!r}] must be a contiguous {tuple(shape)} {td} tensor on {self.device}, got "
-                             f"{tuple(t.shape) if self.torch.is_tensor(t) else type(t)} "
-                             f"{getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}")
+    def _check_out(self, name, t, shape, td, row_stride):
+        """a caller-supplied output must be exactly what the kernels write: they get its data_ptr() and ``row_stride``"""
+        if not self.torch.is_tensor(t):
+            got = type(t)
+        elif tuple(t.shape) == tuple(shape) and t.dtype == td and t.device == self.device and _on_rows(t, row_stride):
+            return
+        else:
+            got = f"{tuple(t.shape)} {t.dtype} on {t.device} with strides {t.stride()}"
+        raise ValueError(f"out[{name!r}] must be a {tuple(shape)} {td} tensor on {self.device} with contiguous rows at row "
+                         f"stride {row_stride}, got {got}")
+
+    def _check_resident(self, what, params, out):
+        """prepare() / capture(): the call reuses the storage of ``params`` and of the three result tensors every time"""
+        torch = self.torch
+        if not (torch.is_tensor(params) and params.dim() == 2 and params.dtype == torch.float64 and params.is_contiguous()
+                and params.device == self.device):
+            raise ValueError(f"{what}() needs a contiguous (27, B) float64 tensor on the engine's device")
+        if out is None or any(k not in out for k in ("R_TOC", "R_TOA", "L_TOA")):
+            raise ValueError(f"{what}() needs preallocated out['R_TOC'|'R_TOA'|'L_TOA']")
 
     def capture(self, params, dtype="float32", out=None, **kw):
         """Record one run() over RESIDENT buffers into a HIP graph and return its replay function (no arguments;
@@ -612,11 +597,7 @@ class Engine:
         calls on this engine do not disturb it.  spart_run_batch allocates nothing and never synchronises, which is
         what makes it capturable."""
         torch = self.torch
-        if not (torch.is_tensor(params) and params.dim() == 2 and params.dtype == torch.float64 and params.is_contiguous()
-                and params.device == self.device):
-            raise ValueError("capture() needs a contiguous (27, B) float64 tensor on the engine's device")
-        if out is None or any(k not in out for k in ("R_TOC", "R_TOA", "L_TOA")):
-            raise ValueError("capture() needs preallocated out['R_TOC'|'R_TOA'|'L_TOA']")
+        self._check_resident("capture", params, out)
         dt = DTYPES[dtype]
         n = int(self.lib.spart_workspace_bytes(self.ctx, dt, params.shape[1]))
         ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
@@ -628,7 +609,7 @@ class Engine:
             with torch.cuda.graph(g, stream=s):
                 res = self.run(params, dtype, out=out, _workspace=ws, **kw)
         torch.cuda.current_stream(self.device).wait_stream(s)
-        keep = (ws, params, res)                                           # buffers the graph points into
+        keep = (ws, params, res, self)                                     # buffers the graph points into, and their context
 
         def replay():
             g.replay()

@@ -71,6 +71,12 @@ def test_canopy_structure_binds_lidf_like_the_reference():
     cb = CanopyStructure(np.array([1.0, 2.0]), a, np.array([0.0, 0.1]), 0.05)
     a[0] = 0.9
     assert np.array_equal(_canopy_state(cb)[0][1], [0.1, 0.2])
+    import torch                                        # ... tensors too (they were kept by reference)
+    ta, tb = torch.tensor([0.1, 0.2], dtype=torch.float64), torch.tensor([0.0, 0.1], dtype=torch.float64)
+    ct = CanopyStructure(np.array([1.0, 2.0]), ta, tb, 0.05)
+    ta[0] = 0.9
+    tb.mul_(3)
+    assert _canopy_state(ct)[0][1].tolist() == [0.1, 0.2] and _canopy_state(ct)[0][2].tolist() == [0.0, 0.1]
 
     class Ref:                                          # any object with the reference's attributes
         LAI, LIDFa, LIDFb, q, nlayers = 2.0, 0.1, 0.2, 0.1, 24
@@ -89,6 +95,50 @@ def test_nlayers_validation_needs_no_gpu():
         Engine._nlayers(0)
     with pytest.raises(ValueError):
         Engine._nlayers(np.array([30, 60]))
+
+
+def test_batch_rule_needs_no_gpu():
+    """engine.batch_size: the one rule every entry point sizes its batch by, on shapes alone; engine.fill_nulls: the None
+    parameters the C ABI lets be NULL"""
+    import torch
+    from spart_amd.engine import batch_size, fill_nulls
+    W, L = 2001, 13
+    assert batch_size() == 1 and batch_size([None, 0.5, np.float32(2)]) == 1
+    assert batch_size([0.5, np.zeros(7), [1.0] * 7, torch.zeros(7)]) == 7
+    for x in (np.zeros(W), np.zeros((W, 1)), np.zeros((1, W)), torch.zeros(W)):          # one row
+        assert batch_size([0.5], [(x, W)]) == 1 and batch_size([np.zeros(5)], [(x, W)]) == 5
+    assert batch_size([0.5], [(np.zeros((4, W)), W), (np.zeros(L), L), (None, L)]) == 4
+    assert batch_size([None, 0.5], [(np.zeros((3, L)), L)]) == 3 and batch_size([0.5], [(np.zeros((L, L)), L)]) == L
+    assert batch_size([np.zeros(6), None], [(np.zeros((6, W)), W)], 6) == 6
+    assert batch_size([0.5], [(np.zeros((L, 1)), L)], 9) == 9 and batch_size((None, None), [(None, W)], 9) == 9
+    refused = [([np.zeros(3), np.zeros(4)], [], None),
+               ([np.zeros(3)], [(np.zeros((4, W)), W)], None),
+               ([], [(np.zeros((5, L)), L)], 1),                  # the tensor path's B = 1 with more lidf rows
+               ([], [(np.zeros((5, L)), L)], 4),
+               ([np.zeros(2)], [], 3),
+               ([], [(np.zeros(W - 1), W)], None),                 # not a row of this width
+               ([], [(np.zeros((W, 2)), W)], None),
+               ([], [(np.zeros((7, 1)), L)], None)]
+    for cols, rows, B in refused:
+        with pytest.raises(ValueError):
+            batch_size(cols, rows, B)
+    # NULL slots: B / lat / lon (params 9-11) with rdry, LIDFa / LIDFb (16-17) with a given lidf; nowhere else
+    p = [1.0] * 27
+    for i, given in ((9, "rdry"), (10, "rdry"), (11, "rdry"), (16, "canopy_lidf"), (17, "canopy_lidf")):
+        q = list(p)
+        q[i] = None
+        assert fill_nulls(q, **{given: np.zeros(W)})[i] == 0.0
+        with pytest.raises(ValueError, match=f"params\\[{i}\\]"):
+            fill_nulls(q)
+    for i in (0, 12, 15, 18, 26):
+        q = list(p)
+        q[i] = None
+        with pytest.raises(ValueError, match=f"params\\[{i}\\]"):
+            fill_nulls(q, rdry=np.zeros(W), canopy_lidf=np.zeros(L))
+    assert fill_nulls([None] * 3 + [1.0] * 3, 9, rdry=np.zeros(W)) == [0.0] * 3 + [1.0] * 3      # bsm's soil[6]
+    with pytest.raises(ValueError, match="params\\[12\\]"):
+        fill_nulls([None] * 6, 9, rdry=np.zeros(W))
+    assert fill_nulls([2.0, None, None, 0.1], 15, canopy_lidf=np.zeros(L)) == [2.0, 0.0, 0.0, 0.1]     # sailh's canopy[4]
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the public API
@@ -223,6 +273,8 @@ def test_canopy_state_through_the_c_abi(fx, oracle, tables):
     assert all(torch.equal(a[k], b[k]) for k in ("R_TOC", "R_TOA", "L_TOA"))
     with pytest.raises(ValueError):
         eng.run(cols, "float64", canopy_lidf=lidf[:7])
+    with pytest.raises(ValueError):                     # a (27, 1) block with 360 lidf rows: row 0 alone was evaluated
+        eng.run(torch.as_tensor(P[:1].T.copy(), device="cuda:0"), "float64", canopy_lidf=lidf)
     with pytest.raises(ValueError, match="params\\[16\\]"):
         eng.run(cols, "float64")                        # LIDFa missing without a lidf
 

@@ -578,6 +578,9 @@ def test_soilwat_entry_point(oracle, tables, golden):
     assert rel_err(a[:, 0], b[0], 1e-6) < 1e-9 and rel_err(a[:, 0], b0[0], 1e-6) > 1e-4
     with pytest.raises(ValueError, match="nw"):
         soilwat(rdry, op["nw"][:-1], op["Kw"], 30.0, 25, 0.015)
+    from spart_amd import get_engine                   # with rdry only B / lat / lon may be None (they were all read as 0)
+    with pytest.raises(ValueError, match="params\\[12\\]"):
+        get_engine(None, 0).bsm([None] * 6, "float64", rdry=rdry)
 
 
 def test_all_bands_are_evaluated_and_prune_is_equivalent(oracle, tables, torch_mod):
@@ -801,6 +804,18 @@ def test_prepared_call_is_the_same_call(torch_mod):
         eng.prepare(P, "float64", out=out, rho_thermal=0.01)       # host values would be frozen at prepare time: refused
     with pytest.raises(ValueError):
         eng.prepare(P, "float64", out=out, rdry=torch.zeros((B, 2001), dtype=torch.float64, device="cuda:0"))
+    # the call owns its engine: an engine nothing else holds stays alive, with its context, as long as the call
+    import gc
+    import weakref
+    from spart_amd.engine import Engine
+    own = Engine("Sentinel2A-MSI", 0)
+    alive = weakref.ref(own)
+    call = own.prepare(P, "float64", out=out)
+    del own
+    gc.collect()
+    assert alive() is not None
+    call()
+    assert all(torch.equal(out[k], v) for k, v in eng.run(P, "float64").items())
 
 
 def test_lut_generation_streams_chunks(tmp_path, torch_mod):
