@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/spart_hip.h"
@@ -75,7 +76,7 @@ constexpr size_t NEV = 4;        // events per timed spart_run_batch call: 3 sta
 // context cannot garble each other's message
 static thread_local char g_err[512] = {0};
 
-static int fail(const spart_ctx*, int code, const char* fmt, ...) {
+static int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, 512, fmt, ap);
@@ -83,10 +84,10 @@ static int fail(const spart_ctx*, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(ctx, call)                                                                              \
+#define HIP_TRY(call)                                                                                   \
   do {                                                                                                  \
     hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess) return fail(ctx, SPART_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));      \
+    if (e_ != hipSuccess) return fail(SPART_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));           \
   } while (0)
 
 namespace {
@@ -167,7 +168,7 @@ int ws_acquire(spart_ctx* ctx, const char* base, size_t bytes, hipStream_t st, c
     const hipError_t e = hipStreamWaitEvent(st, u.done, 0);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, SPART_ERR_INVALID, "%s: the workspace is in use by a call on another stream and this call cannot be "
+      return fail(SPART_ERR_INVALID, "%s: the workspace is in use by a call on another stream and this call cannot be "
                   "ordered after it (%s): give every stream its own workspace", who, hipGetErrorString(e));
     }
   }
@@ -207,7 +208,7 @@ int ws_release(spart_ctx* ctx, const char* base, size_t bytes, hipStream_t st, c
     WsUse u;
     if (hipEventCreateWithFlags(&u.done, hipEventDisableTiming) != hipSuccess) {
       (void)hipGetLastError();
-      return fail(ctx, SPART_ERR_HIP, "%s: cannot create the workspace completion event", who);
+      return fail(SPART_ERR_HIP, "%s: cannot create the workspace completion event", who);
     }
     ctx->ws_uses.push_back(u);
     slot = &ctx->ws_uses.back();
@@ -217,7 +218,7 @@ int ws_release(spart_ctx* ctx, const char* base, size_t bytes, hipStream_t st, c
   slot->stream = st;
   slot->captured = capturing;
   const hipError_t e = hipEventRecord(slot->done, st);
-  if (e != hipSuccess) return fail(ctx, SPART_ERR_HIP, "%s: recording the workspace completion event: %s", who, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(SPART_ERR_HIP, "%s: recording the workspace completion event: %s", who, hipGetErrorString(e));
   return SPART_OK;
 }
 
@@ -229,6 +230,8 @@ inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 struct Workspace {
   size_t cstf_off, cstd_off, atm_off, bs_off, total;
   int64_t Bp;       // row pitch of the structure-of-arrays blocks (spart_kernels.h)
+  int chunk;        // samples per workgroup of the band kernels (pick_chunk) ...
+  int64_t nchunk;   // ... and the number of chunks: rows of the band-sum block
 };
 
 // the band kernels address a chunk's rows with a 32-bit byte offset per lane
@@ -255,6 +258,8 @@ Workspace carve(int dtype, int64_t B) {
   size_t es = dtype == SPART_F64 ? 8 : 4;
   Workspace w;
   w.Bp = row_pitch_of(B);
+  w.chunk = pick_chunk(B);
+  w.nchunk = (B + w.chunk - 1) / w.chunk;
   const size_t Bp = (size_t)w.Bp;
   size_t o = 0;
   // float32 constants only in the float32 modes; the float64 constants are there in both (the default float32 mode's
@@ -262,116 +267,80 @@ Workspace carve(int dtype, int64_t B) {
   w.cstf_off = o; o = align_up(o + Bp * NCONST * 4);     // (float64 calls use it with spart_materialize.f32_bands)
   w.cstd_off = o; o = align_up(o + Bp * NCONST * 8);
   w.atm_off = o;  o = align_up(o + Bp * NATM * 8);
-  int chunk = pick_chunk(B);
-  size_t nchunk = (size_t)((B + chunk - 1) / chunk);
-  w.bs_off = o;  o = align_up(o + nchunk * (size_t)(NTILE * TILE) * 4 * es);
+  w.bs_off = o;  o = align_up(o + (size_t)w.nchunk * (size_t)(NTILE * TILE) * 4 * es);
   w.total = o;
   return w;
 }
 
-template <typename T> int upload(const spart_ctx* ctx, T** dst, const std::vector<T>& src) {
-  HIP_TRY(ctx, hipMalloc((void**)dst, src.size() * sizeof(T)));
-  HIP_TRY(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+// the constants block of dtype T in a call's workspace, and the context's table of that dtype
+template <typename T> T* constants(char* wsp, const Workspace& ws) { return (T*)(wsp + (sizeof(T) == 4 ? ws.cstf_off : ws.cstd_off)); }
+template <typename T> const T* table(const spart_ctx* ctx) { return sizeof(T) == 4 ? (const T*)ctx->tabF : (const T*)ctx->tabD; }
+
+template <typename T> int upload(T** dst, const std::vector<T>& src) {
+  HIP_TRY(hipMalloc((void**)dst, src.size() * sizeof(T)));
+  HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
   return SPART_OK;
 }
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
+template <typename F> void with_flag(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The compiled variants of a kernel family: one list per family, in ascending order.  with(v, f) calls
+// f(std::integral_constant<int, v>{}) and returns true if v is in the list; a value the list lacks launches nothing and
+// the caller fails the call.
+template <int... V> struct Variants {
+  template <typename F> static bool with(int v, F&& f) { return ((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
+  // the smallest variant >= need (the largest if none is)
+  static constexpr int at_least(int need) {
+    int r = 0;
+    for (int v : {V...})
+      if ((r = v) >= need) break;
+    return r;
+  }
+};
 
 // fast: Newton LIDF / 8-point hot-spot rule (legacy float32 columns and the float32 stage-level entry points)
-int launch_prelude(spart_ctx* ctx, bool fast, const ParamPtrs& pp, int mask, int64_t B, int64_t Bp, float* cstF,
-                   double* cstD, double* atm, hipStream_t st) {
-  unsigned grid = (unsigned)((B + 255) / 256);
+int launch_prelude(bool fast, ParamPtrs pp, int mask, int64_t B, int64_t Bp, float* cstF, double* cstD, double* atm,
+                   hipStream_t st) {
   const bool user = pp.lidf != nullptr || (pp.nlayers > 0 && pp.nlayers != NLAYER);   // canopy state of the caller's own
-  if (user) {
-    ParamPtrs pu = pp;
-    if (pu.nlayers <= 0) pu.nlayers = NLAYER;
-    if (fast) hipLaunchKernelGGL((k_prelude<true, true>), dim3(grid), dim3(256), 0, st, pu, mask, B, Bp, cstF, cstD, atm);
-    else hipLaunchKernelGGL((k_prelude<false, true>), dim3(grid), dim3(256), 0, st, pu, mask, B, Bp, cstF, cstD, atm);
-  } else if (fast) hipLaunchKernelGGL((k_prelude<true>), dim3(grid), dim3(256), 0, st, pp, mask, B, Bp, cstF, cstD, atm);
-  else hipLaunchKernelGGL((k_prelude<false>), dim3(grid), dim3(256), 0, st, pp, mask, B, Bp, cstF, cstD, atm);
-  HIP_TRY(ctx, hipGetLastError());
+  if (user && pp.nlayers <= 0) pp.nlayers = NLAYER;
+  with_flag(fast, [&](auto F) {
+    with_flag(user, [&](auto U) {
+      hipLaunchKernelGGL((k_prelude<F, U>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, pp, mask, B, Bp, cstF, cstD, atm);
+    });
+  });
+  HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
 
-// the stage-level entry points: constants in the call's dtype
-template <typename T> T* stage_cst(char* wsp, const Workspace& ws) { return (T*)(wsp + (sizeof(T) == 4 ? ws.cstf_off : ws.cstd_off)); }
-template <typename T>
-int launch_stage_prelude(spart_ctx* ctx, const ParamPtrs& pp, int mask, int64_t B, char* wsp, const Workspace& ws, hipStream_t st) {
-  return launch_prelude(ctx, sizeof(T) == 4, pp, mask, B, ws.Bp, sizeof(T) == 4 ? (float*)(wsp + ws.cstf_off) : nullptr,
-                        sizeof(T) == 8 ? (double*)(wsp + ws.cstd_off) : nullptr, nullptr, st);
+// a stage call's parameter columns: params[first + i] = p[i], every other pointer NULL
+ParamPtrs param_slice(int first, const double* const* p, int n) {
+  ParamPtrs pp;
+  std::memset(&pp, 0, sizeof(pp));
+  for (int i = 0; i < n; ++i) pp.p[first + i] = p[i];
+  return pp;
+}
+
+// The full-band kernel k_bands<T, MAT, FULL, NT>.  MAT: 0 no spectra stored, 1 materialised spectra, 2 the same with the
+// caller's dry-soil spectra.  FULL: 0 pruned (the stored spectra only), 1 band sums, 2 four band sums.  MAT = FULL = 0
+// would do nothing and is not compiled; NT (non-temporal row stores) exists for MAT != 0 only, MAT = 0 stores no rows.
+// float MAT = 0, the headline's dominant kernel, is compiled in its own translation unit with its own scheduling strategy
+// (spart_bands_f32.hip, build.py: TU_FLAGS).
+using BandsMat = Variants<0, 1, 2>;
+template <int MAT> using BandsFull = std::conditional_t<MAT == 0, Variants<1, 2>, Variants<0, 1, 2>>;
+template <typename T, int MAT, int FULL>
+hipError_t launch_bands(bool nt, dim3 grid, hipStream_t st, const T* tab, const T* cst, int64_t Bp, int64_t B, int chunk,
+                        const MatPtrs<T>& mp, T* bsum) {
+  if constexpr (MAT == 0 && sizeof(T) == 4)
+    return launch_bands_f32(FULL, grid.x, st, tab, cst, Bp, B, chunk, bsum);
+  else if constexpr (MAT == 0)
+    hipLaunchKernelGGL((k_bands<T, 0, FULL, false>), grid, dim3(TILE), 0, st, tab, cst, Bp, B, chunk, mp, bsum);
+  else
+    with_flag(nt, [&](auto NT) { hipLaunchKernelGGL((k_bands<T, MAT, FULL, NT>), grid, dim3(TILE), 0, st, tab, cst, Bp, B, chunk, mp, bsum); });
+  return hipGetLastError();
 }
 
 }  // namespace
-
-template <typename T>
-static int prospect_impl(spart_ctx* ctx, int64_t B, const double* const leaf[9], void* refl, void* tran, void* kchl,
-                         char* wsp, const Workspace& ws, hipStream_t st) {
-  ParamPtrs pp;
-  std::memset(&pp, 0, sizeof(pp));
-  for (int i = 0; i < 9; ++i) pp.p[i] = leaf[i];
-  T* cst = stage_cst<T>(wsp, ws);
-  int rc = launch_stage_prelude<T>(ctx, pp, PRE_LEAF, B, wsp, ws, st);
-  if (rc) return rc;
-  int chunk = pick_chunk(B);
-  int64_t nchunk = (B + chunk - 1) / chunk;
-  const T* tab = sizeof(T) == 4 ? (const T*)ctx->tabF : (const T*)ctx->tabD;
-  if (!chunk_fits_32bit(chunk, ctx->po, sizeof(T))) return fail(ctx, SPART_ERR_INVALID, "batch too large for one call");
-  if (nt_ok(ctx->po, sizeof(T)))
-    hipLaunchKernelGGL((k_prospect<T, true>), dim3(xcd_grid(nchunk)), dim3(TILE), 0, st, tab, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->po, (T*)refl, (T*)tran, (T*)kchl);
-  else
-    hipLaunchKernelGGL((k_prospect<T, false>), dim3(xcd_grid(nchunk)), dim3(TILE), 0, st, tab, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->po, (T*)refl, (T*)tran, (T*)kchl);
-  HIP_TRY(ctx, hipGetLastError());
-  return SPART_OK;
-}
-
-template <typename T>
-static int bsm_impl(spart_ctx* ctx, int64_t B, const double* const soil[6], const void* rdry_in, void* refl, void* dry,
-                    char* wsp, const Workspace& ws, hipStream_t st) {
-  ParamPtrs pp;
-  std::memset(&pp, 0, sizeof(pp));
-  for (int i = 0; i < 6; ++i) pp.p[9 + i] = soil[i];
-  T* cst = stage_cst<T>(wsp, ws);
-  int rc = launch_stage_prelude<T>(ctx, pp, PRE_SOIL, B, wsp, ws, st);
-  if (rc) return rc;
-  int chunk = pick_chunk(B);
-  int64_t nchunk = (B + chunk - 1) / chunk;
-  const T* tab = sizeof(T) == 4 ? (const T*)ctx->tabF : (const T*)ctx->tabD;
-  if (!chunk_fits_32bit(chunk, ctx->po, sizeof(T))) return fail(ctx, SPART_ERR_INVALID, "batch too large for one call");
-  if (nt_ok(ctx->po, sizeof(T)))
-    hipLaunchKernelGGL((k_bsm<T, true>), dim3(xcd_grid(nchunk)), dim3(TILE), 0, st, tab, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->po, (const T*)rdry_in, (T*)refl, (T*)dry);
-  else
-    hipLaunchKernelGGL((k_bsm<T, false>), dim3(xcd_grid(nchunk)), dim3(TILE), 0, st, tab, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->po, (const T*)rdry_in, (T*)refl, (T*)dry);
-  HIP_TRY(ctx, hipGetLastError());
-  return SPART_OK;
-}
-
-template <typename T>
-static int sailh_impl(spart_ctx* ctx, int64_t B, const void* rho, const void* tau, const void* rs,
-                      const double* const canopy[4], const double* const angles[3], const double* lidf_in, int nlayers,
-                      void* const out4[4], char* wsp, const Workspace& ws, hipStream_t st) {
-  ParamPtrs pp;
-  std::memset(&pp, 0, sizeof(pp));
-  for (int i = 0; i < 4; ++i) pp.p[15 + i] = canopy[i];
-  for (int i = 0; i < 3; ++i) pp.p[19 + i] = angles[i];
-  pp.lidf = lidf_in;
-  pp.nlayers = nlayers;
-  T* cst = stage_cst<T>(wsp, ws);
-  int rc = launch_stage_prelude<T>(ctx, pp, PRE_CANOPY, B, wsp, ws, st);
-  if (rc) return rc;
-  int chunk = pick_chunk(B);
-  int64_t nchunk = (B + chunk - 1) / chunk;
-  if (!chunk_fits_32bit(chunk, ctx->pf, sizeof(T))) return fail(ctx, SPART_ERR_INVALID, "batch too large for one call");
-  if (nt_ok(ctx->pf, sizeof(T)))
-    hipLaunchKernelGGL((k_sailh<T, true>), dim3((unsigned)(nchunk * NTILE_FULL)), dim3(TILE), 0, st, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->pf, (const T*)rho, (const T*)tau, (const T*)rs, (T*)out4[0], (T*)out4[1], (T*)out4[2], (T*)out4[3]);
-  else
-    hipLaunchKernelGGL((k_sailh<T, false>), dim3((unsigned)(nchunk * NTILE_FULL)), dim3(TILE), 0, st, (const T*)cst, ws.Bp, B, chunk,
-                       ctx->pf, (const T*)rho, (const T*)tau, (const T*)rs, (T*)out4[0], (T*)out4[1], (T*)out4[2], (T*)out4[3]);
-  HIP_TRY(ctx, hipGetLastError());
-  return SPART_OK;
-}
 
 // T = dtype of the full-band kernel (band sums, materialised spectra); TG = dtype of the column path: the prelude's
 // constants and the canopy model inside the column kernel (double, except spart_materialize.f32_columns); TO = dtype
@@ -383,21 +352,16 @@ template <typename T, typename TG, typename TO = T>
 static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_NPARAM], const double* rho_th,
                     const double* tau_th, void* R_TOC, void* R_TOA, void* L_TOA, const spart_materialize* opt, char* wsp,
                     const Workspace& ws, hipStream_t st) {
-  ParamPtrs pp;
-  for (int i = 0; i < NPARAM; ++i) pp.p[i] = params[i];
+  ParamPtrs pp = param_slice(0, params, NPARAM);
   pp.rho_th = rho_th;
   pp.tau_th = tau_th;
   pp.lidf = opt ? opt->lidf_in : nullptr;        // canopy.lidf / canopy.nlayers as the caller set them (sailh.py:48, 51)
   pp.nlayers = opt ? opt->nlayers : 0;
   const int64_t Bp = ws.Bp;
-  float* cstF = (float*)(wsp + ws.cstf_off);
-  double* cstD = (double*)(wsp + ws.cstd_off);
-  const T* cst = sizeof(T) == 4 ? (const T*)cstF : (const T*)cstD;       // the full-band kernel's constants
-  const TG* cstG = sizeof(TG) == 4 ? (const TG*)cstF : (const TG*)cstD;  // the column kernel's constants
+  float* cstF = constants<float>(wsp, ws);
+  double* cstD = constants<double>(wsp, ws);
   double* atm = (double*)(wsp + ws.atm_off);
   // ---- everything that can fail on its arguments is checked BEFORE any launch (and before the side stream is forked)
-  int chunk = pick_chunk(B);
-  int64_t nchunk = (B + chunk - 1) / chunk;
   MatPtrs<T> mp;
   std::memset(&mp, 0, sizeof(mp));
   mp.pf = ctx->pf; mp.po = ctx->po;
@@ -410,46 +374,44 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
     mp.rdry_in = (const T*)opt->rdry_in;
     mat = mp.leaf_refl || mp.leaf_tran || mp.leaf_kchl || mp.soil_refl || mp.soil_dry || mp.rso || mp.rdo || mp.rsd || mp.rdd;
   }
-  if ((mat || mp.rdry_in) && !chunk_fits_32bit(chunk, ctx->pf, sizeof(T)))
-    return fail(ctx, SPART_ERR_INVALID, "batch too large for materialised spectra in one call (chunk %d rows x pitch %d)", chunk, ctx->pf);
+  if ((mat || mp.rdry_in) && !chunk_fits_32bit(ws.chunk, ctx->pf, sizeof(T)))
+    return fail(SPART_ERR_INVALID, "batch too large for materialised spectra in one call (chunk %d rows x pitch %d)", ws.chunk, ctx->pf);
   const bool full = !(opt && opt->prune_unused_bands);
   if (opt && opt->band_mean && !full)
-    return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: band_mean needs prune_unused_bands = 0");
+    return fail(SPART_ERR_INVALID, "spart_run_batch: band_mean needs prune_unused_bands = 0");
   int rc;
   // optional per-stage timing: four events per call (before the prelude, after the prelude, after the full-band kernel,
   // after the column kernel)
   const bool prof = ctx->profile && ctx->ev_used + NEV <= ctx->ev.size();
   hipEvent_t* ev = prof ? &ctx->ev[ctx->ev_used] : nullptr;
-  if (prof) HIP_TRY(ctx, hipEventRecord(ev[0], st));
+  if (prof) HIP_TRY(hipEventRecord(ev[0], st));
   const bool four = opt && opt->band_mean;     // the four band sums are only kept apart when their means are asked for
   const bool bands = mat || full;              // the full-band kernel runs (otherwise: pruned, column kernel only)
   {
     Range r("SPART prelude (geometry, LIDF, hot spot, soil factors)");
     // legacy float32 columns (TG = float): the fast prelude; otherwise the literal one.  cstF only when a float32
     // full-band kernel (or the float32 column kernel) will read it.
-    rc = launch_prelude(ctx, sizeof(TG) == 4 || (opt && opt->fast_prelude), pp, PRE_ALL, B, Bp, (sizeof(TG) == 4 || (sizeof(T) == 4 && bands)) ? cstF : nullptr,
+    rc = launch_prelude(sizeof(TG) == 4 || (opt && opt->fast_prelude), pp, PRE_ALL, B, Bp, (sizeof(TG) == 4 || (sizeof(T) == 4 && bands)) ? cstF : nullptr,
                         sizeof(TG) == 8 ? cstD : nullptr, atm, st);
   }
   if (rc) return rc;
   Range rb("SPART bands + sensor (BSM, PROSPECT, SAILH | interp, SMAC, TOC->TOA)");
-  const T* tab = sizeof(T) == 4 ? (const T*)ctx->tabF : (const T*)ctx->tabD;
-  const TG* tabG = sizeof(TG) == 4 ? (const TG*)ctx->tabF : (const TG*)ctx->tabD;
-  dim3 grid(xcd_grid(nchunk));
   T* bsum = (T*)(wsp + ws.bs_off);
-  if (prof) HIP_TRY(ctx, hipEventRecord(ev[1], st));
+  if (prof) HIP_TRY(hipEventRecord(ev[1], st));
   // The columns do not depend on the full-band kernel, so the column kernel runs on the context's side stream BESIDE it
   // and fills issue slots it leaves idle; the caller's stream waits for it at the end.
   SideLane* lane = bands ? lane_for(ctx, st) : nullptr;
   const bool fork = lane != nullptr;
   hipStream_t s2 = fork ? lane->side : st;
   auto columns = [&]() -> int {                // the column kernel, on s2
-    hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, s2, tabG, cstG,
+    hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, s2, table<TG>(ctx),
+                       (const TG*)constants<TG>(wsp, ws),
                        (const double*)atm, Bp, (const int*)ctx->band0, (const int*)ctx->band1, (const double*)ctx->frac,
                        (const double*)ctx->coef, (const double*)ctx->econv, ctx->nb,
                        (const TO*)(opt ? opt->rdry_in : nullptr), ctx->po, B, (TO*)R_TOC,
                        (TO*)R_TOA, (TO*)L_TOA, (TO*)(opt ? opt->rsoil : nullptr), (TO*)(opt ? opt->La : nullptr));
-    HIP_TRY(ctx, hipGetLastError());
-    if (prof) HIP_TRY(ctx, hipEventRecord(ev[3], s2));
+    HIP_TRY(hipGetLastError());
+    if (prof) HIP_TRY(hipEventRecord(ev[3], s2));
     return SPART_OK;
   };
   auto band_kernels = [&]() -> int {           // the full-band kernel (+ the batch-mean reduction), on the caller's stream
@@ -457,37 +419,31 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
     // as the columns (with M = 0 the kernel would mix the GSV soil from params[9..11], which may be NULL with rdry_in)
     const int M = mp.rdry_in ? 2 : (mat ? 1 : 0);
     const int F = !full ? 0 : (four ? 2 : 1);
-#define SPART_CASE(MM, FF)                                                                                                      \
-  if (M == (MM) && F == (FF)) {                                                                                                 \
-    if ((MM) != 0 && nt) hipLaunchKernelGGL((k_bands<T, MM, FF, (MM) != 0>), grid, dim3(TILE), 0, st, tab, cst, Bp, B, chunk, mp, bsum); \
-    else hipLaunchKernelGGL((k_bands<T, MM, FF, false>), grid, dim3(TILE), 0, st, tab, cst, Bp, B, chunk, mp, bsum);            \
-  }
-    if constexpr (sizeof(T) == 4) {
-      // the float32 kernels WITHOUT materialised spectra (the headline's dominant kernel) are compiled in their own
-      // translation unit with their own scheduling strategy (spart_bands_f32.hip, build.py: TU_FLAGS)
-      if (M == 0) HIP_TRY(ctx, launch_bands_f32(F, grid.x, st, (const float*)tab, (const float*)cst, Bp, B, chunk, (float*)bsum));
-    } else {
-      SPART_CASE(0, 1) SPART_CASE(0, 2)
-    }
-    SPART_CASE(1, 0) SPART_CASE(1, 1) SPART_CASE(1, 2) SPART_CASE(2, 0) SPART_CASE(2, 1) SPART_CASE(2, 2)
-#undef SPART_CASE
-    HIP_TRY(ctx, hipGetLastError());
-    if (prof) HIP_TRY(ctx, hipEventRecord(ev[2], st));
+    hipError_t e = hipSuccess;
+    bool compiled = false;
+    BandsMat::with(M, [&](auto MM) {
+      compiled = BandsFull<MM>::with(F, [&](auto FF) {
+        e = launch_bands<T, MM, FF>(nt, dim3(xcd_grid(ws.nchunk)), st, table<T>(ctx), constants<T>(wsp, ws), Bp, B, ws.chunk, mp, bsum);
+      });
+    });
+    if (!compiled) return fail(SPART_ERR_INVALID, "spart_run_batch: no k_bands variant for MAT = %d, FULL = %d", M, F);
+    if (e != hipSuccess) return fail(SPART_ERR_HIP, "spart_run_batch: k_bands<MAT = %d, FULL = %d>: %s", M, F, hipGetErrorString(e));
+    if (prof) HIP_TRY(hipEventRecord(ev[2], st));
     if (opt && opt->band_mean) {
-      hipLaunchKernelGGL((k_bandmean<T>), dim3((4 * NWLS + 255) / 256), dim3(256), 0, st, (const T*)bsum, nchunk, B,
+      hipLaunchKernelGGL((k_bandmean<T>), dim3((4 * NWLS + 255) / 256), dim3(256), 0, st, (const T*)bsum, ws.nchunk, B,
                          (T*)opt->band_mean);
-      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
     return SPART_OK;
   };
   if (!bands) {                                // pruned: the column path alone
-    if (prof) HIP_TRY(ctx, hipEventRecord(ev[2], st));
+    if (prof) HIP_TRY(hipEventRecord(ev[2], st));
     rc = columns();
   } else if (!fork) {
     if ((rc = band_kernels()) == SPART_OK) rc = columns();
   } else {                                     // side stream first: its kernels are queued before the 65k workgroups of k_bands
-    HIP_TRY(ctx, hipEventRecord(lane->fork, st));
-    HIP_TRY(ctx, hipStreamWaitEvent(lane->side, lane->fork, 0));
+    HIP_TRY(hipEventRecord(lane->fork, st));
+    HIP_TRY(hipStreamWaitEvent(lane->side, lane->fork, 0));
     rc = columns();
     const int rc2 = band_kernels();
     // whatever happened after the fork, the caller's stream is ordered after the side stream's work again (and a HIP-graph
@@ -495,7 +451,7 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
     const hipError_t ej = hipEventRecord(lane->join, lane->side);
     const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(st, lane->join, 0) : ej;
     if (rc == SPART_OK) rc = rc2;
-    if (rc == SPART_OK && ew != hipSuccess) rc = fail(ctx, SPART_ERR_HIP, "spart_run_batch: joining the side stream: %s", hipGetErrorString(ew));
+    if (rc == SPART_OK && ew != hipSuccess) rc = fail(SPART_ERR_HIP, "spart_run_batch: joining the side stream: %s", hipGetErrorString(ew));
   }
   if (rc) return rc;
   if (prof) {
@@ -508,19 +464,10 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
 // ---- LUT inversion (csrc/spart_lut.h): GEMM + argmin on the matrix cores as a filter, exact direct evaluation of every
 // candidate, brute-force fallback.  float32: K steps of 2 (v_mfma_f32_32x32x2_f32), KS = ceil((nb + 1) / 2) MFMAs per
 // 32 x 32 comparisons, rounded up to one of the compiled variants; float64: K steps of 4 (v_mfma_f64_16x16x4_f64).
-static int lut_ks(int nb) {
-  const int need = (nb + 2) / 2;
-  for (int ks : {4, 7, 8, 11, 16})
-    if (ks >= need) return ks;
-  return 16;
-}
-static int lut_ks64(int nb) {
-  const int need = (nb + 4) / 4;                      // ceil((nb + 1) / 4)
-  for (int ks : {2, 4, 6, 8})
-    if (ks >= need) return ks;
-  return 8;
-}
-static int lut_to64(int ks) { return ks <= 4 ? 8 : 4; }     // 16-observation blocks per wave (operand registers: 2 KS TO)
+using LutKs = Variants<4, 7, 8, 11, 16>;           // k_lut_prep<float, KS, 32>, k_lut_scan_mfma<KS>
+using LutKs64 = Variants<2, 4, 6, 8>;              // k_lut_prep<double, KS, 16>, k_lut_scan_mfma64<KS, lut_to64(KS)>
+using LutFallback = Variants<4, 8, 12, 16, 20, 24, 28, 32>;   // k_lut_fallback<T, N>: N = nb rounded up to a multiple of 4
+static constexpr int lut_to64(int ks) { return ks <= 4 ? 8 : 4; }     // 16-observation blocks per wave (operand registers: 2 KS TO)
 // workgroups = ceil(M / obs per workgroup) x nslice; slices are whole tiles
 static int lut_slices(int64_t M, int64_t ntile, int obs_per_wg) {
   const int64_t mg = (M + obs_per_wg - 1) / obs_per_wg;
@@ -540,9 +487,9 @@ static LutLayout lut_layout(int dtype, int64_t B, int nb, int64_t M) {
   LutLayout L;
   const size_t es = dtype == SPART_F64 ? 8 : 4;
   if (dtype == SPART_F32) {
-    L.rows = 32; L.ks = lut_ks(nb); L.to = LUT_TO; L.kfma = 2 * L.ks;
+    L.rows = 32; L.ks = LutKs::at_least((nb + 2) / 2); L.to = LUT_TO; L.kfma = 2 * L.ks;
   } else {
-    L.rows = 16; L.ks = lut_ks64(nb); L.to = lut_to64(L.ks); L.kfma = 4 * L.ks;
+    L.rows = 16; L.ks = LutKs64::at_least((nb + 4) / 4); L.to = lut_to64(L.ks); L.kfma = 4 * L.ks;      // ceil((nb + 1) / 4)
   }
   L.ntile = (B + L.rows - 1) / L.rows;
   L.nslice = lut_slices(M, L.ntile, L.rows * L.to * 4);
@@ -582,70 +529,115 @@ static int lut_impl(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lu
   T* fbc = (T*)(wsp + L.fbc);
   int64_t* fbi = (int64_t*)(wsp + L.fbi);
   hipLaunchKernelGGL((k_lut_centre<T>), dim3(nb), dim3(256), 0, st, lut, nb, B, centre, ctl);
-  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(hipGetLastError());
   const dim3 gprep((unsigned)((L.ntile * L.rows + 255) / 256));
   const dim3 grid((unsigned)((M + L.rows * L.to * 4 - 1) / (L.rows * L.to * 4)), (unsigned)L.nslice);
-  if constexpr (sizeof(T) == 4) {
-#define SPART_LUT_KS(K)                                                                                                   \
-  case K:                                                                                                                  \
-    hipLaunchKernelGGL((k_lut_prep<float, K, 32>), gprep, dim3(256), 0, st, lut, w, (const float*)centre, nb, B, L.ntile,  \
-                       tiles, ctl);                                                                                        \
-    hipLaunchKernelGGL((k_lut_scan_mfma<K>), grid, dim3(256), 0, st, (const float*)tiles, obs, w, (const float*)centre,    \
-                       nb, L.ntile, M, L.nslice, pc, ps, pt);                                                              \
-    break;
-    switch (L.ks) { SPART_LUT_KS(4) SPART_LUT_KS(7) SPART_LUT_KS(8) SPART_LUT_KS(11) SPART_LUT_KS(16) }
-#undef SPART_LUT_KS
-  } else {
-#define SPART_LUT_KS(K, TO)                                                                                               \
-  case K:                                                                                                                  \
-    hipLaunchKernelGGL((k_lut_prep<double, K, 16>), gprep, dim3(256), 0, st, lut, w, (const double*)centre, nb, B,         \
-                       L.ntile, tiles, ctl);                                                                               \
-    hipLaunchKernelGGL((k_lut_scan_mfma64<K, TO>), grid, dim3(256), 0, st, (const double*)tiles, obs, w,                   \
-                       (const double*)centre, nb, L.ntile, M, L.nslice, pc, ps, pt);                                       \
-    break;
-    switch (L.ks) { SPART_LUT_KS(2, 8) SPART_LUT_KS(4, 8) SPART_LUT_KS(6, 4) SPART_LUT_KS(8, 4) }
-#undef SPART_LUT_KS
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  bool compiled;
+  if constexpr (sizeof(T) == 4)
+    compiled = LutKs::with(L.ks, [&](auto K) {
+      hipLaunchKernelGGL((k_lut_prep<float, K, 32>), gprep, dim3(256), 0, st, lut, w, (const float*)centre, nb, B, L.ntile, tiles, ctl);
+      hipLaunchKernelGGL((k_lut_scan_mfma<K>), grid, dim3(256), 0, st, (const float*)tiles, obs, w, (const float*)centre, nb, L.ntile,
+                         M, L.nslice, pc, ps, pt);
+    });
+  else
+    compiled = LutKs64::with(L.ks, [&](auto K) {
+      hipLaunchKernelGGL((k_lut_prep<double, K, 16>), gprep, dim3(256), 0, st, lut, w, (const double*)centre, nb, B, L.ntile, tiles, ctl);
+      hipLaunchKernelGGL((k_lut_scan_mfma64<K, lut_to64(K)>), grid, dim3(256), 0, st, (const double*)tiles, obs, w,
+                         (const double*)centre, nb, L.ntile, M, L.nslice, pc, ps, pt);
+    });
+  if (!compiled) return fail(SPART_ERR_INVALID, "spart_lut_nearest: no compiled LUT scan for KS = %d", L.ks);
+  HIP_TRY(hipGetLastError());
   const T coef_ef = (T)lut_coef_ef(nb, L.kfma, (double)LutNum<T>::u), coef_e = (T)lut_coef_e(nb, L.kfma, (double)LutNum<T>::u);
   const dim3 gobs((unsigned)((M + 3) / 4));                // one wave per observation
   hipLaunchKernelGGL((k_lut_reduce_exact<T, (sizeof(T) == 4 ? 32 : 16)>), gobs, dim3(256), 0, st, (const T*)pc, (const T*)ps,
                      (const int*)pt, (const T*)tiles, L.ks, lut, obs, w, (const T*)centre, nb, B, M, L.npart, coef_e, coef_ef, ctl,
                      flags, best_idx, (T*)best_cost);
-  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(hipGetLastError());
   // the flagged observations (normally a handful, possibly all of them for degenerate data): the grid is fixed, the
   // kernels read the count on the device, so the call stays asynchronous and graph-capturable
   const int nbc = (nb + 3) / 4 * 4;
   const size_t fb_lds = (size_t)4 * LUT_FB_ROWS * nbc * sizeof(T);
-#define SPART_LUT_FB(N)                                                                                                   \
-  case N:                                                                                                                  \
-    hipLaunchKernelGGL((k_lut_fallback<T, N>), dim3(LUT_FB_BLOCKS), dim3(256), fb_lds, st, lut, obs, w, nb, B,             \
-                       (const unsigned long long*)ctl, (const int*)flags, fbc, fbi);                                       \
-    break;
-  switch (nbc) {
-    SPART_LUT_FB(4) SPART_LUT_FB(8) SPART_LUT_FB(12) SPART_LUT_FB(16) SPART_LUT_FB(20) SPART_LUT_FB(24) SPART_LUT_FB(28) SPART_LUT_FB(32)
-  }
-#undef SPART_LUT_FB
-  HIP_TRY(ctx, hipGetLastError());
+  if (!LutFallback::with(nbc, [&](auto N) {
+        hipLaunchKernelGGL((k_lut_fallback<T, N>), dim3(LUT_FB_BLOCKS), dim3(256), fb_lds, st, lut, obs, w, nb, B,
+                           (const unsigned long long*)ctl, (const int*)flags, fbc, fbi);
+      }))
+    return fail(SPART_ERR_INVALID, "spart_lut_nearest: no compiled LUT fallback for %d bands", nbc);
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL((k_lut_fallback_merge<T>), dim3(256), dim3(256), 0, st, B, LUT_FB_BLOCKS * 4, (const unsigned long long*)ctl,
                      (const int*)flags, (const T*)fbc, (const int64_t*)fbi, best_idx, (T*)best_cost);
-  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
 
-// lock the context, order the call after other streams' use of the workspace, run `body` (the launches), record the
-// workspace's completion event -- also after a failed body: some of its kernels may already be queued
+// The checks every batched entry point but spart_lut_nearest starts with, in this order.  B == 0 passes them: the caller
+// has nothing to do.  Otherwise `ws` is the layout of the call's workspace.
+static int gate(const spart_ctx* ctx, const char* who, int dtype, int64_t B, const void* workspace, size_t workspace_bytes,
+                Workspace& ws) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (B > SPART_MAX_BATCH) return fail(SPART_ERR_INVALID, "%s: at most %lld samples per call", who, (long long)SPART_MAX_BATCH);
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  if (B < 0) return fail(SPART_ERR_INVALID, "%s: negative batch", who);
+  if (B == 0) return SPART_OK;
+  ws = carve(dtype, B);
+  if (!workspace || workspace_bytes < ws.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, ws.total, workspace_bytes);
+  return SPART_OK;
+}
+
+// Which parameter columns may be NULL (the counterpart of spart_amd.engine.NULLABLE): B, lat, lon (params 9-11) with user
+// dry-soil spectra, LIDFa, LIDFb (16, 17) with a given lidf.  The soil of spart_bsm_batch is params 9-14, the canopy of
+// spart_sailh_batch params 15-18.
+static bool may_be_null(int param, bool rdry, bool lidf) {
+  return (rdry && param >= 9 && param <= 11) || (lidf && (param == 16 || param == 17));
+}
+// the index of the first NULL pointer of p[0 .. n), or n
+template <typename P> static int first_null(const P* p, int n) {
+  int i = 0;
+  while (i < n && p[i]) ++i;
+  return i;
+}
+
+// f(float{}) or f(double{}) for a call's dtype
+template <typename F> static int by_dtype(int dtype, F&& f) { return dtype == SPART_F32 ? f(float{}) : f(double{}); }
+
+// select the context's device, lock the context, order the call after other streams' use of the workspace, run
+// body(stream) (the launches), record the workspace's completion event -- also after a failed body: some of its kernels
+// may already be queued
 template <typename F>
-static int guarded(spart_ctx* ctx, const char* who, const void* wsp, size_t bytes, hipStream_t st, F&& body) {
+static int guarded(spart_ctx* ctx, const char* who, const void* wsp, size_t bytes, void* stream, F&& body) {
+  DeviceGuard guard(ctx->device);
+  const hipStream_t st = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(ctx->mu);
   int rc = ws_acquire(ctx, (const char*)wsp, bytes, st, who);
   if (rc) return rc;
-  rc = body();
+  rc = body(st);
   char keep[512];
   if (rc) std::snprintf(keep, sizeof(keep), "%s", g_err);
   const int rc2 = ws_release(ctx, (const char*)wsp, bytes, st, who);
   if (rc) std::snprintf(g_err, sizeof(g_err), "%s", keep);
   return rc ? rc : rc2;
+}
+
+// A stage-level call (spart_prospect_batch, _bsm_, _sailh_) once its arguments are checked: the 32-bit row offsets of a
+// chunk at `pitch` are checked, the prelude writes the `mask` part of the constants in the call's dtype T, then
+// launch(T{}, nt, st, tab, cst) queues the stage's own kernel (nt: std::true_type when the rows at `pitch` lie on the
+// 128-byte lines, the stores' NT).
+template <typename L>
+static int stage_call(spart_ctx* ctx, const char* who, int dtype, int64_t B, const ParamPtrs& pp, int mask, int pitch,
+                      void* workspace, const Workspace& ws, void* stream, L&& launch) {
+  return guarded(ctx, who, workspace, ws.total, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      if (!chunk_fits_32bit(ws.chunk, pitch, sizeof(T))) return fail(SPART_ERR_INVALID, "batch too large for one call");
+      T* cst = constants<T>((char*)workspace, ws);
+      int rc = launch_prelude(sizeof(T) == 4, pp, mask, B, ws.Bp, sizeof(T) == 4 ? (float*)cst : nullptr,
+                              sizeof(T) == 8 ? (double*)cst : nullptr, nullptr, st);
+      if (rc) return rc;
+      with_flag(nt_ok(pitch, sizeof(T)), [&](auto nt) { launch(t, nt, st, table<T>(ctx), (const T*)cst); });
+      HIP_TRY(hipGetLastError());
+      return SPART_OK;
+    });
+  });
 }
 
 #ifndef SPART_BUILD_ID
@@ -665,11 +657,11 @@ const char* spart_last_error(const spart_ctx*) { return g_err; }
 int spart_ctx_nb(const spart_ctx* ctx) { return ctx ? ctx->nb : 0; }
 
 int spart_ctx_set_row_pitch(spart_ctx* ctx, int64_t pitch_full, int64_t pitch_optical) {
-  if (!ctx) return fail(ctx, SPART_ERR_INVALID, "spart_ctx_set_row_pitch: null context");
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_ctx_set_row_pitch: null context");
   if (pitch_full == 0) pitch_full = NWLS;
   if (pitch_optical == 0) pitch_optical = NWL;
   if (pitch_full < NWLS || pitch_optical < NWL || pitch_full > (1 << 20) || pitch_optical > (1 << 20))
-    return fail(ctx, SPART_ERR_INVALID, "row pitch must be >= the row width (%d / %d elements)", NWLS, NWL);
+    return fail(SPART_ERR_INVALID, "row pitch must be >= the row width (%d / %d elements)", NWLS, NWL);
   std::lock_guard<std::mutex> lock(ctx->mu);
   ctx->pf = (int)pitch_full;
   ctx->po = (int)pitch_optical;
@@ -677,8 +669,8 @@ int spart_ctx_set_row_pitch(spart_ctx* ctx, int64_t pitch_full, int64_t pitch_op
 }
 
 int spart_ctx_econv(const spart_ctx* ctx, double* host_out) {
-  if (!ctx || !host_out) return fail(ctx, SPART_ERR_INVALID, "spart_ctx_econv: null argument");
-  if (ctx->nb == 0) return fail(ctx, SPART_ERR_NOSENSOR, "context has no sensor");
+  if (!ctx || !host_out) return fail(SPART_ERR_INVALID, "spart_ctx_econv: null argument");
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "context has no sensor");
   std::memcpy(host_out, ctx->econv_host.data(), sizeof(double) * ctx->nb);
   return SPART_OK;
 }
@@ -701,22 +693,27 @@ int spart_ctx_destroy(spart_ctx* ctx) {
 }
 
 int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
-  if (!out || !t) return fail(nullptr, SPART_ERR_INVALID, "spart_ctx_create: null argument");
+  if (!out || !t) return fail(SPART_ERR_INVALID, "spart_ctx_create: null argument");
   *out = nullptr;
   const double* req[] = {t->nr, t->Kab, t->Kca, t->Kdm, t->Kw, t->Ks, t->Kant, t->cbc, t->prot, t->GSV, t->nw, t->Ea};
   for (const double* p : req)
-    if (!p) return fail(nullptr, SPART_ERR_INVALID, "spart_ctx_create: a spectral table pointer is null");
-  if (t->nb < 0 || t->nb > MAX_NB) return fail(nullptr, SPART_ERR_INVALID, "spart_ctx_create: nb=%d out of range", t->nb);
+    if (!p) return fail(SPART_ERR_INVALID, "spart_ctx_create: a spectral table pointer is null");
+  if (t->nb < 0 || t->nb > MAX_NB) return fail(SPART_ERR_INVALID, "spart_ctx_create: nb=%d out of range", t->nb);
   if (t->nb > 0 && (!t->wl_smac || !t->coef || !t->wl_srf || !t->p_srf || t->nsrf <= 0))
-    return fail(nullptr, SPART_ERR_INVALID, "spart_ctx_create: sensor block incomplete");
+    return fail(SPART_ERR_INVALID, "spart_ctx_create: sensor block incomplete");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(nullptr, SPART_ERR_HIP, "spart_ctx_create: no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= ndev) return fail(nullptr, SPART_ERR_INVALID, "spart_ctx_create: device %d of %d", device, ndev);
+    return fail(SPART_ERR_HIP, "spart_ctx_create: no HIP device available (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return fail(SPART_ERR_INVALID, "spart_ctx_create: device %d of %d", device, ndev);
   DeviceGuard guard(device);
-  if (!guard.ok) return fail(nullptr, SPART_ERR_HIP, "spart_ctx_create: cannot select device %d", device);
+  if (!guard.ok) return fail(SPART_ERR_HIP, "spart_ctx_create: cannot select device %d", device);
 
-  spart_ctx* ctx = new spart_ctx();
+  struct Owner {         // the half-built context and the temporary SRF buffers, released on every return
+    spart_ctx* ctx = new spart_ctx();
+    double *d_w = nullptr, *d_p = nullptr;
+    ~Owner() { (void)hipFree(d_w); (void)hipFree(d_p); spart_ctx_destroy(ctx); }
+  } own;
+  spart_ctx* ctx = own.ctx;
   ctx->device = device;
   // --- derived per-band tables, float64 on the host
   std::vector<double> tab((size_t)NTAB * NWL);
@@ -744,9 +741,8 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
   }
   std::vector<float> tabf(tab.begin(), tab.end());
   int rc;
-  if ((rc = upload(ctx, &ctx->tabD, tab)) || (rc = upload(ctx, &ctx->tabF, tabf))) { spart_ctx_destroy(ctx); return rc; }
   std::vector<double> ea(t->Ea, t->Ea + NWL);
-  if ((rc = upload(ctx, &ctx->Ea, ea))) { spart_ctx_destroy(ctx); return rc; }
+  if ((rc = upload(&ctx->tabD, tab)) || (rc = upload(&ctx->tabF, tabf)) || (rc = upload(&ctx->Ea, ea))) return rc;
 
   // --- sensor block
   ctx->nb = t->nb;
@@ -756,27 +752,18 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
     for (int j = 0; j < t->nb; ++j) interp_support(t->wl_smac[j], e0[j], e1[j], fr[j]);
     std::vector<double> coef(t->coef, t->coef + (size_t)NCOEF * t->nb);
     std::vector<double> wsrf(t->wl_srf, t->wl_srf + (size_t)t->nsrf * t->nb), psrf(t->p_srf, t->p_srf + (size_t)t->nsrf * t->nb);
-    double *d_w = nullptr, *d_p = nullptr;
     std::vector<double> ec(t->nb, 0.0);
-    if ((rc = upload(ctx, &ctx->band0, e0)) || (rc = upload(ctx, &ctx->band1, e1)) || (rc = upload(ctx, &ctx->frac, fr)) ||
-        (rc = upload(ctx, &ctx->coef, coef)) || (rc = upload(ctx, &ctx->econv, ec)) || (rc = upload(ctx, &d_w, wsrf)) ||
-        (rc = upload(ctx, &d_p, psrf))) {
-      (void)hipFree(d_w); (void)hipFree(d_p);
-      spart_ctx_destroy(ctx);
+    if ((rc = upload(&ctx->band0, e0)) || (rc = upload(&ctx->band1, e1)) || (rc = upload(&ctx->frac, fr)) ||
+        (rc = upload(&ctx->coef, coef)) || (rc = upload(&ctx->econv, ec)) || (rc = upload(&own.d_w, wsrf)) ||
+        (rc = upload(&own.d_p, psrf)))
       return rc;
-    }
     // SRF convolution of the ET irradiance: one wave per sensor band (SPART.py:358-396)
-    hipLaunchKernelGGL(k_econv, dim3(t->nb), dim3(64), 0, 0, ctx->Ea, d_w, d_p, t->nsrf, t->nb, ctx->econv);
+    hipLaunchKernelGGL(k_econv, dim3(t->nb), dim3(64), 0, 0, ctx->Ea, own.d_w, own.d_p, t->nsrf, t->nb, ctx->econv);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     ctx->econv_host.resize(t->nb);
     if (e == hipSuccess) e = hipMemcpy(ctx->econv_host.data(), ctx->econv, sizeof(double) * t->nb, hipMemcpyDeviceToHost);
-    (void)hipFree(d_w); (void)hipFree(d_p);
-    if (e != hipSuccess) {
-      fail(nullptr, SPART_ERR_HIP, "spart_ctx_create: SRF convolution kernel: %s", hipGetErrorString(e));
-      spart_ctx_destroy(ctx);
-      return SPART_ERR_HIP;
-    }
+    if (e != hipSuccess) return fail(SPART_ERR_HIP, "spart_ctx_create: SRF convolution kernel: %s", hipGetErrorString(e));
   }
   {
     const char* e = std::getenv("SPART_SIDE_STREAM");            // "0" keeps every kernel on the caller's stream
@@ -785,11 +772,12 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
     ctx->ws_uses.reserve(WS_PRUNE_AT);
   }
   *out = ctx;
+  own.ctx = nullptr;                                              // (the caller's now)
   return SPART_OK;
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {
-  if (!ctx) return fail(nullptr, SPART_ERR_INVALID, "spart_profile_enable: null context");
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_profile_enable: null context");
   DeviceGuard guard(ctx->device);
   std::lock_guard<std::mutex> lock(ctx->mu);
   ctx->profile = max_calls > 0;
@@ -797,29 +785,29 @@ int spart_profile_enable(spart_ctx* ctx, int max_calls) {
   ctx->ev_forked.clear();
   while (ctx->ev.size() < (size_t)(max_calls > 0 ? NEV * max_calls : 0)) {
     hipEvent_t e;
-    HIP_TRY(ctx, hipEventCreate(&e));
+    HIP_TRY(hipEventCreate(&e));
     ctx->ev.push_back(e);
   }
   return SPART_OK;
 }
 
 int spart_profile_read_stages(spart_ctx* ctx, double stage_ms[SPART_NSTAGE], int* ncalls) {
-  if (!ctx || !stage_ms || !ncalls) return fail(ctx, SPART_ERR_INVALID, "spart_profile_read_stages: null argument");
+  if (!ctx || !stage_ms || !ncalls) return fail(SPART_ERR_INVALID, "spart_profile_read_stages: null argument");
   DeviceGuard guard(ctx->device);
   std::lock_guard<std::mutex> lock(ctx->mu);
   static_assert(SPART_NSTAGE + 1 == NEV, "one event more than stages");
   for (int k = 0; k < SPART_NSTAGE; ++k) stage_ms[k] = 0.0;
   int n = 0;
   for (size_t i = 0; i + NEV <= ctx->ev_used; i += NEV) {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[i + 2]));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[i + NEV - 1]));
+    HIP_TRY(hipEventSynchronize(ctx->ev[i + 2]));
+    HIP_TRY(hipEventSynchronize(ctx->ev[i + NEV - 1]));
     // events: 0 before the prelude, 1 after it, 2 after the full-band kernel, 3 after the column kernel.  When 3 was
     // recorded on the side stream the column kernel started at event 1, beside the band kernel.
     const bool forked = n < (int)ctx->ev_forked.size() && ctx->ev_forked[n];
     const int from[SPART_NSTAGE] = {0, 1, forked ? 1 : 2}, to[SPART_NSTAGE] = {1, 2, 3};
     for (int k = 0; k < SPART_NSTAGE; ++k) {
       float ms = 0.f;
-      HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[i + from[k]], ctx->ev[i + to[k]]));
+      HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[i + from[k]], ctx->ev[i + to[k]]));
       stage_ms[k] += ms;
     }
     ++n;
@@ -831,7 +819,7 @@ int spart_profile_read_stages(spart_ctx* ctx, double stage_ms[SPART_NSTAGE], int
 }
 
 int spart_profile_read(spart_ctx* ctx, double* total_ms, int* ncalls) {
-  if (!ctx || !total_ms || !ncalls) return fail(ctx, SPART_ERR_INVALID, "spart_profile_read: null argument");
+  if (!ctx || !total_ms || !ncalls) return fail(SPART_ERR_INVALID, "spart_profile_read: null argument");
   double st[SPART_NSTAGE];
   int rc = spart_profile_read_stages(ctx, st, ncalls);
   *total_ms = st[1];
@@ -839,7 +827,7 @@ int spart_profile_read(spart_ctx* ctx, double* total_ms, int* ncalls) {
 }
 
 int spart_calculate_tav(double alpha_deg, const double* nr, int64_t n, double* out) {
-  if (!nr || !out || n < 0) { std::snprintf(g_err, 512, "spart_calculate_tav: null pointer or negative length"); return SPART_ERR_INVALID; }
+  if (!nr || !out || n < 0) return fail(SPART_ERR_INVALID, "spart_calculate_tav: null pointer or negative length");
   for (int64_t i = 0; i < n; ++i) out[i] = calculate_tav(alpha_deg, nr[i]);
   return SPART_OK;
 }
@@ -850,130 +838,129 @@ size_t spart_workspace_bytes(const spart_ctx* ctx, int dtype, int64_t B) {
 }
 
 int spart_workspace_bandsum(const spart_ctx* ctx, int dtype, int64_t B, size_t* offset, int64_t* nchunk, int* row_stride) {
-  if (!ctx || !offset || !nchunk || !row_stride) return fail(nullptr, SPART_ERR_INVALID, "spart_workspace_bandsum: null argument");
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(ctx, SPART_ERR_INVALID, "spart_workspace_bandsum: bad dtype %d", dtype);
-  if (B <= 0 || B > SPART_MAX_BATCH) return fail(ctx, SPART_ERR_INVALID, "spart_workspace_bandsum: batch %lld", (long long)B);
-  const int chunk = pick_chunk(B);                 // (the layout of run_impl: one row per workgroup column of k_bands)
-  *offset = carve(dtype, B).bs_off;
-  *nchunk = (B + chunk - 1) / chunk;
+  if (!ctx || !offset || !nchunk || !row_stride) return fail(SPART_ERR_INVALID, "spart_workspace_bandsum: null argument");
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "spart_workspace_bandsum: bad dtype %d", dtype);
+  if (B <= 0 || B > SPART_MAX_BATCH) return fail(SPART_ERR_INVALID, "spart_workspace_bandsum: batch %lld", (long long)B);
+  const Workspace ws = carve(dtype, B);            // (one row per workgroup column of k_bands)
+  *offset = ws.bs_off;
+  *nchunk = ws.nchunk;
   *row_stride = NTILE * TILE;
   return SPART_OK;
 }
 
-#define CHECK_COMMON(name)                                                                                  \
-  if (!ctx) return fail(nullptr, SPART_ERR_INVALID, name ": null context");                                 \
-  if (B > SPART_MAX_BATCH) return fail(ctx, SPART_ERR_INVALID, name ": at most %lld samples per call", (long long)SPART_MAX_BATCH); \
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(ctx, SPART_ERR_INVALID, name ": bad dtype %d", dtype); \
-  if (B < 0) return fail(ctx, SPART_ERR_INVALID, name ": negative batch");                                  \
-  if (B == 0) return SPART_OK;                                                                              \
-  Workspace ws = carve(dtype, B);                                                                           \
-  if (!workspace || workspace_bytes < ws.total)                                                             \
-    return fail(ctx, SPART_ERR_WORKSPACE, name ": workspace of %zu bytes needed, %zu given", ws.total, workspace_bytes); \
-  DeviceGuard guard(ctx->device);                                                                           \
-  hipStream_t st = (hipStream_t)stream;                                                                     \
-  char* wsp = (char*)workspace;
-
-
 int spart_prospect_batch(spart_ctx* ctx, int dtype, int64_t B, const double* const leaf[9], void* refl, void* tran,
                          void* kchl, void* workspace, size_t workspace_bytes, void* stream) {
-  CHECK_COMMON("spart_prospect_batch")
-  if (!leaf) return fail(ctx, SPART_ERR_INVALID, "spart_prospect_batch: null leaf");
-  for (int i = 0; i < 9; ++i)
-    if (!leaf[i]) return fail(ctx, SPART_ERR_INVALID, "spart_prospect_batch: leaf[%d] is null", i);
-  return guarded(ctx, "spart_prospect_batch", wsp, ws.total, st, [&] {
-    return dtype == SPART_F32 ? prospect_impl<float>(ctx, B, leaf, refl, tran, kchl, wsp, ws, st)
-                              : prospect_impl<double>(ctx, B, leaf, refl, tran, kchl, wsp, ws, st);
+  const char* who = "spart_prospect_batch";
+  Workspace ws;
+  if (int rc = gate(ctx, who, dtype, B, workspace, workspace_bytes, ws); rc || B == 0) return rc;
+  if (!leaf) return fail(SPART_ERR_INVALID, "%s: null leaf", who);
+  if (int i = first_null(leaf, 9); i < 9) return fail(SPART_ERR_INVALID, "%s: leaf[%d] is null", who, i);
+  return stage_call(ctx, who, dtype, B, param_slice(0, leaf, 9), PRE_LEAF, ctx->po, workspace, ws, stream,
+                    [&](auto t, auto nt, hipStream_t st, auto tab, auto cst) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_prospect<T, nt>), dim3(xcd_grid(ws.nchunk)), dim3(TILE), 0, st, tab, cst, ws.Bp, B, ws.chunk, ctx->po,
+                       (T*)refl, (T*)tran, (T*)kchl);
   });
 }
 
-
 int spart_bsm_batch(spart_ctx* ctx, int dtype, int64_t B, const double* const soil[6], const void* rdry_in, void* refl,
                     void* refl_dry, void* workspace, size_t workspace_bytes, void* stream) {
-  CHECK_COMMON("spart_bsm_batch")
-  if (!soil) return fail(ctx, SPART_ERR_INVALID, "spart_bsm_batch: null soil");
+  const char* who = "spart_bsm_batch";
+  Workspace ws;
+  if (int rc = gate(ctx, who, dtype, B, workspace, workspace_bytes, ws); rc || B == 0) return rc;
+  if (!soil) return fail(SPART_ERR_INVALID, "%s: null soil", who);
   for (int i = 0; i < 6; ++i)
-    if (!soil[i] && !(rdry_in && i < 3)) return fail(ctx, SPART_ERR_INVALID, "spart_bsm_batch: soil[%d] is null", i);
-  return guarded(ctx, "spart_bsm_batch", wsp, ws.total, st, [&] {
-    return dtype == SPART_F32 ? bsm_impl<float>(ctx, B, soil, rdry_in, refl, refl_dry, wsp, ws, st)
-                              : bsm_impl<double>(ctx, B, soil, rdry_in, refl, refl_dry, wsp, ws, st);
+    if (!soil[i] && !may_be_null(9 + i, rdry_in, false)) return fail(SPART_ERR_INVALID, "%s: soil[%d] is null", who, i);
+  return stage_call(ctx, who, dtype, B, param_slice(9, soil, 6), PRE_SOIL, ctx->po, workspace, ws, stream,
+                    [&](auto t, auto nt, hipStream_t st, auto tab, auto cst) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_bsm<T, nt>), dim3(xcd_grid(ws.nchunk)), dim3(TILE), 0, st, tab, cst, ws.Bp, B, ws.chunk, ctx->po,
+                       (const T*)rdry_in, (T*)refl, (T*)refl_dry);
   });
 }
 
 int spart_lidf_batch(spart_ctx* ctx, int64_t B, const double* LIDFa, const double* LIDFb, double* lidf, void* stream) {
-  if (!ctx) return fail(nullptr, SPART_ERR_INVALID, "spart_lidf_batch: null context");
-  if (B < 0 || !LIDFa || !LIDFb || !lidf) return fail(ctx, SPART_ERR_INVALID, "spart_lidf_batch: bad argument");
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lidf_batch: null context");
+  if (B < 0 || !LIDFa || !LIDFb || !lidf) return fail(SPART_ERR_INVALID, "spart_lidf_batch: bad argument");
   if (B == 0) return SPART_OK;
   DeviceGuard guard(ctx->device);
   hipLaunchKernelGGL(k_lidf, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, LIDFa, LIDFb, B, lidf);
-  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
-
 
 int spart_sailh_batch(spart_ctx* ctx, int dtype, int64_t B, const void* rho, const void* tau, const void* rs,
                       const double* const canopy[4], const double* const angles[3], const double* lidf_in, int32_t nlayers,
                       void* const out4[4], void* workspace, size_t workspace_bytes, void* stream) {
-  CHECK_COMMON("spart_sailh_batch")
-  if (!rho || !tau || !rs || !canopy || !angles || !out4) return fail(ctx, SPART_ERR_INVALID, "spart_sailh_batch: null argument");
-  if (nlayers < 0 || nlayers > SPART_MAX_NLAYERS) return fail(ctx, SPART_ERR_INVALID, "spart_sailh_batch: nlayers = %d (0 = the default 60, else 1 ... %d)", nlayers, SPART_MAX_NLAYERS);
+  const char* who = "spart_sailh_batch";
+  Workspace ws;
+  if (int rc = gate(ctx, who, dtype, B, workspace, workspace_bytes, ws); rc || B == 0) return rc;
+  if (!rho || !tau || !rs || !canopy || !angles || !out4) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  if (nlayers < 0 || nlayers > SPART_MAX_NLAYERS)
+    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, nlayers, SPART_MAX_NLAYERS);
   for (int i = 0; i < 4; ++i)
-    if ((!canopy[i] && !(lidf_in && (i == 1 || i == 2))) || !out4[i])      // LIDFa, LIDFb are unused with a given lidf
-      return fail(ctx, SPART_ERR_INVALID, "spart_sailh_batch: canopy/out4[%d] is null", i);
-  for (int i = 0; i < 3; ++i)
-    if (!angles[i]) return fail(ctx, SPART_ERR_INVALID, "spart_sailh_batch: angles[%d] is null", i);
-  return guarded(ctx, "spart_sailh_batch", wsp, ws.total, st, [&] {
-    return dtype == SPART_F32 ? sailh_impl<float>(ctx, B, rho, tau, rs, canopy, angles, lidf_in, nlayers, out4, wsp, ws, st)
-                              : sailh_impl<double>(ctx, B, rho, tau, rs, canopy, angles, lidf_in, nlayers, out4, wsp, ws, st);
+    if ((!canopy[i] && !may_be_null(15 + i, false, lidf_in)) || !out4[i])
+      return fail(SPART_ERR_INVALID, "%s: canopy/out4[%d] is null", who, i);
+  if (int i = first_null(angles, 3); i < 3) return fail(SPART_ERR_INVALID, "%s: angles[%d] is null", who, i);
+  ParamPtrs pp = param_slice(15, canopy, 4);
+  for (int i = 0; i < 3; ++i) pp.p[19 + i] = angles[i];
+  pp.lidf = lidf_in;
+  pp.nlayers = nlayers;
+  return stage_call(ctx, who, dtype, B, pp, PRE_CANOPY, ctx->pf, workspace, ws, stream,
+                    [&](auto t, auto nt, hipStream_t st, auto, auto cst) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_sailh<T, nt>), dim3((unsigned)(ws.nchunk * NTILE_FULL)), dim3(TILE), 0, st, cst, ws.Bp, B, ws.chunk,
+                       ctx->pf, (const T*)rho, (const T*)tau, (const T*)rs, (T*)out4[0], (T*)out4[1], (T*)out4[2], (T*)out4[3]);
   });
 }
 
 int spart_smac_batch(spart_ctx* ctx, int64_t B, const double* const angles[3], const double* const atm[4],
                      double* const out9[9], void* workspace, size_t workspace_bytes, void* stream) {
-  int dtype = SPART_F64;
-  CHECK_COMMON("spart_smac_batch")
-  if (ctx->nb == 0) return fail(ctx, SPART_ERR_NOSENSOR, "spart_smac_batch: context has no sensor");
-  if (!angles || !atm || !out9) return fail(ctx, SPART_ERR_INVALID, "spart_smac_batch: null argument");
-  for (int i = 0; i < 3; ++i) if (!angles[i]) return fail(ctx, SPART_ERR_INVALID, "spart_smac_batch: angles[%d] is null", i);
-  for (int i = 0; i < 4; ++i) if (!atm[i]) return fail(ctx, SPART_ERR_INVALID, "spart_smac_batch: atm[%d] is null", i);
-  for (int i = 0; i < 9; ++i) if (!out9[i]) return fail(ctx, SPART_ERR_INVALID, "spart_smac_batch: out9[%d] is null", i);
-  return guarded(ctx, "spart_smac_batch", wsp, ws.total, st, [&]() -> int {
-    ParamPtrs pp;
-    std::memset(&pp, 0, sizeof(pp));
-    for (int i = 0; i < 3; ++i) pp.p[19 + i] = angles[i];
+  const char* who = "spart_smac_batch";
+  Workspace ws;
+  if (int rc = gate(ctx, who, SPART_F64, B, workspace, workspace_bytes, ws); rc || B == 0) return rc;
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (!angles || !atm || !out9) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  if (int i = first_null(angles, 3); i < 3) return fail(SPART_ERR_INVALID, "%s: angles[%d] is null", who, i);
+  if (int i = first_null(atm, 4); i < 4) return fail(SPART_ERR_INVALID, "%s: atm[%d] is null", who, i);
+  if (int i = first_null(out9, 9); i < 9) return fail(SPART_ERR_INVALID, "%s: out9[%d] is null", who, i);
+  return guarded(ctx, who, workspace, ws.total, stream, [&](hipStream_t st) -> int {
+    ParamPtrs pp = param_slice(19, angles, 3);
     for (int i = 0; i < 4; ++i) pp.p[22 + i] = atm[i];
-    double* a = (double*)(wsp + ws.atm_off);
-    int rc = launch_prelude(ctx, false, pp, PRE_ATM, B, ws.Bp, nullptr, nullptr, a, st);
+    double* a = (double*)((char*)workspace + ws.atm_off);
+    int rc = launch_prelude(false, pp, PRE_ATM, B, ws.Bp, nullptr, nullptr, a, st);
     if (rc) return rc;
     Out9 o;
     for (int i = 0; i < 9; ++i) o.o[i] = out9[i];
     int64_t n = B * ctx->nb;
     hipLaunchKernelGGL(k_smac, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)ctx->coef, ctx->nb,
                        (const double*)a, ws.Bp, B, o);
-    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SPART_OK;
   });
 }
 
-
 int spart_run_batch(spart_ctx* ctx, int dtype, int64_t B, const double* const params[SPART_NPARAM],
                     const double* rho_thermal, const double* tau_thermal, void* R_TOC, void* R_TOA, void* L_TOA,
                     const spart_materialize* opt, void* workspace, size_t workspace_bytes, void* stream) {
-  CHECK_COMMON("spart_run_batch")
-  if (ctx->nb == 0) return fail(ctx, SPART_ERR_NOSENSOR, "spart_run_batch: context has no sensor");
-  if (!params || !R_TOC || !R_TOA || !L_TOA) return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: null argument");
+  const char* who = "spart_run_batch";
+  Workspace ws;
+  if (int rc = gate(ctx, who, dtype, B, workspace, workspace_bytes, ws); rc || B == 0) return rc;
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (!params || !R_TOC || !R_TOA || !L_TOA) return fail(SPART_ERR_INVALID, "%s: null argument", who);
   for (int i = 0; i < SPART_NPARAM; ++i)
-    if (!params[i] && !(opt && opt->rdry_in && i >= 9 && i <= 11)    // B, lat, lon are unused with user dry spectra
-        && !(opt && opt->lidf_in && (i == 16 || i == 17)))           // LIDFa, LIDFb are unused with a given lidf
-      return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: params[%d] is null", i);
+    if (!params[i] && !may_be_null(i, opt && opt->rdry_in, opt && opt->lidf_in))
+      return fail(SPART_ERR_INVALID, "%s: params[%d] is null", who, i);
   if (opt && (opt->nlayers < 0 || opt->nlayers > SPART_MAX_NLAYERS))
-    return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: nlayers = %d (0 = the default 60, else 1 ... %d)", opt->nlayers, SPART_MAX_NLAYERS);
+    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, opt->nlayers, SPART_MAX_NLAYERS);
   if (dtype == SPART_F64 && opt && opt->f32_bands &&
       (opt->leaf_refl || opt->leaf_tran || opt->leaf_kchl || opt->soil_refl || opt->soil_refl_dry || opt->rso || opt->rdo ||
        opt->rsd || opt->rdd || opt->band_mean || opt->rdry_in || opt->f32_columns))
     // float64 columns (identical to the float64 mode's) over a float32 full-band pass: nothing the float32 kernel
     // would have to write in float64 may be requested
-    return fail(ctx, SPART_ERR_INVALID, "spart_run_batch: f32_bands goes with the sensor columns (and rsoil / La) only");
-  return guarded(ctx, "spart_run_batch", wsp, ws.total, st, [&] {
+    return fail(SPART_ERR_INVALID, "%s: f32_bands goes with the sensor columns (and rsoil / La) only", who);
+  return guarded(ctx, who, workspace, ws.total, stream, [&](hipStream_t st) {
+    char* wsp = (char*)workspace;
     if (dtype == SPART_F64 && opt && opt->f32_bands)
       return run_impl<float, double, double>(ctx, B, params, rho_thermal, tau_thermal, R_TOC, R_TOA, L_TOA, opt, wsp, ws, st);
     if (dtype == SPART_F64)
@@ -992,32 +979,31 @@ size_t spart_lut_workspace_bytes(int dtype, int64_t B, int nb, int64_t M) {
 int spart_lut_nearest(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
                       const void* weights, int64_t* best_idx, void* best_cost, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (!ctx) return fail(nullptr, SPART_ERR_INVALID, "spart_lut_nearest: null context");
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(ctx, SPART_ERR_INVALID, "spart_lut_nearest: bad dtype %d", dtype);
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_nearest: null context");
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "spart_lut_nearest: bad dtype %d", dtype);
   if (B < 0 || M < 0 || nb < 1 || nb > 31 || B > 2000000000LL || M > 2000000000LL)
-    return fail(ctx, SPART_ERR_INVALID, "spart_lut_nearest: bad sizes (B=%lld M=%lld nb=%d; nb <= 31, B and M <= 2e9)", (long long)B, (long long)M, nb);
+    return fail(SPART_ERR_INVALID, "spart_lut_nearest: bad sizes (B=%lld M=%lld nb=%d; nb <= 31, B and M <= 2e9)", (long long)B, (long long)M, nb);
   if (M == 0) return SPART_OK;
-  if (B == 0) return fail(ctx, SPART_ERR_INVALID, "spart_lut_nearest: empty LUT");
-  if (!lut || !obs || !best_idx || !best_cost) return fail(ctx, SPART_ERR_INVALID, "spart_lut_nearest: null argument");
+  if (B == 0) return fail(SPART_ERR_INVALID, "spart_lut_nearest: empty LUT");
+  if (!lut || !obs || !best_idx || !best_cost) return fail(SPART_ERR_INVALID, "spart_lut_nearest: null argument");
   size_t need = spart_lut_workspace_bytes(dtype, B, nb, M);
   if (!workspace || workspace_bytes < need)
-    return fail(ctx, SPART_ERR_WORKSPACE, "spart_lut_nearest: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-  DeviceGuard guard(ctx->device);
-  hipStream_t st = (hipStream_t)stream;
-  return guarded(ctx, "spart_lut_nearest", workspace, need, st, [&] {
-    return dtype == SPART_F32 ? lut_impl<float>(ctx, dtype, B, nb, lut, M, obs, weights, best_idx, best_cost, (char*)workspace, st)
-                              : lut_impl<double>(ctx, dtype, B, nb, lut, M, obs, weights, best_idx, best_cost, (char*)workspace, st);
+    return fail(SPART_ERR_WORKSPACE, "spart_lut_nearest: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+  return guarded(ctx, "spart_lut_nearest", workspace, need, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) {
+      return lut_impl<decltype(t)>(ctx, dtype, B, nb, lut, M, obs, weights, best_idx, best_cost, (char*)workspace, st);
+    });
   });
 }
 
 int spart_lut_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, const void* workspace, int64_t* n_brute_force,
                     double* nmax) {
-  if (!ctx) return fail(nullptr, SPART_ERR_INVALID, "spart_lut_stats: null context");
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_stats: null context");
   if (!workspace || !n_brute_force || !nmax || spart_lut_workspace_bytes(dtype, B, nb, M) == 0)
-    return fail(ctx, SPART_ERR_INVALID, "spart_lut_stats: bad argument");
+    return fail(SPART_ERR_INVALID, "spart_lut_stats: bad argument");
   DeviceGuard guard(ctx->device);
   unsigned long long ctl[LUT_CTL_WORDS];
-  HIP_TRY(ctx, hipMemcpy(ctl, (const char*)workspace + lut_layout(dtype, B, nb, M).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_layout(dtype, B, nb, M).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
   *n_brute_force = (int64_t)ctl[1];
   if (dtype == SPART_F32) {
     const unsigned b = (unsigned)ctl[0];

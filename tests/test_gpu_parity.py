@@ -1553,3 +1553,108 @@ def test_event_queries_do_not_break_a_capture_in_progress(torch_mod):
     torch.cuda.synchronize()
     for k in ref:
         assert torch.equal(out[k], ref[k]), ("second graph", k)
+
+
+def test_c_abi_argument_checks(torch_mod):
+    """The C ABI's own argument checks, called directly on a real context (the engine replaces None before the library sees
+    it): each rejected call returns its code and message before any launch -- the caller's outputs stay untouched -- and
+    the NULL columns the rule allows (params 9-11 with rdry_in, 16-17 with lidf_in) give the engine's columns bit for bit."""
+    import ctypes
+    from spart_amd import _lib, get_engine, workloads
+    torch = torch_mod
+    INVALID, WORKSPACE, NOSENSOR = -1, -3, -4
+    eng = get_engine("Sentinel2A-MSI", 0)
+    lib, ctx, st = eng.lib, eng.ctx, eng._stream()
+    B = 257
+    P = torch.as_tensor(workloads.lhs_params(B, "full", seed=91).T.copy(), device="cuda:0")
+    cols = list(P)
+
+    ws_t = torch.empty(int(lib.spart_workspace_bytes(ctx, 1, B)), dtype=torch.uint8, device="cuda:0")
+    ws, wsn = ctypes.c_void_p(ws_t.data_ptr()), ctypes.c_size_t(ws_t.numel())
+
+    def rejected(rc, code, fragment, c=ctx):
+        msg = lib.spart_last_error(c).decode()
+        assert rc == code and fragment in msg, (rc, msg)
+
+    def with_null(ts, *idx):
+        return eng._ptrs([None if i in idx else t for i, t in enumerate(ts)])
+
+    spec = {w: torch.full((B, w), -7.0, dtype=torch.float64, device="cuda:0") for w in (_lib.NWL, _lib.NWLS)}
+    outs = [torch.full((B, eng.nb), -7.0, dtype=torch.float64, device="cuda:0") for _ in range(3)]
+    optr = [o.data_ptr() for o in outs]
+    s1, s2 = spec[_lib.NWL].data_ptr(), spec[_lib.NWLS].data_ptr()
+
+    # spart_prospect_batch / spart_bsm_batch / spart_sailh_batch / spart_smac_batch
+    rejected(lib.spart_prospect_batch(ctx, 1, B, with_null(cols[:9], 3), s1, s1, s1, ws, wsn, st), INVALID, "leaf[3] is null")
+    rejected(lib.spart_bsm_batch(ctx, 1, B, with_null(cols[9:15], 1), None, s1, s1, ws, wsn, st), INVALID, "soil[1] is null")
+    rejected(lib.spart_bsm_batch(ctx, 1, B, with_null(cols[9:15], 0, 3), s1, s1, s1, ws, wsn, st), INVALID, "soil[3] is null")
+    out4 = eng._ptrs([spec[_lib.NWLS]] * 4)
+    rejected(lib.spart_sailh_batch(ctx, 1, B, s2, s2, s2, with_null(cols[15:19], 1), eng._ptrs(cols[19:22]), None, 0, out4,
+                                   ws, wsn, st), INVALID, "canopy/out4[1] is null")
+    rejected(lib.spart_sailh_batch(ctx, 1, B, s2, s2, s2, eng._ptrs(cols[15:19]), with_null(cols[19:22], 2), None, 0, out4,
+                                   ws, wsn, st), INVALID, "angles[2] is null")
+    for nl in (-1, 1000001):
+        rejected(lib.spart_sailh_batch(ctx, 1, B, s2, s2, s2, eng._ptrs(cols[15:19]), eng._ptrs(cols[19:22]), None, nl, out4,
+                                       ws, wsn, st), INVALID, f"nlayers = {nl}")
+    out9 = eng._ptrs([outs[0]] * 9)
+    rejected(lib.spart_smac_batch(ctx, B, with_null(cols[19:22], 0), eng._ptrs(cols[22:26]), out9, ws, wsn, st), INVALID,
+             "angles[0] is null")
+    rejected(lib.spart_smac_batch(ctx, B, eng._ptrs(cols[19:22]), with_null(cols[22:26], 2), out9, ws, wsn, st), INVALID,
+             "atm[2] is null")
+    # spart_run_batch
+    mat = _lib.SpartMaterialize()
+    run = lambda ptrs, dt=1, b=B, m=None, w=ws, n=wsn: lib.spart_run_batch(ctx, dt, b, ptrs, None, None, *optr,  # noqa: E731
+                                                                            ctypes.byref(m) if m is not None else None, w, n, st)
+    rd = eng._rows(torch.linspace(0.05, 0.4, _lib.NWL, dtype=torch.float64, device="cuda:0"), B, _lib.NWL, torch.float64)
+    lidf = eng.lidf(P[16], P[17])
+    mat.rdry_in, mat.lidf_in = rd.data_ptr(), lidf.data_ptr()
+    rejected(run(with_null(cols, 9, 10, 11, 12, 16, 17), m=mat), INVALID, "params[12] is null")
+    rejected(run(with_null(cols, 9)), INVALID, "params[9] is null")
+    for nl in (-1, 1000001):
+        m = _lib.SpartMaterialize()
+        m.nlayers = nl
+        rejected(run(eng._ptrs(cols), m=m), INVALID, f"nlayers = {nl}")
+    rejected(run(eng._ptrs(cols), dt=2), INVALID, "bad dtype 2")
+    rejected(run(eng._ptrs(cols), b=-1), INVALID, "negative batch")
+    rejected(run(None, b=60_000_001), INVALID, "at most 60000000 samples")
+    rejected(lib.spart_run_batch(None, 1, B, eng._ptrs(cols), None, None, *optr, None, ws, wsn, st), INVALID, "null context")
+    rejected(run(eng._ptrs(cols), n=ctypes.c_size_t(wsn.value - 1)), WORKSPACE,
+             f"workspace of {wsn.value} bytes needed, {wsn.value - 1} given")
+    m = _lib.SpartMaterialize()
+    m.f32_bands, m.leaf_refl = 1, spec[_lib.NWLS].data_ptr()
+    rejected(run(eng._ptrs(cols), m=m), INVALID, "f32_bands")
+    m = _lib.SpartMaterialize()
+    bm = torch.full((4, _lib.NWLS), -7.0, dtype=torch.float64, device="cuda:0")
+    m.prune_unused_bands, m.band_mean = 1, bm.data_ptr()
+    rejected(run(eng._ptrs(cols), m=m), INVALID, "band_mean needs prune_unused_bands = 0")
+    # B = 0: nothing to check, nothing to do, whatever the pointers
+    assert lib.spart_run_batch(ctx, 1, 0, None, None, None, None, None, None, None, None, 0, st) == 0
+    assert lib.spart_prospect_batch(ctx, 1, 0, None, None, None, None, None, 0, st) == 0
+    assert lib.spart_bsm_batch(ctx, 1, 0, None, None, None, None, None, 0, st) == 0
+    assert lib.spart_sailh_batch(ctx, 1, 0, None, None, None, None, None, None, 0, None, None, 0, st) == 0
+    assert lib.spart_smac_batch(ctx, 0, None, None, None, None, 0, st) == 0
+    # a context without a sensor
+    e0 = get_engine(None, 0)
+    ws0 = torch.empty(int(lib.spart_workspace_bytes(e0.ctx, 1, B)), dtype=torch.uint8, device="cuda:0")
+    rejected(lib.spart_smac_batch(e0.ctx, B, eng._ptrs(cols[19:22]), eng._ptrs(cols[22:26]), out9, ws0.data_ptr(),
+                                  ws0.numel(), st), NOSENSOR, "no sensor", e0.ctx)
+    # spart_lut_nearest: its own size rules
+    rejected(lib.spart_lut_nearest(ctx, 0, B, 32, None, 5, None, None, None, None, None, 0, st), INVALID, "bad sizes")
+    rejected(lib.spart_lut_nearest(ctx, 0, 0, 4, None, 5, None, None, None, None, None, 0, st), INVALID, "empty LUT")
+    torch.cuda.synchronize()
+    for t in list(spec.values()) + outs + [bm]:                  # no rejected call launched anything
+        assert bool((t == -7.0).all())
+    # accepted NULLs: B / lat / lon with rdry_in, LIDFa / LIDFb with lidf_in -- the engine's columns, bit for bit
+    for dtype, dt in (("float64", 1), ("float32", 0)):
+        td = torch.float64 if dt else torch.float32
+        ref = eng.run(P, dtype, rdry=rd, canopy_lidf=lidf)
+        got = {k: torch.full((B, eng.nb), -7.0, dtype=td, device="cuda:0") for k in ("R_TOC", "R_TOA", "L_TOA")}
+        rdt = eng._rows(rd, B, _lib.NWL, td)
+        m = _lib.SpartMaterialize()
+        m.rdry_in, m.lidf_in = rdt.data_ptr(), lidf.data_ptr()
+        rc = lib.spart_run_batch(ctx, dt, B, with_null(cols, 9, 10, 11, 16, 17), None, None, *[got[k].data_ptr() for k in got],
+                                 ctypes.byref(m), ws, wsn, st)
+        _lib.check(lib, ctx, rc)
+        torch.cuda.synchronize()
+        for k in got:
+            assert torch.equal(got[k], ref[k]), (dtype, k)
