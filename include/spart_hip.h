@@ -56,8 +56,9 @@ extern "C" {
  * equal the header's a binding was written against (the Python loader checks, so that a library built from another
  * round's header -- e.g. through SPART_HIP_LIB -- is refused instead of being called with shifted arguments).
  *   6: spart_materialize.lidf_in / .nlayers, spart_sailh_batch(lidf_in, nlayers), spart_abi_version itself
- *   7: spart_workspace_bandsum */
-#define SPART_ABI_VERSION 7
+ *   7: spart_workspace_bandsum
+ *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats */
+#define SPART_ABI_VERSION 8
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -248,6 +249,27 @@ int spart_lut_nearest(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *
  * Synchronises the device (a blocking copy of 16 bytes).  No reference counterpart. */
 int spart_lut_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, const void *workspace, int64_t *n_brute_force,
                     double *nmax);
+
+/* The k nearest LUT rows (the usual inversion of an ill-posed LUT: the mean / median / spread of the k best rows; no reference
+ * counterpart).  For each observation m: the k rows with the smallest cost c(b, m) -- the SAME c as spart_lut_nearest, evaluated
+ * the same way -- ordered by (cost ascending, row index ascending); exactly np.argsort(c, kind="stable")[:k] after non-finite
+ * costs are set to +inf.  Rows whose cost is not finite never appear, under spart_lut_nearest's rules (NaN rows, an overflowing
+ * centred norm, -inf); when fewer than k rows qualify the tail is (-1, +inf).  idx (M,k) int64 and cost (M,k) in `dtype`,
+ * row-major; entry [m,0] equals spart_lut_nearest's answer bit for bit.  1 <= k <= 256 (SPART_ERR_INVALID otherwise);
+ * weights, nb <= 31 and the size limits as for spart_lut_nearest.
+ * How (csrc/spart_lut.h derives it): the k = 1 GEMM scan on the matrix cores gives, per observation, k filter values of
+ * distinct rows and so a proven threshold; a second GEMM pass lists every tile with a filter value under it; one wave per
+ * observation evaluates their rows with c itself and keeps the k best; an observation the filter cannot settle is re-done by
+ * a brute-force kernel.  Observations are processed in chunks of 65 536, so the workspace grows with M only by 4 bytes per
+ * observation beyond the first chunk. */
+size_t spart_lut_topk_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k);
+int spart_lut_topk(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut, int64_t M, const void *obs,
+                   const void *weights, int k, int64_t *idx, void *cost, void *workspace, size_t workspace_bytes, void *stream);
+/* Diagnostics of the LAST spart_lut_topk call that used `workspace` (same dtype, B, nb, M, k): observations that took the
+ * brute-force path, candidate tiles (of 32 rows for SPART_F32, 16 for SPART_F64) summed over the observations and their maximum
+ * per observation, and Nmax.  Synchronises the device. */
+int spart_lut_topk_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
+                         int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nmax);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -464,8 +464,9 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
 // ---- LUT inversion (csrc/spart_lut.h): GEMM + argmin on the matrix cores as a filter, exact direct evaluation of every
 // candidate, brute-force fallback.  float32: K steps of 2 (v_mfma_f32_32x32x2_f32), KS = ceil((nb + 1) / 2) MFMAs per
 // 32 x 32 comparisons, rounded up to one of the compiled variants; float64: K steps of 4 (v_mfma_f64_16x16x4_f64).
-using LutKs = Variants<4, 7, 8, 11, 16>;           // k_lut_prep<float, KS, 32>, k_lut_scan_mfma<KS>
-using LutKs64 = Variants<2, 4, 6, 8>;              // k_lut_prep<double, KS, 16>, k_lut_scan_mfma64<KS, lut_to64(KS)>
+using LutKs = Variants<4, 7, 8, 11, 16>;           // k_lut_prep<float, KS, 32>, k_lut_scan_mfma<KS>, k_lut_collect_mfma<KS>
+using LutKs64 = Variants<2, 4, 6, 8>;              // k_lut_prep<double, KS, 16>, k_lut_scan_mfma64<KS, lut_to64(KS)>,
+                                                   // k_lut_collect_mfma64<KS, lut_to64(KS)>
 using LutFallback = Variants<4, 8, 12, 16, 20, 24, 28, 32>;   // k_lut_fallback<T, N>: N = nb rounded up to a multiple of 4
 static constexpr int lut_to64(int ks) { return ks <= 4 ? 8 : 4; }     // 16-observation blocks per wave (operand registers: 2 KS TO)
 // workgroups = ceil(M / obs per workgroup) x nslice; slices are whole tiles
@@ -565,6 +566,120 @@ static int lut_impl(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lu
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL((k_lut_fallback_merge<T>), dim3(256), dim3(256), 0, st, B, LUT_FB_BLOCKS * 4, (const unsigned long long*)ctl,
                      (const int*)flags, (const T*)fbc, (const int64_t*)fbi, best_idx, (T*)best_cost);
+  HIP_TRY(hipGetLastError());
+  return SPART_OK;
+}
+
+// ---- LUT top-k (csrc/spart_lut.h, "top-k"): the k = 1 path's centre / prep / scan, a bound, a collecting second scan,
+// an exact select per observation and a brute force for the flagged ones.  Observations go in chunks of LUT_TOPK_CHUNK.
+struct LutTopkLayout {
+  LutLayout base;                                  // ks, to, rows, kfma, ntile of the k = 1 layout for the same call
+  int nslice, npart, nslice2, cap;
+  int64_t mc;                                      // observations per chunk
+  size_t tiles, pc, ps, pt, thr, cn, cand, centre, ctl, flags, total;
+};
+static LutTopkLayout lut_topk_layout(int dtype, int64_t B, int nb, int64_t M, int k) {
+  LutTopkLayout L;
+  L.base = lut_layout(dtype, B, nb, M < LUT_TOPK_CHUNK ? M : LUT_TOPK_CHUNK);
+  const size_t es = dtype == SPART_F64 ? 8 : 4;
+  const LutLayout& b = L.base;
+  const int groups = 64 / b.rows;
+  L.mc = M < LUT_TOPK_CHUNK ? M : LUT_TOPK_CHUNK;
+  // the bound needs >= k finite partial values of distinct rows: at least 2k values (best + second per partial result)
+  int64_t ns = b.nslice;
+  const int64_t need = (2 * (int64_t)k + groups - 1) / groups;
+  if (ns < need) ns = need;
+  if (ns > LUT_TOPK_MAXPART / groups) ns = LUT_TOPK_MAXPART / groups;
+  if (ns > b.ntile) ns = b.ntile;
+  if (ns < 1) ns = 1;
+  L.nslice = (int)ns;
+  L.npart = groups * L.nslice;
+  L.nslice2 = b.nslice;                            // the collect scan: the k = 1 scan's occupancy rule
+  L.cap = lut_topk_cap(k);
+  const size_t mc = (size_t)L.mc;
+  size_t o = 0;
+  L.tiles = o;  o = align_up(o + (size_t)b.ntile * b.ks * 64 * es);
+  L.pc = o;     o = align_up(o + (size_t)L.npart * mc * es);
+  L.ps = o;     o = align_up(o + (size_t)L.npart * mc * es);
+  L.pt = o;     o = align_up(o + (size_t)L.npart * mc * 4);
+  L.thr = o;    o = align_up(o + mc * es);
+  L.cn = o;     o = align_up(o + mc * 4);
+  L.cand = o;   o = align_up(o + mc * (size_t)L.cap * 4);
+  L.centre = o; o = align_up(o + 32 * es);
+  L.ctl = o;    o = align_up(o + LUT_TOPK_CTL_WORDS * 8);
+  L.flags = o;  o = align_up(o + (size_t)M * 4);
+  L.total = o;
+  return L;
+}
+
+template <typename T>
+static int lut_topk_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int k,
+                         int64_t* idx, void* cost, char* wsp, hipStream_t st) {
+  const char* who = "spart_lut_topk";
+  const LutTopkLayout L = lut_topk_layout(dtype, B, nb, M, k);
+  const LutLayout& b = L.base;
+  constexpr int ROWS = sizeof(T) == 4 ? 32 : 16;
+  const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
+  T* tiles = (T*)(wsp + L.tiles);
+  T* pc = (T*)(wsp + L.pc);
+  T* ps = (T*)(wsp + L.ps);
+  int* pt = (int*)(wsp + L.pt);
+  T* thr = (T*)(wsp + L.thr);
+  int* cn = (int*)(wsp + L.cn);
+  int* cand = (int*)(wsp + L.cand);
+  T* centre = (T*)(wsp + L.centre);
+  unsigned long long* ctl = (unsigned long long*)(wsp + L.ctl);
+  int* flags = (int*)(wsp + L.flags);
+  HIP_TRY(hipMemsetAsync(ctl, 0, LUT_TOPK_CTL_WORDS * 8, st));
+  hipLaunchKernelGGL((k_lut_centre<T>), dim3(nb), dim3(256), 0, st, lut, nb, B, centre, ctl);
+  HIP_TRY(hipGetLastError());
+  const dim3 gprep((unsigned)((b.ntile * b.rows + 255) / 256));
+  const int opw = b.rows * b.to * 4;                 // observations per scan workgroup
+  bool compiled;
+  if constexpr (sizeof(T) == 4)
+    compiled = LutKs::with(b.ks, [&](auto K) {
+      hipLaunchKernelGGL((k_lut_prep<float, K, 32>), gprep, dim3(256), 0, st, lut, w, (const float*)centre, nb, B, b.ntile, tiles, ctl);
+    });
+  else
+    compiled = LutKs64::with(b.ks, [&](auto K) {
+      hipLaunchKernelGGL((k_lut_prep<double, K, 16>), gprep, dim3(256), 0, st, lut, w, (const double*)centre, nb, B, b.ntile, tiles, ctl);
+    });
+  if (!compiled) return fail(SPART_ERR_INVALID, "%s: no compiled LUT scan for KS = %d", who, b.ks);
+  HIP_TRY(hipGetLastError());
+  const T coef_ef = (T)lut_coef_ef(nb, b.kfma, (double)LutNum<T>::u);
+  for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
+    const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
+    const T* ob = obs + m0 * nb;
+    const unsigned gx = (unsigned)((mc + opw - 1) / opw);
+    const dim3 g1(gx, (unsigned)L.nslice), g2(gx, (unsigned)L.nslice2), gobs((unsigned)((mc + 3) / 4));
+    auto bound = [&] {
+      hipLaunchKernelGGL((k_lut_topk_bound<T>), gobs, dim3(256), 0, st, (const T*)pc, (const T*)ps, ob, w, (const T*)centre, nb, mc,
+                         L.npart, k, coef_ef, (const unsigned long long*)ctl, thr, cn);
+    };
+    if constexpr (sizeof(T) == 4)
+      LutKs::with(b.ks, [&](auto K) {
+        hipLaunchKernelGGL((k_lut_scan_mfma<K>), g1, dim3(256), 0, st, (const float*)tiles, ob, w, (const float*)centre, nb, b.ntile,
+                           mc, L.nslice, pc, ps, pt);
+        bound();
+        hipLaunchKernelGGL((k_lut_collect_mfma<K>), g2, dim3(256), 0, st, (const float*)tiles, ob, w, (const float*)centre, nb,
+                           b.ntile, mc, L.nslice2, (const float*)thr, L.cap, cn, cand);
+      });
+    else
+      LutKs64::with(b.ks, [&](auto K) {
+        hipLaunchKernelGGL((k_lut_scan_mfma64<K, lut_to64(K)>), g1, dim3(256), 0, st, (const double*)tiles, ob, w,
+                           (const double*)centre, nb, b.ntile, mc, L.nslice, pc, ps, pt);
+        bound();
+        hipLaunchKernelGGL((k_lut_collect_mfma64<K, lut_to64(K)>), g2, dim3(256), 0, st, (const double*)tiles, ob, w,
+                           (const double*)centre, nb, b.ntile, mc, L.nslice2, (const double*)thr, L.cap, cn, cand);
+      });
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, false>), gobs, dim3(256), 0, st, lut, obs, w, nb, B, m0, mc, k, (const T*)thr,
+                       (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost);
+    HIP_TRY(hipGetLastError());
+  }
+  // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
+  hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, true>), dim3(LUT_FB_BLOCKS), dim3(256), 0, st, lut, obs, w, nb, B, (int64_t)0,
+                     M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost);
   HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
@@ -1005,6 +1120,56 @@ int spart_lut_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, con
   unsigned long long ctl[LUT_CTL_WORDS];
   HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_layout(dtype, B, nb, M).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
   *n_brute_force = (int64_t)ctl[1];
+  if (dtype == SPART_F32) {
+    const unsigned b = (unsigned)ctl[0];
+    float f;
+    std::memcpy(&f, &b, 4);
+    *nmax = f;
+  } else {
+    std::memcpy(nmax, &ctl[0], 8);
+  }
+  return SPART_OK;
+}
+
+size_t spart_lut_topk_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k) {
+  if (B <= 0 || M <= 0 || nb < 1 || nb > 31 || k < 1 || k > LUT_TOPK_MAXK || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
+  return lut_topk_layout(dtype, B, nb, M, k).total;
+}
+
+int spart_lut_topk(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs, const void* weights,
+                   int k, int64_t* idx, void* cost, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_lut_topk";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  if (B < 0 || M < 0 || nb < 1 || nb > 31 || B > 2000000000LL || M > 2000000000LL)
+    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d; nb <= 31, B and M <= 2e9)", who, (long long)B, (long long)M, nb);
+  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
+  if (M == 0) return SPART_OK;
+  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", who);
+  const void* ptrs[4] = {lut, obs, idx, cost};
+  if (first_null(ptrs, 4) < 4) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  const size_t need = spart_lut_topk_workspace_bytes(dtype, B, nb, M, k);
+  if (!workspace || workspace_bytes < need)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) {
+      return lut_topk_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, (char*)workspace, st);
+    });
+  });
+}
+
+int spart_lut_topk_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void* workspace,
+                         int64_t* n_brute_force, int64_t* n_candidates, int64_t* max_candidates, double* nmax) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_topk_stats: null context");
+  const void* ptrs[5] = {workspace, n_brute_force, n_candidates, max_candidates, nmax};
+  if (first_null(ptrs, 5) < 5 || spart_lut_topk_workspace_bytes(dtype, B, nb, M, k) == 0)
+    return fail(SPART_ERR_INVALID, "spart_lut_topk_stats: bad argument");
+  DeviceGuard guard(ctx->device);
+  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
+  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_topk_layout(dtype, B, nb, M, k).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  *n_brute_force = (int64_t)ctl[1];
+  *n_candidates = (int64_t)ctl[2];
+  *max_candidates = (int64_t)ctl[3];
   if (dtype == SPART_F32) {
     const unsigned b = (unsigned)ctl[0];
     float f;

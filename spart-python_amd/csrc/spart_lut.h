@@ -619,4 +619,399 @@ __global__ __launch_bounds__(256) void k_lut_fallback_merge(int64_t B, int W, co
   }
 }
 
+// ---- top-k (spart_lut_topk): the k rows of smallest c_T per observation, ordered by (cost, row)
+//
+// Steps, per chunk of at most LUT_TOPK_CHUNK observations (after k_lut_centre / k_lut_prep, which are shared):
+//   1. k_lut_scan_mfma / _mfma64 as above, with at least 2k / G slices (G = lane groups: 2 for f32, 4 for f64), so that the
+//      partial results hold at least 2k values.  Every partial result belongs to ONE lane group of ONE slice, and each lane
+//      group holds its own rows of every tile (the MFMA output layout), so its smallest and second smallest tile minima
+//      (best, sec) are the filter values a~ of two DIFFERENT rows, and no row appears behind two partial results.
+//   2. k_lut_topk_bound  U = the k-th smallest finite value among the 2 npart values (best, sec) of the observation: the
+//      largest of k filter values a~(a_1) .. a~(a_k) of k DISTINCT rows (bisection on the order-preserving bit pattern).
+//   3. k_lut_collect_mfma / _mfma64  the same GEMM once more; every tile whose minimum (over all its rows) is
+//      <= thr = U + Delta is appended to the observation's candidate list (capacity lut_topk_cap(k) tiles).
+//   4. k_lut_topk_select<BRUTE = false>  one wave per observation evaluates every row of every candidate tile with the
+//      direct cost (the arithmetic of k_lut_reduce_exact) and keeps the k best by (cost, row) in LDS (a 512-entry buffer,
+//      bitonic-sorted and cut back to k whenever it fills; entries at or above the current k-th are not admitted).
+//      An observation whose U or thr is not finite, whose list overflowed, or for which fewer than k rows with a finite cost
+//      were found, is flagged; after the last chunk
+//   5. k_lut_topk_select<BRUTE = true> evaluates EVERY row for the flagged observations (same buffer, same arithmetic).
+//
+// Why the candidate tiles hold the answer.  Let c_k be the k-th smallest c_T over all rows and b any row with c_T(b) <= c_k
+// (every row of the answer, and every row tied with its last place).  The k rows a_1..a_k behind U are distinct, so
+// c_k <= max_i c_T(a_i) = c_T(a*).  With the bounds (i)-(v) above:
+//   a~(b) + Y <= c(b) + E_b <= c_T(b) + E_b + F_b <= c_T(a*) + E_b + F_b <= c(a*) + F_a* + E_b + F_b
+//             <= a~(a*) + Y + (E_a* + F_a*) + (E_b + F_b) <= U + Y + Delta,
+// Delta = (3 nb + 2 K + 13) u [(N_a* + Y) + (N_b + Y)] <= the k = 1 coefficient times 2 (Nmax + Y).  The Na / N* refinements
+// of the k = 1 path are NOT used: a* is not known, and N* rests on c(a) being the smallest cost.  So the tile of b has a
+// minimum <= thr and is a candidate; the select evaluates c_T(b) exactly and orders by (cost, row), which is the stable
+// argsort order, ties included.  If the k rows behind U had no finite direct cost (overflow), fewer than k rows would be
+// found among the candidates: that observation is flagged and decided by the brute force, like every other doubt.
+constexpr int LUT_TOPK_MAXK = 256;
+constexpr int LUT_TOPK_BUF = 512;            // LDS entries per wave of the select (>= LUT_TOPK_MAXK + 64)
+constexpr int LUT_TOPK_MAXPART = 512;        // partial results per observation the bound kernel holds in registers (16 / lane)
+constexpr int LUT_TOPK_CHUNK = 65536;        // observations per pass (bounds the partial results and candidate lists)
+// ctl words of the top-k call: [0] Nmax, [1] flagged observations, [2] candidate tiles (sum), [3] candidate tiles (maximum)
+constexpr int LUT_TOPK_CTL_WORDS = 4;
+__host__ __device__ inline int lut_topk_cap(int k) { return 4 * k + 64; }
+
+template <typename T> struct LutKey;
+template <> struct LutKey<float> {            // order-preserving map of a finite float onto an unsigned integer
+  static __device__ __forceinline__ unsigned long long key(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (unsigned long long)((u >> 31) ? ~u : (u | 0x80000000u));
+  }
+  static __device__ __forceinline__ float value(unsigned long long k) {
+    const unsigned q = (unsigned)k;
+    return __uint_as_float((q >> 31) ? (q ^ 0x80000000u) : ~q);
+  }
+  static constexpr int bits = 32;
+};
+template <> struct LutKey<double> {
+  static __device__ __forceinline__ unsigned long long key(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  }
+  static __device__ __forceinline__ double value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
+  }
+  static constexpr int bits = 64;
+};
+constexpr unsigned long long LUT_NOKEY = ~0ull;     // above every finite key of either type
+
+// One wave per observation of the chunk: U (k-th smallest finite partial value) and thr = U + Delta; resets the
+// observation's candidate count.  A non-finite thr (fewer than k finite values, a non-finite observation, overflow) makes
+// the select flag the observation.
+template <typename T>
+__global__ __launch_bounds__(256) void k_lut_topk_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
+                                                        const T* __restrict__ obs, const T* __restrict__ w,
+                                                        const T* __restrict__ centre, int nb, int64_t M, int npart, int k,
+                                                        T coef_ef, const unsigned long long* __restrict__ ctl,
+                                                        T* __restrict__ thr, int* __restrict__ cand_n) {
+  constexpr int NV = 2 * LUT_TOPK_MAXPART / 64;
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  unsigned long long v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int q = lane + 64 * i;
+    T c = (T)INFINITY;
+    if (q < npart) c = part_cost[(int64_t)q * M + m];
+    else if (q < 2 * npart) c = part_sec[(int64_t)(q - npart) * M + m];
+    v[i] = LutNum<T>::finite(c) ? LutKey<T>::key(c) : LUT_NOKEY;
+  }
+  auto count_le = [&](unsigned long long x) {          // finite values <= x, over the wave
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) n += v[i] <= x ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    return n;
+  };
+  const unsigned long long top = LutKey<T>::bits == 64 ? LUT_NOKEY - 1 : 0xffffffffull;
+  T U = (T)INFINITY;
+  if (count_le(top) >= k) {
+    // the smallest x with count(<= x) >= k: built bit by bit from the top, keeping count(<= x - 1) < k
+    unsigned long long x = 0;
+    for (int b = LutKey<T>::bits - 1; b >= 0; --b) {
+      const unsigned long long step = 1ull << b;
+      if (count_le(x + step - 1) < k) x += step;
+    }
+    U = LutKey<T>::value(x);
+  }
+  T ya = T(0);
+  if (lane < nb) {
+    const T yc = obs[m * nb + lane] - centre[lane];
+    const T wj = w ? w[lane] : T(1);
+    ya = (wj < T(0) ? -wj : wj) * yc * yc;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ya += __shfl_xor(ya, off, 64);
+  const T nmax = LutNum<T>::from_bits(ctl[0]);
+  if (lane == 0) {
+    thr[m] = U + (coef_ef * ((nmax + ya) + (nmax + ya)) + LutNum<T>::tiny);
+    cand_n[m] = 0;
+  }
+}
+
+// The collect scans: k_lut_scan_mfma's GEMM, then per tile and observation the minimum over ALL the tile's rows (the lane
+// groups exchange theirs) compared with thr; a hit is appended to the observation's list (order irrelevant: the select
+// sorts).  The list may overflow its capacity: the count keeps growing and the select flags the observation.
+template <int KS>
+__global__ __launch_bounds__(256, 2) void k_lut_collect_mfma(const float* __restrict__ tiles, const float* __restrict__ obs,
+                                                             const float* __restrict__ w, const float* __restrict__ centre, int nb,
+                                                             int64_t ntile, int64_t M, int nslice, const float* __restrict__ thr,
+                                                             int cap, int* __restrict__ cand_n, int* __restrict__ cand) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (32 * LUT_TO);
+  if (m0 >= M) return;
+  const int slice = blockIdx.y;
+  const int j = lane & 31, half = lane >> 5;
+  float bq[LUT_TO][KS], th[LUT_TO];
+#pragma unroll
+  for (int blk = 0; blk < LUT_TO; ++blk) {
+    const int64_t m = m0 + blk * 32 + j;
+    const int64_t mc = m < M ? m : M - 1;
+    // NaN compares false: nothing is appended past the chunk's end, nor for a non-finite threshold (the select flags m)
+    th[blk] = (m < M && LutNum<float>::finite(thr[mc])) ? thr[mc] : __builtin_nanf("");
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      const int col = 2 * kk + half;
+      bq[blk][kk] = col < nb ? -2.0f * (w ? w[col] : 1.0f) * (obs[mc * nb + col] - centre[col]) : (col == nb ? 1.0f : 0.0f);
+    }
+  }
+  const int64_t per = (ntile + nslice - 1) / nslice;
+  const int64_t t0 = per * slice;
+  const int64_t t1 = (t0 + per < ntile) ? t0 + per : ntile;
+  if (t0 >= t1) return;
+  const float* __restrict__ ap = tiles + t0 * (KS * 64) + lane;
+  float a[KS];
+#pragma unroll
+  for (int kk = 0; kk < KS; ++kk) a[kk] = ap[kk * 64];
+  for (int64_t t = t0; t < t1; ++t) {
+    if (t + 1 < t1) ap += KS * 64;
+    float an[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) an[kk] = ap[kk * 64];
+#pragma unroll
+    for (int blk = 0; blk < LUT_TO; ++blk) {
+      spart_f16v acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bq[blk][kk], acc, 0, 0, 0);
+      float mn;
+      asm("v_min3_f32 %0, %1, %2, %3" : "=v"(mn) : "v"(acc[0]), "v"(acc[1]), "v"(acc[2]));
+#pragma unroll
+      for (int r = 3; r < 15; r += 2) asm("v_min3_f32 %0, %1, %2, %3" : "=v"(mn) : "v"(mn), "v"(acc[r]), "v"(acc[r + 1]));
+      asm("v_min_f32 %0, %1, %2" : "=v"(mn) : "v"(mn), "v"(acc[15]));
+      const float o = __shfl_xor(mn, 32, 64);          // the other lane group's rows of the same tile and observation
+      mn = o < mn ? o : mn;
+      if (half == 0 && mn <= th[blk]) {
+        const int64_t m = m0 + blk * 32 + j;
+        const int pos = atomicAdd(&cand_n[m], 1);
+        if (pos < cap) cand[m * cap + pos] = (int)t;
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) a[kk] = an[kk];
+  }
+}
+
+template <int KS, int TO>
+__global__ __launch_bounds__(256, 2) void k_lut_collect_mfma64(const double* __restrict__ tiles, const double* __restrict__ obs,
+                                                               const double* __restrict__ w, const double* __restrict__ centre,
+                                                               int nb, int64_t ntile, int64_t M, int nslice,
+                                                               const double* __restrict__ thr, int cap, int* __restrict__ cand_n,
+                                                               int* __restrict__ cand) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (16 * TO);
+  if (m0 >= M) return;
+  const int slice = blockIdx.y;
+  const int j = lane & 15, q = lane >> 4;
+  double bq[TO][KS], th[TO];
+#pragma unroll
+  for (int blk = 0; blk < TO; ++blk) {
+    const int64_t m = m0 + blk * 16 + j;
+    const int64_t mc = m < M ? m : M - 1;
+    th[blk] = (m < M && LutNum<double>::finite(thr[mc])) ? thr[mc] : __builtin_nan("");
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      const int col = 4 * kk + q;
+      bq[blk][kk] = col < nb ? -2.0 * (w ? w[col] : 1.0) * (obs[mc * nb + col] - centre[col]) : (col == nb ? 1.0 : 0.0);
+    }
+  }
+  const int64_t per = (ntile + nslice - 1) / nslice;
+  const int64_t t0 = per * slice;
+  const int64_t t1 = (t0 + per < ntile) ? t0 + per : ntile;
+  if (t0 >= t1) return;
+  const double* __restrict__ ap = tiles + t0 * (KS * 64) + lane;
+  double a[KS];
+#pragma unroll
+  for (int kk = 0; kk < KS; ++kk) a[kk] = ap[kk * 64];
+  for (int64_t t = t0; t < t1; ++t) {
+    if (t + 1 < t1) ap += KS * 64;
+    double an[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) an[kk] = ap[kk * 64];
+#pragma unroll
+    for (int blk = 0; blk < TO; ++blk) {
+      spart_d4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], bq[blk][kk], acc, 0, 0, 0);
+      double mn = __builtin_fmin(__builtin_fmin(acc[0], acc[1]), __builtin_fmin(acc[2], acc[3]));
+      mn = __builtin_fmin(mn, __shfl_xor(mn, 16, 64));  // the four lane groups' rows of the same tile and observation
+      mn = __builtin_fmin(mn, __shfl_xor(mn, 32, 64));
+      if (q == 0 && mn <= th[blk]) {
+        const int64_t m = m0 + blk * 16 + j;
+        const int pos = atomicAdd(&cand_n[m], 1);
+        if (pos < cap) cand[m * cap + pos] = (int)t;
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) a[kk] = an[kk];
+  }
+}
+
+// (cost key, row) lexicographic
+__device__ __forceinline__ bool lut_key_less(unsigned long long ka, int ra, unsigned long long kb, int rb) {
+  return ka < kb || (ka == kb && ra < rb);
+}
+
+__device__ __forceinline__ void lut_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// ascending bitonic sort of a wave's LUT_TOPK_BUF (key, row) entries in LDS
+__device__ __forceinline__ void lut_topk_sort(unsigned long long* sk, int* sr, int lane) {
+  for (int size = 2; size <= LUT_TOPK_BUF; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = lane; i < LUT_TOPK_BUF / 2; i += 64) {
+        const int t = ((i & ~(stride - 1)) << 1) | (i & (stride - 1));
+        const int p = t | stride;
+        const unsigned long long kt = sk[t], kp = sk[p];
+        const int rt = sr[t], rp = sr[p];
+        const bool up = (t & size) == 0;
+        if (lut_key_less(kp, rp, kt, rt) == up) {
+          sk[t] = kp; sr[t] = rp;
+          sk[p] = kt; sr[p] = rt;
+        }
+      }
+      lut_wave_sync();
+    }
+  }
+}
+
+// The exact top-k of one observation over a stream of rows (64 per round, one per lane).  BRUTE = false: the rows of the
+// candidate tiles of chunk observation blockIdx.x * 4 + wave; BRUTE = true: every row, for the flagged observations.
+// LDS: 4 waves x LUT_TOPK_BUF x 12 bytes.
+template <typename T, int ROWS, bool BRUTE>
+__global__ __launch_bounds__(256) void k_lut_topk_select(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
+                                                         int nb, int64_t B, int64_t m_off, int64_t Mc, int k,
+                                                         const T* __restrict__ thr, const int* __restrict__ cand_n,
+                                                         const int* __restrict__ cand, int cap, unsigned long long* __restrict__ ctl,
+                                                         int* __restrict__ flag_list, int64_t* __restrict__ out_idx,
+                                                         T* __restrict__ out_cost) {
+  constexpr int NG = 64 / ROWS;
+  __shared__ unsigned long long skey[4][LUT_TOPK_BUF];
+  __shared__ int srow[4][LUT_TOPK_BUF];
+  __shared__ T ysm[4][32], wsm[32];
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  if (threadIdx.x < 32) wsm[threadIdx.x] = (w && (int)threadIdx.x < nb) ? w[threadIdx.x] : T(0);
+  __syncthreads();
+  unsigned long long* sk = skey[wv];
+  int* sr = srow[wv];
+  T* ys = ysm[wv];
+  const unsigned count = BRUTE ? (unsigned)ctl[1] : 0u;
+  const int64_t nwork = BRUTE ? (int64_t)count : Mc;
+  const int64_t stride_w = BRUTE ? (int64_t)gridDim.x * 4 : nwork;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + wv; item < nwork; item += stride_w) {
+    const int64_t m = BRUTE ? (int64_t)flag_list[item] : m_off + item;
+    const T yv = lane < nb ? obs[m * nb + lane] : T(0);
+    lut_wave_sync();                                   // (the previous item's reads of ys are done)
+    if (lane < 32) ys[lane] = yv;                      // zero-padded to 32: a padded band adds (w * 0) * 0 = 0 to the cost
+    lut_wave_sync();
+    int64_t* oi = out_idx + m * k;
+    T* oc = out_cost + m * k;
+    if (__all(LutNum<T>::finite(yv)) == 0) {           // every direct cost is NaN or +inf: nothing qualifies
+      for (int i = lane; i < k; i += 64) {
+        oi[i] = -1;
+        oc[i] = (T)INFINITY;
+      }
+      continue;
+    }
+    int64_t nrows = B;                                 // BRUTE: rows 0 .. B-1
+    int ncand = 0;
+    bool flag = false;
+    if (!BRUTE) {
+      ncand = cand_n[item];
+      flag = !LutNum<T>::finite(thr[item]) || ncand > cap;
+      if (lane == 0) {
+        atomicAdd(&ctl[2], (unsigned long long)ncand);
+        atomicMax(&ctl[3], (unsigned long long)ncand);
+      }
+      nrows = flag ? 0 : (int64_t)ncand * ROWS;
+    }
+    for (int i = lane; i < LUT_TOPK_BUF; i += 64) {
+      sk[i] = LUT_NOKEY;
+      sr[i] = 0x7fffffff;
+    }
+    lut_wave_sync();
+    int cnt = 0;
+    unsigned long long tk = LUT_NOKEY;                 // the k-th entry once k are held: only better ones are admitted
+    int tr = 0x7fffffff;
+    for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+      int64_t r = -1;
+      if (BRUTE) {
+        r = r0 + lane;
+      } else {
+        const int ci = (int)(r0 / ROWS) + lane / ROWS;
+        if (ci < ncand) r = (int64_t)cand[item * cap + ci] * ROWS + lane % ROWS;
+      }
+      unsigned long long key = LUT_NOKEY;
+      if (r >= 0 && r < B) {
+        SPART_NO_CONTRACT
+        const T* x = lut + r * nb;
+        T c = T(0);
+        for (int j = 0; j < nb; j += 4) {              // k_lut_reduce_exact's arithmetic, band for band
+          const T x0 = x[j], x1 = j + 1 < nb ? x[j + 1] : T(0), x2 = j + 2 < nb ? x[j + 2] : T(0), x3 = j + 3 < nb ? x[j + 3] : T(0);
+          const T d0 = x0 - ys[j], d1 = x1 - ys[j + 1], d2 = x2 - ys[j + 2], d3 = x3 - ys[j + 3];
+          if (w) {
+            c = c + (wsm[j] * d0) * d0;
+            c = c + (wsm[j + 1] * d1) * d1;
+            c = c + (wsm[j + 2] * d2) * d2;
+            c = c + (wsm[j + 3] * d3) * d3;
+          } else {
+            c = c + d0 * d0;
+            c = c + d1 * d1;
+            c = c + d2 * d2;
+            c = c + d3 * d3;
+          }
+        }
+        if (LutNum<T>::finite(c)) key = LutKey<T>::key(c);
+      }
+      const int ri = (int)r;
+      bool take = key != LUT_NOKEY && lut_key_less(key, ri, tk, tr);
+      unsigned long long mask = __ballot(take);
+      if (cnt + __builtin_popcountll(mask) > LUT_TOPK_BUF) {   // full: sort, keep the best k, raise the admission bar
+        lut_topk_sort(sk, sr, lane);
+        cnt = cnt < k ? cnt : k;
+        for (int i = cnt + lane; i < LUT_TOPK_BUF; i += 64) {
+          sk[i] = LUT_NOKEY;
+          sr[i] = 0x7fffffff;
+        }
+        if (cnt == k) {
+          tk = sk[k - 1];
+          tr = sr[k - 1];
+        }
+        lut_wave_sync();
+        take = take && lut_key_less(key, ri, tk, tr);
+        mask = __ballot(take);
+      }
+      if (take) {
+        const int pos = cnt + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        sk[pos] = key;
+        sr[pos] = ri;
+      }
+      cnt += __builtin_popcountll(mask);
+      lut_wave_sync();
+    }
+    lut_topk_sort(sk, sr, lane);
+    const int found = cnt < k ? cnt : k;
+    if (!BRUTE && (flag || found < k)) {               // let the brute force decide (it also writes the outputs)
+      if (lane == 0) {
+        const unsigned long long pos = atomicAdd(&ctl[1], 1ull);
+        flag_list[pos] = (int)m;
+      }
+      continue;
+    }
+    for (int i = lane; i < k; i += 64) {
+      const bool ok = i < found;
+      oi[i] = ok ? (int64_t)sr[i] : (int64_t)-1;
+      oc[i] = ok ? LutKey<T>::value(sk[i]) : (T)INFINITY;
+    }
+  }
+}
+
 }  // namespace spart

@@ -653,6 +653,46 @@ class Engine:
                                                                     ctypes.byref(nmax)))
         return idx, cost, {"brute_force": int(nbf.value), "nmax": float(nmax.value)}
 
+    def lut_topk(self, lut, obs, k, weights=None, dtype="float32", stats=False):
+        """The k nearest LUT rows per observation (include/spart_hip.h: spart_lut_topk): the same cost as lut_nearest, rows
+        ordered by (cost, row index) -- np.argsort(cost, kind="stable")[:k] with non-finite costs set to +inf -- bit-exact,
+        padded with (-1, +inf) when fewer than k rows have a finite cost.  1 <= k <= 256.
+        -> (idx (M, k) int64 tensor, cost (M, k) tensor); with ``stats=True`` also a dict with the number of observations that
+        took the brute-force path, the candidate tiles (sum and maximum per observation) and Nmax (spart_lut_topk_stats;
+        synchronises)."""
+        torch = self.torch
+        dt = DTYPES[dtype]
+        td = self._tdtype(dt)
+        k = int(k)
+        lut = torch.as_tensor(lut).to(device=self.device, dtype=td).contiguous()
+        obs = torch.as_tensor(obs).to(device=self.device, dtype=td).contiguous()
+        if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
+            raise ValueError("lut (B, nb) and obs (M, nb) must share nb")
+        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=td).contiguous()
+        if w is not None and w.numel() != lut.shape[1]:
+            raise ValueError(f"weights has {w.numel()} entries, expected nb = {lut.shape[1]}")
+        B, nb = lut.shape
+        M = obs.shape[0]
+        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
+        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
+        n = int(self.lib.spart_lut_topk_workspace_bytes(dt, B, nb, M, k))
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
+        self.calls["spart_lut_topk"] += 1
+        rc = self.lib.spart_lut_topk(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
+                                     w.data_ptr() if w is not None else None, k, idx.data_ptr(), cost.data_ptr(),
+                                     ws.data_ptr(), ctypes.c_size_t(ws.numel()), self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        if not stats:
+            return idx, cost
+        nbf, ncand, mcand, nmax = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        if M > 0:
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
+                                                                         ctypes.byref(nbf), ctypes.byref(ncand),
+                                                                         ctypes.byref(mcand), ctypes.byref(nmax)))
+        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
+                           "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
+
     def profile(self, max_calls):
         """bracket the band kernel of the next ``max_calls`` run() calls with HIP events (0 = off)."""
         _lib.check(self.lib, self.ctx, self.lib.spart_profile_enable(self.ctx, int(max_calls)))

@@ -12,6 +12,7 @@ All .npy files are plain numpy arrays (np.load(..., mmap_mode="r") works for tab
 import ctypes
 import json
 import os
+import warnings
 
 import numpy as np
 
@@ -278,16 +279,19 @@ def load_lut(path, mmap=True):
     return meta, np.load(os.path.join(path, "params.npy"), mmap_mode=mode), cols
 
 
-def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, group=None, device=None, stats=False):
+def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, group=None, device=None, stats=False, k=None):
     """Nearest LUT row per observed spectrum (spart_lut_nearest: exact argmin of the weighted squared distance, lowest index
     on ties) over a LUT directory written by generate_lut (``lut`` = its path) or an in-memory (B, nb) array.
+    ``k`` = None: (idx (M,) int64 numpy, cost (M,) numpy).  An integer ``k`` (1 ... 256): the k nearest rows per observation
+    (spart_lut_topk: ordered by cost, then row index; padded with (-1, +inf)) as (idx (M, k), cost (M, k)).
 
     ``shard=True`` under a process group: every rank searches ITS contiguous block of rows (read from the directory's memmap:
-    only those rows are ever touched) and ONE all_gather of (cost, global row) per observation settles the winner
-    (sharding.lut_nearest_sharded); every rank returns the same (idx (M,) int64 numpy, cost (M,) numpy), equal bit for bit to
-    the single-process search.  ``obs`` must be the same on every rank."""
+    only those rows are ever touched) and ONE all_gather of (cost, global row) per observation (and place) settles the
+    result (sharding.lut_nearest_sharded / lut_topk_sharded); every rank returns the same arrays, equal bit for bit to the
+    single-process search.  ``obs`` must then be the same on every rank.  ``shard=False`` never issues a collective, whether
+    or not a process group is initialised: each process searches the whole table for its own ``obs``."""
     import torch
-    from .sharding import lut_nearest_sharded, shard_bounds
+    from .sharding import lut_nearest_sharded, lut_topk_sharded, shard_bounds
     if isinstance(lut, (str, os.PathLike)):
         meta, _, cols = load_lut(lut)
         table = cols[column]
@@ -308,14 +312,72 @@ def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, 
         if stats:
             info.update(r[2])
         return r[0], r[1]
-    comm = None
+
+    def topk(l, ob, kk):
+        r = eng.lut_topk(l, ob, kk, weights=weights, dtype=dtype, stats=stats)
+        if stats:
+            info.update(r[2])
+        return r[0], r[1]
     if world > 1:
         import torch.distributed as dist
-        if dist.get_backend(group) != "nccl":          # gloo moves host tensors: the (M, 2) winners travel through the host
-            comm = "cpu"
-    idx, cost = lut_nearest_sharded(local, lo, o, nearest, group if world > 1 else None, comm_device=comm)
+        comm = "cpu" if dist.get_backend(group) != "nccl" else None   # gloo moves host tensors: the winners travel through the host
+        if k is None:
+            idx, cost = lut_nearest_sharded(local, lo, o, nearest, group, comm_device=comm)
+        else:
+            idx, cost = lut_topk_sharded(local, lo, o, int(k), topk, group, comm_device=comm)
+    else:                                              # one process, the whole table: no collective, whatever is initialised
+        M = o.shape[0]
+        shape = (M,) if k is None else (M, int(k))
+        if local.shape[0] > 0 and M > 0:
+            idx, cost = nearest(local, o) if k is None else topk(local, o, int(k))
+        else:
+            if k is not None and not 1 <= int(k) <= 256:
+                raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+            idx = torch.full(shape, -1, dtype=torch.int64)
+            cost = torch.full(shape, float("inf"), dtype=td)
     out = (idx.cpu().numpy(), cost.cpu().numpy())
     return out + (dict(info, rows=(lo, hi)),) if stats else out
+
+
+def summarise_rows(params, idx, block_rows=1 << 18):
+    """mean / median / std (numpy's, ddof = 0) of the parameter rows ``params[idx[m]]`` per observation, padding (-1)
+    excluded: params (B, P) array or memmap, idx (M, k) int64 -> three (M, P) float64 arrays (NaN where an observation has no
+    row).  Works in blocks of observations of about ``block_rows`` gathered rows, reading only the rows it needs, so that the
+    host never holds an (M * k, P) copy."""
+    idx = np.asarray(idx)
+    M, k = idx.shape
+    P = params.shape[1]
+    res = [np.full((M, P), np.nan) for _ in range(3)]
+    mb = max(1, int(block_rows) // max(k, 1))
+    for m0 in range(0, M, mb):
+        ii = idx[m0:m0 + mb]
+        ok = ii >= 0
+        if not ok.any():
+            continue
+        rows, inv = np.unique(ii[ok], return_inverse=True)
+        vals = np.asarray(params[rows], dtype=np.float64)            # sorted unique rows: a memmap reads only those
+        g = np.full(ii.shape + (P,), np.nan)
+        g[ok] = vals[inv]
+        full = ok.all(axis=1)
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)          # all-padding observations stay NaN
+            for r, f in zip(res, (np.nanmean, np.nanmedian, np.nanstd)):
+                r[m0:m0 + mb] = f(g, axis=1)
+            if full.any():                                          # the common case: numpy's own mean / median / std
+                gf = g[full]
+                for r, f in zip(res, (np.mean, np.median, np.std)):
+                    r[m0:m0 + mb][full] = f(gf, axis=1)
+    return res
+
+
+def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None):
+    """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
+    mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
+    -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, 27) float64, names (the 27 parameter names)."""
+    idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
+    _, params, _ = load_lut(lut_dir)
+    mean, median, std = summarise_rows(params, idx)
+    return {"idx": idx, "cost": cost, "mean": mean, "median": median, "std": std, "names": list(workloads.PARAM_NAMES)}
 
 
 def lut_to_parquet(path, parquet_path, compression="gzip"):

@@ -9,7 +9,9 @@ The LUT rows of SURVEY.md §8(f) shard the same way (contiguous blocks of ``ceil
   .npy files at its own rows -- no collective on the data path at all, rank 0 writes the manifest;
 * inversion (lut_nearest_sharded below): every rank finds the exact nearest row of ITS block for every observation, then
   ONE all_gather of (cost, global row index) per observation -- 16 bytes x M per rank -- and the same selection rule on
-  every rank: lowest cost, lowest row index on ties (the reference's np.argmin rule, SPART.py:381-387)."""
+  every rank: lowest cost, lowest row index on ties (the reference's np.argmin rule, SPART.py:381-387);
+* the k nearest rows (lut_topk_sharded): every rank's exact top k, ONE all_gather of (cost, global row) per observation and
+  place -- 16 bytes x M x k per rank -- and a merge by (cost, row) on every rank."""
 
 
 def shard_bounds(B, world, rank):
@@ -133,3 +135,54 @@ def lut_nearest_sharded(lut_local, row0, obs, nearest, group=None, comm_device=N
     allp = torch.stack(bufs)                                                                 # (W, M, 2)
     costs = torch.stack([_cost_from_bits(allp[r, :, 0], cost.dtype) for r in range(world)])
     return select_nearest(costs, allp[:, :, 1])
+
+
+def select_nearest_k(costs, idxs):
+    """The k best per observation among per-shard top-k lists: costs (W, M, k) float, idxs (W, M, k) int64 GLOBAL row indices
+    (-1 = padding, cost +inf).  Ordered by (cost, row index); padded with (-1, +inf) when fewer than k rows have a finite
+    cost.  Exact: the merged list is the stable argsort of the union, and every row of the global top k is in its own
+    shard's top k.  Pure tensor arithmetic on whatever device the inputs live on -> (idx (M, k), cost (M, k))."""
+    import torch
+    W, M, k = costs.shape
+    big = torch.iinfo(torch.int64).max
+    c = costs.permute(1, 0, 2).reshape(M, W * k)
+    i = idxs.permute(1, 0, 2).reshape(M, W * k)
+    ok = (i >= 0) & torch.isfinite(c)
+    c = torch.where(ok, c, torch.full_like(c, float("inf")))
+    i = torch.where(ok, i, torch.full_like(i, big))
+    o = torch.argsort(i, dim=1, stable=True)                     # row index ascending, then a stable sort by cost
+    c, i = torch.gather(c, 1, o), torch.gather(i, 1, o)
+    o = torch.argsort(c, dim=1, stable=True)[:, :k]
+    c, i = torch.gather(c, 1, o), torch.gather(i, 1, o)
+    none = i == big
+    return torch.where(none, torch.full_like(i, -1), i), c
+
+
+def lut_topk_sharded(lut_local, row0, obs, k, topk, group=None, comm_device=None):
+    """lut_nearest_sharded for the k nearest rows: topk(lut_local, obs, k) -> (idx (M, k) local rows or -1, cost (M, k)) is
+    the exact single-device search (Engine.lut_topk; the CPU tests inject a brute force).  ONE all_gather of an (M, k, 2)
+    int64 tensor (cost bits, global row) and select_nearest_k on every rank: every rank returns the same (idx (M, k) GLOBAL,
+    cost (M, k)), bit-identical to the single-device search over the whole LUT (with lut_nearest_sharded's caveat on rows
+    whose centred norm overflows)."""
+    import torch
+    import torch.distributed as dist
+
+    M = obs.shape[0]
+    if lut_local.shape[0] > 0 and M > 0:
+        idx, cost = topk(lut_local, obs, k)
+        idx = torch.where(idx >= 0, idx + int(row0), idx)
+    else:
+        cdt = obs.dtype if obs.dtype in (torch.float32, torch.float64) else torch.float32
+        idx = torch.full((M, k), -1, dtype=torch.int64, device=obs.device)
+        cost = torch.full((M, k), float("inf"), dtype=cdt, device=obs.device)
+    if comm_device is not None:
+        idx, cost = idx.to(comm_device), cost.to(comm_device)
+    if not (dist.is_available() and dist.is_initialized()):
+        return idx, cost
+    world = dist.get_world_size(group)
+    pack = torch.stack([_cost_bits(cost), idx.to(torch.int64)], dim=2).contiguous()         # (M, k, 2) int64
+    bufs = [torch.empty_like(pack) for _ in range(world)]
+    dist.all_gather(bufs, pack, group=group)
+    allp = torch.stack(bufs)                                                                 # (W, M, k, 2)
+    costs = torch.stack([_cost_from_bits(allp[r, :, :, 0], cost.dtype) for r in range(world)])
+    return select_nearest_k(costs, allp[:, :, :, 1])

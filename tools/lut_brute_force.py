@@ -1,4 +1,4 @@
-"""Brute-force checkers of spart_lut_nearest (tests/ and bench.py; tooling, not product).
+"""Brute-force checkers of spart_lut_nearest and spart_lut_topk (tests/ and bench.py; tooling, not product).
 
 The cost is DEFINED (include/spart_hip.h) as the sequential evaluation, in the call's dtype and without fused multiply-adds,
 
@@ -62,4 +62,67 @@ def brute_force_torch(lut, obs, w=None, max_elems=1 << 27):
         ok = cmin < inf
         idx[m0:m0 + mb] = torch.where(ok, first, torch.full_like(first, -1))
         cost[m0:m0 + mb] = cmin
+    return idx, cost
+
+
+def _topk_from_costs_numpy(c, k):
+    """c (B,) costs -> the first k of the stable argsort with non-finite costs as +inf, padded with (-1, +inf)"""
+    c = np.where(np.isfinite(c), c, np.inf)
+    o = np.argsort(c, kind="stable")[:k]
+    o = o[c[o] < np.inf]
+    idx = np.full(k, -1, dtype=np.int64)
+    cost = np.full(k, np.inf, dtype=c.dtype)
+    idx[:len(o)], cost[:len(o)] = o, c[o]
+    return idx, cost
+
+
+def brute_force_topk_numpy(lut, obs, k, w=None):
+    """spart_lut_topk's definition: per observation the first k entries of np.argsort(c, kind="stable") after non-finite
+    costs are set to +inf (rows of a non-finite cost never appear; (-1, +inf) pads) -> (idx (M, k) int64, cost (M, k))"""
+    lut = np.ascontiguousarray(lut)
+    dt = lut.dtype
+    obs = np.ascontiguousarray(obs, dtype=dt)
+    w = None if w is None else np.asarray(w, dtype=dt)
+    B, nb = lut.shape
+    M = obs.shape[0]
+    idx = np.full((M, k), -1, dtype=np.int64)
+    cost = np.full((M, k), np.inf, dtype=dt)
+    cols = [np.ascontiguousarray(lut[:, j]) for j in range(nb)]
+    with np.errstate(all="ignore"):
+        for m in range(M):
+            c = np.zeros(B, dtype=dt)
+            for j in range(nb):
+                d = cols[j] - obs[m, j]
+                t = d if w is None else w[j] * d
+                c = c + t * d
+            idx[m], cost[m] = _topk_from_costs_numpy(c, k)
+    return idx, cost
+
+
+def brute_force_topk_torch(lut, obs, k, w=None, max_elems=1 << 27):
+    """the same with eager torch ops (one kernel per operation: no contraction), in blocks of observations: tensors of one
+    dtype on one device -> (idx (M, k) int64, cost (M, k)).  The (cost, row) order is a stable sort by cost of the rows in
+    ascending order, i.e. the lowest row first among equal costs."""
+    import torch
+    B, nb = lut.shape
+    M = obs.shape[0]
+    inf = float("inf")
+    cols = [lut[:, j].contiguous() for j in range(nb)]
+    idx = torch.full((M, k), -1, dtype=torch.int64, device=lut.device)
+    cost = torch.full((M, k), inf, dtype=lut.dtype, device=lut.device)
+    kk = min(k, B)
+    mb = max(1, min(M, max_elems // max(B, 1)))
+    for m0 in range(0, M, mb):
+        o = obs[m0:m0 + mb]
+        c = torch.zeros((o.shape[0], B), dtype=lut.dtype, device=lut.device)
+        for j in range(nb):
+            d = cols[j][None, :] - o[:, j][:, None]
+            t = d if w is None else w[j] * d
+            c = c + t * d
+        c = torch.where(torch.isfinite(c), c, torch.full_like(c, inf))
+        s, order = torch.sort(c, dim=1, stable=True)
+        s, order = s[:, :kk], order[:, :kk]
+        ok = s < inf
+        idx[m0:m0 + mb, :kk] = torch.where(ok, order, torch.full_like(order, -1))
+        cost[m0:m0 + mb, :kk] = s
     return idx, cost
