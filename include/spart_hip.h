@@ -57,8 +57,9 @@ extern "C" {
  * round's header -- e.g. through SPART_HIP_LIB -- is refused instead of being called with shifted arguments).
  *   6: spart_materialize.lidf_in / .nlayers, spart_sailh_batch(lidf_in, nlayers), spart_abi_version itself
  *   7: spart_workspace_bandsum
- *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats */
-#define SPART_ABI_VERSION 8
+ *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats
+ *   9: spart_lut_topk_wide, spart_lut_topk_wide_workspace_bytes, spart_lut_topk_wide_stats; sensors of up to SPART_NWLS bands */
+#define SPART_ABI_VERSION 9
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -81,7 +82,8 @@ typedef struct spart_tables {
   const double *GSV;                                                /* (2001,3) row-major, bsm.py:45 */
   const double *nw;                                                 /* bsm.py:55 */
   const double *Ea;                                                 /* SPART.py:181 */
-  int32_t nb;                                                       /* sensor bands */
+  int32_t nb;                                                       /* sensor bands, 0 ... SPART_NWLS (2162: one per evaluation
+                                                                       band of the model, thermal ones included); any centres */
   const double *wl_smac;                                            /* (nb,) band centres, nm */
   const double *coef;                                               /* (48, nb) row-major, rows in smac.py:44-92 order
                                                                        (ah2o nh2o ao3 no3 ao2 no2 po2 aco2 nco2 pco2 ach4 nch4 pch4
@@ -270,6 +272,25 @@ int spart_lut_topk(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut
  * per observation, and Nmax.  Synchronises the device. */
 int spart_lut_topk_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
                          int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nmax);
+
+/* The k nearest LUT rows for ANY 1 <= nb <= SPART_NWLS (hyperspectral sensors): word for word spart_lut_topk's semantics -- the
+ * same cost c, evaluated the same way, the same (cost, row) order, the same rules for non-finite rows, observations and norms,
+ * (-1, +inf) padding, 1 <= k <= 256, B and M <= 2e9 -- so for nb <= 31 its output equals spart_lut_topk's bit for bit, and
+ * column 0 is the exact nearest row (k = 1: spart_lut_nearest's answer).  An nb outside 1..SPART_NWLS is a bad size
+ * (SPART_ERR_INVALID).
+ * How (csrc/spart_lut.h, "wide top-k", derives the bound): the same filter-then-exact structure with K streamed instead of
+ * held in registers -- a norm pass over the LUT (no copy of it: the workspace grows with B and with M nb, never with B nb),
+ * a GEMM scan on the matrix cores that stages LUT rows and pre-scaled observations through LDS in chunks of 32 bands, a
+ * collecting second GEMM pass, one wave per observation evaluating the candidate rows with c itself, and a brute force for
+ * the observations the filter cannot settle.  Observations go in chunks of 16 384. */
+size_t spart_lut_topk_wide_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k);
+int spart_lut_topk_wide(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut, int64_t M, const void *obs,
+                        const void *weights, int k, int64_t *idx, void *cost, void *workspace, size_t workspace_bytes,
+                        void *stream);
+/* Diagnostics of the LAST spart_lut_topk_wide call that used `workspace` (same dtype, B, nb, M, k), as spart_lut_topk_stats:
+ * brute-forced observations, candidate tiles (32 rows for SPART_F32, 16 for SPART_F64; sum and maximum) and Nmax. */
+int spart_lut_topk_wide_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
+                              int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nmax);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

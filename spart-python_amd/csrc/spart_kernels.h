@@ -17,7 +17,7 @@ namespace spart {
 constexpr int TILE = 256;                 // lanes (= bands) per workgroup
 constexpr int NTILE = 8;                  // 8 * 256 = 2048 >= NEVAL
 constexpr int NTILE_FULL = 9;             // 9 * 256 >= 2162 (standalone SAILH: arbitrary thermal inputs)
-constexpr int MAX_NB = 64;
+constexpr int MAX_NB = NWLS;             // sensor bands: any number up to the model's 2162 evaluation bands
 
 // XCD-aware blockIdx -> (chunk, tile) map (cdna guide T1).  Workgroups are dealt round-robin over the 8
 // XCDs, so blocks b and b + 8 share an XCD (a speed assumption only).  Within each group of 64 consecutive

@@ -679,19 +679,12 @@ template <> struct LutKey<double> {
 };
 constexpr unsigned long long LUT_NOKEY = ~0ull;     // above every finite key of either type
 
-// One wave per observation of the chunk: U (k-th smallest finite partial value) and thr = U + Delta; resets the
-// observation's candidate count.  A non-finite thr (fewer than k finite values, a non-finite observation, overflow) makes
-// the select flag the observation.
+// U of observation m: the k-th smallest finite value among its 2 npart partial values (best, sec); +inf if fewer than k are
+// finite.  Called by the whole wave (lane = threadIdx.x & 63); every lane returns U.
 template <typename T>
-__global__ __launch_bounds__(256) void k_lut_topk_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
-                                                        const T* __restrict__ obs, const T* __restrict__ w,
-                                                        const T* __restrict__ centre, int nb, int64_t M, int npart, int k,
-                                                        T coef_ef, const unsigned long long* __restrict__ ctl,
-                                                        T* __restrict__ thr, int* __restrict__ cand_n) {
+__device__ __forceinline__ T lut_topk_kth(const T* __restrict__ part_cost, const T* __restrict__ part_sec, int64_t m, int64_t M,
+                                          int npart, int k, int lane) {
   constexpr int NV = 2 * LUT_TOPK_MAXPART / 64;
-  const int lane = threadIdx.x & 63;
-  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= M) return;                                  // (whole wave)
   unsigned long long v[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -720,6 +713,22 @@ __global__ __launch_bounds__(256) void k_lut_topk_bound(const T* __restrict__ pa
     }
     U = LutKey<T>::value(x);
   }
+  return U;
+}
+
+// One wave per observation of the chunk: U (k-th smallest finite partial value) and thr = U + Delta; resets the
+// observation's candidate count.  A non-finite thr (fewer than k finite values, a non-finite observation, overflow) makes
+// the select flag the observation.
+template <typename T>
+__global__ __launch_bounds__(256) void k_lut_topk_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
+                                                        const T* __restrict__ obs, const T* __restrict__ w,
+                                                        const T* __restrict__ centre, int nb, int64_t M, int npart, int k,
+                                                        T coef_ef, const unsigned long long* __restrict__ ctl,
+                                                        T* __restrict__ thr, int* __restrict__ cand_n) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  const T U = lut_topk_kth<T>(part_cost, part_sec, m, M, npart, k, lane);
   T ya = T(0);
   if (lane < nb) {
     const T yc = obs[m * nb + lane] - centre[lane];
@@ -967,6 +976,414 @@ __global__ __launch_bounds__(256) void k_lut_topk_select(const T* __restrict__ l
             c = c + d1 * d1;
             c = c + d2 * d2;
             c = c + d3 * d3;
+          }
+        }
+        if (LutNum<T>::finite(c)) key = LutKey<T>::key(c);
+      }
+      const int ri = (int)r;
+      bool take = key != LUT_NOKEY && lut_key_less(key, ri, tk, tr);
+      unsigned long long mask = __ballot(take);
+      if (cnt + __builtin_popcountll(mask) > LUT_TOPK_BUF) {   // full: sort, keep the best k, raise the admission bar
+        lut_topk_sort(sk, sr, lane);
+        cnt = cnt < k ? cnt : k;
+        for (int i = cnt + lane; i < LUT_TOPK_BUF; i += 64) {
+          sk[i] = LUT_NOKEY;
+          sr[i] = 0x7fffffff;
+        }
+        if (cnt == k) {
+          tk = sk[k - 1];
+          tr = sr[k - 1];
+        }
+        lut_wave_sync();
+        take = take && lut_key_less(key, ri, tk, tr);
+        mask = __ballot(take);
+      }
+      if (take) {
+        const int pos = cnt + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        sk[pos] = key;
+        sr[pos] = ri;
+      }
+      cnt += __builtin_popcountll(mask);
+      lut_wave_sync();
+    }
+    lut_topk_sort(sk, sr, lane);
+    const int found = cnt < k ? cnt : k;
+    if (!BRUTE && (flag || found < k)) {               // let the brute force decide (it also writes the outputs)
+      if (lane == 0) {
+        const unsigned long long pos = atomicAdd(&ctl[1], 1ull);
+        flag_list[pos] = (int)m;
+      }
+      continue;
+    }
+    for (int i = lane; i < k; i += 64) {
+      const bool ok = i < found;
+      oi[i] = ok ? (int64_t)sr[i] : (int64_t)-1;
+      oc[i] = ok ? LutKey<T>::value(sk[i]) : (T)INFINITY;
+    }
+  }
+}
+
+// ---- wide top-k (spart_lut_topk_wide): the k rows of smallest c_T for any 1 <= nb <= 2162
+//
+// The answer is spart_lut_topk's, word for word (the same c_T, order, non-finite rules and padding); only the filter is built
+// for long spectra.  Nothing of the LUT is copied or re-laid out (a 1M x 2001 float32 LUT is 8 GB): the workspace grows with B
+// (one norm per row) and with the observations of a chunk times nb, never with B x nb.
+//   1. k_lut_centre          as above (column centres c_j)
+//   2. k_lutw_norm           n_b = sum_j w_j x'_bj^2 per row (+inf for a row k_lut_prep would reject: a non-finite entry or
+//                            an overflowing norm, decided by k_lut_prep's own arithmetic) and Nmax.  float32: n_b is
+//                            accumulated in float64 and rounded once.
+//   per chunk of at most LUTW_CHUNK observations:
+//   3. k_lutw_obs            Bq = fl(-2 w_j y'_j) (the narrow scan's rounding), 1 in column nb, zero-padded to nbp = a multiple
+//                            of LUTW_KC; Y = sum_j |w_j| y'_j^2 (float64, rounded once; non-finite for a non-finite observation)
+//   4. k_lutw_gemm<false>    the GEMM a~(b, m) = [x'_b, n_b] . Bq_m with K streamed: a workgroup stages 128 (float32) / 64
+//                            (float64) LUT rows and as many observations, LUTW_KC bands at a time, through LDS, centring the
+//                            rows on the way in (fl(x - c_j), k_lut_prep's rounding; rows with n_b = +inf enter as
+//                            (0, .., 0, +inf)), on v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64.  Each K chunk has its
+//                            own accumulators, added to a running sum: the rounding chain of a filter value is
+//                            LUTW_KC + nch long, not nb.  Per (slice, row half of the workgroup, lane group) and observation
+//                            it keeps the two smallest tile minima: filter values of two distinct rows, no row behind two
+//                            partial results (the narrow scan's invariant)
+//   5. k_lutw_bound          U = the k-th smallest partial value (lut_topk_kth), thr = U + Delta (below)
+//   6. k_lutw_gemm<true>     the same GEMM; every tile (32 / 16 rows) with a minimum <= thr goes on the candidate list
+//   7. k_lutw_select<false>  one wave per observation evaluates the candidate rows with c_T (the observation and the
+//                            weights in dynamic LDS, nb entries each) and keeps the k best: k_lut_topk_select's buffer
+//   8. k_lutw_select<true>   brute force over every row for the flagged observations (lanes over rows, bands in order)
+//
+// Delta.  With the notation of the top of this file, a~(b) + Y - c(b) is bounded term by term as for the narrow scan except:
+//   (ii)  float32: n_b = fl(sum w x'^2 accumulated in float64): <= (1 + (nb + 2) 2^-29) u N_b <= 1.01 u N_b;
+//         float64: (nb + 2) u N_b as before;
+//   (iv)  each term of the dot product (n_b included) passes through at most LUTW_KC roundings inside its chunk's MFMA chain
+//         and nch - 1 additions of chunk sums (the first chunk is copied, not added): h = LUTW_KC + nch + 1 is a safe depth,
+//         and the error is <= h u (|n_b| + 2 sum |w x' y'|) <= 2 h u (N_b + Y);
+//   =>    E_b <= ce (N_b + Y),  ce = (4 + nn + 1 + 2 h) u,  nn = 1.01 (float32) / nb + 2 (float64)
+//   (v)   the direct evaluation: |c_T(b) - c(b)| <= F_b = (nb + 3) u sum |w| d_b^2.
+// For the k rows a_1..a_k behind U and a* the one of largest c_T (the narrow argument): every b with c_T(b) <= c_k satisfies
+//     a~(b) <= U + E_a* + E_b + F_a* + F_b.
+// E: N_a*, N_b <= Nmax.  F: with non-negative weights sum |w| d^2 = c itself, and
+//     c(a*) <= a~(a*) + Y + E_a* <= C1 = U + Y + ce (Nmax + Y),   c(b) <= c(a*) (1 + f) / (1 - f),  f = (nb + 3) u,
+// so F_a* + F_b <= 2.01 (nb + 3) u max(C1, 0).  That is the term that made the narrow Delta grow with 3 nb: here it scales with
+// the cost of the rows that matter, not with their norms.  With a negative weight F falls back to (2 nb + 6) u (Nmax + Y) per row.
+//     Delta = 2 ce (Nmax + Y) + F,   every coefficient times 1.01,
+// evaluated in float64 and rounded up to the dtype (thr = t + 4 u |t| + tiny covers the rounding of t = U + Delta itself).
+// float32, nb = 211: ce = 86 u (the narrow rule's 2 x (3 nb + 2 K + 16) u would be 2 146 u per (Nmax + Y)).
+constexpr int LUTW_KC = 32;                  // bands per K chunk staged through LDS
+constexpr int LUTW_TR = 2, LUTW_TB = 2;      // LUT tiles x observation blocks per wave; the four waves are 2 x 2
+constexpr int LUTW_CHUNK = 16384;            // observations per pass (bounds Bq, the partial results and the candidate lists)
+constexpr int LUTW_SELECT_BLOCKS = 8192;     // single-wave workgroups of the brute-force select
+
+template <typename T> struct LutWide;
+template <> struct LutWide<float> {          // v_mfma_f32_32x32x2_f32: 32 rows x 32 observations, K steps of 2, 2 lane groups
+  static constexpr int ROWS = 32, KSTEP = 2, NACC = 16;
+  typedef spart_f16v acc_t;
+  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+};
+template <> struct LutWide<double> {         // v_mfma_f64_16x16x4_f64: 16 x 16, K steps of 4, 4 lane groups
+  static constexpr int ROWS = 16, KSTEP = 4, NACC = 4;
+  typedef spart_d4v acc_t;
+  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+};
+
+// one thread per LUT row: k_lut_prep's acceptance test and Nmax, and the filter norm n_b (+inf for a rejected row)
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutw_norm(const T* __restrict__ lut, const T* __restrict__ w, const T* __restrict__ centre,
+                                                   int nb, int64_t B, T* __restrict__ norm, unsigned long long* __restrict__ ctl) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  T na = T(0);
+  if (row < B) {
+    bool ok = true;
+    T n = T(0);
+    double nd = 0.0;
+    const T* x = lut + row * nb;
+    for (int j = 0; j < nb; ++j) {                     // (k_lut_prep's loop, plus the float64 accumulation)
+      const T v = x[j];
+      ok = ok && LutNum<T>::finite(v);
+      const T xc = v - centre[j];
+      const T wj = w ? w[j] : T(1);
+      n += wj * xc * xc;
+      na += (wj < T(0) ? -wj : wj) * xc * xc;
+      if (sizeof(T) == 4) nd += (double)wj * (double)xc * (double)xc;
+    }
+    ok = ok && LutNum<T>::finite(n) && LutNum<T>::finite(na);
+    if (!ok) na = T(0);
+    norm[row] = ok ? (sizeof(T) == 4 ? (T)nd : n) : (T)INFINITY;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const T o = __shfl_down(na, off, 64);
+    na = o > na ? o : na;
+  }
+  if ((threadIdx.x & 63) == 0 && na > T(0)) atomicMax(&ctl[0], LutNum<T>::bits(na));
+}
+
+// one wave per observation of the chunk: the GEMM operand row Bq (nbp entries) and Y
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutw_obs(const T* __restrict__ obs, const T* __restrict__ w, const T* __restrict__ centre,
+                                                  int nb, int nbp, int64_t M, T* __restrict__ bq, T* __restrict__ ya) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  double y = 0.0;
+  for (int j = lane; j < nbp; j += 64) {
+    T v = j == nb ? T(1) : T(0);
+    if (j < nb) {
+      const T wj = w ? w[j] : T(1);
+      const T yc = obs[m * nb + j] - centre[j];
+      v = T(-2) * wj * yc;                             // the narrow scan's operand, -2.0 * w * (y - c)
+      y += (double)(wj < T(0) ? -wj : wj) * (double)yc * (double)yc;
+    }
+    bq[m * nbp + j] = v;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) y += __shfl_xor(y, off, 64);
+  if (lane == 0) ya[m] = (T)y;
+}
+
+// The K-streamed GEMM of the scan (COLLECT = false: partial results) and of the collect pass (COLLECT = true: candidate
+// tiles).  Grid (observation blocks of 2 TB ROWS, slices of row blocks of 2 TR ROWS); wave (wr, wc) computes TR tiles x TB
+// observation blocks of the workgroup's block.
+template <typename T, bool COLLECT>
+__global__ __launch_bounds__(256) void k_lutw_gemm(const T* __restrict__ lut, const T* __restrict__ norm, const T* __restrict__ centre,
+                                                   int nb, int64_t B, const T* __restrict__ bq, int nbp, int64_t M, int nslice,
+                                                   T* __restrict__ part_cost, T* __restrict__ part_sec, const T* __restrict__ thr,
+                                                   int cap, int* __restrict__ cand_n, int* __restrict__ cand) {
+  using W = LutWide<T>;
+  constexpr int ROWS = W::ROWS, KSTEP = W::KSTEP, NACC = W::NACC, G = 64 / ROWS, KC = LUTW_KC;
+  constexpr int TR = LUTW_TR, TB = LUTW_TB, RWG = 2 * TR * ROWS, OWG = 2 * TB * ROWS;
+  constexpr int PA = RWG + 1, PB = OWG + 1;            // LDS row pitches ([k][row]; +1: the transposing stores spread over banks)
+  __shared__ T As[KC * PA], Bs[KC * PB], nsm[RWG];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int col = lane % ROWS, grp = lane / ROWS;      // operand lane: row / observation col of the tile, k = grp
+  const int64_t m0 = (int64_t)blockIdx.x * OWG;
+  const int slice = blockIdx.y;
+  const int64_t ntile = (B + ROWS - 1) / ROWS;
+  const int64_t nrb = (B + RWG - 1) / RWG;
+  const int64_t per = (nrb + nslice - 1) / nslice;
+  const int64_t rb0 = per * slice;
+  const int64_t rb1 = rb0 + per < nrb ? rb0 + per : nrb;
+  T best[TB], sec[TB], th[TB];
+#pragma unroll
+  for (int b2 = 0; b2 < TB; ++b2) {
+    const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+    best[b2] = (T)INFINITY;
+    sec[b2] = (T)INFINITY;
+    // NaN compares false: nothing is appended past the chunk's end, nor for a non-finite threshold (the select flags m)
+    th[b2] = (T)__builtin_nan("");
+    if (COLLECT && m < M && LutNum<T>::finite(thr[m])) th[b2] = thr[m];
+  }
+  for (int64_t rb = rb0; rb < rb1; ++rb) {
+    const int64_t r0 = rb * RWG;
+    __syncthreads();                                   // (the previous block's LDS is read)
+    if (tid < RWG) nsm[tid] = r0 + tid < B ? norm[r0 + tid] : (T)INFINITY;
+    typename W::acc_t run[TR][TB];
+    for (int k0 = 0; k0 < nbp; k0 += KC) {
+      __syncthreads();
+      for (int e = tid; e < RWG * KC; e += 256) {     // LUT rows, centred on the way in; column nb = n_b
+        const int r = e / KC, j = e % KC, kk = k0 + j;
+        const T n = nsm[r];
+        T v = T(0);
+        if (kk < nb) {
+          if (LutNum<T>::finite(n)) v = lut[(r0 + r) * nb + kk] - centre[kk];
+        } else if (kk == nb) {
+          v = n;
+        }
+        As[j * PA + r] = v;
+      }
+      for (int e = tid; e < OWG * KC; e += 256) {
+        const int mm = e / KC, j = e % KC;
+        const int64_t m = m0 + mm;
+        Bs[j * PB + mm] = m < M ? bq[m * nbp + k0 + j] : T(0);
+      }
+      __syncthreads();
+      typename W::acc_t acc[TR][TB];
+#pragma unroll
+      for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2)
+#pragma unroll
+          for (int i = 0; i < NACC; ++i) acc[t2][b2][i] = T(0);
+#pragma unroll
+      for (int s = 0; s < KC / KSTEP; ++s) {
+        const int kq = s * KSTEP + grp;
+        T a[TR], b[TB];
+#pragma unroll
+        for (int t2 = 0; t2 < TR; ++t2) a[t2] = As[kq * PA + (wr * TR + t2) * ROWS + col];
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2) b[b2] = Bs[kq * PB + (wc * TB + b2) * ROWS + col];
+#pragma unroll
+        for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+          for (int b2 = 0; b2 < TB; ++b2) acc[t2][b2] = W::mfma(a[t2], b[b2], acc[t2][b2]);
+      }
+#pragma unroll
+      for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2) {
+          if (k0 == 0) run[t2][b2] = acc[t2][b2];
+          else {
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) run[t2][b2][i] = run[t2][b2][i] + acc[t2][b2][i];
+          }
+        }
+    }
+#pragma unroll
+    for (int t2 = 0; t2 < TR; ++t2) {
+      const int64_t tg = rb * (2 * TR) + wr * TR + t2;  // tile of ROWS LUT rows
+      if (tg >= ntile) break;                           // (wave-uniform)
+#pragma unroll
+      for (int b2 = 0; b2 < TB; ++b2) {
+        T mn = run[t2][b2][0];
+#pragma unroll
+        for (int i = 1; i < NACC; ++i) mn = __builtin_fmin(mn, run[t2][b2][i]);
+        if (mn != mn) mn = (T)INFINITY;                // (an overflowing dot product of a rejected row: never a minimum)
+        if (!COLLECT) {
+          sec[b2] = __builtin_fmin(sec[b2], __builtin_fmax(best[b2], mn));   // a tie with the best becomes `sec`
+          best[b2] = __builtin_fmin(best[b2], mn);
+        } else {
+#pragma unroll
+          for (int off = ROWS; off < 64; off <<= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, off, 64));   // all rows of the tile
+          if (grp == 0 && mn <= th[b2]) {
+            const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+            const int pos = atomicAdd(&cand_n[m], 1);
+            if (pos < cap) cand[m * cap + pos] = (int)tg;
+          }
+        }
+      }
+    }
+  }
+  if (!COLLECT) {
+#pragma unroll
+    for (int b2 = 0; b2 < TB; ++b2) {
+      const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+      if (m < M) {
+        const int64_t o = (((int64_t)slice * 2 + wr) * G + grp) * M + m;
+        part_cost[o] = best[b2];
+        part_sec[o] = sec[b2];
+      }
+    }
+  }
+}
+
+// one wave per observation of the chunk: thr = U + Delta (the derivation above; ce, cf, cw are its coefficients with the
+// 1 % slack), resets the candidate count
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutw_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
+                                                    const T* __restrict__ ya, const T* __restrict__ w, int nb, int64_t M, int npart,
+                                                    int k, double ce, double cf, double cw, const unsigned long long* __restrict__ ctl,
+                                                    T* __restrict__ thr, int* __restrict__ cand_n) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  const T U = lut_topk_kth<T>(part_cost, part_sec, m, M, npart, k, lane);
+  bool neg = false;
+  if (w)
+    for (int j = lane; j < nb; j += 64) neg = neg || w[j] < T(0);
+  neg = __any(neg) != 0;
+  if (lane == 0) {
+    const double Y = (double)ya[m], nmax = (double)LutNum<T>::from_bits(ctl[0]);
+    const double E = ce * (nmax + Y);
+    double F;
+    if (!neg) {
+      const double c1 = (double)U + Y + E;
+      F = cf * (c1 > 0.0 ? c1 : 0.0);
+    } else {
+      F = cw * (nmax + Y);
+    }
+    double t = (double)U + (2.0 * E + F);
+    t = t + (4.0 * (double)LutNum<T>::u * __builtin_fabs(t) + (double)LutNum<T>::tiny);
+    T tt = (T)t;                                       // (NaN / inf stay non-finite: the select flags m)
+    if constexpr (sizeof(T) == 4) {
+      if ((double)tt < t) {                            // round up: the next float above
+        const unsigned b = __float_as_uint(tt);
+        tt = tt > 0.0f ? __uint_as_float(b + 1u) : (tt == 0.0f ? __uint_as_float(1u) : __uint_as_float(b - 1u));
+      }
+    }
+    thr[m] = tt;
+    cand_n[m] = 0;
+  }
+}
+
+// The exact top-k of one observation (k_lut_topk_select for any nb): single-wave workgroups; dynamic LDS = the key / row
+// buffer, the observation and the weights (LUT_TOPK_BUF x 12 + 2 nb sizeof(T) bytes: 40.7 KB at nb = 2162 in float64).
+// BRUTE = false: the rows of the candidate tiles of chunk observation blockIdx.x; BRUTE = true: every row, for the flagged ones.
+template <typename T, int ROWS, bool BRUTE>
+__global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
+                                                    int nb, int64_t B, int64_t m_off, int64_t Mc, int k, const T* __restrict__ thr,
+                                                    const int* __restrict__ cand_n, const int* __restrict__ cand, int cap,
+                                                    unsigned long long* __restrict__ ctl, int* __restrict__ flag_list,
+                                                    int64_t* __restrict__ out_idx, T* __restrict__ out_cost) {
+  extern __shared__ __attribute__((aligned(16))) char lutw_smem[];
+  unsigned long long* sk = reinterpret_cast<unsigned long long*>(lutw_smem);
+  int* sr = reinterpret_cast<int*>(sk + LUT_TOPK_BUF);
+  T* ys = reinterpret_cast<T*>(sr + LUT_TOPK_BUF);
+  T* wsm = ys + nb;
+  const int lane = threadIdx.x & 63;
+  if (w)
+    for (int j = lane; j < nb; j += 64) wsm[j] = w[j];
+  const unsigned count = BRUTE ? (unsigned)ctl[1] : 0u;
+  const int64_t nwork = BRUTE ? (int64_t)count : Mc;
+  const int64_t stride_w = BRUTE ? (int64_t)gridDim.x : nwork;
+  for (int64_t item = blockIdx.x; item < nwork; item += stride_w) {
+    const int64_t m = BRUTE ? (int64_t)flag_list[item] : m_off + item;
+    lut_wave_sync();                                   // (the previous item's reads of ys are done)
+    bool fin = true;
+    for (int j = lane; j < nb; j += 64) {
+      const T v = obs[m * nb + j];
+      ys[j] = v;
+      fin = fin && LutNum<T>::finite(v);
+    }
+    lut_wave_sync();
+    int64_t* oi = out_idx + m * k;
+    T* oc = out_cost + m * k;
+    if (__all(fin) == 0) {                             // every direct cost is NaN or +inf: nothing qualifies
+      for (int i = lane; i < k; i += 64) {
+        oi[i] = -1;
+        oc[i] = (T)INFINITY;
+      }
+      continue;
+    }
+    int64_t nrows = B;
+    int ncand = 0;
+    bool flag = false;
+    if (!BRUTE) {
+      ncand = cand_n[item];
+      flag = !LutNum<T>::finite(thr[item]) || ncand > cap;
+      if (lane == 0) {
+        atomicAdd(&ctl[2], (unsigned long long)ncand);
+        atomicMax(&ctl[3], (unsigned long long)ncand);
+      }
+      nrows = flag ? 0 : (int64_t)ncand * ROWS;
+    }
+    for (int i = lane; i < LUT_TOPK_BUF; i += 64) {
+      sk[i] = LUT_NOKEY;
+      sr[i] = 0x7fffffff;
+    }
+    lut_wave_sync();
+    int cnt = 0;
+    unsigned long long tk = LUT_NOKEY;
+    int tr = 0x7fffffff;
+    for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+      int64_t r = -1;
+      if (BRUTE) {
+        r = r0 + lane;
+      } else {
+        const int ci = (int)(r0 / ROWS) + lane / ROWS;
+        if (ci < ncand) r = (int64_t)cand[item * cap + ci] * ROWS + lane % ROWS;
+      }
+      unsigned long long key = LUT_NOKEY;
+      if (r >= 0 && r < B) {
+        SPART_NO_CONTRACT
+        const T* x = lut + r * nb;
+        T c = T(0);
+        if (w) {
+          for (int j = 0; j < nb; ++j) {
+            const T d = x[j] - ys[j];
+            c = c + (wsm[j] * d) * d;
+          }
+        } else {
+          for (int j = 0; j < nb; ++j) {
+            const T d = x[j] - ys[j];
+            c = c + d * d;
           }
         }
         if (LutNum<T>::finite(c)) key = LutKey<T>::key(c);

@@ -82,6 +82,7 @@ def fill_nulls(vals, first=0, **given):
 # on the 128 B line grid, which nearly doubles the HBM store rate of the materialised spectra on MI355X
 # (include/spart_hip.h: spart_ctx_set_row_pitch).  Spectra are returned as [:, :width] views of padded storage.
 ROW_PITCH = (2176, 2048)
+LUT_NARROW_NB = 31     # spart_lut_nearest / spart_lut_topk take nb <= 31; above it lut_nearest / lut_topk call spart_lut_topk_wide
 
 
 # ---- the static tables a context is built from (spart_tables): the reference reads them from the dicts it is HANDED at call
@@ -635,6 +636,9 @@ class Engine:
             raise ValueError(f"weights has {w.numel()} entries, expected nb = {lut.shape[1]}")
         B, nb = lut.shape
         M = obs.shape[0]
+        if nb > LUT_NARROW_NB:                                   # hyperspectral: the wide top-k with k = 1
+            res = self._lut_topk_wide(lut, obs, w, 1, dt, td, stats)
+            return (res[0][:, 0], res[1][:, 0]) + tuple(res[2:])
         idx = torch.empty((M,), dtype=torch.int64, device=self.device)
         cost = torch.empty((M,), dtype=td, device=self.device)
         n = int(self.lib.spart_lut_workspace_bytes(dt, B, nb, M))
@@ -673,6 +677,8 @@ class Engine:
             raise ValueError(f"weights has {w.numel()} entries, expected nb = {lut.shape[1]}")
         B, nb = lut.shape
         M = obs.shape[0]
+        if nb > LUT_NARROW_NB:
+            return self._lut_topk_wide(lut, obs, w, k, dt, td, stats)
         idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
         cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
         n = int(self.lib.spart_lut_topk_workspace_bytes(dt, B, nb, M, k))
@@ -690,6 +696,31 @@ class Engine:
             _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
                                                                          ctypes.byref(nbf), ctypes.byref(ncand),
                                                                          ctypes.byref(mcand), ctypes.byref(nmax)))
+        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
+                           "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
+
+    def _lut_topk_wide(self, lut, obs, w, k, dt, td, stats):
+        """spart_lut_topk_wide on prepared device tensors (lut_nearest / lut_topk above LUT_NARROW_NB bands)."""
+        torch = self.torch
+        B, nb = lut.shape
+        M = obs.shape[0]
+        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
+        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
+        n = int(self.lib.spart_lut_topk_wide_workspace_bytes(dt, B, nb, M, k))
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
+        self.calls["spart_lut_topk_wide"] += 1
+        rc = self.lib.spart_lut_topk_wide(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
+                                          w.data_ptr() if w is not None else None, k, idx.data_ptr(), cost.data_ptr(),
+                                          ws.data_ptr(), ctypes.c_size_t(ws.numel()), self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        if not stats:
+            return idx, cost
+        nbf, ncand, mcand, nmax = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        if M > 0:
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_wide_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
+                                                                              ctypes.byref(nbf), ctypes.byref(ncand),
+                                                                              ctypes.byref(mcand), ctypes.byref(nmax)))
         return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
                            "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
 

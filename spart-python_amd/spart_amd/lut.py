@@ -89,7 +89,7 @@ def open_lut_files(path, files, world=1, rank=0, group=None):
 
 
 def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, device=None, prune=True, fault_threads=8,
-                 f32_bands=False, shard=False, group=None, out=None):
+                 f32_bands=False, shard=False, group=None, out=None, sensor_info=None):
     """params: (B, 27) array-like on the HOST (numpy / memmap).  Returns dict of host arrays (np.memmap when
     ``path`` is given).
 
@@ -103,6 +103,10 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     ``prune=True`` (default: a LUT holds the sensor columns only) evaluates just the <= 2 nb bands those columns
     depend on -- bit-identical columns; ``prune=False`` also evaluates the other bands of every spectrum (band sums);
     ``dtype="float64", f32_bands=True`` gives float64 columns identical to the float64 mode's at the float32 mode's speed.
+    ``sensor_info``: a reference-style sensorinfo dict (wl_smac, SMAC_coef, wl_srf_smac, p_srf_smac, optional band_id_smac;
+    up to 2162 bands, e.g. a hyperspectral imager) instead of a packaged sensor: the engine is then
+    get_engine(sensor, device, sensor_info=sensor_info), and meta.json records ``sensor`` as given with that dict's bands and
+    centres.
     ``out``: optional dict of caller-owned host arrays for the three columns (this rank's rows), e.g. a previous call's result:
     their pages are already resident.  Fresh arrays cost 1.25 GB of first-touch page faults per 8M spectra even with the helper
     threads -- 8M pruned: 57 ms fresh, 40 ms reused (2.0e8 spectra/s; the two PCIe directions alone need 33 ms);
@@ -132,7 +136,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     Btot = P.shape[0]
     world, rank = _group_info(shard, group)
     lo0, hi0 = shard_bounds(Btot, world, rank)
-    eng = get_engine(sensor, device)
+    eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
     nb = eng.nb
     npdt = np.float32 if dtype in ("float32", "fp32", "f32") else np.float64
     tdt = torch.float32 if npdt is np.float32 else torch.float64
@@ -260,7 +264,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
             import torch.distributed as dist
             dist.barrier(group)                    # every rank's rows are in the files
         if rank == 0:
-            meta = {"sensor": sensor, "bands": list(eng.band_id), "wavelengths": [float(w) for w in eng.wl_smac],
+            meta = {"sensor": sensor, "bands": [str(b) for b in eng.band_id], "wavelengths": [float(w) for w in eng.wl_smac],
                     "dtype": np.dtype(npdt).name, "rows": int(Btot), "param_names": workloads.PARAM_NAMES,
                     "columns": list(COLUMNS), "pruned": bool(prune)}
             with open(os.path.join(path, "meta.json"), "w") as f:
