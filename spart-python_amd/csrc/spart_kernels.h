@@ -372,7 +372,7 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
     // order: leaf -> canopy solve for the leaf alone -> soil -> coupling with the soil background.  The soil model
     // sits between the two canopy parts because that schedule measured fastest (interleaved A/B of four orders).
     const CanopyPar<T> cp = load_canopy<T>(c);
-    const CanopyCore<T> core = canopy_core<T>(cp, rho, tau, ab);
+    const CanopyCore<T> core = canopy_core_l<T>(cp, rho, tau, ab, c[C_KSL], c[C_KOL]);
     T rdry = (MAT == 2) ? mat.rdry_in[s * mat.po + ti] : soil_dry<T>(tb, c[C_F1], c[C_F2], c[C_F3]);
     T fm[7] = {c[C_FM0], c[C_FM1], c[C_FM2], c[C_FM3], c[C_FM4], c[C_FM5], c[C_FM6]};
     T rwet;
@@ -386,12 +386,18 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
       if (mat.soil_refl) store_row<NT>(mat.soil_refl, off_f, rwet);
       if (!thermal && mat.soil_dry) store_row<NT>(mat.soil_dry, off_o, rdry);
     }
+    // FULL = 1 without materialised spectra (float32): the one observable rso + rdo + rsd + rdd is formed directly
+    constexpr bool SUM_ONLY = FULL == 1 && MAT == 0 && sizeof(T) == 4;
     T rso, rdo, rsd, rdd;
-    canopy_soil<T>(cp, core, rwet, rso, rdo, rsd, rdd);
-    if (FULL == 2) {
-      sum_so += rso; sum_do += rdo; sum_sd += rsd; sum_dd += rdd;
-    } else if (FULL == 1) {
-      sum_so += (rso + rdo) + (rsd + rdd);
+    if (SUM_ONLY) {
+      sum_so += canopy_soil_sum<T>(cp, core, rwet, c[C_TSTO]);
+    } else {
+      canopy_soil<T>(cp, core, rwet, rso, rdo, rsd, rdd);
+      if (FULL == 2) {
+        sum_so += rso; sum_do += rdo; sum_sd += rsd; sum_dd += rdd;
+      } else if (FULL == 1) {
+        sum_so += (rso + rdo) + (rsd + rdd);
+      }
     }
     if (MAT) {
       if (active) {

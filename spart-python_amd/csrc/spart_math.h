@@ -138,6 +138,41 @@ template <> struct Mx<float> {
     return -::expm1f(-z);
 #endif
   }
+  // The same two in base 2 (the float32 N-layer chain of leaf_band: log2 -> times N-1 -> exp2 with no ln 2 / log2(e)
+  // factors in between).  log2(1 + x), x >= 0: the series above times log2(e) below 0.5 (the factor rides on the 2 s
+  // multiply), v_log_f32 above.
+  static SPART_HD float log2_1p(float x) {
+#if defined(SPART_FAST_MATH)
+    float s = x * rcp(2.0f + x);
+    float s2 = s * s;
+    float p = 2.88539008f * s * (1.0f + s2 * (0.333333333f + s2 * (0.2f + s2 * (0.142857143f + s2 * 0.111111111f))));
+    return (x < 0.5f) ? p : log2(1.0f + x);
+#else
+    return ::log1pf(x) * 1.44269504f;
+#endif
+  }
+  // 1 - 2^-z for z >= 0 with e = 2^-z at hand: 1 - e^-y, y = z ln 2, Taylor below y = 0.25 (coefficients ln2^k / k!)
+  static SPART_HD float one_minus_exp2_neg(float z, float e) {
+#if defined(SPART_FAST_MATH)
+    float v = 1.0f - e;
+    if (SPART_WAVE_ANY(z < 0.360673760f)) {
+      float p = z * (0.693147181f + z * (-0.240226507f + z * (5.55041087e-2f + z * (-9.61812911e-3f + z * (1.33335581e-3f +
+                z * (-1.54035304e-4f + z * 1.52527338e-5f))))));
+      v = (z < 0.360673760f) ? p : v;
+    }
+    return v;
+#else
+    (void)e;
+    return -::expm1f(-z * 0.693147181f);
+#endif
+  }
+  static SPART_HD float log2(float x) {   // (positive normal arguments)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(SPART_FAST_MATH)
+    return __builtin_amdgcn_logf(x);          // v_log_f32
+#else
+    return ::log2f(x);
+#endif
+  }
   static SPART_HD float fabs(float x) { return ::fabsf(x); }
   static SPART_HD float fmax(float a, float b) { return ::fmaxf(a, b); }
   static SPART_HD float tiny() { return 1e-30f; }
@@ -463,52 +498,31 @@ template <typename T> SPART_HD void plate_tau(T K, T& tau, T& u) {
   // zero-absorption limit (prospect_5d.py:233-235) continuously.  NaN propagates.
   T x = (K < Mx<T>::tiny()) ? Mx<T>::tiny() : K;   // (a select, not fmax: a NaN K must stay NaN)
   const bool small = x < T(1);
-  if (sizeof(T) == 8) {   // float64: tau and u formed in each branch (a select of a double is two instructions)
-    T tl, ul;             // (locals, not the reference arguments: those made the compiler route the values through scratch)
-    if (small) {
-      const auto cg = C::gt();
-      T g = cg[C::GD];
-#pragma unroll
-      for (int i = C::GD - 1; i >= 0; --i) g = horner_uniform(g, x, cg[i]);
-      ul = x * (g + x * Mx<T>::log(x));
-      tl = T(1) - ul;
-    } else {
-      const auto cp = C::pt(), cq = C::qt();
-      T pn = C::PSCALE * cp[0], qn = cq[0];
-#pragma unroll
-      for (int i = 1; i <= C::WD; ++i) {
-        pn = horner_uniform(pn, x, C::PSCALE * cp[i]);
-        qn = horner_uniform(qn, x, cq[i]);
-      }
-      tl = Mx<T>::exp(-x) * pn * Mx<T>::rcp((x + T(3)) * qn);
-      ul = T(1) - tl;
-    }
-    tau = tl;
-    u = ul;
-    return;
-  }
-  T v;  // u on the small branch, tau on the large one (one value, so nothing is spilled to select them)
+  // tau and u are formed in each branch: no select after it (float64: a select is two instructions; float32: the
+  // two v_cndmask and the compare they need were 3 of the 7 instructions of bookkeeping around the branch)
+  T tl, ul;   // (locals, not the reference arguments: those made the compiler route the values through scratch)
   if (small) {
     const auto cg = C::gt();
     T g = cg[C::GD];
 #pragma unroll
     for (int i = C::GD - 1; i >= 0; --i) g = horner_uniform(g, x, cg[i]);
-    v = x * (g + x * Mx<T>::log(x));
+    ul = x * (g + x * Mx<T>::log(x));
+    tl = T(1) - ul;
   } else {
     // P(t)/Q(t) with t = 1/x, written in x (coefficients reversed) so that a single reciprocal is needed:
-    // tau = e^-x * 2 Pr(x) / ((x + 3) Qr(x)),  Pr(x) = x^n P(1/x)
+    // tau = e^-x * 2 Pr(x) / ((x + 3) Qr(x)),  Pr(x) = x^n P(1/x)  (the factor 2 is folded into P's constants: exact)
     const auto cp = C::pt(), cq = C::qt();
-    T pn = C::PSCALE * cp[0], qn = cq[0];  // (the factor 2 is folded into P's constants: exact)
+    T pn = C::PSCALE * cp[0], qn = cq[0];
 #pragma unroll
     for (int i = 1; i <= C::WD; ++i) {
       pn = horner_uniform(pn, x, C::PSCALE * cp[i]);
       qn = horner_uniform(qn, x, cq[i]);
     }
-    v = Mx<T>::exp(-x) * pn * Mx<T>::rcp((x + T(3)) * qn);
+    tl = Mx<T>::exp(-x) * pn * Mx<T>::rcp((x + T(3)) * qn);
+    ul = T(1) - tl;
   }
-  T w = T(1) - v;
-  u = small ? v : w;
-  tau = small ? w : v;
+  tau = tl;
+  u = ul;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -584,10 +598,11 @@ enum ConstIdx {
   // canopy (sailh.py:93-97, 200-203, 216, 219); the six geometric factors of sailh.py:100-105 are (k +- bf)/2,
   // (1 +- bf)/2, (K +- bf)/2 and are formed from ks, ko, bf/2 where they are used (canopy_core)
   C_SOB, C_SOF, C_HBF, C_KS, C_KO, C_LAI, C_LAI2, C_TSS, C_TOO, C_Z, C_HOT, C_PSO2W,
-  C_RSV0, C_RSV1, C_RSV2, C_RSV3,
-  NCONST  // 40: 36 used, padded to a multiple of 8 (stage_constants)
+  // read by the float32 band kernels only: ks LAI, ko LAI, tss too (canopy_core's (m - k) L as one FMA, canopy_soil_sum)
+  C_KSL, C_KOL, C_TSTO, C_RSV3,
+  NCONST  // 40: 39 used, padded to a multiple of 8 (stage_constants)
 };
-constexpr int NCONST_USED = C_RSV0;   // rows the prelude writes
+constexpr int NCONST_USED = C_KSL;    // rows the column kernel reads
 static_assert(NCONST == 40, "constant block is 40 values");
 
 // per-sample atmosphere scalars (double), read by the sensor-band kernel
@@ -613,10 +628,17 @@ SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T
   T r21 = T(1) - tb.t21, r12 = T(1) - tb.t12, ralf = T(1) - tb.talf;  // :201-205
   T x = r21 * tau;
   T inv = Mx<T>::rcp(T(1) - x * x);  // :208
-  T c = tau * tb.t21 * inv;
-  T Ta = tb.talf * c;   // :209
+  T Ta, t;
+  if constexpr (sizeof(T) == 4) {   // float32: talf t21 and t12 t21 are band constants (hoisted out of the sample loop)
+    T ti = tau * inv;
+    Ta = (tb.talf * tb.t21) * ti;
+    t = (tb.t12 * tb.t21) * ti;
+  } else {
+    T c = tau * tb.t21 * inv;
+    Ta = tb.talf * c;    // :209
+    t = tb.t12 * c;      // :213
+  }
   T Ra = ralf + x * Ta;  // :210
-  T t = tb.t12 * c;      // :213
   T r = r12 + x * t;     // :214
   // 1 - r - t = t12 (1-tau)/(1 - r21 tau);  1 - Ra - Ta = talf (1-tau)/(1 - r21 tau);  1/(1-x) = (1+x)/(1-x^2)
   T gq = u * (T(1) + x) * inv;
@@ -629,9 +651,16 @@ SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T
   T am1 = (a1 * (T(1) - r + tt) + D) * (tt * i2rt);            // a - 1, a from :222
   T bm1 = (a1 * (T(1) - tt + r) + D) * (r * i2rt);             // b - 1, b from :223
   T a = T(1) + am1;
-  T z = nm1 * Mx<T>::log1p(bm1);  // (N-1) ln b
-  T sq = Mx<T>::exp(-z);          // b^-(N-1)
-  T omsq = Mx<T>::one_minus_exp_neg(z, sq);  // 1 - b^-(N-1)
+  T sq, omsq;                     // b^-(N-1), 1 - b^-(N-1)
+  if constexpr (sizeof(T) == 4) { // float32 in base 2: (N-1) log2 b
+    T z2 = nm1 * Mx<T>::log2_1p(bm1);
+    sq = Mx<T>::exp2(-z2);
+    omsq = Mx<T>::one_minus_exp2_neg(z2, sq);
+  } else {
+    T z = nm1 * Mx<T>::log1p(bm1);  // (N-1) ln b
+    sq = Mx<T>::exp(-z);
+    omsq = Mx<T>::one_minus_exp_neg(z, sq);
+  }
   T omq = omsq * (T(1) + sq);     // 1 - b^-2(N-1)
   T A2 = am1 * (a + T(1));        // a^2 - 1
   // Rsub = a omq / den, Tsub = sq A2 / den, den = A2 + omq (:229-230 divided by b^2(N-1)); combined with the top
@@ -654,6 +683,27 @@ template <typename T> SPART_HD T soil_tw1(const BandTab<T>& tb, T film2l) { retu
 
 template <typename T>
 SPART_HD void soil_band_tw(const BandTab<T>& tb, T rdry, T wet, const T fm[7], T fmsum16, T tw1, T& rwet) {
+  if constexpr (sizeof(T) == 4) {
+    // float32: rbac = rdry (1 + c (1 - rdry)), c = 1 - cbac (the same polynomial in rdry; c and 1 + c are band
+    // constants), and sum_k f_k x_k / d_k as ONE fraction N / D built up term by term (N <- N d_k + f_k x_k D,
+    // D <- D d_k: every term and factor is positive, 0 < d_k <= 1) -- 6 instructions per term and one reciprocal
+    // instead of the prefix / peel-off products below (7 per term)
+    const T cb = T(1) - tb.cbac;
+    T rbac = rdry * (cb * (T(1) - rdry) + T(1));                  // :110-112
+    T xv = rbac * tw1;
+    T D = T(1) - tb.pw * xv;
+    T N = fm[1] * xv;
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      xv *= tw1;
+      const T d = T(1) - tb.pw * xv;
+      N = N * d + fm[k + 1] * xv * D;
+      D *= d;
+    }
+    T v = rdry * fm[0] + tb.rw * fmsum16 + (T(1) - tb.rw) * (T(1) - tb.pw) * N * Mx<T>::rcp(D);
+    rwet = (wet > T(0)) ? v : rdry;                                // :102-103
+    return;
+  }
   T rbac = T(1) - (T(1) - rdry) * (rdry * tb.cbac + T(1) - rdry);  // :110-112
   // rwet = rdry f0 + sum_k f_k [Rw + (1-Rw)(1-p) x_k/(1 - p x_k)],  x_k = tw1^k rbac   (:123-124)
   // The six reciprocals 1/d_k, d_k = 1 - p x_k, come from ONE reciprocal of their product (prefix products
@@ -702,8 +752,10 @@ template <typename T> struct CanopyCore {
   T rho_so, rho_dd, tau_dd, tau_sd, tau_do, rho_sd, rho_do;
 };
 
+// ksl = ks LAI, kol = ko LAI (constant rows C_KSL / C_KOL in the band kernels): float32 forms (m - k) L as m L - k L,
+// one FMA each; float64 keeps (m - k) L and does not read them
 template <typename T>
-SPART_HD CanopyCore<T> canopy_core(const CanopyPar<T>& c, T rho, T tau, T absb) {
+SPART_HD CanopyCore<T> canopy_core_l(const CanopyPar<T>& c, T rho, T tau, T absb, T ksl, T kol) {
   // scattering coefficients (:142-148).  With sdb/sdf = (k +- bf)/2, ddb/ddf = (1 +- bf)/2, dob/dof = (K +- bf)/2
   // (:100-105) they are P, k P, K P plus/minus Mn, where P = (rho + tau)/2 and Mn = bf (rho - tau)/2:
   //   sigb = P + Mn, sigf = P - Mn, sb/sf = k P +- Mn, vb/vf = K P +- Mn
@@ -732,7 +784,15 @@ SPART_HD CanopyCore<T> canopy_core(const CanopyPar<T>& c, T rho, T tau, T absb) 
   // J1(-1) = (e^-mL - e^-kL)/(k - m), J2(0) = (1 - e^-kL e^-mL)/(k + m)   (:154-183)
   T e1 = Mx<T>::exp2(-m * c.lai2);     // e^-mL, :185-189
   const T thr = SailJ<T>::THRESH;
-  T d1 = (m - c.ks) * L, d2 = (m - c.ko) * L;
+  T d1, d2;
+  if constexpr (sizeof(T) == 4) {
+    d1 = m * L - ksl;
+    d2 = m * L - kol;
+  } else {
+    (void)ksl, (void)kol;
+    d1 = (m - c.ks) * L;
+    d2 = (m - c.ko) * L;
+  }
   T d1s = (Mx<T>::fabs(d1) < thr) ? T(1) : d1, d2s = (Mx<T>::fabs(d2) < thr) ? T(1) : d2;   // (the Taylor side needs no 1/d)
   T idd = Mx<T>::rcp(d1s * d2s);
   T J1k = sail_j1_d<T>(L, c.tss, e1, d1, idd * d2s);
@@ -764,6 +824,10 @@ SPART_HD CanopyCore<T> canopy_core(const CanopyPar<T>& c, T rho, T tau, T absb) 
   return CanopyCore<T>{rho_so, rho_dd, tau_dd, tau_sd, tau_do, rho_sd, rho_do};
 }
 
+template <typename T> SPART_HD CanopyCore<T> canopy_core(const CanopyPar<T>& c, T rho, T tau, T absb) {
+  return canopy_core_l<T>(c, rho, tau, absb, c.ks * c.lai, c.ko * c.lai);
+}
+
 template <typename T>
 SPART_HD void canopy_soil(const CanopyPar<T>& c, const CanopyCore<T>& k, T rs, T& rso, T& rdo, T& rsd, T& rdd) {
   const T rho_so = k.rho_so, rho_dd = k.rho_dd, tau_dd = k.tau_dd, tau_sd = k.tau_sd, tau_do = k.tau_do, rho_sd = k.rho_sd,
@@ -775,6 +839,17 @@ SPART_HD void canopy_soil(const CanopyPar<T>& c, const CanopyCore<T>& k, T rs, T
   rdo = rho_do + (c.too + tau_do) * h;                            // :231
   rsd = rho_sd + tst * h;                                         // :232
   rdd = rho_dd + tau_dd * h;                                      // :233
+}
+
+// rso + rdo + rsd + rdd of canopy_soil as one expression (the float32 band kernel's FULL = 1 observable); tsto = tss too.
+// With q = rs rho_dd, g = rs / (1 - q), h = g tau_dd and tst = tss + tau_sd the four outputs add up to
+//   rho_so + rho_do + rho_sd + rho_dd + rs pso2w + g [tau_sd (too + tau_do) + tss tau_do + tsto q + tau_dd (tst + too + tau_do + tau_dd)]
+template <typename T> SPART_HD T canopy_soil_sum(const CanopyPar<T>& c, const CanopyCore<T>& k, T rs, T tsto) {
+  T q = rs * k.rho_dd;
+  T g = rs * Mx<T>::rcp(T(1) - q);                                 // (:222)
+  T tdo = c.too + k.tau_do;
+  T inner = k.tau_sd * tdo + c.tss * k.tau_do + tsto * q + k.tau_dd * ((c.tss + k.tau_sd) + tdo + k.tau_dd);
+  return ((k.rho_so + k.rho_do) + (k.rho_sd + k.rho_dd)) + rs * c.pso2w + g * inner;   // :224-233
 }
 
 template <typename T>
@@ -1345,6 +1420,9 @@ SPART_HD void sample_prelude_to(const In& in /* in(i) = parameter i of 27, read 
   double tss = ::exp(-ks * LAI), too = ::exp(-ko * LAI);  // :200-201
   out.c(C_TSS, tss);
   out.c(C_TOO, too);
+  out.c(C_KSL, ks * LAI);
+  out.c(C_KOL, ko * LAI);
+  out.c(C_TSTO, tss * too);
   out.c(C_Z, (1.0 - tss * too) / (ko + ks));             // :203
   double ic, p2w;
   hotspot_integrals<FAST>(ko, ks, LAI, q, dso, ic, p2w, nl);

@@ -47,9 +47,9 @@ def section_of_source_lines():
         l = src[i]
         if "leaf_band<" in l:
             s = "leaf_band"
-        elif "canopy_core<" in l or "load_canopy<" in l:
+        elif any(k in l for k in ("canopy_core<", "canopy_core_l<", "load_canopy<")):
             s = "canopy_core"
-        elif "canopy_soil<" in l:
+        elif "canopy_soil<" in l or "canopy_soil_sum<" in l:
             s = "canopy_soil"
         elif any(k in l for k in ("soil_dry<", "soil_band", "soil_tw1", "T fm[7]", "film_same", "C_FILM2L")):
             s = "soil"
