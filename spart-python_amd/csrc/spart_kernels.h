@@ -9,6 +9,8 @@
 // 2002 of the 2048 lanes of eight workgroups.
 #pragma once
 
+#include <type_traits>
+
 #include "spart_math.h"
 
 namespace spart {
@@ -341,6 +343,23 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
   T lc[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) lc[i] = lds_c[i];
+  // Common case (float32, one band sum, no materialised spectra): when the 32 samples staged here all share the film
+  // thickness and all have cbc = prot = 0 (the PROSPECT-5D leaf -- the usual LUT setting; BASELINE config 4 fixes both),
+  // the wave runs a second instantiation of the sample loop with the film's single-layer transmittance formed once per
+  // lane and stage and the two PRO terms of K left off.  Both give the same numbers as the general body
+  // (leaf_band<T, false>, soil_tw1).  The choice is one wave-uniform branch per stage: every wave tests the same samples
+  // (lane l: sample l).
+  constexpr bool COMMON = sizeof(T) == 4 && MAT == 0 && FULL == 1;   // (FULL = 2, band means: one body, not measured with two)
+  bool common = false;
+  T tw1c = T(0);
+  if (COMMON) {
+    const int l = threadIdx.x & 63;
+    const T* cl = lds_c + (l < nsub ? l : 0) * NCONST;
+    common = __all(cl[C_FILM2L] == lds_c[C_FILM2L] && cl[C_CBC] == T(0) && cl[C_PROT] == T(0)) != 0;   // (NaN: general body)
+    if (common) tw1c = soil_tw1<T>(tb, lds_c[C_FILM2L]);
+  }
+  auto sample_loop = [&](auto common_tag) __attribute__((always_inline)) {
+  constexpr bool FAST = decltype(common_tag)::value;
   for (int si = 0; si < nsub; ++si) {
     const int64_t s = sb + si;
     const T* c = lds_c + si * NCONST;                  // uniform LDS address -> broadcast ds_read into VGPRs
@@ -350,7 +369,7 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
 #pragma unroll
       for (int i = 0; i < 9; ++i) lc[i] = c[i];
     }
-    leaf_band<T>(tb, lc[0], lc[1], lc[2], lc[3], lc[4], lc[5], lc[6], lc[7], lc[8], refl, tran, absb, K);
+    leaf_band<T, !FAST>(tb, lc[0], lc[1], lc[2], lc[3], lc[4], lc[5], lc[6], lc[7], lc[8], refl, tran, absb, K);
     if (AHEAD) {
       const T* cn = lds_c + ((si + 1 < nsub) ? si + 1 : si) * NCONST;   // next sample's leaf constants, in flight early
 #pragma unroll
@@ -376,7 +395,9 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
     T rdry = (MAT == 2) ? mat.rdry_in[s * mat.po + ti] : soil_dry<T>(tb, c[C_F1], c[C_F2], c[C_F3]);
     T fm[7] = {c[C_FM0], c[C_FM1], c[C_FM2], c[C_FM3], c[C_FM4], c[C_FM5], c[C_FM6]};
     T rwet;
-    if (HOIST_FILM) {
+    if (FAST) {
+      soil_band_tw<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1c, rwet);
+    } else if (HOIST_FILM) {
       const T tw1 = film_same ? tw1s : soil_tw1<T>(tb, c[C_FILM2L]);      // (wave-uniform choice)
       soil_band_tw<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1, rwet);
     } else {
@@ -428,6 +449,13 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
       off_f += (unsigned)mat.pf * (unsigned)sizeof(T);
       off_o += (unsigned)mat.po * (unsigned)sizeof(T);
     }
+  }
+  };
+  if constexpr (COMMON) {
+    if (common) sample_loop(std::true_type{});
+    else sample_loop(std::false_type{});
+  } else {
+    sample_loop(std::false_type{});
   }
   if (PINGPONG) {
     if (nnext > 0) stage_put<T, SUB>(lds_all + (cur ^ 1) * (SUB * NCONST), stg, nnext);

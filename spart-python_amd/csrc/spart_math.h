@@ -426,6 +426,17 @@ template <typename T> SPART_HD T sail_j1_d(T L, T tk, T e1, T d, T id) {
   }
   return v;
 }
+// float32: the same with ia = 1/|d| (id's magnitude).  tk - e1 = e^-kL (1 - e^-d) has the sign of d, so J1 = L |tk - e1| / |d|
+// and the caller may clamp |d| below at THRESH (one v_max) to get a safe divisor where the Taylor side is taken
+template <typename T> SPART_HD T sail_j1_a(T L, T tk, T e1, T d, T ia) {
+  T v = L * Mx<T>::fabs(tk - e1) * ia;
+  const bool small = Mx<T>::fabs(d) < SailJ<T>::THRESH;
+  if (SPART_WAVE_ANY(small)) {
+    SPART_KEEP_BRANCH(d);
+    v = small ? L * tk * SailJ<T>::poly(d) : v;
+  }
+  return v;
+}
 // J2 = (1 - tk e1)/(k + m), kpm = k + m > 0, ikpm = 1/kpm; (k + m) L < THRESH selects L phi((k + m) L) -- rare, and
 // the Taylor side is only issued when some lane of the wave needs it
 template <typename T> SPART_HD T sail_j2_d(T L, T tk, T e1, T kpm, T ikpm) {
@@ -617,11 +628,14 @@ constexpr int NATM_USED = A_RSV;      // rows the prelude writes
 // ------------------------------------------------------------------------------------------
 // PROSPECT-5D / PRO, one band                                        (prospect_5d.py:170-241)
 // cN[] = concentrations / N.  Returns refl, tran, absorptance = 1 - refl - tran, K = Kall.
-template <typename T>
+// PRO = false: the caller knows cbc = prot = 0 (PROSPECT-5D, the default leaf) and the two PRO terms are not issued.  K is the
+// same number either way: the sum is the same chain with the last two terms left off, and x + 0 k == x (finite table values).
+template <typename T, bool PRO = true>
 SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T cant, T cbc, T prot, T nm1,
                         T& refl, T& tran, T& absb, T& Kall) {
-  T K = cab * tb.kab + cca * tb.kca + cdm * tb.kdm + cw * tb.kw + cs * tb.ks + cant * tb.kant + cbc * tb.kcbc +
-        prot * tb.kprot;  // :170-179
+  T K = cab * tb.kab + cca * tb.kca + cdm * tb.kdm + cw * tb.kw + cs * tb.ks + cant * tb.kant;  // :170-179
+  if (PRO) K = K + cbc * tb.kcbc + prot * tb.kprot;
+  else (void)cbc, (void)prot;
   Kall = K;
   T tau, u;
   plate_tau(K, tau, u);  // :182-196
@@ -641,7 +655,9 @@ SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T
   T Ra = ralf + x * Ta;  // :210
   T r = r12 + x * t;     // :214
   // 1 - r - t = t12 (1-tau)/(1 - r21 tau);  1 - Ra - Ta = talf (1-tau)/(1 - r21 tau);  1/(1-x) = (1+x)/(1-x^2)
-  T gq = u * (T(1) + x) * inv;
+  T gq;
+  if constexpr (sizeof(T) == 4) gq = u * __builtin_fmaf(x, inv, inv);   // (1 + x) inv as one FMA
+  else gq = u * (T(1) + x) * inv;
   T a1 = tb.t12 * gq;
   T atop = tb.talf * gq;
   // Stokes system for the N-1 lower layers (:219-230), written in a-1, b-1 and b^-(N-1)
@@ -649,7 +665,8 @@ SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T
   T D = Mx<T>::sqrt((T(1) + r + tt) * (T(1) + r - tt) * (T(1) - r + tt) * a1);  // :219
   T i2rt = Mx<T>::rcp(T(2) * r * tt);                          // 1/(2r) = tt i2rt, 1/(2tt) = r i2rt
   T am1 = (a1 * (T(1) - r + tt) + D) * (tt * i2rt);            // a - 1, a from :222
-  T bm1 = (a1 * (T(1) - tt + r) + D) * (r * i2rt);             // b - 1, b from :223
+  // (float32: 1 + r - tt as in D, formed once; float64 keeps its order)
+  T bm1 = (a1 * (sizeof(T) == 4 ? T(1) + r - tt : T(1) - tt + r) + D) * (r * i2rt);   // b - 1, b from :223
   T a = T(1) + am1;
   T sq, omsq;                     // b^-(N-1), 1 - b^-(N-1)
   if constexpr (sizeof(T) == 4) { // float32 in base 2: (N-1) log2 b
@@ -685,22 +702,26 @@ template <typename T>
 SPART_HD void soil_band_tw(const BandTab<T>& tb, T rdry, T wet, const T fm[7], T fmsum16, T tw1, T& rwet) {
   if constexpr (sizeof(T) == 4) {
     // float32: rbac = rdry (1 + c (1 - rdry)), c = 1 - cbac (the same polynomial in rdry; c and 1 + c are band
-    // constants), and sum_k f_k x_k / d_k as ONE fraction N / D built up term by term (N <- N d_k + f_k x_k D,
-    // D <- D d_k: every term and factor is positive, 0 < d_k <= 1) -- 6 instructions per term and one reciprocal
-    // instead of the prefix / peel-off products below (7 per term)
+    // constants).  With y_k = p x_k and d_k = 1 - y_k, x_k / d_k = (1 / d_k - 1) / p, so
+    //   sum_k f_k x_k / d_k = (sum_k f_k / d_k - F) / p,   F = sum_{k>=1} f_k = fmsum16,
+    // and sum_k f_k / d_k is ONE fraction N / D built up term by term (N <- N d_k + f_k D, D <- D d_k: every term and
+    // factor is positive, 0 < d_k <= 1) -- 5 instructions per term and one reciprocal; (1 - Rw)(1 - p) / p is a band
+    // constant.  N / D - F cancels where p x_k is small, but there the whole film term is small next to Rw F:
+    // the absolute error is a few ulp of F (tests/test_f32_forms.py bounds it over all bands).
     const T cb = T(1) - tb.cbac;
+    const T c2 = (T(1) - tb.rw) * (T(1) - tb.pw) * Mx<T>::rcp(tb.pw);
     T rbac = rdry * (cb * (T(1) - rdry) + T(1));                  // :110-112
-    T xv = rbac * tw1;
-    T D = T(1) - tb.pw * xv;
-    T N = fm[1] * xv;
+    T y = rbac * (tb.pw * tw1);
+    T D = T(1) - y;
+    T N = fm[1];
 #pragma unroll
     for (int k = 1; k < 6; ++k) {
-      xv *= tw1;
-      const T d = T(1) - tb.pw * xv;
-      N = N * d + fm[k + 1] * xv * D;
+      y *= tw1;
+      const T d = T(1) - y;
+      N = N * d + fm[k + 1] * D;
       D *= d;
     }
-    T v = rdry * fm[0] + tb.rw * fmsum16 + (T(1) - tb.rw) * (T(1) - tb.pw) * N * Mx<T>::rcp(D);
+    T v = rdry * fm[0] + tb.rw * fmsum16 + c2 * (N * Mx<T>::rcp(D) - fmsum16);
     rwet = (wet > T(0)) ? v : rdry;                                // :102-103
     return;
   }
@@ -793,10 +814,18 @@ SPART_HD CanopyCore<T> canopy_core_l(const CanopyPar<T>& c, T rho, T tau, T absb
     d1 = (m - c.ks) * L;
     d2 = (m - c.ko) * L;
   }
-  T d1s = (Mx<T>::fabs(d1) < thr) ? T(1) : d1, d2s = (Mx<T>::fabs(d2) < thr) ? T(1) : d2;   // (the Taylor side needs no 1/d)
-  T idd = Mx<T>::rcp(d1s * d2s);
-  T J1k = sail_j1_d<T>(L, c.tss, e1, d1, idd * d2s);
-  T J1K = sail_j1_d<T>(L, c.too, e1, d2, idd * d1s);
+  T J1k, J1K;
+  if constexpr (sizeof(T) == 4) {   // float32: |d| clamped at THRESH, one v_max instead of a compare / select pair per d
+    T d1a = Mx<T>::fmax(Mx<T>::fabs(d1), thr), d2a = Mx<T>::fmax(Mx<T>::fabs(d2), thr);
+    T idd = Mx<T>::rcp(d1a * d2a);
+    J1k = sail_j1_a<T>(L, c.tss, e1, d1, idd * d2a);
+    J1K = sail_j1_a<T>(L, c.too, e1, d2, idd * d1a);
+  } else {
+    T d1s = (Mx<T>::fabs(d1) < thr) ? T(1) : d1, d2s = (Mx<T>::fabs(d2) < thr) ? T(1) : d2;   // (the Taylor side needs no 1/d)
+    T idd = Mx<T>::rcp(d1s * d2s);
+    J1k = sail_j1_d<T>(L, c.tss, e1, d1, idd * d2s);
+    J1K = sail_j1_d<T>(L, c.too, e1, d2, idd * d1s);
+  }
   T J2k = sail_j2_d<T>(L, c.tss, e1, ksm, iks);
   T J2K = sail_j2_d<T>(L, c.too, e1, kom, iko);
   T ome2 = T(1) - e1 * e1;
@@ -844,12 +873,13 @@ SPART_HD void canopy_soil(const CanopyPar<T>& c, const CanopyCore<T>& k, T rs, T
 // rso + rdo + rsd + rdd of canopy_soil as one expression (the float32 band kernel's FULL = 1 observable); tsto = tss too.
 // With q = rs rho_dd, g = rs / (1 - q), h = g tau_dd and tst = tss + tau_sd the four outputs add up to
 //   rho_so + rho_do + rho_sd + rho_dd + rs pso2w + g [tau_sd (too + tau_do) + tss tau_do + tsto q + tau_dd (tst + too + tau_do + tau_dd)]
+// = rho_so + rho_do + rho_sd + rho_dd + rs [pso2w + inner / (1 - q)]   (rs taken out: g is never formed)
 template <typename T> SPART_HD T canopy_soil_sum(const CanopyPar<T>& c, const CanopyCore<T>& k, T rs, T tsto) {
   T q = rs * k.rho_dd;
-  T g = rs * Mx<T>::rcp(T(1) - q);                                 // (:222)
+  T iq = Mx<T>::rcp(T(1) - q);                                     // (:222)
   T tdo = c.too + k.tau_do;
   T inner = k.tau_sd * tdo + c.tss * k.tau_do + tsto * q + k.tau_dd * ((c.tss + k.tau_sd) + tdo + k.tau_dd);
-  return ((k.rho_so + k.rho_do) + (k.rho_sd + k.rho_dd)) + rs * c.pso2w + g * inner;   // :224-233
+  return ((k.rho_so + k.rho_do) + (k.rho_sd + k.rho_dd)) + rs * (c.pso2w + inner * iq);   // :224-233
 }
 
 template <typename T>

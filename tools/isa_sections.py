@@ -5,7 +5,8 @@
 Each translation unit is compiled to assembly with its own flags (build.TU_FLAGS) plus -gline-tables-only, which adds `.loc`
 directives carrying the whole inline chain of every instruction and does not change the code (the instruction count equals the
 product build's; checked below).  The sample loop of k_bands is found as the innermost loop (backward branch) with the most
-VALU instructions; every instruction in it is attributed to the line of k_bands (spart_kernels.h) at the OUTER end of its inline
+VALU instructions -- in the float32 kernel the general body; its common-case body (a stage of samples that share the film
+thickness and have cbc = prot = 0) is the innermost loop with the second most (inner_loops); every instruction in it is attributed to the line of k_bands (spart_kernels.h) at the OUTER end of its inline
 chain, and that line to a section of the model by what the source line calls:
 
     leaf_band     PROSPECT-5D / PRO plate model             (prospect_5d.py:170-241)
@@ -45,7 +46,9 @@ def section_of_source_lines():
     out = {}
     for i in range(start, end):
         l = src[i]
-        if "leaf_band<" in l:
+        if "sample_loop(" in l:
+            s = None                    # the call of the sample-loop lambda: its own lines say where an instruction belongs
+        elif "leaf_band<" in l:
             s = "leaf_band"
         elif any(k in l for k in ("canopy_core<", "canopy_core_l<", "load_canopy<")):
             s = "canopy_core"
@@ -77,8 +80,15 @@ def kernel_body(lines, frag):
     return lines[start].split(":")[0], lines[start + 1:end]
 
 
-def sample_loop(body):
-    """(first, last) index into body of the innermost loop with the most VALU instructions"""
+def _nv(body, a, b):
+    return sum(1 for l in body[a:b + 1] if l.strip().startswith("v_"))
+
+
+def inner_loops(body):
+    """(first, last) index into body of every loop (backward branch) that is innermost by VALU, most VALU first.  A loop whose
+    nested loops TOGETHER hold more than half of its VALU instructions is an outer loop: in the float32
+    k_bands<float,0,1,false> the stage loop holds two sample loops of about the same size (the general body and the
+    common-case body), neither of which alone holds half of it."""
     labels = {}
     for i, l in enumerate(body):
         m = re.match(r"^(\.LBB\d+_\d+):", l)
@@ -89,14 +99,25 @@ def sample_loop(body):
         m = re.match(r"\s+s_cbranch_\w+\s+(\.LBB\d+_\d+)", l) or re.match(r"\s+s_branch\s+(\.LBB\d+_\d+)", l)
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             loops.append((labels[m.group(1)], i))
-    nv = lambda a, b: sum(1 for l in body[a:b + 1] if l.strip().startswith("v_"))          # noqa: E731
-    inner = [lp for lp in loops if not any(o != lp and lp[0] <= o[0] and o[1] <= lp[1] and nv(*o) > 0.5 * nv(*lp) for o in loops)]
-    return max(inner, key=lambda lp: nv(*lp))
+    out = []
+    for lp in loops:
+        inside = set()
+        for o in loops:
+            if o != lp and lp[0] <= o[0] and o[1] <= lp[1]:
+                inside.update(i for i in range(o[0], o[1] + 1) if body[i].strip().startswith("v_"))
+        if not len(inside) > 0.5 * _nv(body, *lp):
+            out.append(lp)
+    return sorted(out, key=lambda lp: -_nv(body, *lp))
 
 
-def budget(lines, frag, secmap, k0, k1):
+def sample_loop(body, rank=0):
+    """(first, last) index into body of the innermost loop with the most VALU instructions (rank 1: the second most)"""
+    return inner_loops(body)[rank]
+
+
+def budget(lines, frag, secmap, k0, k1, rank=0):
     name, body = kernel_body(lines, frag)
-    a, b = sample_loop(body)
+    a, b = sample_loop(body, rank)
     cur = "loop"
     counts = {s: collections.Counter() for s in SECTIONS}
     labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
@@ -115,7 +136,7 @@ def budget(lines, frag, secmap, k0, k1):
             frames = re.findall(r"(\S+?):(\d+):\d+", t.split(";", 1)[1]) if ";" in t else []
             cur = "loop"
             for f, ln in reversed(frames):
-                if f.endswith("spart_kernels.h") and k0 <= int(ln) <= k1:
+                if f.endswith("spart_kernels.h") and k0 <= int(ln) <= k1 and secmap.get(int(ln), "loop") is not None:
                     cur = secmap.get(int(ln), "loop")
                     break
             continue
@@ -142,12 +163,13 @@ def product_valu_count(src, frag):
 def main():
     secmap, k0, k1 = section_of_source_lines()
     rows = []
-    for src, frag, label in ((build.SOURCES[1], "k_bandsIfLi0ELi1ELb0E", "float32 `k_bands<float,0,1,false>`"),
-                             (build.SOURCES[0], "k_bandsIdLi0ELi1ELb0E", "float64 `k_bands<double,0,1,false>`")):
+    for src, frag, label, ranks in ((build.SOURCES[1], "k_bandsIfLi0ELi1ELb0E", "float32 `k_bands<float,0,1,false>`", (0, 1)),
+                                    (build.SOURCES[0], "k_bandsIdLi0ELi1ELb0E", "float64 `k_bands<double,0,1,false>`", (0,))):
         lines = asm_with_lines(src)
-        name, counts, total_g = budget(lines, frag, secmap, k0, k1)
-        assert total_g == product_valu_count(src, frag), "-gline-tables-only changed the code"
-        rows.append((label, counts))
+        for rank in ranks:
+            name, counts, total_g = budget(lines, frag, secmap, k0, k1, rank)
+            assert total_g == product_valu_count(src, frag), "-gline-tables-only changed the code"
+            rows.append((label + (" common-case body" if rank else ""), counts))
     md = "--md" in sys.argv
     if md:
         print("| section | " + " | ".join(f"{lab}: VALU always + cond (transcendental) / LDS / SALU" for lab, _ in rows) + " |")
