@@ -58,8 +58,9 @@ extern "C" {
  *   6: spart_materialize.lidf_in / .nlayers, spart_sailh_batch(lidf_in, nlayers), spart_abi_version itself
  *   7: spart_workspace_bandsum
  *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats
- *   9: spart_lut_topk_wide, spart_lut_topk_wide_workspace_bytes, spart_lut_topk_wide_stats; sensors of up to SPART_NWLS bands */
-#define SPART_ABI_VERSION 9
+ *   9: spart_lut_topk_wide, spart_lut_topk_wide_workspace_bytes, spart_lut_topk_wide_stats; sensors of up to SPART_NWLS bands
+ *  10: spart_lut_topk_obs_weights, spart_lut_topk_obs_weights_workspace_bytes, spart_lut_topk_obs_weights_stats */
+#define SPART_ABI_VERSION 10
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -291,6 +292,32 @@ int spart_lut_topk_wide(spart_ctx *ctx, int dtype, int64_t B, int nb, const void
  * brute-forced observations, candidate tiles (32 rows for SPART_F32, 16 for SPART_F64; sum and maximum) and Nmax. */
 int spart_lut_topk_wide_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
                               int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nmax);
+
+/* The k nearest LUT rows with ONE WEIGHT ROW PER OBSERVATION (per-pixel noise and per-pixel band masks; no reference
+ * counterpart).  weights (M, nb) in `dtype`, device memory, required (NULL: SPART_ERR_INVALID).  For each observation m the
+ * cost of row b is, evaluated in `dtype` with every operation rounded and no FMA,
+ *     c = 0;  for j = 0 .. nb-1:  if (w[m,j] == 0) continue;  d = lut[b,j] - obs[m,j];  c = c + (w[m,j] * d) * d
+ * -- spart_lut_topk_wide's cost plus one rule: a band of weight exactly zero is skipped, so obs[m,j] may be NaN or inf there
+ * (the mask).  Rows are ordered by (cost, row), i.e. np.argsort(c, kind="stable")[:k] after non-finite costs are set to +inf;
+ * the tail is padded with (-1, +inf); 1 <= k <= 256, 1 <= nb <= SPART_NWLS, B and M <= 2e9 (SPART_ERR_INVALID otherwise).
+ *   Rows: a row with a non-finite entry never appears, nor one whose UNWEIGHTED centred norm sum_j (lut[b,j] - centre_j)^2
+ *   overflows; row acceptance does not depend on the observation.
+ *   Observations: one with a negative, NaN or infinite weight, or a non-finite value in a band of non-zero weight, matches
+ *   no row: its whole output row is (-1, +inf).  All weights zero: every accepted row costs 0, the first k accepted rows.
+ * So with every weight row equal to w, finite observations and no norm near overflow the result is spart_lut_topk_wide(w)'s
+ * bit for bit, and zero weights on a band set S give the answer of the LUT and observation with the columns of S removed.
+ * How (csrc/spart_lut.h, "per-observation weights", derives the bound): the wide pipeline with the filter
+ * sum_j w_mj x'_bj^2 - 2 sum_j w_mj y'_mj x'_bj as one GEMM of K = 2 nb on the matrix cores; observations go in chunks of at
+ * most 16 384 (fewer above ~1000 bands in float64: the operand rows stay within 256 MiB). */
+size_t spart_lut_topk_obs_weights_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k);
+int spart_lut_topk_obs_weights(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut, int64_t M, const void *obs,
+                               const void *weights, int k, int64_t *idx, void *cost, void *workspace, size_t workspace_bytes,
+                               void *stream);
+/* Diagnostics of the LAST spart_lut_topk_obs_weights call that used `workspace` (same dtype, B, nb, M, k): brute-forced
+ * observations, candidate tiles (32 rows for SPART_F32, 16 for SPART_F64; sum and maximum) and the largest
+ * Nbound_m = sum_j w[m,j] max_b (lut[b,j] - centre_j)^2, the scale of the rounding bound. */
+int spart_lut_topk_obs_weights_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
+                                     int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nbound);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

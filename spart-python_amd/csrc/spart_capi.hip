@@ -688,18 +688,25 @@ static int lut_topk_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
 struct LutWideLayout {
   int rows, nbp, nch, nslice, nslice2, npart, cap;
   int64_t mc, gx;                                  // observations per chunk, observation blocks of a full chunk
-  size_t centre, norm, ctl, bq, ya, pc, ps, thr, cn, cand, flags, total;
+  size_t centre, norm, ctl, bq, ya, pc, ps, thr, cn, cand, flags, q, total;
 };
-static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, int k) {
+// obsw = true: spart_lut_topk_obs_weights -- Bq holds 2 nbp entries per observation, the chunk is cut so that Bq stays
+// within LUTOW_BQ_BYTES, ya holds (Y, Nbound) in float64, q the per-band Q_j, and the ctl words gain Nmax of the norm pass
+static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, int k, bool obsw = false) {
   LutWideLayout L;
   const size_t es = dtype == SPART_F64 ? 8 : 4;
   L.rows = dtype == SPART_F64 ? 16 : 32;
   const int groups = 64 / L.rows;
   const int64_t owg = 2 * LUTW_TB * L.rows, rwg = 2 * LUTW_TR * L.rows;
   const int64_t nrb = (B + rwg - 1) / rwg;
-  L.mc = M < LUTW_CHUNK ? M : LUTW_CHUNK;
-  L.gx = (L.mc + owg - 1) / owg;
   L.nbp = (nb + 1 + LUTW_KC - 1) / LUTW_KC * LUTW_KC;        // K = nb + 1 (the n_b column), whole chunks
+  int64_t chunk = LUTW_CHUNK;
+  if (obsw) {
+    const int64_t fit = (int64_t)(LUTOW_BQ_BYTES / (2 * (size_t)L.nbp * es)) / 1024 * 1024;
+    chunk = fit < 1024 ? 1024 : (fit < chunk ? fit : chunk);
+  }
+  L.mc = M < chunk ? M : chunk;
+  L.gx = (L.mc + owg - 1) / owg;
   L.nch = L.nbp / LUTW_KC;
   // slices: enough workgroups to fill the device (~2048), and for the bound at least 2k values (two per partial result)
   int64_t occ = (2048 + L.gx - 1) / L.gx;
@@ -718,15 +725,17 @@ static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, in
   size_t o = 0;
   L.centre = o; o = align_up(o + (size_t)nb * es);
   L.norm = o;   o = align_up(o + (size_t)B * es);
-  L.ctl = o;    o = align_up(o + LUT_TOPK_CTL_WORDS * 8);
-  L.bq = o;     o = align_up(o + mc * (size_t)L.nbp * es);
-  L.ya = o;     o = align_up(o + mc * es);
+  L.ctl = o;    o = align_up(o + (obsw ? 2 * LUT_TOPK_CTL_WORDS : LUT_TOPK_CTL_WORDS) * 8);
+  L.bq = o;     o = align_up(o + mc * (size_t)L.nbp * es * (obsw ? 2 : 1));
+  L.ya = o;     o = align_up(o + mc * (obsw ? 16 : es));
   L.pc = o;     o = align_up(o + (size_t)L.npart * mc * es);
   L.ps = o;     o = align_up(o + (size_t)L.npart * mc * es);
   L.thr = o;    o = align_up(o + mc * es);
   L.cn = o;     o = align_up(o + mc * 4);
   L.cand = o;   o = align_up(o + mc * (size_t)L.cap * 4);
   L.flags = o;  o = align_up(o + (size_t)M * 4);
+  L.q = o;
+  if (obsw) o = align_up(o + (size_t)nb * 8);
   L.total = o;
   return L;
 }
@@ -779,6 +788,68 @@ static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
   // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
   hipLaunchKernelGGL((k_lutw_select<T, ROWS, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B, (int64_t)0, M,
                      k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost);
+  HIP_TRY(hipGetLastError());
+  return SPART_OK;
+}
+
+// ---- per-observation weights (csrc/spart_lut.h, "per-observation weights"): the wide pipeline with K = 2 nbp.
+template <typename T>
+static int lut_obsw_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int k,
+                         int64_t* idx, void* cost, char* wsp, hipStream_t st) {
+  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, k, true);
+  constexpr int ROWS = LutWide<T>::ROWS;
+  constexpr int OWG = 2 * LUTW_TB * ROWS;
+  const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
+  T* centre = (T*)(wsp + L.centre);
+  T* norm = (T*)(wsp + L.norm);
+  unsigned long long* ctl = (unsigned long long*)(wsp + L.ctl);
+  T* bq = (T*)(wsp + L.bq);
+  double* yn = (double*)(wsp + L.ya);
+  T* pc = (T*)(wsp + L.pc);
+  T* ps = (T*)(wsp + L.ps);
+  T* thr = (T*)(wsp + L.thr);
+  int* cn = (int*)(wsp + L.cn);
+  int* cand = (int*)(wsp + L.cand);
+  int* flags = (int*)(wsp + L.flags);
+  unsigned long long* qb = (unsigned long long*)(wsp + L.q);
+  // the coefficients of Delta (spart_lut.h, per-observation weights), with the 1 % slack
+  const double u = (double)LutNum<T>::u;
+  const double h = 2.0 * LUTW_KC + L.nch + 1.0;
+  const double ce = (4.0 + 1.0 + 1.0 + 2.0 * h) * 1.01 * u;
+  const double cf = 2.01 * (nb + 3.0) * 1.01 * u;
+  HIP_TRY(hipMemsetAsync(ctl, 0, 2 * LUT_TOPK_CTL_WORDS * 8, st));
+  HIP_TRY(hipMemsetAsync(qb, 0, (size_t)nb * 8, st));
+  hipLaunchKernelGGL((k_lut_centre<T>), dim3(nb), dim3(256), 0, st, lut, nb, B, centre, ctl);
+  HIP_TRY(hipGetLastError());
+  // the row rule without weights; its Nmax goes to a word of its own (ctl[0] is the largest Nbound_m)
+  hipLaunchKernelGGL((k_lutw_norm<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, lut, (const T*)nullptr,
+                     (const T*)centre, nb, B, norm, ctl + LUT_TOPK_CTL_WORDS);
+  HIP_TRY(hipGetLastError());
+  const int64_t qy = (B + 3) / 4;
+  hipLaunchKernelGGL((k_lutow_q<T>), dim3((unsigned)((nb + 63) / 64), (unsigned)(qy < 1024 ? qy : 1024)), dim3(256), 0, st, lut,
+                     (const T*)norm, (const T*)centre, nb, B, qb);
+  HIP_TRY(hipGetLastError());
+  const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
+  for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
+    const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
+    const unsigned gx = (unsigned)((mc + OWG - 1) / OWG), gobs = (unsigned)((mc + 3) / 4);
+    hipLaunchKernelGGL((k_lutow_obs<T>), dim3(gobs), dim3(256), 0, st, obs + m0 * nb, w + m0 * nb, (const T*)centre,
+                       (const unsigned long long*)qb, nb, L.nbp, mc, bq, yn, ctl);
+    hipLaunchKernelGGL((k_lutow_gemm<T, false>), dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm,
+                       (const T*)centre, nb, B, (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr,
+                       (int*)nullptr);
+    hipLaunchKernelGGL((k_lutow_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const double*)yn, nb, mc, L.npart,
+                       k, ce, cf, thr, cn);
+    hipLaunchKernelGGL((k_lutow_gemm<T, true>), dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm,
+                       (const T*)centre, nb, B, (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap,
+                       cn, cand);
+    hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, true>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
+                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, (const T*)norm);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
+                     (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost,
+                     (const T*)norm);
   HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
@@ -1328,6 +1399,59 @@ int spart_lut_topk_wide_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int6
     *nmax = f;
   } else {
     std::memcpy(nmax, &ctl[0], 8);
+  }
+  return SPART_OK;
+}
+
+
+size_t spart_lut_topk_obs_weights_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k) {
+  if (B <= 0 || M <= 0 || nb < 1 || nb > NWLS || k < 1 || k > LUT_TOPK_MAXK || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
+  return lut_wide_layout(dtype, B, nb, M, k, true).total;
+}
+
+int spart_lut_topk_obs_weights(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
+                               const void* weights, int k, int64_t* idx, void* cost, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  const char* who = "spart_lut_topk_obs_weights";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  if (B < 0 || M < 0 || nb < 1 || nb > NWLS || B > 2000000000LL || M > 2000000000LL)
+    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d; 1 <= nb <= %d, B and M <= 2e9)", who, (long long)B,
+                (long long)M, nb, NWLS);
+  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
+  if (M == 0) return SPART_OK;
+  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", who);
+  const void* ptrs[5] = {lut, obs, weights, idx, cost};         // weights (M, nb) are required
+  if (first_null(ptrs, 5) < 5) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  const size_t need = spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k);
+  if (!workspace || workspace_bytes < need)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) {
+      return lut_obsw_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, (char*)workspace, st);
+    });
+  });
+}
+
+int spart_lut_topk_obs_weights_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void* workspace,
+                                     int64_t* n_brute_force, int64_t* n_candidates, int64_t* max_candidates, double* nbound) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_topk_obs_weights_stats: null context");
+  const void* ptrs[5] = {workspace, n_brute_force, n_candidates, max_candidates, nbound};
+  if (first_null(ptrs, 5) < 5 || spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k) == 0)
+    return fail(SPART_ERR_INVALID, "spart_lut_topk_obs_weights_stats: bad argument");
+  DeviceGuard guard(ctx->device);
+  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
+  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_wide_layout(dtype, B, nb, M, k, true).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  *n_brute_force = (int64_t)ctl[1];
+  *n_candidates = (int64_t)ctl[2];
+  *max_candidates = (int64_t)ctl[3];
+  if (dtype == SPART_F32) {
+    const unsigned b = (unsigned)ctl[0];
+    float f;
+    std::memcpy(&f, &b, 4);
+    *nbound = f;
+  } else {
+    std::memcpy(nbound, &ctl[0], 8);
   }
   return SPART_OK;
 }

@@ -1306,20 +1306,26 @@ __global__ __launch_bounds__(256) void k_lutw_bound(const T* __restrict__ part_c
 // The exact top-k of one observation (k_lut_topk_select for any nb): single-wave workgroups; dynamic LDS = the key / row
 // buffer, the observation and the weights (LUT_TOPK_BUF x 12 + 2 nb sizeof(T) bytes: 40.7 KB at nb = 2162 in float64).
 // BRUTE = false: the rows of the candidate tiles of chunk observation blockIdx.x; BRUTE = true: every row, for the flagged ones.
-template <typename T, int ROWS, bool BRUTE>
+// OBSW = true (spart_lut_topk_obs_weights): w is (M, nb), one weight row per observation, loaded with the observation; a band
+// of weight zero is skipped; an observation with a negative or non-finite weight, or a non-finite value in a band of non-zero
+// weight, matches nothing; a row counts only if its norm (k_lutw_norm without weights) is finite, whatever the observation.
+template <typename T, int ROWS, bool BRUTE, bool OBSW = false>
 __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
                                                     int nb, int64_t B, int64_t m_off, int64_t Mc, int k, const T* __restrict__ thr,
                                                     const int* __restrict__ cand_n, const int* __restrict__ cand, int cap,
                                                     unsigned long long* __restrict__ ctl, int* __restrict__ flag_list,
-                                                    int64_t* __restrict__ out_idx, T* __restrict__ out_cost) {
+                                                    int64_t* __restrict__ out_idx, T* __restrict__ out_cost,
+                                                    const T* __restrict__ norm = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char lutw_smem[];
   unsigned long long* sk = reinterpret_cast<unsigned long long*>(lutw_smem);
   int* sr = reinterpret_cast<int*>(sk + LUT_TOPK_BUF);
   T* ys = reinterpret_cast<T*>(sr + LUT_TOPK_BUF);
   T* wsm = ys + nb;
   const int lane = threadIdx.x & 63;
-  if (w)
-    for (int j = lane; j < nb; j += 64) wsm[j] = w[j];
+  if constexpr (!OBSW) {
+    if (w)
+      for (int j = lane; j < nb; j += 64) wsm[j] = w[j];
+  }
   const unsigned count = BRUTE ? (unsigned)ctl[1] : 0u;
   const int64_t nwork = BRUTE ? (int64_t)count : Mc;
   const int64_t stride_w = BRUTE ? (int64_t)gridDim.x : nwork;
@@ -1330,7 +1336,13 @@ __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, c
     for (int j = lane; j < nb; j += 64) {
       const T v = obs[m * nb + j];
       ys[j] = v;
-      fin = fin && LutNum<T>::finite(v);
+      if constexpr (OBSW) {
+        const T wj = w[m * nb + j];
+        wsm[j] = wj;
+        fin = fin && wj >= T(0) && LutNum<T>::finite(wj) && (wj == T(0) || LutNum<T>::finite(v));
+      } else {
+        fin = fin && LutNum<T>::finite(v);
+      }
     }
     lut_wave_sync();
     int64_t* oi = out_idx + m * k;
@@ -1375,7 +1387,16 @@ __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, c
         SPART_NO_CONTRACT
         const T* x = lut + r * nb;
         T c = T(0);
-        if (w) {
+        if constexpr (OBSW) {
+          if (!LutNum<T>::finite(norm[r])) c = (T)INFINITY;            // a rejected row: never a candidate
+          else
+            for (int j = 0; j < nb; ++j) {
+              const T wj = wsm[j];
+              if (wj == T(0)) continue;                                 // the mask: no operation at all
+              const T d = x[j] - ys[j];
+              c = c + (wj * d) * d;
+            }
+        } else if (w) {
           for (int j = 0; j < nb; ++j) {
             const T d = x[j] - ys[j];
             c = c + (wsm[j] * d) * d;
@@ -1428,6 +1449,293 @@ __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, c
       oi[i] = ok ? (int64_t)sr[i] : (int64_t)-1;
       oc[i] = ok ? LutKey<T>::value(sk[i]) : (T)INFINITY;
     }
+  }
+}
+
+// ---- per-observation weights (spart_lut_topk_obs_weights): the k rows of smallest
+//
+//     c_T(b, m):  c = 0;  for j = 0 .. nb-1:  if (w_mj == 0) continue;  d = x_bj - y_mj;  c = c + (w_mj * d) * d
+//
+// for any 1 <= nb <= 2162, with a weight row w_m per observation.  A band of weight zero adds no operation, so y_mj may be NaN
+// or inf there: that is the mask.  A row is accepted by k_lutw_norm without weights (finite entries, finite unweighted centred
+// norm), whatever the observation; an observation with a negative or non-finite weight, or a non-finite value in a band of
+// non-zero weight, matches no row.  Order, padding and the non-finite rules are otherwise spart_lut_topk_wide's.
+//   1. k_lut_centre, k_lutw_norm (w = NULL)   centres, and n_b = +inf for a rejected row (the filter norm itself is unused)
+//   2. k_lutow_q             Q_j = max over the accepted rows of fl(x'_bj^2), the per-band scale of the bound
+//   per chunk of observations:
+//   3. k_lutow_obs           the operand row Bq_m = [(w_mj, fl(-2 w_mj y'_mj)) for j < nb, (1, 0), (0, 0) ...] (pairs, zero for a
+//                            masked band), Y_m = sum w_mj y'_mj^2 and Nbound_m = sum w_mj Q_j (float64); Y_m = NaN for an
+//                            observation the filter must not touch (invalid, or an operand that overflows)
+//   4. k_lutow_gemm<false>   a~(b, m) = sum_j w_mj fl(x'_bj^2) - 2 w_mj y'_mj x'_bj: K = 2 nbp, LUT rows staged once per
+//                            LUTW_KC-band chunk exactly as k_lutw_gemm does, the squares formed in registers.  On
+//                            v_mfma_f32_32x32x2_f32 an MFMA takes one band (lane group 0: x'^2 against w, group 1: x' against
+//                            -2 w y'); on v_mfma_f64_16x16x4_f64 two.  A rejected row enters as x' = 0 in every band and
+//                            2^100 / 2^600 in the extra slot (band nb, operand (1, 0)): its square is +inf, its product with
+//                            0 is 0, so its filter value is +inf and it is never a minimum.  Partial results as k_lutw_gemm.
+//   5. k_lutow_bound         thr = U + Delta (below); NaN when Y_m or Nbound_m is non-finite or 4 (Nbound_m + Y_m) overflows
+//   6. k_lutow_gemm<true>    candidate tiles under thr
+//   7. k_lutw_select<., ., false, true>   the exact top-k over the candidate rows: the observation's own weight row in the
+//                            select's dynamic LDS, the zero-skip rule, the row rule through n_b
+//   8. k_lutw_select<., ., true, true>    the brute force for the flagged observations
+//
+// Delta.  N_bm = sum_j w_mj x'_bj^2 over the accepted row b, Y_m = sum_j w_mj y'_mj^2, c(b) the real-number cost, all sums over
+// the bands of non-zero weight (a masked band adds exactly 0 to a~ and to c_T).  The weights are non-negative by definition.
+//   (i)   centring: | sum w (x - y)^2 - sum w (x' - y')^2 |                <= 4 u (N_bm + Y_m)
+//   (ii)  the squares: | sum w fl(x'^2) - sum w x'^2 |                      <= u N_bm
+//   (iii) Bq = fl(-2 w y') (the -2 w is exact): | 2 sum w x' y' e |         <= u (N_bm + Y_m)
+//   (iv)  a K chunk carries 2 LUTW_KC operand entries; every term passes through at most 2 LUTW_KC roundings in its chunk's MFMA
+//         chain and nch - 1 additions of chunk sums: depth h = 2 LUTW_KC + nch + 1 over terms whose absolute sum is
+//         sum w fl(x'^2) + 2 sum w |x' y'| <= 2 (N_bm + Y_m) (to first order), so the error is <= 2 h u (N_bm + Y_m)
+//   =>    | a~(b) + Y_m - c(b) | <= E_b = ce (N_bm + Y_m),  ce = (4 + 1 + 1 + 2 h) u
+//   (v)   the direct evaluation: skipping a band adds no rounding, so |c_T(b) - c(b)| <= F_b = (nb + 3) u c(b).
+// For the k rows a_1..a_k behind U and a* the one of largest c_T (the narrow argument) every b with c_T(b) <= c_k satisfies
+//     a~(b) <= U + E_a* + E_b + F_a* + F_b.
+// N for the rows that matter (a* and every such b), with N_0 = Nbound_m = sum_j w_mj Q_j >= N_bm for every accepted row:
+//     c(a*) <= a~(a*) + Y_m + E_a* <= C(N) = max(U + Y_m + ce (N + Y_m), 0)  and  c(b) <= c(a*) (1 + f) / (1 - f), f = (nb + 3) u;
+//     sqrt(N_b) = |x'_b|_w <= |y'|_w + |x'_b - y'|_w = sqrt(Y_m) + sqrt(c'(b)), c'(b) <= c(b) + 4 u (N + Y_m) (term (i)),
+//   so N_{i+1} = min(N_i, (sqrt(Y_m) + sqrt(C(N_i) (1 + f) / (1 - f) + 4 u (N_i + Y_m)))^2) bounds N_a* and N_b again; two steps
+//   are taken.  With relative-noise weights (w ~ 1 / y^2) Nbound_m can be 10^4 x Y_m; N_2 is about Y_m.
+// Then E_a* + E_b <= 2 ce (N_2 + Y_m) and F_a* + F_b <= 2.01 (nb + 3) u C(N_2):
+//     Delta = 2 ce (N_2 + Y_m) + cf C(N_2),   every coefficient times 1.01,
+// evaluated in float64 (the square roots and the squares with 1 % slack) and rounded up to the dtype as k_lutw_bound does.
+// Workspace: Bq is 2 nbp entries per observation; the chunk is LUTW_CHUNK observations, cut so that Bq stays within
+// LUTOW_BQ_BYTES (float64 at 2162 bands: 7 168 observations per chunk).
+constexpr size_t LUTOW_BQ_BYTES = size_t(1) << 28;
+
+// Q_j (bit patterns of non-negative values, combined with atomicMax): grid (bands / 64, row slices), a wave reads 64
+// consecutive bands of one row at a time
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutow_q(const T* __restrict__ lut, const T* __restrict__ norm, const T* __restrict__ centre,
+                                                 int nb, int64_t B, unsigned long long* __restrict__ qb) {
+  __shared__ T qs[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;
+  T mx = T(0);
+  if (j < nb) {
+    const T c = centre[j];
+    for (int64_t r = (int64_t)blockIdx.y * 4 + wv; r < B; r += (int64_t)gridDim.y * 4)
+      if (LutNum<T>::finite(norm[r])) {
+        const T xc = lut[r * nb + j] - c;
+        const T sq = xc * xc;                          // k_lutow_gemm's square, rounding for rounding
+        mx = sq > mx ? sq : mx;
+      }
+  }
+  qs[wv][lane] = mx;
+  __syncthreads();
+  if (wv == 0 && j < nb) {
+#pragma unroll
+    for (int i = 1; i < 4; ++i) mx = qs[i][lane] > mx ? qs[i][lane] : mx;
+    if (mx > T(0)) atomicMax(&qb[j], LutNum<T>::bits(mx));
+  }
+}
+
+// one wave per observation of the chunk: the operand pairs Bq (2 nbp entries), and yn[2 m] = Y_m, yn[2 m + 1] = Nbound_m;
+// ctl[0] = the largest finite Nbound_m (bit pattern in the dtype)
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutow_obs(const T* __restrict__ obs, const T* __restrict__ w, const T* __restrict__ centre,
+                                                   const unsigned long long* __restrict__ qb, int nb, int nbp, int64_t M,
+                                                   T* __restrict__ bq, double* __restrict__ yn, unsigned long long* __restrict__ ctl) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  double y = 0.0, nq = 0.0;
+  bool bad = false;
+  for (int j = lane; j < nbp; j += 64) {
+    T v0 = j == nb ? T(1) : T(0), v1 = T(0);
+    if (j < nb) {
+      const T wj = w[m * nb + j];
+      bad = bad || !(wj >= T(0)) || !LutNum<T>::finite(wj);
+      if (wj != T(0)) {
+        const T yv = obs[m * nb + j];
+        const T yc = yv - centre[j];
+        v0 = wj;
+        v1 = T(-2) * wj * yc;                          // k_lutw_obs's operand, -2.0 * w * (y - c)
+        bad = bad || !LutNum<T>::finite(yv) || !LutNum<T>::finite(v1);
+        y += (double)wj * (double)yc * (double)yc;
+        nq += (double)wj * (double)LutNum<T>::from_bits(qb[j]);
+      }
+      if (!LutNum<T>::finite(v0) || !LutNum<T>::finite(v1)) v0 = v1 = T(0);   // no NaN reaches the GEMM
+    }
+    bq[m * 2 * nbp + 2 * j] = v0;
+    bq[m * 2 * nbp + 2 * j + 1] = v1;
+  }
+  bad = __any(bad) != 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    y += __shfl_xor(y, off, 64);
+    nq += __shfl_xor(nq, off, 64);
+  }
+  if (lane == 0) {
+    yn[2 * m] = bad ? __builtin_nan("") : y;
+    yn[2 * m + 1] = nq;
+    const T nt = (T)nq;
+    if (!bad && LutNum<T>::finite(nt)) atomicMax(&ctl[0], LutNum<T>::bits(nt));
+  }
+}
+
+// k_lutw_gemm with K = 2 nbp: the operand pairs of the observation-weighted cost (the derivation above)
+template <typename T, bool COLLECT>
+__global__ __launch_bounds__(256) void k_lutow_gemm(const T* __restrict__ lut, const T* __restrict__ norm, const T* __restrict__ centre,
+                                                    int nb, int64_t B, const T* __restrict__ bq, int nbp, int64_t M, int nslice,
+                                                    T* __restrict__ part_cost, T* __restrict__ part_sec, const T* __restrict__ thr,
+                                                    int cap, int* __restrict__ cand_n, int* __restrict__ cand) {
+  using W = LutWide<T>;
+  constexpr int ROWS = W::ROWS, KSTEP = W::KSTEP, NACC = W::NACC, G = 64 / ROWS, KC = LUTW_KC, KQ = 2 * KC;
+  constexpr int TR = LUTW_TR, TB = LUTW_TB, RWG = 2 * TR * ROWS, OWG = 2 * TB * ROWS;
+  constexpr int PA = RWG + 1, PB = OWG + 1;            // LDS row pitches ([k][row]; +1: the transposing stores spread over banks)
+  const T huge = sizeof(T) == 4 ? (T)0x1p100 : (T)0x1p600;   // squares to +inf
+  __shared__ T As[KC * PA], Bs[KQ * PB], nsm[RWG];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int col = lane % ROWS, grp = lane / ROWS;      // operand lane: row / observation col of the tile, k = grp
+  const bool sq = (grp & 1) == 0;                      // this lane's K entries are the squares (against w)
+  const int64_t m0 = (int64_t)blockIdx.x * OWG;
+  const int slice = blockIdx.y;
+  const int64_t ntile = (B + ROWS - 1) / ROWS;
+  const int64_t nrb = (B + RWG - 1) / RWG;
+  const int64_t per = (nrb + nslice - 1) / nslice;
+  const int64_t rb0 = per * slice;
+  const int64_t rb1 = rb0 + per < nrb ? rb0 + per : nrb;
+  const int64_t bqp = 2 * (int64_t)nbp;
+  T best[TB], sec[TB], th[TB];
+#pragma unroll
+  for (int b2 = 0; b2 < TB; ++b2) {
+    const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+    best[b2] = (T)INFINITY;
+    sec[b2] = (T)INFINITY;
+    th[b2] = (T)__builtin_nan("");
+    if (COLLECT && m < M && LutNum<T>::finite(thr[m])) th[b2] = thr[m];
+  }
+  for (int64_t rb = rb0; rb < rb1; ++rb) {
+    const int64_t r0 = rb * RWG;
+    __syncthreads();                                   // (the previous block's LDS is read)
+    if (tid < RWG) nsm[tid] = r0 + tid < B ? norm[r0 + tid] : (T)INFINITY;
+    typename W::acc_t run[TR][TB];
+    for (int k0 = 0; k0 < nbp; k0 += KC) {
+      __syncthreads();
+      for (int e = tid; e < RWG * KC; e += 256) {     // LUT rows, centred on the way in; band nb = the rejection slot
+        const int r = e / KC, j = e % KC, kk = k0 + j;
+        const bool ok = LutNum<T>::finite(nsm[r]);
+        T v = T(0);
+        if (kk < nb) {
+          if (ok) v = lut[(r0 + r) * nb + kk] - centre[kk];
+        } else if (kk == nb) {
+          v = ok ? T(0) : huge;
+        }
+        As[j * PA + r] = v;
+      }
+      for (int e = tid; e < OWG * KQ; e += 256) {
+        const int mm = e / KQ, j = e % KQ;
+        const int64_t m = m0 + mm;
+        Bs[j * PB + mm] = m < M ? bq[m * bqp + 2 * (int64_t)k0 + j] : T(0);
+      }
+      __syncthreads();
+      typename W::acc_t acc[TR][TB];
+#pragma unroll
+      for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2)
+#pragma unroll
+          for (int i = 0; i < NACC; ++i) acc[t2][b2][i] = T(0);
+#pragma unroll
+      for (int s = 0; s < KQ / KSTEP; ++s) {
+        const int kq = s * KSTEP + grp, band = kq >> 1;
+        T a[TR], b[TB];
+#pragma unroll
+        for (int t2 = 0; t2 < TR; ++t2) {
+          const T x = As[band * PA + (wr * TR + t2) * ROWS + col];
+          a[t2] = x * (sq ? x : T(1));                 // fl(x'^2), or x' itself
+        }
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2) b[b2] = Bs[kq * PB + (wc * TB + b2) * ROWS + col];
+#pragma unroll
+        for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+          for (int b2 = 0; b2 < TB; ++b2) acc[t2][b2] = W::mfma(a[t2], b[b2], acc[t2][b2]);
+      }
+#pragma unroll
+      for (int t2 = 0; t2 < TR; ++t2)
+#pragma unroll
+        for (int b2 = 0; b2 < TB; ++b2) {
+          if (k0 == 0) run[t2][b2] = acc[t2][b2];
+          else {
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) run[t2][b2][i] = run[t2][b2][i] + acc[t2][b2][i];
+          }
+        }
+    }
+#pragma unroll
+    for (int t2 = 0; t2 < TR; ++t2) {
+      const int64_t tg = rb * (2 * TR) + wr * TR + t2;  // tile of ROWS LUT rows
+      if (tg >= ntile) break;                           // (wave-uniform)
+#pragma unroll
+      for (int b2 = 0; b2 < TB; ++b2) {
+        T mn = run[t2][b2][0];
+#pragma unroll
+        for (int i = 1; i < NACC; ++i) mn = __builtin_fmin(mn, run[t2][b2][i]);
+        if (mn != mn) mn = (T)INFINITY;
+        if (!COLLECT) {
+          sec[b2] = __builtin_fmin(sec[b2], __builtin_fmax(best[b2], mn));   // a tie with the best becomes `sec`
+          best[b2] = __builtin_fmin(best[b2], mn);
+        } else {
+#pragma unroll
+          for (int off = ROWS; off < 64; off <<= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, off, 64));   // all rows of the tile
+          if (grp == 0 && mn <= th[b2]) {
+            const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+            const int pos = atomicAdd(&cand_n[m], 1);
+            if (pos < cap) cand[m * cap + pos] = (int)tg;
+          }
+        }
+      }
+    }
+  }
+  if (!COLLECT) {
+#pragma unroll
+    for (int b2 = 0; b2 < TB; ++b2) {
+      const int64_t m = m0 + (wc * TB + b2) * ROWS + col;
+      if (m < M) {
+        const int64_t o = (((int64_t)slice * 2 + wr) * G + grp) * M + m;
+        part_cost[o] = best[b2];
+        part_sec[o] = sec[b2];
+      }
+    }
+  }
+}
+
+// one wave per observation of the chunk: thr = U + Delta (ce, cf with the 1 % slack), resets the candidate count
+template <typename T>
+__global__ __launch_bounds__(256) void k_lutow_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
+                                                     const double* __restrict__ yn, int nb, int64_t M, int npart, int k, double ce,
+                                                     double cf, T* __restrict__ thr, int* __restrict__ cand_n) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;                                  // (whole wave)
+  const T U = lut_topk_kth<T>(part_cost, part_sec, m, M, npart, k, lane);
+  if (lane == 0) {
+    const double Y = yn[2 * m], nq = yn[2 * m + 1];
+    const double big = sizeof(T) == 4 ? 3.4028234663852886e38 : 1.7976931348623157e308;
+    const double u = (double)LutNum<T>::u, f = (nb + 3.0) * u, grow = 1.01 * (1.0 + f) / (1.0 - f);
+    double N = nq, C = 0.0;
+    for (int it = 0; it < 3; ++it) {                   // C(N_0), N_1, C(N_1), N_2, C(N_2)
+      C = (double)U + Y + ce * (N + Y);
+      C = C > 0.0 ? C : 0.0;
+      if (it == 2) break;
+      const double s = __builtin_sqrt(Y) + __builtin_sqrt(C * grow + 4.04 * u * (N + Y));
+      const double ns = 1.01 * s * s;
+      N = ns < N ? ns : N;
+    }
+    double t = (double)U + (2.0 * ce * (N + Y) + cf * C);
+    t = t + (4.0 * (double)LutNum<T>::u * __builtin_fabs(t) + (double)LutNum<T>::tiny);
+    if (!(4.0 * (nq + Y) < big)) t = __builtin_nan("");   // (NaN Y: an observation the filter must not decide)
+    T tt = (T)t;                                       // (NaN / inf stay non-finite: the select flags m)
+    if constexpr (sizeof(T) == 4) {
+      if ((double)tt < t) {                            // round up: the next float above
+        const unsigned b = __float_as_uint(tt);
+        tt = tt > 0.0f ? __uint_as_float(b + 1u) : (tt == 0.0f ? __uint_as_float(1u) : __uint_as_float(b - 1u));
+      }
+    }
+    thr[m] = tt;
+    cand_n[m] = 0;
   }
 }
 

@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 9         # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 10        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -74,6 +74,13 @@ SIGNATURES = {
     "spart_lut_topk_wide_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp,
                                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                                  ctypes.POINTER(ctypes.c_int64), c_dp]),
+    "spart_lut_topk_obs_weights_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                                                     ctypes.c_int]),
+    "spart_lut_topk_obs_weights": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp,
+                                                  ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spart_lut_topk_obs_weights_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                                        vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                                        ctypes.POINTER(ctypes.c_int64), c_dp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

@@ -85,6 +85,20 @@ ROW_PITCH = (2176, 2048)
 LUT_NARROW_NB = 31     # spart_lut_nearest / spart_lut_topk take nb <= 31; above it lut_nearest / lut_topk call spart_lut_topk_wide
 
 
+def lut_weights_kind(shape, M, nb):
+    """Which LUT search a ``weights`` argument of Engine.lut_nearest / lut_topk selects: shape None -> "none"; (nb,) ->
+    "shared" (one weight per band for every observation: spart_lut_nearest / _topk / _topk_wide); (M, nb) -> "per_observation"
+    (one weight row per observation, zero = masked band: spart_lut_topk_obs_weights).  Any other shape: ValueError."""
+    if shape is None:
+        return "none"
+    shape = tuple(int(n) for n in shape)
+    if shape == (nb,):
+        return "shared"
+    if shape == (M, nb):
+        return "per_observation"
+    raise ValueError(f"weights has shape {shape}, expected (nb,) = ({nb},) or (M, nb) = ({M}, {nb})")
+
+
 # ---- the static tables a context is built from (spart_tables): the reference reads them from the dicts it is HANDED at call
 # time -- PROSPECT_5D(leafbio, optical_params) prospect_5d.py:158-167, BSM(soilpar, optical_params) bsm.py:45, 54-55,
 # SPART.run() self.optipar / self.ETpar / self.sensorinfo SPART.py:93-95, 181-184, 192, 202, 228 -- so an engine is keyed on
@@ -623,7 +637,8 @@ class Engine:
         distance ``c = sum_j (w_j * d_j) * d_j``, ``d = lut - obs`` (sequential, rounded to ``dtype``, no FMA), lowest index on
         ties, and that distance -- bit-exact against a brute-force loop (include/spart_hip.h: spart_lut_nearest).
         -> (idx (M,) int64 tensor, cost (M,) tensor); with ``stats=True`` also a dict with the number of observations that
-        took the brute-force path and the scale Nmax of the rounding bound (spart_lut_stats; synchronises)."""
+        took the brute-force path and the scale Nmax of the rounding bound (spart_lut_stats; synchronises).
+        ``weights`` (M, nb): one weight row per observation, a zero weight masking its band (lut_topk with k = 1)."""
         torch = self.torch
         dt = DTYPES[dtype]
         td = self._tdtype(dt)
@@ -632,10 +647,11 @@ class Engine:
         if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
             raise ValueError("lut (B, nb) and obs (M, nb) must share nb")
         w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=td).contiguous()
-        if w is not None and w.numel() != lut.shape[1]:
-            raise ValueError(f"weights has {w.numel()} entries, expected nb = {lut.shape[1]}")
         B, nb = lut.shape
         M = obs.shape[0]
+        if lut_weights_kind(None if w is None else w.shape, M, nb) == "per_observation":
+            res = self._lut_topk_obs_weights(lut, obs, w, 1, dt, td, stats)
+            return (res[0][:, 0], res[1][:, 0]) + tuple(res[2:])
         if nb > LUT_NARROW_NB:                                   # hyperspectral: the wide top-k with k = 1
             res = self._lut_topk_wide(lut, obs, w, 1, dt, td, stats)
             return (res[0][:, 0], res[1][:, 0]) + tuple(res[2:])
@@ -663,7 +679,9 @@ class Engine:
         padded with (-1, +inf) when fewer than k rows have a finite cost.  1 <= k <= 256.
         -> (idx (M, k) int64 tensor, cost (M, k) tensor); with ``stats=True`` also a dict with the number of observations that
         took the brute-force path, the candidate tiles (sum and maximum per observation) and Nmax (spart_lut_topk_stats;
-        synchronises)."""
+        synchronises).  ``weights`` is None, (nb,) -- one weight per band for every observation -- or (M, nb): one weight row
+        per observation (spart_lut_topk_obs_weights, any nb): a band of weight zero is skipped, so the observation may be NaN
+        there; the stats then report "nbound" (the largest per-observation bound scale) in place of "nmax"."""
         torch = self.torch
         dt = DTYPES[dtype]
         td = self._tdtype(dt)
@@ -673,10 +691,10 @@ class Engine:
         if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
             raise ValueError("lut (B, nb) and obs (M, nb) must share nb")
         w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=td).contiguous()
-        if w is not None and w.numel() != lut.shape[1]:
-            raise ValueError(f"weights has {w.numel()} entries, expected nb = {lut.shape[1]}")
         B, nb = lut.shape
         M = obs.shape[0]
+        if lut_weights_kind(None if w is None else w.shape, M, nb) == "per_observation":
+            return self._lut_topk_obs_weights(lut, obs, w, k, dt, td, stats)
         if nb > LUT_NARROW_NB:
             return self._lut_topk_wide(lut, obs, w, k, dt, td, stats)
         idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
@@ -723,6 +741,31 @@ class Engine:
                                                                               ctypes.byref(mcand), ctypes.byref(nmax)))
         return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
                            "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
+
+    def _lut_topk_obs_weights(self, lut, obs, w, k, dt, td, stats):
+        """spart_lut_topk_obs_weights on prepared device tensors (lut_nearest / lut_topk with (M, nb) weights)."""
+        torch = self.torch
+        B, nb = lut.shape
+        M = obs.shape[0]
+        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
+        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
+        n = int(self.lib.spart_lut_topk_obs_weights_workspace_bytes(dt, B, nb, M, k))
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
+        self.calls["spart_lut_topk_obs_weights"] += 1
+        rc = self.lib.spart_lut_topk_obs_weights(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(), w.data_ptr(), k,
+                                                 idx.data_ptr(), cost.data_ptr(), ws.data_ptr(), ctypes.c_size_t(ws.numel()),
+                                                 self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        if not stats:
+            return idx, cost
+        nbf, ncand, mcand, nbound = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        if M > 0:
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_obs_weights_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
+                                                                                     ctypes.byref(nbf), ctypes.byref(ncand),
+                                                                                     ctypes.byref(mcand), ctypes.byref(nbound)))
+        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
+                           "max_candidate_tiles": int(mcand.value), "nbound": float(nbound.value)}
 
     def profile(self, max_calls):
         """bracket the band kernel of the next ``max_calls`` run() calls with HIP events (0 = off)."""

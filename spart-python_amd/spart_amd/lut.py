@@ -293,7 +293,11 @@ def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, 
     only those rows are ever touched) and ONE all_gather of (cost, global row) per observation (and place) settles the
     result (sharding.lut_nearest_sharded / lut_topk_sharded); every rank returns the same arrays, equal bit for bit to the
     single-process search.  ``obs`` must then be the same on every rank.  ``shard=False`` never issues a collective, whether
-    or not a process group is initialised: each process searches the whole table for its own ``obs``."""
+    or not a process group is initialised: each process searches the whole table for its own ``obs``.
+
+    ``weights``: None, (nb,) (one weight per band) or (M, nb): one weight row per observation (spart_lut_topk_obs_weights;
+    a band of weight zero is skipped, so the observation may be NaN there -- noise_weights() builds such rows).  Under
+    ``shard=True`` (M, nb) weights must, like ``obs``, be the same on every rank."""
     import torch
     from .sharding import lut_nearest_sharded, lut_topk_sharded, shard_bounds
     if isinstance(lut, (str, os.PathLike)):
@@ -343,6 +347,29 @@ def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, 
     return out + (dict(info, rows=(lo, hi)),) if stats else out
 
 
+def noise_weights(obs, abs_sigma=0.0, rel_sigma=0.0):
+    """Per-observation weights of the usual noise model for invert_lut / retrieve / Engine.lut_topk: sigma_mj^2 =
+    abs_sigma_j^2 + (rel_sigma * obs_mj)^2, weight 1 / sigma_mj^2, and weight 0 -- a masked band -- wherever obs is not finite
+    (saturated, flagged or missing bands marked with NaN).  ``abs_sigma`` is a scalar or (nb,); ``rel_sigma`` a scalar.
+    -> (M, nb) float64.  A band whose sigma is exactly 0 gets weight +inf, which the search refuses: give abs_sigma > 0
+    when an observation can be exactly 0."""
+    o = np.asarray(obs, dtype=np.float64)
+    if o.ndim != 2:
+        raise ValueError(f"obs must be (M, nb), got shape {o.shape}")
+    a = np.asarray(abs_sigma, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != o.shape[1]):
+        raise ValueError(f"abs_sigma must be a scalar or ({o.shape[1]},), got shape {a.shape}")
+    r = float(rel_sigma)
+    if not (np.all(a >= 0) and r >= 0):
+        raise ValueError("abs_sigma and rel_sigma must be >= 0")
+    if not (np.any(a > 0) or r > 0):
+        raise ValueError("noise_weights needs abs_sigma or rel_sigma > 0")
+    ok = np.isfinite(o)
+    with np.errstate(divide="ignore"):
+        w = 1.0 / (a * a + (r * np.where(ok, o, 0.0)) ** 2)
+    return np.where(ok, w, 0.0)
+
+
 def summarise_rows(params, idx, block_rows=1 << 18):
     """mean / median / std (numpy's, ddof = 0) of the parameter rows ``params[idx[m]]`` per observation, padding (-1)
     excluded: params (B, P) array or memmap, idx (M, k) int64 -> three (M, P) float64 arrays (NaN where an observation has no
@@ -377,6 +404,7 @@ def summarise_rows(params, idx, block_rows=1 << 18):
 def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None):
     """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
     mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
+    ``weights`` as for invert_lut: (nb,) or (M, nb), e.g. noise_weights(obs, rel_sigma=0.02).
     -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, 27) float64, names (the 27 parameter names)."""
     idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
     _, params, _ = load_lut(lut_dir)

@@ -1,4 +1,5 @@
-"""Brute-force checkers of spart_lut_nearest and spart_lut_topk (tests/ and bench.py; tooling, not product).
+"""Brute-force checkers of spart_lut_nearest, spart_lut_topk and spart_lut_topk_obs_weights (tests/ and bench.py; tooling,
+not product).
 
 The cost is DEFINED (include/spart_hip.h) as the sequential evaluation, in the call's dtype and without fused multiply-adds,
 
@@ -124,5 +125,75 @@ def brute_force_topk_torch(lut, obs, k, w=None, max_elems=1 << 27):
         s, order = s[:, :kk], order[:, :kk]
         ok = s < inf
         idx[m0:m0 + mb, :kk] = torch.where(ok, order, torch.full_like(order, -1))
+        cost[m0:m0 + mb, :kk] = s
+    return idx, cost
+
+
+def _obs_weights_checks(lut, obs, w):
+    """the row and observation rules of spart_lut_topk_obs_weights: rows with a non-finite entry never appear; an observation
+    with a negative or non-finite weight, or a non-finite value in a band of non-zero weight, matches nothing"""
+    row_ok = np.isfinite(lut).all(axis=1)
+    obs_ok = ((w >= 0) & np.isfinite(w) & ((w == 0) | np.isfinite(obs))).all(axis=1)
+    return row_ok, obs_ok
+
+
+def brute_force_topk_obs_weights_numpy(lut, obs, k, w):
+    """spart_lut_topk_obs_weights' definition, literally: per observation m
+        c = 0;  for j: if w[m, j] == 0: skip;  d = lut[:, j] - obs[m, j];  c = c + (w[m, j] * d) * d
+    then the first k of the stable argsort (non-finite costs as +inf), padded with (-1, +inf).  lut (B, nb), obs and w (M, nb)
+    of one float dtype -> (idx (M, k) int64, cost (M, k)).  The rule on rows whose centred norm overflows depends on the
+    device's column centres and is not modelled: keep test LUTs far from overflow."""
+    lut = np.ascontiguousarray(lut)
+    dt = lut.dtype
+    obs = np.ascontiguousarray(obs, dtype=dt)
+    w = np.ascontiguousarray(w, dtype=dt)
+    B, nb = lut.shape
+    M = obs.shape[0]
+    idx = np.full((M, k), -1, dtype=np.int64)
+    cost = np.full((M, k), np.inf, dtype=dt)
+    row_ok, obs_ok = _obs_weights_checks(lut, obs, w)
+    cols = [np.ascontiguousarray(lut[:, j]) for j in range(nb)]
+    with np.errstate(all="ignore"):
+        for m in range(M):
+            if not obs_ok[m]:
+                continue
+            c = np.zeros(B, dtype=dt)
+            for j in range(nb):
+                if w[m, j] == 0:
+                    continue
+                d = cols[j] - obs[m, j]
+                c = c + (w[m, j] * d) * d
+            c[~row_ok] = np.inf
+            idx[m], cost[m] = _topk_from_costs_numpy(c, k)
+    return idx, cost
+
+
+def brute_force_topk_obs_weights_torch(lut, obs, k, w, max_elems=1 << 27):
+    """the same with eager torch ops, in blocks of observations; a masked band keeps the running cost as it is
+    (torch.where), which is the skip.  Tensors of one dtype on one device -> (idx (M, k) int64, cost (M, k))"""
+    import torch
+    B, nb = lut.shape
+    M = obs.shape[0]
+    inf = float("inf")
+    cols = [lut[:, j].contiguous() for j in range(nb)]
+    row_ok = torch.isfinite(lut).all(dim=1)
+    obs_ok = ((w >= 0) & torch.isfinite(w) & ((w == 0) | torch.isfinite(obs))).all(dim=1)
+    idx = torch.full((M, k), -1, dtype=torch.int64, device=lut.device)
+    cost = torch.full((M, k), inf, dtype=lut.dtype, device=lut.device)
+    kk = min(k, B)
+    mb = max(1, min(M, max_elems // max(B, 1)))
+    for m0 in range(0, M, mb):
+        o, ww = obs[m0:m0 + mb], w[m0:m0 + mb]
+        c = torch.zeros((o.shape[0], B), dtype=lut.dtype, device=lut.device)
+        for j in range(nb):
+            wj = ww[:, j][:, None]
+            d = cols[j][None, :] - o[:, j][:, None]
+            c = torch.where(wj == 0, c, c + (wj * d) * d)
+        ok = torch.isfinite(c) & row_ok[None, :] & obs_ok[m0:m0 + mb, None]
+        c = torch.where(ok, c, torch.full_like(c, inf))
+        s, order = torch.sort(c, dim=1, stable=True)
+        s, order = s[:, :kk], order[:, :kk]
+        fin = s < inf
+        idx[m0:m0 + mb, :kk] = torch.where(fin, order, torch.full_like(order, -1))
         cost[m0:m0 + mb, :kk] = s
     return idx, cost
