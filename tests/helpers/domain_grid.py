@@ -1,0 +1,193 @@
+"""The domain grid of the per-sample band tests (tests/test_band_sum_f32.py on the CPU, tests/test_gpu_band_sums.py on the
+GPU): deterministic rows at and past the corners of the LHS ranges, each tagged with its kind, with per-row thermal values,
+the float64 oracle's spectra and a conditioning-aware float32 bound.  Imports no part of the HIP package.
+
+kinds:  ota_full / ota_pro    one column of varying_columns(kind) at the min or the max of its RANGES, the others at
+                              default_row (pro: Cdm = 0, as lhs_params sets it)
+        past                  EDGE_ROWS (test_gpu_parity.test_hot_spot_and_geometry_edges) and values past the LHS ranges
+                              that the reference still accepts
+        corner_full / corner_pro   128 seeded corners per kind: every varying column at the min or the max of its range
+        golden                the rows of tests/golden/edge.npz whose leaf has water or dry matter (Cdm + Cw > 0)
+The first two and the corners lie inside the LHS ranges (INSIDE), the others outside.
+
+The float32 bound (bound32) comes from the oracle alone: SAILH is run a second time on the row's leaf and soil spectra
+rounded to float32, delta(row, band) = the relative change of its output with a floor of 1e-2, taken as the maximum over
++-SMOOTH neighbouring bands (one rounding can land near zero by chance), and bound = max(1e-4, C32 * delta).  Where delta
+is negligible this is the 1e-4 contract of the float32 spectra; where the model itself amplifies a float32 rounding of its
+inputs (weakly absorbing leaves in the near infrared at high LAI) the bound grows with it.
+"""
+import os
+
+import numpy as np
+
+from spart_amd_workloads import PARAM_NAMES, RANGES, default_row, varying_columns
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+COL = {n: i for i, n in enumerate(PARAM_NAMES)}
+SPECTRA = ("rso", "rdo", "rsd", "rdd")
+NEV = 2002             # band evaluations 0..2001 (2001 = the thermal evaluation)
+FLOOR = 1e-2           # rel_err floor of every comparison of the grid's spectra
+C32 = 4.0              # factor of the float32 bound on the conditioning delta
+SMOOTH = 3             # delta is the maximum over band +- SMOOTH
+DROPPED = 0            # rows the builder drops because the oracle is non-finite in some band
+INSIDE = ("ota_full", "ota_pro", "corner_full", "corner_pro")
+_D = default_row
+# the rows of test_gpu_parity.test_hot_spot_and_geometry_edges: hot spot exactly (dso == 0, nadir and off-nadir), tiny and
+# large q, tiny and large LAI, psi folding (270, 365 deg), grazing sun, SMp below the 5 % threshold, N = 1 (single plate),
+# PRO leaves.  Row 16 (Cdm = 0, PROT = 0.001, CBC = 0) is the nearly non-absorbing leaf of DESIGN.md section 5.
+EDGE_ROWS = [_D(tts=30, tto=30, psi=0), _D(tts=0, tto=0, psi=0), _D(q=0.001, tts=60, tto=30, psi=160),
+             _D(q=0.001, tts=5, tto=5, psi=1), _D(q=0.5), _D(LAI=0.01), _D(LAI=8), _D(psi=270), _D(psi=365), _D(psi=-40),
+             _D(tts=80, tto=60, psi=90), _D(SMp=3), _D(SMp=5), _D(N=1.0), _D(N=3.0, Cab=80, Cw=0.05),
+             _D(PROT=0.003, CBC=0.01), _D(Cdm=0.0, PROT=0.001, CBC=0.0), _D(Cs=1.0), _D(B=0.9, lat=30, lon=120, SMp=55),
+             _D(LIDFa=-1, LIDFb=0), _D(LIDFa=1, LIDFb=0), _D(LIDFa=0, LIDFb=-1), _D(aot550=0.0), _D(uh2o=0.0, uo3=0.0),
+             _D(Pa=500.0), _D(DOY=1), _D(DOY=365.5)]
+
+
+def thermal_draw(B, seed):
+    """per-row (rho, tau) with rho + tau <= 0.9, away from rho = tau = 0 (the reference's SAILH is NaN there)"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.005, 0.45, B), rng.uniform(0.005, 0.45, B)
+
+
+def _base(kind):
+    return _D(Cdm=0.0) if kind == "pro" else _D()
+
+
+def _one_at_a_time(kind):
+    rows = []
+    for n in varying_columns(kind):
+        for v in RANGES[n]:
+            r = _base(kind)
+            r[0, COL[n]] = v
+            rows.append(r)
+    return np.concatenate(rows)
+
+
+def _past():
+    D = _D
+    rows = list(EDGE_ROWS)
+    rows += [D(LAI=0.01), D(LAI=10)]
+    rows += [D(tts=t) for t in (70, 80, 85)] + [D(tto=t) for t in (45, 60, 75)]
+    rows += [D(psi=p) for p in (0, 90, 180, 270, 360)]
+    rows += [D(tts=30, tto=30, psi=0, q=q) for q in (0.001, 0.5, 1.0)]          # the exact hot spot
+    rows += [D(N=1.0), D(N=3.5), D(Cab=0), D(Cab=100), D(Cw=1e-4), D(Cw=0.08), D(Cdm=0), D(Cdm=0.04), D(Cs=0), D(Cs=1)]
+    rows += [D(film=f) for f in (1e-4, 4e-3, 0.05)] + [D(SMp=s) for s in (3, 5, 55, 70)] + [D(B=0.05), D(B=1.0)]
+    rows += [D(LIDFa=a, LIDFb=b) for a, b in ((1, 0), (-1, 0), (0, 1), (0, -1), (0.5, 0.5), (0.5, -0.5), (-0.5, 0.5),
+                                               (-0.5, -0.5), (0.75, -0.25), (-0.25, 0.75))]
+    return np.concatenate(rows)
+
+
+def _corners(kind, n, seed):
+    cols = varying_columns(kind)
+    pick = np.random.default_rng(seed).integers(0, 2, (n, len(cols)))
+    P = np.repeat(_base(kind), n, axis=0)
+    for j, c in enumerate(cols):
+        P[:, COL[c]] = np.where(pick[:, j] == 1, RANGES[c][1], RANGES[c][0])
+    return P
+
+
+def _golden_edge():
+    P = np.load(os.path.join(ROOT, "tests", "golden", "edge.npz"))["P"]
+    return P[(P[:, COL["Cdm"]] + P[:, COL["Cw"]]) > 0]
+
+
+def grid_params():
+    """(P (N, 27), kind (N,) str) before the oracle has seen them"""
+    parts = [("ota_full", _one_at_a_time("full")), ("ota_pro", _one_at_a_time("pro")), ("past", _past()),
+             ("corner_full", _corners("full", 128, 71)), ("corner_pro", _corners("pro", 128, 72)), ("golden", _golden_edge())]
+    P = np.concatenate([p for _, p in parts])
+    kind = np.concatenate([np.full(len(p), k) for k, p in parts])
+    return P, kind
+
+
+def common_body(P):
+    """rows whose own stage (chunk 1) runs the float32 band kernel's common-case body: cbc = prot = 0"""
+    return (P[:, COL["PROT"]] == 0) & (P[:, COL["CBC"]] == 0)
+
+
+def _f32(x):
+    return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def _smooth(d):
+    out = d.copy()
+    for s in range(1, SMOOTH + 1):
+        out[:, s:] = np.maximum(out[:, s:], d[:, :-s])
+        out[:, :-s] = np.maximum(out[:, :-s], d[:, s:])
+    return out
+
+
+def oracle_grid(oracle, tables, P, rho, tau, block=256):
+    """the float64 oracle on P (pso = "gl", per-row thermal values): padded leaf / soil spectra and rso, rdo, rsd, rdd at
+    bands 0..2001, kChlrel at bands 0..2000, and the conditioning delta (relative change of each spectrum and of their sum when SAILH is given the
+    leaf and soil spectra rounded to float32; floor 1e-2, smoothed)"""
+    out = {k: [] for k in ("leaf_refl", "leaf_tran", "leaf_kchl", "soil_refl") + SPECTRA + ("sum", "d_sum") + tuple("d_" + k for k in SPECTRA)}
+    for a in range(0, len(P), block):
+        p, r, t = P[a:a + block], rho[a:a + block], tau[a:a + block]
+        with np.errstate(all="ignore"):
+            o = oracle.spart_run(p, "Sentinel2A-MSI", tables, pso="gl", full=True, rho_thermal=r, tau_thermal=t)
+            lr, lt = oracle.pad_leaf(o["leaf_refl"], o["leaf_tran"], r, t)
+            rs = oracle.pad_soil(o["soil_refl"])
+            q = oracle.sailh(_f32(lr), _f32(lt), _f32(rs), p[:, 15:19], p[:, 19:22], pso="gl")
+        s0 = sum(o[k][:, :NEV] for k in SPECTRA)
+        s1 = sum(q[k][:, :NEV] for k in SPECTRA)
+        out["leaf_refl"].append(lr[:, :NEV])
+        out["leaf_tran"].append(lt[:, :NEV])
+        out["leaf_kchl"].append(o["kChlrel"])
+        out["soil_refl"].append(rs[:, :NEV])
+        out["sum"].append(s0)
+        out["d_sum"].append(np.abs(s1 - s0) / np.maximum(np.abs(s0), FLOOR))
+        for k in SPECTRA:
+            out[k].append(o[k][:, :NEV])
+            out["d_" + k].append(np.abs(q[k][:, :NEV] - o[k][:, :NEV]) / np.maximum(np.abs(o[k][:, :NEV]), FLOOR))
+    out = {k: np.concatenate(v) for k, v in out.items()}
+    for k in ("sum",) + SPECTRA:
+        out["d_" + k] = _smooth(out["d_" + k])
+    return out
+
+
+def build_grid(oracle, tables):
+    """the grid with the oracle's values: dict P, kind, rho, tau, inside (bool), common (bool) and oracle_grid's arrays.
+    Rows where the oracle is non-finite in any band are dropped (DROPPED of them)."""
+    P, kind = grid_params()
+    rho, tau = thermal_draw(len(P), 73)
+    ref = oracle_grid(oracle, tables, P, rho, tau)
+    ok = np.all(np.isfinite(ref["sum"]), axis=1)
+    for k in SPECTRA:
+        ok &= np.all(np.isfinite(ref[k]), axis=1)
+    assert (~ok).sum() == DROPPED, np.flatnonzero(~ok)
+    g = {k: v[ok] for k, v in ref.items()}
+    g.update(P=P[ok], kind=kind[ok], rho=rho[ok], tau=tau[ok])
+    g["inside"] = np.isin(g["kind"], INSIDE)
+    g["common"] = common_body(g["P"])
+    return g
+
+
+def bare_soil(P):
+    """The one exception regime of the float32 bound: LAI <= 1e-3 (edge.npz has LAI = 0 and 1e-4).  There rso, rdo, rsd and
+    rdd are each the soil reflectance, so their sum carries four times the soil model's float32 error against one floor;
+    edge.npz's soils reach |rs| < 1e-3 (GSV at |lat| > 30, negative dry soil), where that error is a few 1e-7 absolute.
+    The sum of such a row is held to 4e-4 (four times the 1e-4 contract of each spectrum); each spectrum to the usual bound."""
+    return P[:, COL["LAI"]] <= 1e-3
+
+
+BARE_SOIL_ROWS = 13    # rows of the grid in that regime (all from edge.npz)
+
+
+def bound32(g, key="sum"):
+    """(rows, 2002) float32 bound on |x - ref| / max(|ref|, FLOOR) of spectrum `key` ("sum" = rso + rdo + rsd + rdd)"""
+    b = np.maximum(1e-4, C32 * g["d_" + key])
+    if key == "sum":
+        b[bare_soil(g["P"])] = np.maximum(b[bare_soil(g["P"])], 4e-4)
+    return b
+
+
+def excess(got, g, key="sum"):
+    """(rows, 2002) error / bound: <= 1 everywhere is a pass"""
+    ref = g[key]
+    err = np.abs(np.asarray(got, dtype=np.float64) - ref) / np.maximum(np.abs(ref), FLOOR)
+    return err / bound32(g, key)
+
+
+def rel(got, ref):
+    return np.abs(np.asarray(got, dtype=np.float64) - ref) / np.maximum(np.abs(ref), FLOOR)

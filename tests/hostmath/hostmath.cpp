@@ -138,6 +138,38 @@ void hm_hotspot(int64_t n, const double* K, const double* k, const double* LAI, 
   }
 }
 
+// the float32 FULL = 1 sample of the headline band kernel (k_bands<float, 0, 1>) composed as its sample loop composes it:
+// constants from the literal prelude (the default float32 mode's), leaf_band<float, PRO>, canopy_core_l with C_KSL / C_KOL,
+// soil_dry -> soil_band_tw, canopy_soil_sum with C_TSTO.  common = 1: the common-case body (PRO = false, the film's
+// single-layer transmittance formed once per band and passed in); 0: the general body.  out: (B, 2002) rso + rdo + rsd + rdd
+void hm_band_sum_f32(int common, int64_t B, const double* tab, const double* P, const double* rho_th, const double* tau_th,
+                     double* out) {
+  for (int64_t s = 0; s < B; ++s) {
+    float c[NCONST];
+    double a[NATM], li[NLINCL];
+    sample_prelude<float, false>(P + s * NPARAM, rho_th[s], tau_th[s], PRE_ALL, c, a, li);
+    CanopyPar<float> cp;
+    cp.sob = c[C_SOB]; cp.sof = c[C_SOF]; cp.hbf = c[C_HBF]; cp.ks = c[C_KS]; cp.ko = c[C_KO]; cp.lai = c[C_LAI];
+    cp.lai2 = c[C_LAI2]; cp.tss = c[C_TSS]; cp.too = c[C_TOO]; cp.Z = c[C_Z]; cp.hot = c[C_HOT]; cp.pso2w = c[C_PSO2W];
+    for (int band = 0; band < NEVAL; ++band) {
+      const bool thermal = band == NWL;
+      const BandTab<float> tb = tab_at<float>(tab, thermal ? NWL - 1 : band);
+      float refl, tran, absb, K;
+      if (common) leaf_band<float, false>(tb, c[C_CAB], c[C_CCA], c[C_CDM], c[C_CW], c[C_CS], c[C_CANT], c[C_CBC], c[C_PROT], c[C_NM1], refl, tran, absb, K);
+      else leaf_band<float, true>(tb, c[C_CAB], c[C_CCA], c[C_CDM], c[C_CW], c[C_CS], c[C_CANT], c[C_CBC], c[C_PROT], c[C_NM1], refl, tran, absb, K);
+      const float rho = thermal ? c[C_RHO_TH] : refl, tau = thermal ? c[C_TAU_TH] : tran;
+      const float ab = thermal ? (1.0f - c[C_RHO_TH] - c[C_TAU_TH]) : absb;
+      const CanopyCore<float> core = canopy_core_l<float>(cp, rho, tau, ab, c[C_KSL], c[C_KOL]);
+      const float rdry = soil_dry<float>(tb, c[C_F1], c[C_F2], c[C_F3]);
+      const float fm[7] = {c[C_FM0], c[C_FM1], c[C_FM2], c[C_FM3], c[C_FM4], c[C_FM5], c[C_FM6]};
+      const float tw1 = soil_tw1<float>(tb, c[C_FILM2L]);
+      float rwet;
+      soil_band_tw<float>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1, rwet);
+      out[(size_t)s * NEVAL + band] = canopy_soil_sum<float>(cp, core, rwet, c[C_TSTO]);
+    }
+  }
+}
+
 void hm_log1p(int dtype, int64_t n, const double* x, double* out) {
   for (int64_t i = 0; i < n; ++i) out[i] = dtype == 0 ? (double)Mx<float>::log1p((float)x[i]) : Mx<double>::log1p(x[i]);
 }

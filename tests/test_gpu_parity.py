@@ -620,15 +620,9 @@ def test_lidf_full_reference_grid(oracle, torch_mod):
 def test_hot_spot_and_geometry_edges(oracle, tables, dtype, torch_mod):
     """hot spot exactly (dso == 0, nadir and off-nadir), tiny and large q, tiny and large LAI, psi folding
     (270, 365 deg), grazing sun, SMp below the 5 % threshold, N = 1 (single plate), PRO leaves."""
-    from spart_amd import get_engine, workloads
-    D = workloads.default_row
-    rows = [D(tts=30, tto=30, psi=0), D(tts=0, tto=0, psi=0), D(q=0.001, tts=60, tto=30, psi=160),
-            D(q=0.001, tts=5, tto=5, psi=1), D(q=0.5), D(LAI=0.01), D(LAI=8), D(psi=270), D(psi=365), D(psi=-40),
-            D(tts=80, tto=60, psi=90), D(SMp=3), D(SMp=5), D(N=1.0), D(N=3.0, Cab=80, Cw=0.05),
-            D(PROT=0.003, CBC=0.01), D(Cdm=0.0, PROT=0.001, CBC=0.0), D(Cs=1.0), D(B=0.9, lat=30, lon=120, SMp=55),
-            D(LIDFa=-1, LIDFb=0), D(LIDFa=1, LIDFb=0), D(LIDFa=0, LIDFb=-1), D(aot550=0.0), D(uh2o=0.0, uo3=0.0),
-            D(Pa=500.0), D(DOY=1), D(DOY=365.5)]
-    P = np.concatenate(rows)
+    from spart_amd import get_engine
+    from helpers.domain_grid import EDGE_ROWS
+    P = np.concatenate(EDGE_ROWS)
     ref = oracle.spart_run(P, "Sentinel2A-MSI", tables, pso="quad", full=True)
     eng = get_engine("Sentinel2A-MSI", 0)
     out = eng.run(torch_mod.as_tensor(P.T.copy(), device="cuda:0"), dtype, materialize=("rso", "rdd", "leaf_refl", "soil_refl"))

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_err
+from helpers.domain_grid import thermal_draw as _thermal_draw
 from test_thermal import COLUMNS, GROUPS, SENSORS, SPECTRA, edited_tables
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
@@ -34,12 +35,6 @@ def fx():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     return np.load(os.path.join(ROOT, "tests", "golden", "thermal.npz"))
-
-
-def _thermal_draw(B, seed):
-    """per-row (rho, tau) with rho + tau <= 0.9, away from rho = tau = 0 (the reference's SAILH is NaN there)"""
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.005, 0.45, B), rng.uniform(0.005, 0.45, B)
 
 
 def finite_limit(a):
