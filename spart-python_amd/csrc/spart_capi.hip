@@ -479,6 +479,16 @@ static int lut_slices(int64_t M, int64_t ntile, int obs_per_wg) {
   return (int)n;
 }
 
+// a workspace handed out field by field: take(bytes) is the field's offset, and the next field starts align_up later
+struct Carver {
+  size_t o = 0;
+  size_t take(size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes);
+    return at;
+  }
+};
+
 struct LutLayout {
   int ks, to, rows, nslice, npart, kfma;
   int64_t ntile, nfb;
@@ -497,17 +507,17 @@ static LutLayout lut_layout(int dtype, int64_t B, int nb, int64_t M) {
   L.npart = (64 / L.rows) * L.nslice;
   const int64_t mgroups = (M + 63) / 64;
   L.nfb = mgroups > (int64_t)LUT_FB_BLOCKS * 4 ? mgroups : (int64_t)LUT_FB_BLOCKS * 4;
-  size_t o = 0;
-  L.tiles = o;  o = align_up(o + (size_t)L.ntile * L.ks * 64 * es);
-  L.pc = o;     o = align_up(o + (size_t)L.npart * M * es);
-  L.ps = o;     o = align_up(o + (size_t)L.npart * M * es);
-  L.pt = o;     o = align_up(o + (size_t)L.npart * M * 4);
-  L.centre = o; o = align_up(o + 32 * es);
-  L.ctl = o;    o = align_up(o + LUT_CTL_WORDS * 8);
-  L.flags = o;  o = align_up(o + (size_t)M * 4);
-  L.fbc = o;    o = align_up(o + (size_t)L.nfb * 64 * es);
-  L.fbi = o;    o = align_up(o + (size_t)L.nfb * 64 * 8);
-  L.total = o;
+  Carver c;
+  L.tiles = c.take((size_t)L.ntile * L.ks * 64 * es);
+  L.pc = c.take((size_t)L.npart * M * es);
+  L.ps = c.take((size_t)L.npart * M * es);
+  L.pt = c.take((size_t)L.npart * M * 4);
+  L.centre = c.take(32 * es);
+  L.ctl = c.take(LUT_CTL_WORDS * 8);
+  L.flags = c.take((size_t)M * 4);
+  L.fbc = c.take((size_t)L.nfb * 64 * es);
+  L.fbi = c.take((size_t)L.nfb * 64 * 8);
+  L.total = c.o;
   return L;
 }
 // Delta = coef_ef * [(N_a + Y) + (N_b + Y)]: spart_lut.h derives (3 nb + 2 K + 13) u; + 3 and 1 % for the second-order terms.
@@ -597,18 +607,18 @@ static LutTopkLayout lut_topk_layout(int dtype, int64_t B, int nb, int64_t M, in
   L.nslice2 = b.nslice;                            // the collect scan: the k = 1 scan's occupancy rule
   L.cap = lut_topk_cap(k);
   const size_t mc = (size_t)L.mc;
-  size_t o = 0;
-  L.tiles = o;  o = align_up(o + (size_t)b.ntile * b.ks * 64 * es);
-  L.pc = o;     o = align_up(o + (size_t)L.npart * mc * es);
-  L.ps = o;     o = align_up(o + (size_t)L.npart * mc * es);
-  L.pt = o;     o = align_up(o + (size_t)L.npart * mc * 4);
-  L.thr = o;    o = align_up(o + mc * es);
-  L.cn = o;     o = align_up(o + mc * 4);
-  L.cand = o;   o = align_up(o + mc * (size_t)L.cap * 4);
-  L.centre = o; o = align_up(o + 32 * es);
-  L.ctl = o;    o = align_up(o + LUT_TOPK_CTL_WORDS * 8);
-  L.flags = o;  o = align_up(o + (size_t)M * 4);
-  L.total = o;
+  Carver c;
+  L.tiles = c.take((size_t)b.ntile * b.ks * 64 * es);
+  L.pc = c.take((size_t)L.npart * mc * es);
+  L.ps = c.take((size_t)L.npart * mc * es);
+  L.pt = c.take((size_t)L.npart * mc * 4);
+  L.thr = c.take(mc * es);
+  L.cn = c.take(mc * 4);
+  L.cand = c.take(mc * (size_t)L.cap * 4);
+  L.centre = c.take(32 * es);
+  L.ctl = c.take(LUT_TOPK_CTL_WORDS * 8);
+  L.flags = c.take((size_t)M * 4);
+  L.total = c.o;
   return L;
 }
 
@@ -692,7 +702,7 @@ struct LutWideLayout {
 };
 // obsw = true: spart_lut_topk_obs_weights -- Bq holds 2 nbp entries per observation, the chunk is cut so that Bq stays
 // within LUTOW_BQ_BYTES, ya holds (Y, Nbound) in float64, q the per-band Q_j, and the ctl words gain Nmax of the norm pass
-static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, int k, bool obsw = false) {
+static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, int k, bool obsw) {
   LutWideLayout L;
   const size_t es = dtype == SPART_F64 ? 8 : 4;
   L.rows = dtype == SPART_F64 ? 16 : 32;
@@ -722,140 +732,101 @@ static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, in
   L.nslice2 = (int)(occ < 1 ? 1 : occ);
   L.cap = lut_topk_cap(k);
   const size_t mc = (size_t)L.mc;
-  size_t o = 0;
-  L.centre = o; o = align_up(o + (size_t)nb * es);
-  L.norm = o;   o = align_up(o + (size_t)B * es);
-  L.ctl = o;    o = align_up(o + (obsw ? 2 * LUT_TOPK_CTL_WORDS : LUT_TOPK_CTL_WORDS) * 8);
-  L.bq = o;     o = align_up(o + mc * (size_t)L.nbp * es * (obsw ? 2 : 1));
-  L.ya = o;     o = align_up(o + mc * (obsw ? 16 : es));
-  L.pc = o;     o = align_up(o + (size_t)L.npart * mc * es);
-  L.ps = o;     o = align_up(o + (size_t)L.npart * mc * es);
-  L.thr = o;    o = align_up(o + mc * es);
-  L.cn = o;     o = align_up(o + mc * 4);
-  L.cand = o;   o = align_up(o + mc * (size_t)L.cap * 4);
-  L.flags = o;  o = align_up(o + (size_t)M * 4);
-  L.q = o;
-  if (obsw) o = align_up(o + (size_t)nb * 8);
-  L.total = o;
+  Carver c;
+  L.centre = c.take((size_t)nb * es);
+  L.norm = c.take((size_t)B * es);
+  L.ctl = c.take((obsw ? 2 * LUT_TOPK_CTL_WORDS : LUT_TOPK_CTL_WORDS) * 8);
+  L.bq = c.take(mc * (size_t)L.nbp * es * (obsw ? 2 : 1));
+  L.ya = c.take(mc * (obsw ? 16 : es));
+  L.pc = c.take((size_t)L.npart * mc * es);
+  L.ps = c.take((size_t)L.npart * mc * es);
+  L.thr = c.take(mc * es);
+  L.cn = c.take(mc * 4);
+  L.cand = c.take(mc * (size_t)L.cap * 4);
+  L.flags = c.take((size_t)M * 4);
+  L.q = c.take(obsw ? (size_t)nb * 8 : 0);
+  L.total = c.o;
   return L;
 }
 
-template <typename T>
+// OBSW: per-observation weights (csrc/spart_lut.h, "per-observation weights") -- the same pipeline with K = 2 nbp: its own
+// observation pass, GEMM and bound, a per-band pass k_lutow_q before the chunks, and the select's OBSW flag.
+template <typename T, bool OBSW>
 static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int k,
                          int64_t* idx, void* cost, char* wsp, hipStream_t st) {
-  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, k);
+  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, k, OBSW);
   constexpr int ROWS = LutWide<T>::ROWS;
   constexpr int OWG = 2 * LUTW_TB * ROWS;
+  constexpr auto gemm_scan = OBSW ? k_lutow_gemm<T, false> : k_lutw_gemm<T, false>;
+  constexpr auto gemm_collect = OBSW ? k_lutow_gemm<T, true> : k_lutw_gemm<T, true>;
   const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
   T* centre = (T*)(wsp + L.centre);
   T* norm = (T*)(wsp + L.norm);
   unsigned long long* ctl = (unsigned long long*)(wsp + L.ctl);
   T* bq = (T*)(wsp + L.bq);
-  T* ya = (T*)(wsp + L.ya);
+  void* ya = wsp + L.ya;                               // Y in the dtype; OBSW: (Y, Nbound) in float64
   T* pc = (T*)(wsp + L.pc);
   T* ps = (T*)(wsp + L.ps);
   T* thr = (T*)(wsp + L.thr);
   int* cn = (int*)(wsp + L.cn);
   int* cand = (int*)(wsp + L.cand);
   int* flags = (int*)(wsp + L.flags);
-  // the coefficients of Delta (spart_lut.h, wide top-k), with the 1 % slack
+  unsigned long long* qb = (unsigned long long*)(wsp + L.q);       // OBSW only: the per-band Q_j
+  // the coefficients of Delta (spart_lut.h, wide top-k and per-observation weights), with the 1 % slack
   const double u = (double)LutNum<T>::u;
-  const double h = LUTW_KC + L.nch + 1.0;
-  const double ce = (4.0 + (sizeof(T) == 4 ? 1.01 : nb + 2.0) + 1.0 + 2.0 * h) * 1.01 * u;
+  const double h = (OBSW ? 2.0 * LUTW_KC : LUTW_KC) + L.nch + 1.0;
+  const double ce = (4.0 + (OBSW ? 1.0 : sizeof(T) == 4 ? 1.01 : nb + 2.0) + 1.0 + 2.0 * h) * 1.01 * u;
   const double cf = 2.01 * (nb + 3.0) * 1.01 * u;
-  const double cw = 2.0 * (2.0 * nb + 6.0) * 1.01 * u;
-  HIP_TRY(hipMemsetAsync(ctl, 0, LUT_TOPK_CTL_WORDS * 8, st));
+  const double cw = 2.0 * (2.0 * nb + 6.0) * 1.01 * u;             // (the shared-weights bound only)
+  HIP_TRY(hipMemsetAsync(ctl, 0, (OBSW ? 2 : 1) * LUT_TOPK_CTL_WORDS * 8, st));
+  if constexpr (OBSW) HIP_TRY(hipMemsetAsync(qb, 0, (size_t)nb * 8, st));
   hipLaunchKernelGGL((k_lut_centre<T>), dim3(nb), dim3(256), 0, st, lut, nb, B, centre, ctl);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL((k_lutw_norm<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, lut, w, (const T*)centre, nb, B, norm, ctl);
+  // OBSW: the row rule without weights; its Nmax goes to a word of its own (ctl[0] is the largest Nbound_m)
+  hipLaunchKernelGGL((k_lutw_norm<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, lut, OBSW ? (const T*)nullptr : w,
+                     (const T*)centre, nb, B, norm, ctl + (OBSW ? LUT_TOPK_CTL_WORDS : 0));
   HIP_TRY(hipGetLastError());
+  if constexpr (OBSW) {
+    const int64_t qy = (B + 3) / 4;
+    hipLaunchKernelGGL((k_lutow_q<T>), dim3((unsigned)((nb + 63) / 64), (unsigned)(qy < 1024 ? qy : 1024)), dim3(256), 0, st, lut,
+                       (const T*)norm, (const T*)centre, nb, B, qb);
+    HIP_TRY(hipGetLastError());
+  }
   const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
+  const T* sel_norm = OBSW ? norm : nullptr;
   for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
     const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
     const T* ob = obs + m0 * nb;
     const unsigned gx = (unsigned)((mc + OWG - 1) / OWG), gobs = (unsigned)((mc + 3) / 4);
-    hipLaunchKernelGGL((k_lutw_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w, (const T*)centre, nb, L.nbp, mc, bq, ya);
-    hipLaunchKernelGGL((k_lutw_gemm<T, false>), dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre,
-                       nb, B, (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL((k_lutw_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const T*)ya, w, nb, mc, L.npart,
-                       k, ce, cf, cw, (const unsigned long long*)ctl, thr, cn);
-    hipLaunchKernelGGL((k_lutw_gemm<T, true>), dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre,
-                       nb, B, (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap, cn, cand);
-    hipLaunchKernelGGL((k_lutw_select<T, ROWS, false>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc, k,
-                       (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost);
+    if constexpr (OBSW)
+      hipLaunchKernelGGL((k_lutow_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w + m0 * nb, (const T*)centre,
+                         (const unsigned long long*)qb, nb, L.nbp, mc, bq, (double*)ya, ctl);
+    else
+      hipLaunchKernelGGL((k_lutw_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w, (const T*)centre, nb, L.nbp, mc, bq, (T*)ya);
+    hipLaunchKernelGGL(gemm_scan, dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
+                       (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr, (int*)nullptr);
+    if constexpr (OBSW)
+      hipLaunchKernelGGL((k_lutow_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const double*)ya, nb, mc,
+                         L.npart, k, ce, cf, thr, cn);
+    else
+      hipLaunchKernelGGL((k_lutw_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const T*)ya, w, nb, mc,
+                         L.npart, k, ce, cf, cw, (const unsigned long long*)ctl, thr, cn);
+    hipLaunchKernelGGL(gemm_collect, dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
+                       (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap, cn, cand);
+    hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, OBSW>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
+                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, sel_norm);
     HIP_TRY(hipGetLastError());
   }
   // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
-  hipLaunchKernelGGL((k_lutw_select<T, ROWS, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B, (int64_t)0, M,
-                     k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost);
-  HIP_TRY(hipGetLastError());
-  return SPART_OK;
-}
-
-// ---- per-observation weights (csrc/spart_lut.h, "per-observation weights"): the wide pipeline with K = 2 nbp.
-template <typename T>
-static int lut_obsw_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int k,
-                         int64_t* idx, void* cost, char* wsp, hipStream_t st) {
-  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, k, true);
-  constexpr int ROWS = LutWide<T>::ROWS;
-  constexpr int OWG = 2 * LUTW_TB * ROWS;
-  const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
-  T* centre = (T*)(wsp + L.centre);
-  T* norm = (T*)(wsp + L.norm);
-  unsigned long long* ctl = (unsigned long long*)(wsp + L.ctl);
-  T* bq = (T*)(wsp + L.bq);
-  double* yn = (double*)(wsp + L.ya);
-  T* pc = (T*)(wsp + L.pc);
-  T* ps = (T*)(wsp + L.ps);
-  T* thr = (T*)(wsp + L.thr);
-  int* cn = (int*)(wsp + L.cn);
-  int* cand = (int*)(wsp + L.cand);
-  int* flags = (int*)(wsp + L.flags);
-  unsigned long long* qb = (unsigned long long*)(wsp + L.q);
-  // the coefficients of Delta (spart_lut.h, per-observation weights), with the 1 % slack
-  const double u = (double)LutNum<T>::u;
-  const double h = 2.0 * LUTW_KC + L.nch + 1.0;
-  const double ce = (4.0 + 1.0 + 1.0 + 2.0 * h) * 1.01 * u;
-  const double cf = 2.01 * (nb + 3.0) * 1.01 * u;
-  HIP_TRY(hipMemsetAsync(ctl, 0, 2 * LUT_TOPK_CTL_WORDS * 8, st));
-  HIP_TRY(hipMemsetAsync(qb, 0, (size_t)nb * 8, st));
-  hipLaunchKernelGGL((k_lut_centre<T>), dim3(nb), dim3(256), 0, st, lut, nb, B, centre, ctl);
-  HIP_TRY(hipGetLastError());
-  // the row rule without weights; its Nmax goes to a word of its own (ctl[0] is the largest Nbound_m)
-  hipLaunchKernelGGL((k_lutw_norm<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, lut, (const T*)nullptr,
-                     (const T*)centre, nb, B, norm, ctl + LUT_TOPK_CTL_WORDS);
-  HIP_TRY(hipGetLastError());
-  const int64_t qy = (B + 3) / 4;
-  hipLaunchKernelGGL((k_lutow_q<T>), dim3((unsigned)((nb + 63) / 64), (unsigned)(qy < 1024 ? qy : 1024)), dim3(256), 0, st, lut,
-                     (const T*)norm, (const T*)centre, nb, B, qb);
-  HIP_TRY(hipGetLastError());
-  const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
-  for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
-    const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
-    const unsigned gx = (unsigned)((mc + OWG - 1) / OWG), gobs = (unsigned)((mc + 3) / 4);
-    hipLaunchKernelGGL((k_lutow_obs<T>), dim3(gobs), dim3(256), 0, st, obs + m0 * nb, w + m0 * nb, (const T*)centre,
-                       (const unsigned long long*)qb, nb, L.nbp, mc, bq, yn, ctl);
-    hipLaunchKernelGGL((k_lutow_gemm<T, false>), dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm,
-                       (const T*)centre, nb, B, (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr,
-                       (int*)nullptr);
-    hipLaunchKernelGGL((k_lutow_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const double*)yn, nb, mc, L.npart,
-                       k, ce, cf, thr, cn);
-    hipLaunchKernelGGL((k_lutow_gemm<T, true>), dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm,
-                       (const T*)centre, nb, B, (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap,
-                       cn, cand);
-    hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, true>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
-                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, (const T*)norm);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
+  hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, OBSW>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
                      (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost,
-                     (const T*)norm);
+                     sel_norm);
   HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
 
-// The checks every batched entry point but spart_lut_nearest starts with, in this order.  B == 0 passes them: the caller
-// has nothing to do.  Otherwise `ws` is the layout of the call's workspace.
+// The checks every batched entry point over B samples starts with, in this order (the LUT searches have lut_search's).
+// B == 0 passes them: the caller has nothing to do.  Otherwise `ws` is the layout of the call's workspace.
 static int gate(const spart_ctx* ctx, const char* who, int dtype, int64_t B, const void* workspace, size_t workspace_bytes,
                 Workspace& ws) {
   if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
@@ -924,6 +895,77 @@ static int stage_call(spart_ctx* ctx, const char* who, int dtype, int64_t B, con
     });
   });
 }
+
+// ---- the four LUT searches: what differs between their entry points
+struct LutCall {
+  const char* who;
+  int nb_max;               // the widest LUT the search takes
+  bool has_k;               // top-k: 1 <= k <= LUT_TOPK_MAXK (spart_lut_nearest has no k)
+  bool weights_required;    // weights (M, nb) may not be NULL
+  bool nb_ok(int nb) const { return nb >= 1 && nb <= nb_max; }
+  bool k_ok(int k) const { return !has_k || (k >= 1 && k <= LUT_TOPK_MAXK); }
+};
+constexpr LutCall LUT_NEAREST = {"spart_lut_nearest", 31, false, false};
+constexpr LutCall LUT_TOPK = {"spart_lut_topk", 31, true, false};
+constexpr LutCall LUT_WIDE = {"spart_lut_topk_wide", NWLS, true, false};
+constexpr LutCall LUT_OBSW = {"spart_lut_topk_obs_weights", NWLS, true, true};
+
+static bool dtype_ok(int dtype) { return dtype == SPART_F32 || dtype == SPART_F64; }
+
+// The sizes a search has a workspace for: every *_workspace_bytes is its layout's total when this holds and 0 otherwise,
+// and the *_stats calls take that 0 as their size check.  (lut_search also refuses B or M above 2e9.)
+static bool lut_sizes_ok(const LutCall& c, int dtype, int64_t B, int nb, int64_t M, int k) {
+  return B > 0 && M > 0 && c.nb_ok(nb) && c.k_ok(k) && dtype_ok(dtype);
+}
+
+// A LUT search from its entry point: the argument checks, in this order, then impl(T{}, workspace, stream) (the launches)
+// under guarded().  M == 0 passes the checks with nothing to do.  `need` is the search's own *_workspace_bytes.
+template <typename F>
+static int lut_search(spart_ctx* ctx, const LutCall& c, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
+                      const void* weights, int k, const void* idx, const void* cost, void* workspace, size_t workspace_bytes,
+                      size_t need, void* stream, F&& impl) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", c.who);
+  if (!dtype_ok(dtype)) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", c.who, dtype);
+  if (B < 0 || M < 0 || !c.nb_ok(nb) || B > 2000000000LL || M > 2000000000LL)
+    // (two wordings of the nb range, as the narrow and the wide searches have always reported it)
+    return fail(SPART_ERR_INVALID, c.nb_max == 31 ? "%s: bad sizes (B=%lld M=%lld nb=%d; nb <= %d, B and M <= 2e9)"
+                                                  : "%s: bad sizes (B=%lld M=%lld nb=%d; 1 <= nb <= %d, B and M <= 2e9)",
+                c.who, (long long)B, (long long)M, nb, c.nb_max);
+  if (!c.k_ok(k)) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", c.who, k, LUT_TOPK_MAXK);
+  if (M == 0) return SPART_OK;
+  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", c.who);
+  if (!lut || !obs || !idx || !cost || (c.weights_required && !weights)) return fail(SPART_ERR_INVALID, "%s: null argument", c.who);
+  if (!workspace || workspace_bytes < need)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", c.who, need, workspace_bytes);
+  return guarded(ctx, c.who, workspace, need, stream,
+                 [&](hipStream_t st) { return by_dtype(dtype, [&](auto t) { return impl(t, (char*)workspace, st); }); });
+}
+
+// The control words of the last search that used `workspace`, for its *_stats call `who`: word 0 is the scale of the
+// rounding bound as a bit pattern in the search's dtype, words 1 .. ncount are counters.  Only the search's own words are
+// read (the k = 1 layout reserves LUT_CTL_WORDS).  sizes_ok: the search's *_workspace_bytes is not 0; only then is
+// ctl_offset() -- the offset of the words in the search's layout -- evaluated.
+template <typename F>
+static int lut_read_stats(spart_ctx* ctx, const char* who, int dtype, const void* workspace, bool sizes_ok, F&& ctl_offset,
+                          int64_t* const* counts, int ncount, double* scale) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (!workspace || first_null(counts, ncount) < ncount || !scale || !sizes_ok)
+    return fail(SPART_ERR_INVALID, "%s: bad argument", who);
+  DeviceGuard guard(ctx->device);
+  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
+  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + ctl_offset(), (size_t)(1 + ncount) * 8, hipMemcpyDeviceToHost));
+  for (int i = 0; i < ncount; ++i) *counts[i] = (int64_t)ctl[1 + i];
+  if (dtype == SPART_F32) {
+    const unsigned b = (unsigned)ctl[0];
+    float f;
+    std::memcpy(&f, &b, 4);
+    *scale = f;
+  } else {
+    std::memcpy(scale, &ctl[0], 8);
+  }
+  return SPART_OK;
+}
+static_assert(LUT_CTL_WORDS <= LUT_TOPK_CTL_WORDS, "lut_read_stats: the buffer holds either search's control words");
 
 #ifndef SPART_BUILD_ID
 #define SPART_BUILD_ID "unidentified"      // built outside spart-python_amd/build.py
@@ -1257,203 +1299,84 @@ int spart_run_batch(spart_ctx* ctx, int dtype, int64_t B, const double* const pa
 }
 
 size_t spart_lut_workspace_bytes(int dtype, int64_t B, int nb, int64_t M) {
-  if (B <= 0 || M <= 0 || nb < 1 || nb > 31 || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
-  return lut_layout(dtype, B, nb, M).total;
+  return lut_sizes_ok(LUT_NEAREST, dtype, B, nb, M, 0) ? lut_layout(dtype, B, nb, M).total : 0;
 }
 
 int spart_lut_nearest(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
                       const void* weights, int64_t* best_idx, void* best_cost, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_nearest: null context");
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "spart_lut_nearest: bad dtype %d", dtype);
-  if (B < 0 || M < 0 || nb < 1 || nb > 31 || B > 2000000000LL || M > 2000000000LL)
-    return fail(SPART_ERR_INVALID, "spart_lut_nearest: bad sizes (B=%lld M=%lld nb=%d; nb <= 31, B and M <= 2e9)", (long long)B, (long long)M, nb);
-  if (M == 0) return SPART_OK;
-  if (B == 0) return fail(SPART_ERR_INVALID, "spart_lut_nearest: empty LUT");
-  if (!lut || !obs || !best_idx || !best_cost) return fail(SPART_ERR_INVALID, "spart_lut_nearest: null argument");
-  size_t need = spart_lut_workspace_bytes(dtype, B, nb, M);
-  if (!workspace || workspace_bytes < need)
-    return fail(SPART_ERR_WORKSPACE, "spart_lut_nearest: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-  return guarded(ctx, "spart_lut_nearest", workspace, need, stream, [&](hipStream_t st) {
-    return by_dtype(dtype, [&](auto t) {
-      return lut_impl<decltype(t)>(ctx, dtype, B, nb, lut, M, obs, weights, best_idx, best_cost, (char*)workspace, st);
-    });
-  });
+  return lut_search(ctx, LUT_NEAREST, dtype, B, nb, lut, M, obs, weights, 0, best_idx, best_cost, workspace, workspace_bytes,
+                    spart_lut_workspace_bytes(dtype, B, nb, M), stream, [&](auto t, char* wsp, hipStream_t st) {
+                      return lut_impl<decltype(t)>(ctx, dtype, B, nb, lut, M, obs, weights, best_idx, best_cost, wsp, st);
+                    });
 }
 
 int spart_lut_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, const void* workspace, int64_t* n_brute_force,
                     double* nmax) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_stats: null context");
-  if (!workspace || !n_brute_force || !nmax || spart_lut_workspace_bytes(dtype, B, nb, M) == 0)
-    return fail(SPART_ERR_INVALID, "spart_lut_stats: bad argument");
-  DeviceGuard guard(ctx->device);
-  unsigned long long ctl[LUT_CTL_WORDS];
-  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_layout(dtype, B, nb, M).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-  *n_brute_force = (int64_t)ctl[1];
-  if (dtype == SPART_F32) {
-    const unsigned b = (unsigned)ctl[0];
-    float f;
-    std::memcpy(&f, &b, 4);
-    *nmax = f;
-  } else {
-    std::memcpy(nmax, &ctl[0], 8);
-  }
-  return SPART_OK;
+  int64_t* const counts[] = {n_brute_force};
+  return lut_read_stats(ctx, "spart_lut_stats", dtype, workspace, spart_lut_workspace_bytes(dtype, B, nb, M) != 0,
+                        [&] { return lut_layout(dtype, B, nb, M).ctl; }, counts, 1, nmax);
 }
 
 size_t spart_lut_topk_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k) {
-  if (B <= 0 || M <= 0 || nb < 1 || nb > 31 || k < 1 || k > LUT_TOPK_MAXK || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
-  return lut_topk_layout(dtype, B, nb, M, k).total;
+  return lut_sizes_ok(LUT_TOPK, dtype, B, nb, M, k) ? lut_topk_layout(dtype, B, nb, M, k).total : 0;
 }
 
 int spart_lut_topk(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs, const void* weights,
                    int k, int64_t* idx, void* cost, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "spart_lut_topk";
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-  if (B < 0 || M < 0 || nb < 1 || nb > 31 || B > 2000000000LL || M > 2000000000LL)
-    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d; nb <= 31, B and M <= 2e9)", who, (long long)B, (long long)M, nb);
-  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
-  if (M == 0) return SPART_OK;
-  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", who);
-  const void* ptrs[4] = {lut, obs, idx, cost};
-  if (first_null(ptrs, 4) < 4) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  const size_t need = spart_lut_topk_workspace_bytes(dtype, B, nb, M, k);
-  if (!workspace || workspace_bytes < need)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
-    return by_dtype(dtype, [&](auto t) {
-      return lut_topk_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, (char*)workspace, st);
-    });
-  });
+  return lut_search(ctx, LUT_TOPK, dtype, B, nb, lut, M, obs, weights, k, idx, cost, workspace, workspace_bytes,
+                    spart_lut_topk_workspace_bytes(dtype, B, nb, M, k), stream, [&](auto t, char* wsp, hipStream_t st) {
+                      return lut_topk_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, wsp, st);
+                    });
 }
 
 int spart_lut_topk_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void* workspace,
                          int64_t* n_brute_force, int64_t* n_candidates, int64_t* max_candidates, double* nmax) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_topk_stats: null context");
-  const void* ptrs[5] = {workspace, n_brute_force, n_candidates, max_candidates, nmax};
-  if (first_null(ptrs, 5) < 5 || spart_lut_topk_workspace_bytes(dtype, B, nb, M, k) == 0)
-    return fail(SPART_ERR_INVALID, "spart_lut_topk_stats: bad argument");
-  DeviceGuard guard(ctx->device);
-  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
-  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_topk_layout(dtype, B, nb, M, k).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-  *n_brute_force = (int64_t)ctl[1];
-  *n_candidates = (int64_t)ctl[2];
-  *max_candidates = (int64_t)ctl[3];
-  if (dtype == SPART_F32) {
-    const unsigned b = (unsigned)ctl[0];
-    float f;
-    std::memcpy(&f, &b, 4);
-    *nmax = f;
-  } else {
-    std::memcpy(nmax, &ctl[0], 8);
-  }
-  return SPART_OK;
+  int64_t* const counts[] = {n_brute_force, n_candidates, max_candidates};
+  return lut_read_stats(ctx, "spart_lut_topk_stats", dtype, workspace, spart_lut_topk_workspace_bytes(dtype, B, nb, M, k) != 0,
+                        [&] { return lut_topk_layout(dtype, B, nb, M, k).ctl; }, counts, 3, nmax);
 }
 
 size_t spart_lut_topk_wide_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k) {
-  if (B <= 0 || M <= 0 || nb < 1 || nb > NWLS || k < 1 || k > LUT_TOPK_MAXK || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
-  return lut_wide_layout(dtype, B, nb, M, k).total;
+  return lut_sizes_ok(LUT_WIDE, dtype, B, nb, M, k) ? lut_wide_layout(dtype, B, nb, M, k, false).total : 0;
 }
 
 int spart_lut_topk_wide(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
                         const void* weights, int k, int64_t* idx, void* cost, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  const char* who = "spart_lut_topk_wide";
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-  if (B < 0 || M < 0 || nb < 1 || nb > NWLS || B > 2000000000LL || M > 2000000000LL)
-    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d; 1 <= nb <= %d, B and M <= 2e9)", who, (long long)B,
-                (long long)M, nb, NWLS);
-  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
-  if (M == 0) return SPART_OK;
-  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", who);
-  const void* ptrs[4] = {lut, obs, idx, cost};
-  if (first_null(ptrs, 4) < 4) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  const size_t need = spart_lut_topk_wide_workspace_bytes(dtype, B, nb, M, k);
-  if (!workspace || workspace_bytes < need)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
-    return by_dtype(dtype, [&](auto t) {
-      return lut_wide_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, (char*)workspace, st);
-    });
-  });
+  return lut_search(ctx, LUT_WIDE, dtype, B, nb, lut, M, obs, weights, k, idx, cost, workspace, workspace_bytes,
+                    spart_lut_topk_wide_workspace_bytes(dtype, B, nb, M, k), stream, [&](auto t, char* wsp, hipStream_t st) {
+                      return lut_wide_impl<decltype(t), false>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, wsp, st);
+                    });
 }
 
 int spart_lut_topk_wide_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void* workspace,
                               int64_t* n_brute_force, int64_t* n_candidates, int64_t* max_candidates, double* nmax) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_topk_wide_stats: null context");
-  const void* ptrs[5] = {workspace, n_brute_force, n_candidates, max_candidates, nmax};
-  if (first_null(ptrs, 5) < 5 || spart_lut_topk_wide_workspace_bytes(dtype, B, nb, M, k) == 0)
-    return fail(SPART_ERR_INVALID, "spart_lut_topk_wide_stats: bad argument");
-  DeviceGuard guard(ctx->device);
-  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
-  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_wide_layout(dtype, B, nb, M, k).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-  *n_brute_force = (int64_t)ctl[1];
-  *n_candidates = (int64_t)ctl[2];
-  *max_candidates = (int64_t)ctl[3];
-  if (dtype == SPART_F32) {
-    const unsigned b = (unsigned)ctl[0];
-    float f;
-    std::memcpy(&f, &b, 4);
-    *nmax = f;
-  } else {
-    std::memcpy(nmax, &ctl[0], 8);
-  }
-  return SPART_OK;
+  int64_t* const counts[] = {n_brute_force, n_candidates, max_candidates};
+  return lut_read_stats(ctx, "spart_lut_topk_wide_stats", dtype, workspace,
+                        spart_lut_topk_wide_workspace_bytes(dtype, B, nb, M, k) != 0,
+                        [&] { return lut_wide_layout(dtype, B, nb, M, k, false).ctl; }, counts, 3, nmax);
 }
 
-
 size_t spart_lut_topk_obs_weights_workspace_bytes(int dtype, int64_t B, int nb, int64_t M, int k) {
-  if (B <= 0 || M <= 0 || nb < 1 || nb > NWLS || k < 1 || k > LUT_TOPK_MAXK || (dtype != SPART_F32 && dtype != SPART_F64)) return 0;
-  return lut_wide_layout(dtype, B, nb, M, k, true).total;
+  return lut_sizes_ok(LUT_OBSW, dtype, B, nb, M, k) ? lut_wide_layout(dtype, B, nb, M, k, true).total : 0;
 }
 
 int spart_lut_topk_obs_weights(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int64_t M, const void* obs,
                                const void* weights, int k, int64_t* idx, void* cost, void* workspace, size_t workspace_bytes,
                                void* stream) {
-  const char* who = "spart_lut_topk_obs_weights";
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (dtype != SPART_F32 && dtype != SPART_F64) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-  if (B < 0 || M < 0 || nb < 1 || nb > NWLS || B > 2000000000LL || M > 2000000000LL)
-    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d; 1 <= nb <= %d, B and M <= 2e9)", who, (long long)B,
-                (long long)M, nb, NWLS);
-  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
-  if (M == 0) return SPART_OK;
-  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty LUT", who);
-  const void* ptrs[5] = {lut, obs, weights, idx, cost};         // weights (M, nb) are required
-  if (first_null(ptrs, 5) < 5) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  const size_t need = spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k);
-  if (!workspace || workspace_bytes < need)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
-    return by_dtype(dtype, [&](auto t) {
-      return lut_obsw_impl<decltype(t)>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, (char*)workspace, st);
-    });
-  });
+  return lut_search(ctx, LUT_OBSW, dtype, B, nb, lut, M, obs, weights, k, idx, cost, workspace, workspace_bytes,
+                    spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k), stream, [&](auto t, char* wsp, hipStream_t st) {
+                      return lut_wide_impl<decltype(t), true>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, wsp, st);
+                    });
 }
 
 int spart_lut_topk_obs_weights_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void* workspace,
                                      int64_t* n_brute_force, int64_t* n_candidates, int64_t* max_candidates, double* nbound) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "spart_lut_topk_obs_weights_stats: null context");
-  const void* ptrs[5] = {workspace, n_brute_force, n_candidates, max_candidates, nbound};
-  if (first_null(ptrs, 5) < 5 || spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k) == 0)
-    return fail(SPART_ERR_INVALID, "spart_lut_topk_obs_weights_stats: bad argument");
-  DeviceGuard guard(ctx->device);
-  unsigned long long ctl[LUT_TOPK_CTL_WORDS];
-  HIP_TRY(hipMemcpy(ctl, (const char*)workspace + lut_wide_layout(dtype, B, nb, M, k, true).ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-  *n_brute_force = (int64_t)ctl[1];
-  *n_candidates = (int64_t)ctl[2];
-  *max_candidates = (int64_t)ctl[3];
-  if (dtype == SPART_F32) {
-    const unsigned b = (unsigned)ctl[0];
-    float f;
-    std::memcpy(&f, &b, 4);
-    *nbound = f;
-  } else {
-    std::memcpy(nbound, &ctl[0], 8);
-  }
-  return SPART_OK;
+  int64_t* const counts[] = {n_brute_force, n_candidates, max_candidates};
+  return lut_read_stats(ctx, "spart_lut_topk_obs_weights_stats", dtype, workspace,
+                        spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k) != 0,
+                        [&] { return lut_wide_layout(dtype, B, nb, M, k, true).ctl; }, counts, 3, nbound);
 }
 
 }  // extern "C"

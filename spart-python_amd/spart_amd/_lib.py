@@ -31,6 +31,12 @@ class SpartMaterialize(ctypes.Structure):
                                                                                           ("nlayers", ctypes.c_int32)]
 
 
+# the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
+c_i64p = ctypes.POINTER(ctypes.c_int64)
+_LUT_SIZES = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]
+_LUT_TOPK_CALL = [vp] + _LUT_SIZES[:3] + [vp, ctypes.c_int64, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
+_LUT_TOPK_STATS = [vp] + _LUT_SIZES + [ctypes.c_int, vp, c_i64p, c_i64p, c_i64p, c_dp]
+
 # name -> (restype, argtypes): every symbol include/spart_hip.h declares
 SIGNATURES = {
     "spart_ctx_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(SpartTables)]),
@@ -56,31 +62,13 @@ SIGNATURES = {
                                         vp, ctypes.c_size_t, vp]),
     "spart_run_batch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(vp), vp, vp, vp, vp, vp,
                                        ctypes.POINTER(SpartMaterialize), vp, ctypes.c_size_t, vp]),
-    "spart_lut_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
-    "spart_lut_nearest": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, vp,
-                                         vp, ctypes.c_size_t, vp]),
-    "spart_lut_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp,
-                                       ctypes.POINTER(ctypes.c_int64), c_dp]),
-    "spart_lut_topk_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
-    "spart_lut_topk": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, ctypes.c_int, vp,
-                                      vp, vp, ctypes.c_size_t, vp]),
-    "spart_lut_topk_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp,
-                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                            ctypes.POINTER(ctypes.c_int64), c_dp]),
-    "spart_lut_topk_wide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                                              ctypes.c_int]),
-    "spart_lut_topk_wide": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, ctypes.c_int,
-                                           vp, vp, vp, ctypes.c_size_t, vp]),
-    "spart_lut_topk_wide_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp,
-                                                 ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                                 ctypes.POINTER(ctypes.c_int64), c_dp]),
-    "spart_lut_topk_obs_weights_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                                                     ctypes.c_int]),
-    "spart_lut_topk_obs_weights": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp,
-                                                  ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
-    "spart_lut_topk_obs_weights_stats": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                                                        vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                                        ctypes.POINTER(ctypes.c_int64), c_dp]),
+    "spart_lut_workspace_bytes": (ctypes.c_size_t, _LUT_SIZES),
+    "spart_lut_nearest": (ctypes.c_int, [vp] + _LUT_SIZES[:3] + [vp, ctypes.c_int64, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spart_lut_stats": (ctypes.c_int, [vp] + _LUT_SIZES + [vp, c_i64p, c_dp]),
+    **{name + suffix: sig for name in ("spart_lut_topk", "spart_lut_topk_wide", "spart_lut_topk_obs_weights")
+       for suffix, sig in (("_workspace_bytes", (ctypes.c_size_t, _LUT_SIZES + [ctypes.c_int])),
+                           ("", (ctypes.c_int, _LUT_TOPK_CALL)),
+                           ("_stats", (ctypes.c_int, _LUT_TOPK_STATS)))},
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

@@ -85,6 +85,14 @@ ROW_PITCH = (2176, 2048)
 LUT_NARROW_NB = 31     # spart_lut_nearest / spart_lut_topk take nb <= 31; above it lut_nearest / lut_topk call spart_lut_topk_wide
 
 
+# LUT search -> (its *_workspace_bytes, its *_stats, the key of the float64 word of its stats)
+_LUT_SEARCHES = {
+    "spart_lut_nearest": ("spart_lut_workspace_bytes", "spart_lut_stats", "nmax"),
+    "spart_lut_topk": ("spart_lut_topk_workspace_bytes", "spart_lut_topk_stats", "nmax"),
+    "spart_lut_topk_wide": ("spart_lut_topk_wide_workspace_bytes", "spart_lut_topk_wide_stats", "nmax"),
+    "spart_lut_topk_obs_weights": ("spart_lut_topk_obs_weights_workspace_bytes", "spart_lut_topk_obs_weights_stats", "nbound")}
+
+
 def lut_weights_kind(shape, M, nb):
     """Which LUT search a ``weights`` argument of Engine.lut_nearest / lut_topk selects: shape None -> "none"; (nb,) ->
     "shared" (one weight per band for every observation: spart_lut_nearest / _topk / _topk_wide); (M, nb) -> "per_observation"
@@ -639,39 +647,7 @@ class Engine:
         -> (idx (M,) int64 tensor, cost (M,) tensor); with ``stats=True`` also a dict with the number of observations that
         took the brute-force path and the scale Nmax of the rounding bound (spart_lut_stats; synchronises).
         ``weights`` (M, nb): one weight row per observation, a zero weight masking its band (lut_topk with k = 1)."""
-        torch = self.torch
-        dt = DTYPES[dtype]
-        td = self._tdtype(dt)
-        lut = torch.as_tensor(lut).to(device=self.device, dtype=td).contiguous()
-        obs = torch.as_tensor(obs).to(device=self.device, dtype=td).contiguous()
-        if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
-            raise ValueError("lut (B, nb) and obs (M, nb) must share nb")
-        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=td).contiguous()
-        B, nb = lut.shape
-        M = obs.shape[0]
-        if lut_weights_kind(None if w is None else w.shape, M, nb) == "per_observation":
-            res = self._lut_topk_obs_weights(lut, obs, w, 1, dt, td, stats)
-            return (res[0][:, 0], res[1][:, 0]) + tuple(res[2:])
-        if nb > LUT_NARROW_NB:                                   # hyperspectral: the wide top-k with k = 1
-            res = self._lut_topk_wide(lut, obs, w, 1, dt, td, stats)
-            return (res[0][:, 0], res[1][:, 0]) + tuple(res[2:])
-        idx = torch.empty((M,), dtype=torch.int64, device=self.device)
-        cost = torch.empty((M,), dtype=td, device=self.device)
-        n = int(self.lib.spart_lut_workspace_bytes(dt, B, nb, M))
-        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
-        self.calls["spart_lut_nearest"] += 1
-        rc = self.lib.spart_lut_nearest(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
-                                        w.data_ptr() if w is not None else None, idx.data_ptr(), cost.data_ptr(),
-                                        ws.data_ptr(), ctypes.c_size_t(ws.numel()), self._stream())
-        _lib.check(self.lib, self.ctx, rc)
-        if not stats:
-            return idx, cost
-        nbf, nmax = ctypes.c_int64(0), ctypes.c_double(0.0)
-        if M > 0:
-            torch.cuda.current_stream(self.device).synchronize()
-            _lib.check(self.lib, self.ctx, self.lib.spart_lut_stats(self.ctx, dt, B, nb, M, ws.data_ptr(), ctypes.byref(nbf),
-                                                                    ctypes.byref(nmax)))
-        return idx, cost, {"brute_force": int(nbf.value), "nmax": float(nmax.value)}
+        return self._lut_search(lut, obs, weights, None, dtype, stats)
 
     def lut_topk(self, lut, obs, k, weights=None, dtype="float32", stats=False):
         """The k nearest LUT rows per observation (include/spart_hip.h: spart_lut_topk): the same cost as lut_nearest, rows
@@ -682,10 +658,19 @@ class Engine:
         synchronises).  ``weights`` is None, (nb,) -- one weight per band for every observation -- or (M, nb): one weight row
         per observation (spart_lut_topk_obs_weights, any nb): a band of weight zero is skipped, so the observation may be NaN
         there; the stats then report "nbound" (the largest per-observation bound scale) in place of "nmax"."""
+        return self._lut_search(lut, obs, weights, k, dtype, stats)
+
+    def _lut_search(self, lut, obs, weights, k, dtype, stats):
+        """lut_nearest (``k`` None) and lut_topk: the tensors on the device, in ``dtype`` and contiguous; the choice of the
+        search; its outputs and workspace; the counted and checked call; with ``stats`` a synchronise and the search's *_stats.
+        The search: (M, nb) weights -> spart_lut_topk_obs_weights; else above LUT_NARROW_NB bands -> spart_lut_topk_wide;
+        else spart_lut_nearest / spart_lut_topk.  Only spart_lut_nearest has no k ((M,) outputs, no candidate counters): the
+        other two serve lut_nearest with k = 1 and column 0 of their answer."""
         torch = self.torch
         dt = DTYPES[dtype]
         td = self._tdtype(dt)
-        k = int(k)
+        if k is not None:
+            k = int(k)
         lut = torch.as_tensor(lut).to(device=self.device, dtype=td).contiguous()
         obs = torch.as_tensor(obs).to(device=self.device, dtype=td).contiguous()
         if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
@@ -694,78 +679,33 @@ class Engine:
         B, nb = lut.shape
         M = obs.shape[0]
         if lut_weights_kind(None if w is None else w.shape, M, nb) == "per_observation":
-            return self._lut_topk_obs_weights(lut, obs, w, k, dt, td, stats)
-        if nb > LUT_NARROW_NB:
-            return self._lut_topk_wide(lut, obs, w, k, dt, td, stats)
-        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
-        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
-        n = int(self.lib.spart_lut_topk_workspace_bytes(dt, B, nb, M, k))
-        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
-        self.calls["spart_lut_topk"] += 1
-        rc = self.lib.spart_lut_topk(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
-                                     w.data_ptr() if w is not None else None, k, idx.data_ptr(), cost.data_ptr(),
-                                     ws.data_ptr(), ctypes.c_size_t(ws.numel()), self._stream())
+            entry = "spart_lut_topk_obs_weights"
+        elif nb > LUT_NARROW_NB:
+            entry = "spart_lut_topk_wide"
+        else:
+            entry = "spart_lut_nearest" if k is None else "spart_lut_topk"
+        workspace_bytes, read_stats, scale = _LUT_SEARCHES[entry]
+        kk = () if entry == "spart_lut_nearest" else (1 if k is None else k,)
+        shape = (M, max(kk[0], 0)) if kk else (M,)
+        idx = torch.empty(shape, dtype=torch.int64, device=self.device)
+        cost = torch.empty(shape, dtype=td, device=self.device)
+        nbytes = max(getattr(self.lib, workspace_bytes)(dt, B, nb, M, *kk), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls[entry] += 1
+        rc = getattr(self.lib, entry)(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
+                                      w.data_ptr() if w is not None else None, *kk, idx.data_ptr(), cost.data_ptr(),
+                                      ws.data_ptr(), nbytes, self._stream())
         _lib.check(self.lib, self.ctx, rc)
+        res = (idx[:, 0], cost[:, 0]) if kk and k is None else (idx, cost)
         if not stats:
-            return idx, cost
-        nbf, ncand, mcand, nmax = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+            return res
+        names = ("brute_force", "candidate_tiles", "max_candidate_tiles") if kk else ("brute_force",)
+        counts, word = [ctypes.c_int64(0) for _ in names], ctypes.c_double(0.0)
         if M > 0:
             torch.cuda.current_stream(self.device).synchronize()
-            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
-                                                                         ctypes.byref(nbf), ctypes.byref(ncand),
-                                                                         ctypes.byref(mcand), ctypes.byref(nmax)))
-        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
-                           "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
-
-    def _lut_topk_wide(self, lut, obs, w, k, dt, td, stats):
-        """spart_lut_topk_wide on prepared device tensors (lut_nearest / lut_topk above LUT_NARROW_NB bands)."""
-        torch = self.torch
-        B, nb = lut.shape
-        M = obs.shape[0]
-        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
-        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
-        n = int(self.lib.spart_lut_topk_wide_workspace_bytes(dt, B, nb, M, k))
-        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
-        self.calls["spart_lut_topk_wide"] += 1
-        rc = self.lib.spart_lut_topk_wide(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
-                                          w.data_ptr() if w is not None else None, k, idx.data_ptr(), cost.data_ptr(),
-                                          ws.data_ptr(), ctypes.c_size_t(ws.numel()), self._stream())
-        _lib.check(self.lib, self.ctx, rc)
-        if not stats:
-            return idx, cost
-        nbf, ncand, mcand, nmax = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-        if M > 0:
-            torch.cuda.current_stream(self.device).synchronize()
-            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_wide_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
-                                                                              ctypes.byref(nbf), ctypes.byref(ncand),
-                                                                              ctypes.byref(mcand), ctypes.byref(nmax)))
-        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
-                           "max_candidate_tiles": int(mcand.value), "nmax": float(nmax.value)}
-
-    def _lut_topk_obs_weights(self, lut, obs, w, k, dt, td, stats):
-        """spart_lut_topk_obs_weights on prepared device tensors (lut_nearest / lut_topk with (M, nb) weights)."""
-        torch = self.torch
-        B, nb = lut.shape
-        M = obs.shape[0]
-        idx = torch.empty((M, max(k, 0)), dtype=torch.int64, device=self.device)
-        cost = torch.empty((M, max(k, 0)), dtype=td, device=self.device)
-        n = int(self.lib.spart_lut_topk_obs_weights_workspace_bytes(dt, B, nb, M, k))
-        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=self.device)
-        self.calls["spart_lut_topk_obs_weights"] += 1
-        rc = self.lib.spart_lut_topk_obs_weights(self.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(), w.data_ptr(), k,
-                                                 idx.data_ptr(), cost.data_ptr(), ws.data_ptr(), ctypes.c_size_t(ws.numel()),
-                                                 self._stream())
-        _lib.check(self.lib, self.ctx, rc)
-        if not stats:
-            return idx, cost
-        nbf, ncand, mcand, nbound = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-        if M > 0:
-            torch.cuda.current_stream(self.device).synchronize()
-            _lib.check(self.lib, self.ctx, self.lib.spart_lut_topk_obs_weights_stats(self.ctx, dt, B, nb, M, k, ws.data_ptr(),
-                                                                                     ctypes.byref(nbf), ctypes.byref(ncand),
-                                                                                     ctypes.byref(mcand), ctypes.byref(nbound)))
-        return idx, cost, {"brute_force": int(nbf.value), "candidate_tiles": int(ncand.value),
-                           "max_candidate_tiles": int(mcand.value), "nbound": float(nbound.value)}
+            _lib.check(self.lib, self.ctx, getattr(self.lib, read_stats)(
+                self.ctx, dt, B, nb, M, *kk, ws.data_ptr(), *[ctypes.byref(c) for c in counts], ctypes.byref(word)))
+        return res + ({**{n: int(c.value) for n, c in zip(names, counts)}, scale: float(word.value)},)
 
     def profile(self, max_calls):
         """bracket the band kernel of the next ``max_calls`` run() calls with HIP events (0 = off)."""

@@ -72,6 +72,27 @@ def test_null_context_errors_do_not_need_a_gpu(lib_path):
     assert rc == -1 and b"null" in lib.spart_last_error(None)
 
 
+@pytest.mark.parametrize("name,nb_max,has_k", [("spart_lut", 31, False), ("spart_lut_topk", 31, True),
+                                               ("spart_lut_topk_wide", 2162, True), ("spart_lut_topk_obs_weights", 2162, True)])
+def test_lut_workspace_bytes_is_zero_exactly_for_refused_sizes(lib_path, name, nb_max, has_k):
+    """the *_workspace_bytes of the LUT searches take no context and touch no GPU: 0 for every size or dtype the search
+    refuses (and for an empty LUT or no observations), a layout for both ends of the nb and k ranges"""
+    f = getattr(ctypes.CDLL(lib_path), name + "_workspace_bytes")
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * has_k
+
+    def size(dtype=0, B=1000, nb=13, M=10, k=8):
+        return f(dtype, B, nb, M, *([k] * has_k))
+    for bad in ({"nb": 0}, {"nb": nb_max + 1}, {"dtype": 2}, {"dtype": -1}, {"B": 0}, {"M": 0}, {"B": -1}, {"M": -1}):
+        assert size(**bad) == 0, bad
+    for nb in (1, nb_max):
+        assert size(nb=nb) > 0 and size(dtype=1, nb=nb) > 0, nb
+    if has_k:
+        assert size(k=0) == 0 and size(k=257) == 0 and size(k=-1) == 0
+        assert size(k=1) > 0 and size(k=256) > 0
+    assert size(0, 2_000_000_000, nb_max, 1_000_000, 256) > 0 and size(1, 1, 1, 1, 1) > 0
+
+
 def test_build_id_ties_the_binary_to_its_sources(lib_path, tmp_path):
     """spart_build_id() == the hash of the sources / flags next to the library (build.source_id), read both from the loaded
     code and from the file's bytes; a file without (or with another) id is detected without loading it."""

@@ -1,89 +1,21 @@
 """spart_lut_topk_obs_weights / Engine.lut_topk with (M, nb) weights on the MI355X: one weight row per observation, a band of
 weight zero skipped (the observation may be NaN there); index AND cost bit-equal to the brute force of the defined cost
 (tools/lut_brute_force.py), ordered by (cost, row), padded with (-1, +inf); the identities with the shared-weights search."""
-import ctypes
-import os
-import sys
-
 import numpy as np
 import pytest
 
+from helpers.lut_calls import (bf, eng, hyper_si, spectra, torch_mod,  # noqa: F401  (fixtures)
+                               equal_rows_case, lut_call, near_rows_case, tdtype)
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-FIXTURE = os.path.join(ROOT, "tests", "golden", "hyperspectral.npz")
-DT = {"float32": 0, "float64": 1}
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def bf():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import lut_brute_force
-    return lut_brute_force
-
-
-@pytest.fixture(scope="module")
-def eng(torch_mod):
-    from spart_amd import get_engine
-    return get_engine(None, 0)
-
-
-@pytest.fixture(scope="module")
-def hyper_si():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_hyperspectral import sensorinfo_from_npz
-    return sensorinfo_from_npz(dict(np.load(FIXTURE)))
-
-
-@pytest.fixture(scope="module")
-def spectra(torch_mod, hyper_si):
-    """(4096, 211) float64 R_TOC spectra of the 211-band sensor on LHS parameters"""
-    from spart_amd import get_engine, workloads
-    e = get_engine(None, 0, sensor_info=hyper_si)
-    P = workloads.lhs_params(4096, "full", seed=321)
-    r = e.run(torch_mod.as_tensor(P.T.copy(), device="cuda:0"), "float64")["R_TOC"]
-    return torch_mod.nan_to_num(r, nan=0.5)
 
 
 def obsw(torch, eng, lut, obs, w, k, dtype="float32", ws_bytes=None):
-    """spart_lut_topk_obs_weights through ctypes -> (rc, idx, cost, stats dict)"""
-    B, nb = lut.shape
-    M = obs.shape[0]
-    dt = DT[dtype]
-    idx = torch.empty((M, k), dtype=torch.int64, device=lut.device)
-    cost = torch.empty((M, k), dtype=lut.dtype, device=lut.device)
-    need = int(eng.lib.spart_lut_topk_obs_weights_workspace_bytes(dt, B, nb, M, k))
-    n = need if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(n, 256), dtype=torch.uint8, device=lut.device)
-    rc = eng.lib.spart_lut_topk_obs_weights(eng.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
-                                            None if w is None else w.data_ptr(), k, idx.data_ptr(), cost.data_ptr(),
-                                            ws.data_ptr(), ctypes.c_size_t(n), None)
-    st = {}
-    if rc == 0 and M > 0:
-        torch.cuda.synchronize()
-        a, b, c, d = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
-        assert eng.lib.spart_lut_topk_obs_weights_stats(eng.ctx, dt, B, nb, M, k, ws.data_ptr(), ctypes.byref(a), ctypes.byref(b),
-                                                        ctypes.byref(c), ctypes.byref(d)) == 0
-        st = {"brute_force": a.value, "candidate_tiles": b.value, "max_candidate_tiles": c.value, "nbound": d.value}
-    return rc, idx, cost, st
+    return lut_call(torch, eng, "spart_lut_topk_obs_weights", lut, obs, k, w, dtype, ws_bytes)
 
 
 def wide(torch, eng, lut, obs, w, k, dtype):
-    B, nb = lut.shape
-    M = obs.shape[0]
-    idx = torch.empty((M, k), dtype=torch.int64, device=lut.device)
-    cost = torch.empty((M, k), dtype=lut.dtype, device=lut.device)
-    n = int(eng.lib.spart_lut_topk_wide_workspace_bytes(DT[dtype], B, nb, M, k))
-    ws = torch.empty(max(n, 256), dtype=torch.uint8, device=lut.device)
-    rc = eng.lib.spart_lut_topk_wide(eng.ctx, DT[dtype], B, nb, lut.data_ptr(), M, obs.data_ptr(), w.data_ptr(), k,
-                                     idx.data_ptr(), cost.data_ptr(), ws.data_ptr(), ctypes.c_size_t(n), None)
+    rc, idx, cost, _ = lut_call(torch, eng, "spart_lut_topk_wide", lut, obs, k, w, dtype)
     assert rc == 0
     return idx, cost
 
@@ -113,12 +45,10 @@ def masked_weights(torch, g, M, nb, td, obs):
 @pytest.mark.parametrize("nb", [1, 6, 13, 31, 32, 97, 211, 2162])
 def test_obs_weights_grid(torch_mod, eng, bf, nb, dtype):
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     g = torch.Generator(device="cuda:0").manual_seed(nb)
     B, M = (1537, 37) if nb > 300 else (3001, 53)
-    lut = torch.rand((B, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
-    obs = (lut[torch.arange(M, device="cuda:0") * 13 % B] + 0.05 * torch.randn((M, nb), generator=g, device="cuda:0",
-                                                                             dtype=torch.float64).to(td)).contiguous()
+    lut, obs = near_rows_case(torch, g, B, M, nb, td)
     w = masked_weights(torch, g, M, nb, td, obs)
     for k in (1, 10, 256):
         check(torch, eng, bf, lut, obs, w, k, dtype)
@@ -130,7 +60,7 @@ def test_identities(torch_mod, eng, nb, dtype):
     """(I1) every weight row = w: lut_topk(weights=w)'s answer; (I2) zero weight on a band set S: the wide search over the
     columns outside S with the remaining weights -- bit for bit"""
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     g = torch.Generator(device="cuda:0").manual_seed(200 + nb)
     B, M = 4001, 61
     lut = torch.rand((B, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
@@ -161,7 +91,7 @@ def test_identities(torch_mod, eng, nb, dtype):
 @pytest.mark.parametrize("nb", [13, 97])
 def test_obs_weights_edges(torch_mod, eng, bf, nb, dtype):
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     B, M = 2049, 40
     g = torch.Generator(device="cuda:0").manual_seed(5)
     lut = torch.rand((B, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
@@ -208,14 +138,10 @@ def test_obs_weights_edges(torch_mod, eng, bf, nb, dtype):
 def test_obs_weights_fallback_is_exercised(torch_mod, eng, bf, dtype):
     """all rows equal but one: every tile is a candidate, the lists overflow, the brute force decides (and is checked)"""
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
-    nb, B = 211, 32 * 300 + 5
+    td = tdtype(torch, dtype)
     g = torch.Generator(device="cuda:0").manual_seed(3)
-    base = torch.rand((1, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
-    lut = base.repeat(B, 1).contiguous()
-    lut[4000] = base[0] * 0.999
-    obs = (base.repeat(9, 1) * (1 + 0.001 * torch.randn((9, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td))).contiguous()
-    w = masked_weights(torch, g, 9, nb, td, obs)
+    lut, obs = equal_rows_case(torch, g, td)
+    w = masked_weights(torch, g, 9, lut.shape[1], td, obs)
     for k in (1, 10):
         st = check(torch, eng, bf, lut, obs, w, k, dtype)
         assert st["brute_force"] > 0, st
@@ -227,7 +153,7 @@ def test_filter_settles_noisy_spectra(torch_mod, eng, bf, spectra, dtype):
     filter decides every observation (no brute force) and the answer is exact"""
     from spart_amd import noise_weights
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     lut = spectra[:3900].to(td).contiguous()
     g = torch.Generator(device="cuda:0").manual_seed(8)
     o = spectra[3900:] * (1 + 0.02 * torch.randn(spectra[3900:].shape, generator=g, device="cuda:0", dtype=torch.float64))

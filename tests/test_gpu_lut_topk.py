@@ -1,37 +1,14 @@
 """spart_lut_topk / Engine.lut_topk / retrieve on the MI355X: the k nearest LUT rows, index AND cost bit-equal to a brute force
 of the defined cost (tools/lut_brute_force.py; its numpy and torch forms agree: tests/test_lut_topk_host.py), ordered by
 (cost, row), padded with (-1, +inf)."""
-import ctypes
-import os
-import sys
-
 import numpy as np
 import pytest
 
+from helpers.lut_calls import bf, eng, lut_call, torch_mod  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 KS = (1, 2, 10, 64, 256)
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def bf():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import lut_brute_force
-    return lut_brute_force
-
-
-@pytest.fixture(scope="module")
-def eng(torch_mod):
-    from spart_amd import get_engine
-    return get_engine(None, 0)
 
 
 def _check(torch, eng, bf, lut, obs, k, w, dtype, nearest=True):
@@ -192,22 +169,18 @@ def test_topk_at_size(torch_mod, eng, bf):
 def test_topk_abi_refusals(torch_mod, eng):
     """k outside 1 ... 256, NULL outputs, a workspace that is too small: refused with the documented codes"""
     torch = torch_mod
-    lib, ctx = eng.lib, eng.ctx
+    lib = eng.lib
     lut = torch.rand((1000, 13), device="cuda:0")
     obs = torch.rand((10, 13), device="cuda:0")
-    idx = torch.empty((10, 256), dtype=torch.int64, device="cuda:0")
-    cost = torch.empty((10, 256), device="cuda:0")
     n = int(lib.spart_lut_topk_workspace_bytes(0, 1000, 13, 10, 8))
-    ws = torch.empty(n, dtype=torch.uint8, device="cuda:0")
 
-    def call(k, i=idx.data_ptr(), c=cost.data_ptr(), nbytes=n):
-        return lib.spart_lut_topk(ctx, 0, 1000, 13, lut.data_ptr(), 10, obs.data_ptr(), None, k, i, c, ws.data_ptr(),
-                                  ctypes.c_size_t(nbytes), None)
+    def call(k, **kw):
+        return lut_call(torch, eng, "spart_lut_topk", lut, obs, k, **kw)[0]
     assert lib.spart_lut_topk_workspace_bytes(0, 1000, 13, 10, 0) == 0
     assert lib.spart_lut_topk_workspace_bytes(0, 1000, 13, 10, 257) == 0
     assert call(0) == -1 and call(257) == -1
-    assert call(8, i=None) == -1 and call(8, c=None) == -1
-    assert call(8, nbytes=n - 1) == -3
+    assert call(8, null=("idx",)) == -1 and call(8, null=("cost",)) == -1
+    assert call(8, ws_bytes=n - 1) == -3
     assert call(8) == 0
     torch.cuda.synchronize()
     with pytest.raises(RuntimeError):

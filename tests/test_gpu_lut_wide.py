@@ -1,78 +1,17 @@
 """spart_lut_topk_wide / Engine.lut_nearest / lut_topk above 31 bands on the MI355X: the k nearest LUT rows for hyperspectral
 nb, index AND cost bit-equal to the brute force of the defined cost (tools/lut_brute_force.py), ordered by (cost, row), padded
 with (-1, +inf); for nb <= 31 the wide entry point equals spart_lut_topk / spart_lut_nearest bit for bit."""
-import ctypes
-import os
-import sys
-
 import numpy as np
 import pytest
 
+from helpers.lut_calls import (bf, eng, hyper_si, spectra, torch_mod,  # noqa: F401  (fixtures)
+                               equal_rows_case, lut_call, near_rows_case, tdtype)
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-FIXTURE = os.path.join(ROOT, "tests", "golden", "hyperspectral.npz")
-DT = {"float32": 0, "float64": 1}
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def bf():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import lut_brute_force
-    return lut_brute_force
-
-
-@pytest.fixture(scope="module")
-def eng(torch_mod):
-    from spart_amd import get_engine
-    return get_engine(None, 0)
-
-
-@pytest.fixture(scope="module")
-def hyper_si():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from make_hyperspectral import sensorinfo_from_npz
-    return sensorinfo_from_npz(dict(np.load(FIXTURE)))
-
-
-@pytest.fixture(scope="module")
-def spectra(torch_mod, hyper_si):
-    """(4096, 211) float64 R_TOC spectra of the 211-band sensor on LHS parameters (the first 2 rows' NaN-free)"""
-    from spart_amd import get_engine, workloads
-    eng = get_engine(None, 0, sensor_info=hyper_si)
-    P = workloads.lhs_params(4096, "full", seed=321)
-    r = eng.run(torch_mod.as_tensor(P.T.copy(), device="cuda:0"), "float64")["R_TOC"]
-    return torch_mod.nan_to_num(r, nan=0.5)
 
 
 def wide(torch, eng, lut, obs, k, w=None, dtype="float32", ws_bytes=None):
-    """spart_lut_topk_wide through ctypes -> (rc, idx, cost, stats dict)"""
-    B, nb = lut.shape
-    M = obs.shape[0]
-    dt = DT[dtype]
-    idx = torch.empty((M, k), dtype=torch.int64, device=lut.device)
-    cost = torch.empty((M, k), dtype=lut.dtype, device=lut.device)
-    need = int(eng.lib.spart_lut_topk_wide_workspace_bytes(dt, B, nb, M, k))
-    n = need if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(n, 256), dtype=torch.uint8, device=lut.device)
-    rc = eng.lib.spart_lut_topk_wide(eng.ctx, dt, B, nb, lut.data_ptr(), M, obs.data_ptr(),
-                                     None if w is None else w.data_ptr(), k, idx.data_ptr(), cost.data_ptr(), ws.data_ptr(),
-                                     ctypes.c_size_t(n), None)
-    st = {}
-    if rc == 0 and M > 0:
-        torch.cuda.synchronize()
-        a, b, c, d = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
-        assert eng.lib.spart_lut_topk_wide_stats(eng.ctx, dt, B, nb, M, k, ws.data_ptr(), ctypes.byref(a), ctypes.byref(b),
-                                                 ctypes.byref(c), ctypes.byref(d)) == 0
-        st = {"brute_force": a.value, "candidate_tiles": b.value, "max_candidate_tiles": c.value, "nmax": d.value}
-    return rc, idx, cost, st
+    return lut_call(torch, eng, "spart_lut_topk_wide", lut, obs, k, w, dtype, ws_bytes)
 
 
 def check(torch, eng, bf, lut, obs, k, w=None, dtype="float32"):
@@ -89,12 +28,9 @@ def check(torch, eng, bf, lut, obs, k, w=None, dtype="float32"):
 @pytest.mark.parametrize("nb", [32, 33, 64, 211, 2001, 2162])
 def test_wide_grid_uniform(torch_mod, eng, bf, nb, dtype):
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
     g = torch.Generator(device="cuda:0").manual_seed(nb)
     B, M = (1537, 53) if nb > 300 else (3001, 71)
-    lut = torch.rand((B, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
-    obs = (lut[torch.arange(M, device="cuda:0") * 13 % B] + 0.05 * torch.randn((M, nb), generator=g, device="cuda:0",
-                                                                             dtype=torch.float64).to(td)).contiguous()
+    lut, obs = near_rows_case(torch, g, B, M, nb, tdtype(torch, dtype))
     for k in (1, 2, 10, 256):
         check(torch, eng, bf, lut, obs, k, dtype=dtype)
 
@@ -103,7 +39,7 @@ def test_wide_grid_uniform(torch_mod, eng, bf, nb, dtype):
 def test_wide_weights_and_edges(torch_mod, eng, bf, dtype):
     """weights with one zero; a NaN row; exact members; a row repeated so that ties straddle the k-th place"""
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     nb, B, M = 97, 2049, 40
     g = torch.Generator(device="cuda:0").manual_seed(5)
     lut = torch.rand((B, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
@@ -124,7 +60,7 @@ def test_wide_weights_and_edges(torch_mod, eng, bf, dtype):
 def test_wide_on_spectra(torch_mod, eng, bf, spectra, dtype):
     """a LUT of real R_TOC spectra of the 211-band sensor, observations = other rows x (1 + 0.02 N(0, 1))"""
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     lut = spectra[:3900].to(td).contiguous()
     g = torch.Generator(device="cuda:0").manual_seed(8)
     obs = (spectra[3900:] * (1 + 0.02 * torch.randn(spectra[3900:].shape, generator=g, device="cuda:0",
@@ -138,7 +74,7 @@ def test_wide_on_spectra(torch_mod, eng, bf, spectra, dtype):
 @pytest.mark.parametrize("nb", [1, 13, 31])
 def test_wide_equals_narrow(torch_mod, eng, nb, dtype):
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
+    td = tdtype(torch, dtype)
     g = torch.Generator(device="cuda:0").manual_seed(100 + nb)
     lut = torch.rand((5003, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
     lut[3] = float("nan")
@@ -159,13 +95,7 @@ def test_wide_equals_narrow(torch_mod, eng, nb, dtype):
 def test_wide_fallback_is_exercised(torch_mod, eng, bf, dtype):
     """all rows equal but one: every tile is a candidate, the lists overflow, the brute force decides (and is checked)"""
     torch = torch_mod
-    td = torch.float32 if dtype == "float32" else torch.float64
-    nb, B = 211, 32 * 300 + 5
-    g = torch.Generator(device="cuda:0").manual_seed(3)
-    base = torch.rand((1, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td)
-    lut = base.repeat(B, 1).contiguous()
-    lut[4000] = base[0] * 0.999
-    obs = (base.repeat(9, 1) * (1 + 0.001 * torch.randn((9, nb), generator=g, device="cuda:0", dtype=torch.float64).to(td))).contiguous()
+    lut, obs = equal_rows_case(torch, torch.Generator(device="cuda:0").manual_seed(3), tdtype(torch, dtype))
     for k in (1, 10):
         st = check(torch, eng, bf, lut, obs, k, dtype=dtype)
         assert st["brute_force"] > 0, st

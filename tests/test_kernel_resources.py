@@ -4,41 +4,17 @@ The band kernel's speed depends on resident waves per SIMD (512 VGPRs / wave bud
 (<= 96 VGPRs, no scratch), 3 for the float64 ones (<= 168).  A change that silently pushes a kernel over the edge
 would only show up as a slower benchmark; this test makes it a failure on the build machine."""
 import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-
-
-def _hipcc():
-    for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
 
 @pytest.fixture(scope="module")
-def kernel_meta(tmp_path_factory):
-    cc = _hipcc()
-    if cc is None:
+def kernel_meta():
+    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
         pytest.skip("hipcc not available")
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "spart-python_amd"))
-    import build                      # every translation unit with ITS flags (build.TU_FLAGS)
-    meta, cur = {}, None
-    for line in (l for f in build.device_asm(str(tmp_path_factory.mktemp("isa"))) for l in open(f)):
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
-        if m:
-            cur = m.group(1)
-            meta[cur] = {}
-            continue
-        m = re.match(r"\s+\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-        if m and cur:
-            meta[cur][m.group(1)] = int(m.group(2))
-    return meta
+    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
+    return compiled()
 
 
 def _find(meta, fragment):

@@ -1,32 +1,17 @@
 """Resource guard of the wide LUT search (no GPU: hipcc cross-compiles): the K-streamed MFMA scan and collect kernels of
 spart_lut_topk_wide keep everything in registers and LDS -- no scratch, no spills -- in both dtypes."""
 import os
-import re
 import shutil
-import sys
 
 import pytest
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-
 
 @pytest.fixture(scope="module")
-def kernel_meta(tmp_path_factory):
+def kernel_meta():
     if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
         pytest.skip("hipcc not available")
-    sys.path.insert(0, os.path.join(ROOT, "spart-python_amd"))
-    import build
-    meta, cur = {}, None
-    for line in (l for f in build.device_asm(str(tmp_path_factory.mktemp("isa"))) for l in open(f)):
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
-        if m:
-            cur = m.group(1)
-            meta[cur] = {}
-            continue
-        m = re.match(r"\s+\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-        if m and cur:
-            meta[cur][m.group(1)] = int(m.group(2))
-    return meta
+    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
+    return compiled()
 
 
 @pytest.mark.parametrize("frag", ["k_lutw_gemmIfLb0E", "k_lutw_gemmIfLb1E", "k_lutw_gemmIdLb0E", "k_lutw_gemmIdLb1E"])
