@@ -38,3 +38,11 @@ print("recovered the generating row for", float((idx == pick).mean()) * 100, "% 
 from spart_amd import invert_lut  # noqa: E402
 idx2, cost2 = invert_lut(out, obs, column="R_TOA")              # one process: the whole directory on this GPU
 assert np.array_equal(idx2, idx)
+
+# a scene in, parameter maps out: the k = 10 nearest rows per spectrum, summarised on the GPU (mean / median / std per
+# parameter), the observations streamed through in chunks beside their copies
+from spart_amd import retrieve_stream  # noqa: E402
+maps = retrieve_stream(out, obs, 10, column="R_TOA", params_cols=["LAI", "Cab"], chunk=1024)
+print("k = 10 mean of the nearest rows: median |LAI error| =", float(np.median(np.abs(maps["mean"][:, 0] - params[pick, 15]))),
+      "beside the nearest row's", float(np.median(np.abs(params[idx, 15] - params[pick, 15]))),
+      "; median LAI spread (std) =", float(np.median(maps["std"][:, 0])))

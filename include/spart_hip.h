@@ -59,8 +59,9 @@ extern "C" {
  *   7: spart_workspace_bandsum
  *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats
  *   9: spart_lut_topk_wide, spart_lut_topk_wide_workspace_bytes, spart_lut_topk_wide_stats; sensors of up to SPART_NWLS bands
- *  10: spart_lut_topk_obs_weights, spart_lut_topk_obs_weights_workspace_bytes, spart_lut_topk_obs_weights_stats */
-#define SPART_ABI_VERSION 10
+ *  10: spart_lut_topk_obs_weights, spart_lut_topk_obs_weights_workspace_bytes, spart_lut_topk_obs_weights_stats
+ *  11: spart_lut_summarise */
+#define SPART_ABI_VERSION 11
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -318,6 +319,29 @@ int spart_lut_topk_obs_weights(spart_ctx *ctx, int dtype, int64_t B, int nb, con
  * Nbound_m = sum_j w[m,j] max_b (lut[b,j] - centre_j)^2, the scale of the rounding bound. */
 int spart_lut_topk_obs_weights_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
                                      int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nbound);
+
+/* Parameter summaries of the rows a top-k search selected (what a LUT retrieval reports: maps of LAI, Cab, ... with a spread;
+ * no reference counterpart).  params (B, P) float64 row-major, the LUT's parameter table; idx (M, k) int64, the output of any
+ * of the three top-k searches; mean / median / std (M, P) float64 and count (M,) int32, any of which may be NULL (not all
+ * four).  All device memory.  1 <= P <= 64, 1 <= k <= 256, B and M <= 2e9 (SPART_ERR_INVALID otherwise); M = 0 launches
+ * nothing; no workspace; one kernel launch on `stream`.
+ * Definition.  For observation m let j_1 < j_2 < ... < j_n be the places with 0 <= idx[m, j] < B, in place order.  Every other
+ * value of idx (the -1 padding of the searches, or anything out of range) is skipped: the kernel never forms an address from
+ * an index it has not range-checked.  With x_i = params[idx[m, j_i], p], all in float64, no FMA contraction:
+ *   count[m]     = n
+ *   mean[m, p]   = (((x_1 + x_2) + x_3) + ... + x_n) / n
+ *   std[m, p]    = sqrt((((x_1 - mean)^2 + (x_2 - mean)^2) + ...) / n)      (ddof = 0, two passes, the sum in place order)
+ *   median[m, p] = NaN if any x_i is NaN; else with s the ascending sort of the x_i: s[(n-1)/2] for odd n and
+ *                  (s[n/2 - 1] + s[n/2]) / 2 for even n
+ *   n = 0: all three are NaN.
+ * These are numpy's mean / median / std(axis=1) of the gathered block with the order of summation pinned, so that the result
+ * is one defined number.  Duplicated rows in idx[m] count as often as they appear.  NaN parameter VALUES propagate (numpy's
+ * nan* forms, which a host summary may use for padded observations, drop them; LUT parameter tables hold no NaN).
+ * How (csrc/spart_lut.h, "parameter summaries"): lane = parameter, 64 / P observations per wave for k <= 64; each place is one
+ * coalesced read of a P * 8-byte row; the values wait in LDS, one column per lane, for the second pass of std and for the
+ * median, which is selected by rank counting. */
+int spart_lut_summarise(spart_ctx *ctx, int64_t B, int P, const double *params, int64_t M, int k, const int64_t *idx,
+                        double *mean, double *median, double *std, int32_t *count, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -967,8 +967,22 @@ static int lut_read_stats(spart_ctx* ctx, const char* who, int dtype, const void
 }
 static_assert(LUT_CTL_WORDS <= LUT_TOPK_CTL_WORDS, "lut_read_stats: the buffer holds either search's control words");
 
+// spart_lut_summarise once its arguments are checked: one launch of single-wave workgroups, no workspace.  Only a launch
+// above LUT_SUM_SMALL_K can ask for more dynamic LDS than the 64 KiB a kernel gets without opting in.
+static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t M, int k, const int64_t* idx, double* mean,
+                                double* median, double* sdev, int32_t* count, hipStream_t st) {
+  const int G = lut_sum_group(P, k);
+  const size_t lds = lut_sum_lds_bytes(P, k);
+  if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void*)k_lut_summarise, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t items = (M + G - 1) / G;
+  const unsigned blocks = (unsigned)(items < LUT_SUM_MAX_BLOCKS ? items : LUT_SUM_MAX_BLOCKS);
+  hipLaunchKernelGGL(k_lut_summarise, dim3(blocks), dim3(64), lds, st, params, B, P, idx, M, k, G, mean, median, sdev, count);
+  HIP_TRY(hipGetLastError());
+  return SPART_OK;
+}
+
 #ifndef SPART_BUILD_ID
-#define SPART_BUILD_ID "unidentified"      // built outside spart-python_amd/build.py
+#define SPART_BUILD_ID "unidentified"     // built outside spart-python_amd/build.py
 #endif
 // tag + id: build.py finds the id in the file's bytes (binary_id), spart_build_id() returns the part after the tag
 static const char k_build_id[] = "SPART_BUILD_ID:" SPART_BUILD_ID;
@@ -1377,6 +1391,22 @@ int spart_lut_topk_obs_weights_stats(spart_ctx* ctx, int dtype, int64_t B, int n
   return lut_read_stats(ctx, "spart_lut_topk_obs_weights_stats", dtype, workspace,
                         spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k) != 0,
                         [&] { return lut_wide_layout(dtype, B, nb, M, k, true).ctl; }, counts, 3, nbound);
+}
+
+// (the argument checks of lut_search, in its order, for a call without dtype, bands and workspace)
+int spart_lut_summarise(spart_ctx* ctx, int64_t B, int P, const double* params, int64_t M, int k, const int64_t* idx,
+                        double* mean, double* median, double* std, int32_t* count, void* stream) {
+  const char* who = "spart_lut_summarise";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (B < 0 || M < 0 || P < 1 || P > LUT_SUM_MAXP || B > 2000000000LL || M > 2000000000LL)
+    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld P=%d; 1 <= P <= %d, B and M <= 2e9)", who, (long long)B,
+                (long long)M, P, LUT_SUM_MAXP);
+  if (k < 1 || k > LUT_TOPK_MAXK) return fail(SPART_ERR_INVALID, "%s: k = %d, expected 1 <= k <= %d", who, k, LUT_TOPK_MAXK);
+  if (M == 0) return SPART_OK;
+  if (B == 0) return fail(SPART_ERR_INVALID, "%s: empty table", who);
+  if (!params || !idx || (!mean && !median && !std && !count)) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  return guarded(ctx, who, nullptr, 0, stream,
+                 [&](hipStream_t st) { return launch_lut_summarise(B, P, params, M, k, idx, mean, median, std, count, st); });
 }
 
 }  // extern "C"

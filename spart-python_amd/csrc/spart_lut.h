@@ -1739,4 +1739,146 @@ __global__ __launch_bounds__(256) void k_lutow_bound(const T* __restrict__ part_
   }
 }
 
+// ---- parameter summaries (spart_lut_summarise): count, mean, median and standard deviation of the parameter rows a
+// search selected, per observation and parameter, as include/spart_hip.h defines them (float64, place order, no FMA).
+//
+// Mapping.  Single-wave workgroups; lane = (observation g of the wave, parameter p) with G observations side by side:
+// G = 64 / P for k <= LUT_SUM_SMALL_K (two at P = 27, one above 32 parameters), G = 1 above it.  A = G P lanes work, and
+// lane l of work item t writes the output elements t A + l: the stores of a wave are one contiguous run.
+//   gather   place j of observation m is ONE row of P doubles read by the P lanes of its group (216 B at P = 27); the index
+//            idx[m, j] is read by every lane of the group (one address: a broadcast) and range-checked by the lane that uses
+//            it, as an unsigned compare against B, before it becomes part of an address; four places are in flight per lane.
+//   LDS      the accepted values x_1 .. x_n of a lane sit at [i][l], row stride A doubles: a lane only ever touches its own
+//            column, so the wave needs no barrier, and the A consecutive doubles of a row are conflict-free (ds_read_b64:
+//            two groups of 32 lanes over 64 banks).  k (rounded up to a multiple of 4) x A x 8 bytes of dynamic LDS: 5.2 KB at
+//            k = 10, P = 27; at most
+//            LUT_SUM_SMALL_LDS_BYTES = 32 KB for k <= 64, so the common case is never sized by k = 256 (where it is k P 8
+//            bytes, 128 KB at P = 64: one wave per CU, a case that is recorded, not tuned).
+//   mean     the running sum of the gather; std re-reads the column.
+//   median   by rank, not by sorting: in the order (value, place) x_i has rank #{j < i: x_j <= x_i} + #{j > i: x_j < x_i}, and
+//            the value of rank r is s[r].  n^2 compares per lane with no data-dependent branch; four x_i are held in
+//            registers per sweep over the column, which is read four places at a time.
+constexpr int LUT_SUM_MAXP = 64;
+constexpr int LUT_SUM_SMALL_K = 64;
+constexpr int LUT_SUM_SMALL_LDS_BYTES = 32768;       // the most dynamic LDS a launch with k <= LUT_SUM_SMALL_K asks for
+constexpr int LUT_SUM_MAX_BLOCKS = 1 << 16;
+static_assert(LUT_SUM_SMALL_K * 64 * 8 == LUT_SUM_SMALL_LDS_BYTES, "k <= LUT_SUM_SMALL_K: at most 64 working lanes x k doubles");
+
+// observations per wave and dynamic LDS bytes of a launch
+inline int lut_sum_group(int P, int k) { return k <= LUT_SUM_SMALL_K ? 64 / P : 1; }
+inline size_t lut_sum_lds_bytes(int P, int k) { return (size_t)((k + 3) & ~3) * (size_t)(lut_sum_group(P, k) * P) * 8; }
+
+__global__ __launch_bounds__(64) void k_lut_summarise(const double* __restrict__ params, int64_t B, int P,
+                                                      const int64_t* __restrict__ idx, int64_t M, int k, int G,
+                                                      double* __restrict__ mean, double* __restrict__ median,
+                                                      double* __restrict__ sdev, int32_t* __restrict__ count) {
+  SPART_NO_CONTRACT
+  extern __shared__ __attribute__((aligned(16))) char lut_sum_smem[];
+  double* xs = reinterpret_cast<double*>(lut_sum_smem);
+  const int lane = threadIdx.x;
+  const int A = G * P;
+  const int g = lane / P, p = lane - g * P;
+  const int64_t items = (M + G - 1) / G;
+  const double qnan = __builtin_nan("");
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int64_t m = item * G + g;
+    if (lane >= A || m >= M) continue;                 // (no barrier below: a lane works on its own LDS column only)
+    const int64_t* row = idx + m * k;
+    double* x = xs + lane;
+    int n = 0;
+    double sum = 0.0;
+    bool has_nan = false;
+    for (int j0 = 0; j0 < k; j0 += 4) {
+      int64_t r[4];
+      double v[4];
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) r[u] = j0 + u < k ? row[j0 + u] : (int64_t)-1;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        // THE range check: 0 <= r < B as one unsigned compare.  Nothing below forms an address from r[u] itself: a refused
+        // index is replaced by row 0 (B > 0 here) and its load is skipped as well
+        ok[u] = (unsigned long long)r[u] < (unsigned long long)B;
+        const int64_t rr = ok[u] ? r[u] : (int64_t)0;
+        v[u] = ok[u] ? params[rr * P + p] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (!ok[u]) continue;
+        x[n * A] = v[u];
+        sum = n == 0 ? v[u] : sum + v[u];
+        has_nan = has_nan || v[u] != v[u];
+        ++n;
+      }
+    }
+    const int64_t o = m * P + p;
+    if (count && p == 0) count[m] = n;
+    if (n == 0) {
+      if (mean) mean[o] = qnan;
+      if (median) median[o] = qnan;
+      if (sdev) sdev[o] = qnan;
+      continue;
+    }
+    const double mu = sum / (double)n;
+    if (mean) mean[o] = mu;
+    if (sdev) {
+      double s2 = 0.0;
+      for (int i = 0; i < n; ++i) {
+        const double d = x[i * A] - mu;
+        const double q = d * d;
+        s2 = i == 0 ? q : s2 + q;
+      }
+      sdev[o] = __builtin_sqrt(s2 / (double)n);
+    }
+    if (median) {
+      double med = qnan;
+      if (!has_nan) {
+        // rank of x_i in the order (value, place): #{j < i: x_j <= x_i} + #{j > i: x_j < x_i}, one compare per pair; the
+        // ranks are a permutation of 0 .. n-1, and the value of rank r is s[r].  Four x_i per sweep, four x_j per step;
+        // the column is padded to a multiple of four with +inf, which lies behind every x_i and is never "<" anything
+        const int npad = (n + 3) & ~3;
+        for (int i = n; i < npad; ++i) x[i * A] = __builtin_inf();
+        const int r1 = (n - 1) >> 1, r2 = n >> 1;
+        double s1 = 0.0, s2 = 0.0;
+        for (int i0 = 0; i0 < n; i0 += 4) {
+          double xi[4];
+          int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) xi[u] = x[(i0 + u) * A];
+          for (int j0 = 0; j0 < i0; j0 += 4) {
+            double xj[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) xj[v] = x[(j0 + v) * A];
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+#pragma unroll
+              for (int u = 0; u < 4; ++u) rank[u] += xj[v] <= xi[u] ? 1 : 0;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+              if (v != u) rank[u] += (v < u ? xi[v] <= xi[u] : xi[v] < xi[u]) ? 1 : 0;
+          for (int j0 = i0 + 4; j0 < npad; j0 += 4) {
+            double xj[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) xj[v] = x[(j0 + v) * A];
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+#pragma unroll
+              for (int u = 0; u < 4; ++u) rank[u] += xj[v] < xi[u] ? 1 : 0;
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (i0 + u < n && rank[u] == r1) s1 = xi[u];
+            if (i0 + u < n && rank[u] == r2) s2 = xi[u];
+          }
+        }
+        med = r1 == r2 ? s1 : (s1 + s2) / 2.0;
+      }
+      median[o] = med;
+    }
+  }
+}
+
 }  // namespace spart

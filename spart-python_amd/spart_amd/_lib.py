@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 10        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 11        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -69,6 +69,7 @@ SIGNATURES = {
        for suffix, sig in (("_workspace_bytes", (ctypes.c_size_t, _LUT_SIZES + [ctypes.c_int])),
                            ("", (ctypes.c_int, _LUT_TOPK_CALL)),
                            ("_stats", (ctypes.c_int, _LUT_TOPK_STATS)))},
+    "spart_lut_summarise": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

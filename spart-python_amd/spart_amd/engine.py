@@ -707,6 +707,31 @@ class Engine:
                 self.ctx, dt, B, nb, M, *kk, ws.data_ptr(), *[ctypes.byref(c) for c in counts], ctypes.byref(word)))
         return res + ({**{n: int(c.value) for n, c in zip(names, counts)}, scale: float(word.value)},)
 
+    def lut_summarise(self, params, idx):
+        """count, mean, median and standard deviation (ddof = 0) of the parameter rows ``params[idx[m]]`` per observation,
+        on the device (include/spart_hip.h: spart_lut_summarise, which pins the order of every sum): entries of ``idx`` outside
+        0 ... B-1 -- the -1 padding of lut_topk -- are skipped, duplicated rows count as often as they appear, an observation
+        without rows gets count 0 and NaN.  Unlike spart_amd.summarise_rows on a padded observation (numpy's nan* forms), NaN
+        parameter VALUES propagate; LUT parameter tables hold none, so the two agree on every real table.
+        ``params`` (B, P): anything torch.as_tensor takes, moved to the engine's device as contiguous float64 (a tensor already
+        there is used as it is, no copy); ``idx`` (M, k) int64, e.g. lut_topk's.  1 <= P <= 64, 1 <= k <= 256.
+        -> dict of device tensors: mean, median, std (M, P) float64 and count (M,) int32."""
+        torch = self.torch
+        params = torch.as_tensor(params).to(device=self.device, dtype=torch.float64).contiguous()
+        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
+        if params.dim() != 2 or idx.dim() != 2:
+            raise ValueError("params must be (B, P) and idx (M, k)")
+        B, P = params.shape
+        M, k = idx.shape
+        res = {n: torch.empty((M, P), dtype=torch.float64, device=self.device) for n in ("mean", "median", "std")}
+        res["count"] = torch.empty((M,), dtype=torch.int32, device=self.device)
+        self.calls["spart_lut_summarise"] += 1
+        rc = self.lib.spart_lut_summarise(self.ctx, B, P, params.data_ptr(), M, k, idx.data_ptr(), res["mean"].data_ptr(),
+                                          res["median"].data_ptr(), res["std"].data_ptr(), res["count"].data_ptr(),
+                                          self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        return res
+
     def profile(self, max_calls):
         """bracket the band kernel of the next ``max_calls`` run() calls with HIP events (0 = off)."""
         _lib.check(self.lib, self.ctx, self.lib.spart_profile_enable(self.ctx, int(max_calls)))

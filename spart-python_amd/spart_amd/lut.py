@@ -88,6 +88,32 @@ def open_lut_files(path, files, world=1, rank=0, group=None):
     return whole
 
 
+def _run_pipeline(nchunks, upload, launch, download, ahead=None):
+    """The double-buffered schedule generate_lut and retrieve_stream share.  Chunk i lives in buffer i % 2; ``upload(i)`` and
+    ``launch(i)`` are called on this thread, ``download(i)`` on ONE helper thread (so that it overlaps the next upload; torch
+    releases the GIL inside the copies) and must return only when buffer i % 2 may be overwritten; ``ahead(i)`` is called
+    before chunk i + 1 is touched (generate_lut pre-faults its destination pages there).  The order per chunk i:
+    upload(i + 1) beside the kernels of chunk i, the download of chunk i - 1 awaited, launch(i + 1), download(i) submitted."""
+    from concurrent.futures import ThreadPoolExecutor
+    fut = [None, None]
+    with ThreadPoolExecutor(1) as pool:
+        if nchunks:
+            upload(0)
+            launch(0)
+        for i in range(nchunks):
+            if ahead is not None:
+                ahead(i)
+            if i + 1 < nchunks:
+                upload(i + 1)                                  # overlaps the kernels of chunk i
+                if fut[(i + 1) % 2] is not None:
+                    fut[(i + 1) % 2].result()                  # the output buffer (i+1) % 2 has been drained (chunk i-1)
+                launch(i + 1)
+            fut[i % 2] = pool.submit(download, i)              # overlaps the kernels of chunk i+1
+        for f in fut:
+            if f is not None:
+                f.result()
+
+
 def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, device=None, prune=True, fault_threads=8,
                  f32_bands=False, shard=False, group=None, out=None, sensor_info=None):
     """params: (B, 27) array-like on the HOST (numpy / memmap).  Returns dict of host arrays (np.memmap when
@@ -233,27 +259,12 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
                 as_tensor(out[k][lo:lo + n]).copy_(dout[j][q, :n], non_blocking=True)
             d2h.synchronize()                                      # dout[j] may be overwritten by chunk i+2
 
-    # downloads (which also take the first-touch page faults of the destination) run on one helper thread so that
-    # they overlap the uploads issued by this thread; torch releases the GIL inside the copies
-    fut = [None, None]
+    # downloads (which also take the first-touch page faults of the destination) run on the pipeline's helper thread so
+    # that they overlap the uploads issued by this thread
     try:
-        with ThreadPoolExecutor(1) as pool:
-            prefault(0)
-            prefault(1)
-            if nchunks:
-                upload(0)
-                launch(0)
-            for i in range(nchunks):
-                prefault(i + 2)
-                if i + 1 < nchunks:
-                    upload(i + 1)                                  # overlaps the kernels of chunk i
-                    if fut[(i + 1) % 2] is not None:
-                        fut[(i + 1) % 2].result()                  # dout[(i+1) % 2] has been drained (chunk i-1)
-                    launch(i + 1)
-                fut[i % 2] = pool.submit(download, i)              # overlaps the kernels of chunk i+1
-            for f in fut:
-                if f is not None:
-                    f.result()
+        prefault(0)
+        prefault(1)
+        _run_pipeline(nchunks, upload, launch, download, ahead=lambda i: prefault(i + 2))
     finally:                                                       # also on an exception in upload / launch / download
         if fpool is not None:
             fpool.shutdown(wait=True, cancel_futures=True)
@@ -401,15 +412,216 @@ def summarise_rows(params, idx, block_rows=1 << 18):
     return res
 
 
-def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None):
+SUMMARIES = ("host", "device")
+STREAM_MAPS = ("mean", "median", "std")            # the (M, P) float64 arrays of retrieve_stream, then count and best_cost
+
+
+def _param_columns(params_cols):
+    """params_cols (None = every parameter, or a list of names from workloads.PARAM_NAMES) -> (names, column numbers)"""
+    if params_cols is None:
+        return list(workloads.PARAM_NAMES), list(range(workloads.NPARAM))
+    names = list(params_cols)
+    unknown = [n for n in names if n not in workloads.PARAM_NAMES]
+    if unknown or not names:
+        raise ValueError(f"params_cols: unknown parameter name(s) {unknown}; expected names from {list(workloads.PARAM_NAMES)}")
+    return names, [workloads.PARAM_NAMES.index(n) for n in names]
+
+
+def _np_dtype(name):
+    """the numpy dtype of a LUT's columns (meta.json "dtype"), which is the dtype its searches run in"""
+    return np.float32 if name in ("float32", "fp32", "f32") else np.float64
+
+
+def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None, summary="host",
+             params_cols=None):
     """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
     mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
     ``weights`` as for invert_lut: (nb,) or (M, nb), e.g. noise_weights(obs, rel_sigma=0.02).
-    -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, 27) float64, names (the 27 parameter names)."""
-    idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
-    _, params, _ = load_lut(lut_dir)
-    mean, median, std = summarise_rows(params, idx)
-    return {"idx": idx, "cost": cost, "mean": mean, "median": median, "std": std, "names": list(workloads.PARAM_NAMES)}
+    ``params_cols``: a list of names from workloads.PARAM_NAMES, to summarise only those columns (``names`` follows it).
+    ``summary="host"`` (default): summarise_rows on the host, in numpy.  ``summary="device"``: params.npy (or the chosen columns)
+    is uploaded once, the indices stay on the device between the search and Engine.lut_summarise (spart_lut_summarise), and
+    the result gains ``count`` (M,) int32, the rows found per observation.  The search is the same, so idx and cost are equal
+    bit for bit; median too; mean and std differ from the host's by the rounding of another summation order at most.  One
+    known difference: for an observation WITH padding summarise_rows goes through numpy's nan* forms, which also drop NaN
+    parameter VALUES; the device definition propagates them.  LUT parameter tables hold no NaN, so the two agree on every real
+    table.  ``summary="device"`` with ``shard=True`` under a process group of more than one rank raises ValueError: each rank
+    holds only its own rows (the sharded summary is not built yet).
+    -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, P) float64, names (the P parameter names)."""
+    if summary not in SUMMARIES:
+        raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
+    names, cols = _param_columns(params_cols)
+    if summary == "host":
+        idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
+        _, params, _ = load_lut(lut_dir)
+        mean, median, std = summarise_rows(params, idx)
+        if params_cols is not None:
+            mean, median, std = (np.ascontiguousarray(a[:, cols]) for a in (mean, median, std))
+        return {"idx": idx, "cost": cost, "mean": mean, "median": median, "std": std, "names": names}
+    if _group_info(shard, group)[0] > 1:
+        raise ValueError('retrieve(summary="device") does not take shard=True under a process group of more than one rank: '
+                         'every rank holds only its own rows; use summary="host"')
+    import torch
+    meta, params, tabs = load_lut(lut_dir)
+    table = tabs[column]
+    npdt = _np_dtype(meta["dtype"])
+    td = torch.float32 if npdt is np.float32 else torch.float64
+    k = int(k)
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+    eng = get_engine(None, device)
+    o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=td)
+    M, B, P = o.shape[0], table.shape[0], len(cols)
+    if B > 0 and M > 0:
+        lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=td)          # (a copy: memmaps opened read-only)
+        par_t = torch.as_tensor(np.ascontiguousarray(np.asarray(params)[:, cols], dtype=np.float64)).to(eng.device)
+        idx_t, cost_t = eng.lut_topk(lut_t, o, k, weights=weights, dtype=meta["dtype"])
+        res = eng.lut_summarise(par_t, idx_t)                                             # idx never left the device
+        out = {"idx": idx_t.cpu().numpy(), "cost": cost_t.cpu().numpy()}
+        out.update({n: res[n].cpu().numpy() for n in STREAM_MAPS + ("count",)})
+    else:
+        out = {"idx": np.full((M, k), -1, dtype=np.int64), "cost": np.full((M, k), np.inf, dtype=npdt)}
+        out.update({n: np.full((M, P), np.nan) for n in STREAM_MAPS})
+        out["count"] = np.zeros(M, dtype=np.int32)
+    out["names"] = names
+    return out
+
+
+class _DeviceStage:
+    """The device side of retrieve_stream: the LUT column and the parameter columns, uploaded once; two sets of chunk
+    buffers; three streams.  upload / launch / download are what _run_pipeline calls for buffer j = chunk number % 2."""
+
+    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights):
+        import torch
+        self.torch, self.eng, self.lut, self.par, self.k, self.dtype = torch, eng, lut_t, par_t, k, dtype
+        dev = self.dev = eng.device
+        nb = lut_t.shape[1]
+        self.compute = torch.cuda.current_stream(dev)
+        self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.obs = [torch.empty((chunk, nb), dtype=lut_t.dtype, device=dev) for _ in range(2)]
+        self.w = [torch.empty((chunk, nb), dtype=lut_t.dtype, device=dev) for _ in range(2)] if per_obs_weights else None
+        self.shared = shared_weights
+        self.ev_in = [torch.cuda.Event() for _ in range(2)]
+        self.ev_done = [torch.cuda.Event() for _ in range(2)]
+        self.used = [False, False]
+        self.keep = [None, None]        # host sources of the upload in flight on buffer j
+        self.res = [None, None]         # device results of the chunk in buffer j, until its download is done
+
+    def _tensor(self, a):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")          # read-only inputs (memmaps opened "r") are only read
+            return self.torch.from_numpy(a)
+
+    def upload(self, j, obs, w):
+        n = obs.shape[0]
+        with self.torch.cuda.stream(self.h2d):
+            if self.used[j]:
+                self.h2d.wait_event(self.ev_done[j])               # the kernels that read buffer j last have run
+            self.keep[j] = (obs, w)
+            self.obs[j][:n].copy_(self._tensor(obs), non_blocking=True)
+            if w is not None:
+                self.w[j][:n].copy_(self._tensor(w), non_blocking=True)
+            self.ev_in[j].record(self.h2d)
+        self.used[j] = True
+
+    def launch(self, j, n):
+        self.compute.wait_event(self.ev_in[j])
+        w = self.w[j][:n] if self.w is not None else self.shared
+        idx, cost = self.eng.lut_topk(self.lut, self.obs[j][:n], self.k, weights=w, dtype=self.dtype)
+        res = self.eng.lut_summarise(self.par, idx)
+        res["best_cost"] = cost[:, 0].contiguous()
+        self.res[j] = res
+        self.ev_done[j].record(self.compute)
+
+    def download(self, j, n, dest):                                # runs on the pipeline's helper thread
+        with self.torch.cuda.device(self.dev), self.torch.cuda.stream(self.d2h):
+            self.d2h.wait_event(self.ev_done[j])
+            for name, a in dest.items():
+                self._tensor(a).copy_(self.res[j][name], non_blocking=True)
+            self.d2h.synchronize()                                 # res[j] may be replaced by chunk i + 2
+
+
+def _stream_chunks(obs, weights, chunk, out, stage, npdt):
+    """retrieve_stream's chunk arithmetic: observations lo ... lo + n of chunk i go up as C-contiguous ``npdt`` arrays (with
+    their own rows of (M, nb) ``weights``; None otherwise), and the stage's results land in rows lo ... lo + n of every array
+    of ``out``.  ``stage``: upload(j, obs, w), launch(j, n), download(j, n, dest) for buffer j = i % 2 (_DeviceStage)."""
+    M = obs.shape[0]
+    chunk = int(max(1, min(int(chunk), max(M, 1))))
+    nchunks = (M + chunk - 1) // chunk
+
+    def bounds(i):
+        lo = i * chunk
+        return lo, min(chunk, M - lo)
+
+    def upload(i):
+        lo, n = bounds(i)
+        stage.upload(i % 2, np.ascontiguousarray(obs[lo:lo + n], dtype=npdt),
+                     None if weights is None else np.ascontiguousarray(weights[lo:lo + n], dtype=npdt))
+
+    def launch(i):
+        stage.launch(i % 2, bounds(i)[1])
+
+    def download(i):
+        lo, n = bounds(i)
+        stage.download(i % 2, n, {name: a[lo:lo + n] for name, a in out.items()})
+    _run_pipeline(nchunks, upload, launch, download)
+    return nchunks
+
+
+def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=None, chunk=1 << 16, device=None, out=None,
+                    _stage=None):
+    """A scene in, parameter maps out: retrieve(summary="device") for any number of observations, in chunks.
+    ``obs`` (M, nb) on the HOST (array or memmap; any M, also 0); ``weights`` None, (nb,) or (M, nb) (sliced with the chunks),
+    as for invert_lut; ``params_cols`` as for retrieve.  The LUT column and the chosen parameter columns are uploaded ONCE;
+    chunks of ``chunk`` observations then run through Engine.lut_topk + Engine.lut_summarise with the upload of chunk i + 1 and
+    the download of chunk i - 1 on their own streams beside the kernels of chunk i (generate_lut's schedule, _run_pipeline).
+    -> dict of host arrays: mean, median, std (M, P) float64, count (M,) int32, best_cost (M,) in the LUT's dtype (the cost of
+    the nearest row, the usual quality flag), and names.  The (M, k) indices are not returned: at scene size they are the bulk
+    of the download and the summary replaces them.  A pixel that matches nothing (a NaN observation without a mask, a negative
+    weight) comes back with count 0 and NaN maps (best_cost +inf).  Every array equals retrieve(summary="device")'s bit for
+    bit, whatever the chunk size.  ``out``: caller-owned arrays of those shapes and dtypes (e.g. a previous call's result)."""
+    meta, params, tabs = load_lut(lut_dir)
+    table = tabs[column]
+    names, cols = _param_columns(params_cols)
+    k = int(k)
+    if not 1 <= k <= 256:
+        raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+    B, nb = table.shape
+    npdt = _np_dtype(meta["dtype"])
+    obs = obs if isinstance(obs, np.memmap) else np.asarray(obs)
+    if obs.ndim != 2 or obs.shape[1] != nb:
+        raise ValueError(f"obs must be (M, {nb}), got shape {obs.shape}")
+    M, P = obs.shape[0], len(cols)
+    from .engine import lut_weights_kind
+    if weights is not None and not isinstance(weights, np.memmap):
+        weights = np.asarray(weights)
+    kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
+    shapes = {**{n: ((M, P), np.float64) for n in STREAM_MAPS}, "count": ((M,), np.int32), "best_cost": ((M,), npdt)}
+    if out is None:
+        res = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
+    else:
+        for n, (s, d) in shapes.items():
+            a = out.get(n)
+            if not isinstance(a, np.ndarray) or a.shape != s or a.dtype != d or not a.flags.c_contiguous or not a.flags.writeable:
+                raise ValueError(f"out[{n!r}] must be a writable C-contiguous {s} {np.dtype(d).name} array")
+        res = {n: out[n] for n in shapes}
+    if B == 0:                                                     # an empty table matches nothing
+        for n in STREAM_MAPS:
+            res[n][...] = np.nan
+        res["count"][...] = 0
+        res["best_cost"][...] = np.inf
+    elif M > 0:
+        stage = _stage
+        if stage is None:
+            import torch
+            eng = get_engine(None, device)
+            td = torch.float32 if npdt is np.float32 else torch.float64
+            lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=td)      # (a copy: memmaps opened read-only)
+            par_t = torch.as_tensor(np.ascontiguousarray(np.asarray(params)[:, cols], dtype=np.float64)).to(eng.device)
+            shared = None if kind != "shared" else torch.as_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
+            stage = _DeviceStage(eng, lut_t, par_t, k, meta["dtype"], max(1, min(int(chunk), M)), kind == "per_observation", shared)
+        _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt)
+    res["names"] = names
+    return res
 
 
 def lut_to_parquet(path, parquet_path, compression="gzip"):

@@ -1,5 +1,5 @@
-"""Brute-force checkers of spart_lut_nearest, spart_lut_topk and spart_lut_topk_obs_weights (tests/ and bench.py; tooling,
-not product).
+"""Brute-force checkers of spart_lut_nearest, spart_lut_topk, spart_lut_topk_obs_weights and spart_lut_summarise (tests/ and
+bench.py; tooling, not product).
 
 The cost is DEFINED (include/spart_hip.h) as the sequential evaluation, in the call's dtype and without fused multiply-adds,
 
@@ -197,3 +197,47 @@ def brute_force_topk_obs_weights_torch(lut, obs, k, w, max_elems=1 << 27):
         idx[m0:m0 + mb, :kk] = torch.where(fin, order, torch.full_like(order, -1))
         cost[m0:m0 + mb, :kk] = s
     return idx, cost
+
+
+def summarise_defined(params, idx):
+    """spart_lut_summarise's definition (include/spart_hip.h), literally, in float64.  For observation m the places j with
+    0 <= idx[m, j] < B are taken in place order (every other value -- the -1 padding, anything out of range -- is skipped),
+    x_i = params[idx[m, j_i]], and per parameter
+        count = n;   mean = (((x_1 + x_2) + x_3) + ... + x_n) / n;   std = sqrt((((x_1 - mean)^2 + (x_2 - mean)^2) + ...) / n)
+        median = NaN if any x_i is NaN, else s[(n-1)/2] (n odd) or (s[n/2 - 1] + s[n/2]) / 2 (n even), s the ascending sort
+    and NaN for all three when n = 0.  The sums are plain loops over the places, all observations at once (no np.sum: its order is not
+    promised); numpy rounds every elementwise operation to float64 on its own, so the loops ARE the definition.
+    params (B, P), idx (M, k) -> (mean, median, std (M, P) float64, count (M,) int32)"""
+    params = np.asarray(params, dtype=np.float64)
+    idx = np.asarray(idx, dtype=np.int64)
+    B, P = params.shape
+    M, k = idx.shape
+    ok = (idx >= 0) & (idx < B)                                       # the places that count
+    safe = np.where(ok, idx, 0)
+    rows = params if B > 0 else np.full((1, P), np.nan)               # (an empty table: nothing is in range)
+    count = np.zeros(M, dtype=np.int32)
+    s = np.zeros((M, P))
+    with np.errstate(all="ignore"):
+        for j in range(k):                                            # place by place, every observation at once
+            x, take = rows[safe[:, j]], ok[:, j]
+            first = take & (count == 0)
+            s = np.where(first[:, None], x, np.where(take[:, None], s + x, s))
+            count += take
+        n = count.astype(np.float64)[:, None]
+        mean = np.where(n > 0, s / n, np.nan)
+        q, seen = np.zeros((M, P)), np.zeros(M, dtype=np.int32)
+        for j in range(k):
+            x, take = rows[safe[:, j]], ok[:, j]
+            d = x - mean
+            first = take & (seen == 0)
+            q = np.where(first[:, None], d * d, np.where(take[:, None], q + d * d, q))
+            seen += take
+        std = np.where(n > 0, np.sqrt(q / n), np.nan)
+        X = np.where(ok[:, :, None], rows[safe], np.nan)              # (M, k, P); skipped places sort last, as NaN
+        has_nan = (np.isnan(X) & ok[:, :, None]).any(axis=1)
+        srt = np.sort(X, axis=1)
+        m = np.arange(M)
+        a, b = srt[m, np.maximum(count - 1, 0) // 2], srt[m, np.minimum(count // 2, k - 1)]
+        median = np.where((count % 2 == 1)[:, None], a, (a + b) / np.float64(2))
+        median = np.where(has_nan | (count == 0)[:, None], np.nan, median)
+    return mean, median, std, count
