@@ -237,7 +237,11 @@ int spart_run_batch(spart_ctx *ctx, int dtype, int64_t B, const double *const pa
  * (divide by nb and take the root for an RMSE).  Rows or observations whose cost is not finite -- NaN, +inf, or -inf (negative
  * weights with overflowing products) -- never win (-1 / +inf when no row has a finite cost); so does a LUT row that holds a
  * non-finite value or whose centred weighted norm sum_j |w_j| (lut[b,j] - centre_j)^2 overflows `dtype` (values near the
- * largest finite number), even if its cost against a particular observation would be finite.
+ * largest finite number), even if its cost against a particular observation would be finite -- whichever path of the search
+ * decides the observation, the brute force included.  A row is judged on its OWN entries: the centres are column means over
+ * the entries of magnitude <= 2^62 (SPART_F32) / 2^510 (SPART_F64), a quarter of the square root of the largest number.  A fill
+ * value such as FLT_MAX, or an entry of a row that blew up but stayed finite, is thus left out of the centres; the row that holds
+ * it is ineligible if its own norm overflows, and every other row's verdict and answer are what they are without it.
  * How: a GEMM with K = nb + 1 on the matrix cores -- exact-f32 v_mfma_f32_32x32x2_f32 for SPART_F32,
  * v_mfma_f64_16x16x4_f64 for SPART_F64 -- over the CENTRED LUT (per-band mean removed) ranks the tiles of 32 / 16 LUT rows by
  * |x'|^2 - 2 x'.y'; every tile whose minimum lies within a proven rounding bound of the best one is then evaluated row by

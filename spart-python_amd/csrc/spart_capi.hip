@@ -570,7 +570,7 @@ static int lut_impl(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lu
   const size_t fb_lds = (size_t)4 * LUT_FB_ROWS * nbc * sizeof(T);
   if (!LutFallback::with(nbc, [&](auto N) {
         hipLaunchKernelGGL((k_lut_fallback<T, N>), dim3(LUT_FB_BLOCKS), dim3(256), fb_lds, st, lut, obs, w, nb, B,
-                           (const unsigned long long*)ctl, (const int*)flags, fbc, fbi);
+                           (const T*)tiles, L.ks, (const unsigned long long*)ctl, (const int*)flags, fbc, fbi);
       }))
     return fail(SPART_ERR_INVALID, "spart_lut_nearest: no compiled LUT fallback for %d bands", nbc);
   HIP_TRY(hipGetLastError());
@@ -683,13 +683,14 @@ static int lut_topk_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
                            (const double*)centre, nb, b.ntile, mc, L.nslice2, (const double*)thr, L.cap, cn, cand);
       });
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, false>), gobs, dim3(256), 0, st, lut, obs, w, nb, B, m0, mc, k, (const T*)thr,
-                       (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost);
+    hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, false>), gobs, dim3(256), 0, st, lut, obs, w, nb, B, (const T*)tiles, b.ks, m0, mc,
+                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost);
     HIP_TRY(hipGetLastError());
   }
   // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
-  hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, true>), dim3(LUT_FB_BLOCKS), dim3(256), 0, st, lut, obs, w, nb, B, (int64_t)0,
-                     M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost);
+  hipLaunchKernelGGL((k_lut_topk_select<T, ROWS, true>), dim3(LUT_FB_BLOCKS), dim3(256), 0, st, lut, obs, w, nb, B,
+                     (const T*)tiles, b.ks, (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl,
+                     flags, idx, (T*)cost);
   HIP_TRY(hipGetLastError());
   return SPART_OK;
 }
@@ -793,7 +794,6 @@ static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
     HIP_TRY(hipGetLastError());
   }
   const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
-  const T* sel_norm = OBSW ? norm : nullptr;
   for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
     const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
     const T* ob = obs + m0 * nb;
@@ -814,13 +814,13 @@ static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
     hipLaunchKernelGGL(gemm_collect, dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
                        (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap, cn, cand);
     hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, OBSW>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
-                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, sel_norm);
+                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, (const T*)norm);
     HIP_TRY(hipGetLastError());
   }
   // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
   hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, OBSW>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
                      (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost,
-                     sel_norm);
+                     (const T*)norm);
   HIP_TRY(hipGetLastError());
   return SPART_OK;
 }

@@ -58,12 +58,14 @@ namespace spart {
 template <typename T> struct LutNum;
 template <> struct LutNum<float> {
   static constexpr float u = 5.9604644775390625e-8f, tiny = 7.888609052210118e-31f;
+  static constexpr float centre_cap = 4.611686018427387904e18f;           // 2^62 = sqrt(2^128) / 4
   static __device__ __forceinline__ bool finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
   static __device__ __forceinline__ unsigned long long bits(float v) { return (unsigned long long)__float_as_uint(v); }
   static __device__ __forceinline__ float from_bits(unsigned long long b) { return __uint_as_float((unsigned)b); }
 };
 template <> struct LutNum<double> {
   static constexpr double u = 1.1102230246251565e-16, tiny = 1e-290;
+  static constexpr double centre_cap = 0x1p510;                           // sqrt(2^1024) / 4
   static __device__ __forceinline__ bool finite(double v) {
     return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
   }
@@ -83,7 +85,11 @@ constexpr int LUT_FB_BLOCKS = 2048;        // workgroups (x 4 waves) of the brut
 // (profiles/r4_lut_to_sweep2.txt); nb = 6: 9.25 -> 9.10 ms, nb = 21: unchanged.
 constexpr int LUT_TO = 8;
 
-// column means of a strided sample (finite entries only) -> centre[nb]; also resets the control words
+// column means of a strided sample -> centre[nb]; also resets the control words.  Entries that are not finite, or so large
+// that their own square overflows (|v| > centre_cap), are left out of the mean: one fill value such as FLT_MAX would otherwise
+// drag the centre so far that EVERY row's centred norm overflows and no row is eligible.  The row that holds such an entry is
+// judged like any other, by its own norm (k_lut_prep / k_lutw_norm): rejected if that overflows (an entry above ~2^64 / 2^512),
+// eligible otherwise; a LUT without such an entry gets the centres it always got.
 template <typename T>
 __global__ __launch_bounds__(256) void k_lut_centre(const T* __restrict__ lut, int nb, int64_t B, T* __restrict__ centre,
                                                     unsigned long long* __restrict__ ctl) {
@@ -96,7 +102,7 @@ __global__ __launch_bounds__(256) void k_lut_centre(const T* __restrict__ lut, i
   int n = 0;
   for (int64_t i = threadIdx.x; i < ns; i += 256) {
     const T v = lut[i * stride * nb + j];
-    if (LutNum<T>::finite(v)) {
+    if (__builtin_fabs((double)v) <= (double)LutNum<T>::centre_cap) {      // (false for NaN and +-inf)
       s += (double)v;
       ++n;
     }
@@ -323,6 +329,14 @@ __global__ __launch_bounds__(256, 2) void k_lut_scan_mfma64(const double* __rest
   }
 }
 
+// the verdict of k_lut_prep on row r, read back from the operand image (column nb of its tile holds n_b, +inf for a rejected
+// row): the exact evaluations ask it too, so that a row whose centred norm overflows never wins whichever path decides
+template <typename T, int ROWS>
+__device__ __forceinline__ bool lut_row_ok(const T* __restrict__ tiles, int ks, int nb, int64_t r) {
+  constexpr int NG = 64 / ROWS;
+  return LutNum<T>::finite(tiles[((r / ROWS) * ks + nb / NG) * 64 + (nb % NG) * ROWS + (r % ROWS)]);
+}
+
 // One WAVE per observation (four per workgroup): lanes over the partial results (threshold), then the candidate tiles
 // are evaluated with the direct cost by 64 / ROWS lane groups at a time, one LUT row per lane.
 // coef = 2 (3 nb + 2 K + 16) * 1.01 * u (host: lut_delta_coef).
@@ -462,7 +476,7 @@ __global__ __launch_bounds__(256) void k_lut_reduce_exact(const T* __restrict__ 
             c = c + d3 * d3;
           }
         }
-        if (lut_better(c, r, bc, bi)) {
+        if (lut_row_ok<T, ROWS>(tiles, ks, nb, r) && lut_better(c, r, bc, bi)) {
           bc = c;
           bi = r;
         }
@@ -512,7 +526,8 @@ constexpr int LUT_FB_ROWS = 32;
 
 template <typename T, int NBC>
 __global__ __launch_bounds__(256) void k_lut_fallback(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
-                                                      int nb, int64_t B, const unsigned long long* __restrict__ ctl,
+                                                      int nb, int64_t B, const T* __restrict__ tiles, int ks,
+                                                      const unsigned long long* __restrict__ ctl,
                                                       const int* __restrict__ flag_list, T* __restrict__ fb_cost,
                                                       int64_t* __restrict__ fb_idx) {
   SPART_NO_CONTRACT
@@ -551,6 +566,7 @@ __global__ __launch_bounds__(256) void k_lut_fallback(const T* __restrict__ lut,
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       for (int rr = 0; rr < nrow; ++rr) {
+        if (!lut_row_ok<T, (sizeof(T) == 4 ? 32 : 16)>(tiles, ks, nb, rb + rr)) continue;      // (wave-uniform)
         const T* x = xs + rr * NBC;
         T c = T(0);
         if (w) {
@@ -897,8 +913,9 @@ __device__ __forceinline__ void lut_topk_sort(unsigned long long* sk, int* sr, i
 // LDS: 4 waves x LUT_TOPK_BUF x 12 bytes.
 template <typename T, int ROWS, bool BRUTE>
 __global__ __launch_bounds__(256) void k_lut_topk_select(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
-                                                         int nb, int64_t B, int64_t m_off, int64_t Mc, int k,
-                                                         const T* __restrict__ thr, const int* __restrict__ cand_n,
+                                                         int nb, int64_t B, const T* __restrict__ tiles, int ks, int64_t m_off,
+                                                         int64_t Mc, int k, const T* __restrict__ thr,
+                                                         const int* __restrict__ cand_n,
                                                          const int* __restrict__ cand, int cap, unsigned long long* __restrict__ ctl,
                                                          int* __restrict__ flag_list, int64_t* __restrict__ out_idx,
                                                          T* __restrict__ out_cost) {
@@ -978,7 +995,7 @@ __global__ __launch_bounds__(256) void k_lut_topk_select(const T* __restrict__ l
             c = c + d3 * d3;
           }
         }
-        if (LutNum<T>::finite(c)) key = LutKey<T>::key(c);
+        if (LutNum<T>::finite(c) && lut_row_ok<T, ROWS>(tiles, ks, nb, r)) key = LutKey<T>::key(c);
       }
       const int ri = (int)r;
       bool take = key != LUT_NOKEY && lut_key_less(key, ri, tk, tr);
@@ -1308,14 +1325,15 @@ __global__ __launch_bounds__(256) void k_lutw_bound(const T* __restrict__ part_c
 // BRUTE = false: the rows of the candidate tiles of chunk observation blockIdx.x; BRUTE = true: every row, for the flagged ones.
 // OBSW = true (spart_lut_topk_obs_weights): w is (M, nb), one weight row per observation, loaded with the observation; a band
 // of weight zero is skipped; an observation with a negative or non-finite weight, or a non-finite value in a band of non-zero
-// weight, matches nothing; a row counts only if its norm (k_lutw_norm without weights) is finite, whatever the observation.
+// weight, matches nothing.  In every variant a row counts only if its norm is finite (k_lutw_norm's verdict: with the shared
+// weights, or without weights for OBSW), whatever the observation and whichever path evaluates it.
 template <typename T, int ROWS, bool BRUTE, bool OBSW = false>
 __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
                                                     int nb, int64_t B, int64_t m_off, int64_t Mc, int k, const T* __restrict__ thr,
                                                     const int* __restrict__ cand_n, const int* __restrict__ cand, int cap,
                                                     unsigned long long* __restrict__ ctl, int* __restrict__ flag_list,
                                                     int64_t* __restrict__ out_idx, T* __restrict__ out_cost,
-                                                    const T* __restrict__ norm = nullptr) {
+                                                    const T* __restrict__ norm) {
   extern __shared__ __attribute__((aligned(16))) char lutw_smem[];
   unsigned long long* sk = reinterpret_cast<unsigned long long*>(lutw_smem);
   int* sr = reinterpret_cast<int*>(sk + LUT_TOPK_BUF);
@@ -1387,15 +1405,15 @@ __global__ __launch_bounds__(64) void k_lutw_select(const T* __restrict__ lut, c
         SPART_NO_CONTRACT
         const T* x = lut + r * nb;
         T c = T(0);
-        if constexpr (OBSW) {
-          if (!LutNum<T>::finite(norm[r])) c = (T)INFINITY;            // a rejected row: never a candidate
-          else
-            for (int j = 0; j < nb; ++j) {
-              const T wj = wsm[j];
-              if (wj == T(0)) continue;                                 // the mask: no operation at all
-              const T d = x[j] - ys[j];
-              c = c + (wj * d) * d;
-            }
+        if (!LutNum<T>::finite(norm[r])) {
+          c = (T)INFINITY;                                              // a rejected row: never a candidate
+        } else if constexpr (OBSW) {
+          for (int j = 0; j < nb; ++j) {
+            const T wj = wsm[j];
+            if (wj == T(0)) continue;                                   // the mask: no operation at all
+            const T d = x[j] - ys[j];
+            c = c + (wj * d) * d;
+          }
         } else if (w) {
           for (int j = 0; j < nb; ++j) {
             const T d = x[j] - ys[j];

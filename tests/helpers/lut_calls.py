@@ -16,6 +16,7 @@ ENTRIES = {"spart_lut_nearest": ("spart_lut", 31, "nmax"),
            "spart_lut_topk_wide": ("spart_lut_topk_wide", 2162, "nmax"),
            "spart_lut_topk_obs_weights": ("spart_lut_topk_obs_weights", 2162, "nbound")}
 FILL = -7          # what lut_call writes into idx and cost before the call: a refused call leaves it there
+GUARD = 4096       # lut_call(guard=True): bytes kept behind the workspace that the call must leave as they were
 
 
 @pytest.fixture(scope="module")
@@ -55,11 +56,14 @@ def spectra(torch_mod, hyper_si):
     return torch_mod.nan_to_num(r, nan=0.5)
 
 
-def lut_call(torch, eng, entry, lut, obs, k, w=None, dtype="float32", ws_bytes=None, null=(), **sizes):
+def lut_call(torch, eng, entry, lut, obs, k, w=None, dtype="float32", ws_bytes=None, null=(), guard=False, **sizes):
     """One LUT search through ctypes -> (rc, idx, cost, stats dict).  ``k`` None goes with spart_lut_nearest: no k argument,
     (M,) outputs, two stats.  ``ws_bytes``: the workspace size handed in, in place of the search's *_workspace_bytes;
     ``null``: which of lut / obs / w / idx / cost to pass as NULL; ``sizes``: B / nb / M / dt (the dtype code) to pass in
-    place of the tensors' own -- for the refusal cases, which return before anything is read."""
+    place of the tensors' own -- for the refusal cases, which return before anything is read.
+    ``guard``: the workspace is allocated GUARD bytes longer than *_workspace_bytes says and filled with 0xFF bytes throughout
+    (a buffer the call does not write then holds NaN patterns, not an earlier chunk's plausible values); the call is given the
+    size it asked for, and afterwards the GUARD bytes behind it must still be 0xFF."""
     family, _, scale = ENTRIES[entry]
     B, nb, M = (sizes.get(n, v) for n, v in zip(("B", "nb", "M"), (*lut.shape, obs.shape[0])))
     dt = sizes.get("dt", DT[dtype])
@@ -69,7 +73,11 @@ def lut_call(torch, eng, entry, lut, obs, k, w=None, dtype="float32", ws_bytes=N
     cost = torch.full(shape, FILL, dtype=lut.dtype, device=lut.device)
     need = int(getattr(eng.lib, family + "_workspace_bytes")(dt, B, nb, M, *kk))
     n = need if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(n, 256), dtype=torch.uint8, device=lut.device)
+    if guard:
+        assert ws_bytes is None and need > 0
+        ws = torch.full((need + GUARD,), 0xFF, dtype=torch.uint8, device=lut.device)
+    else:
+        ws = torch.empty(max(n, 256), dtype=torch.uint8, device=lut.device)
     p = {"lut": lut, "obs": obs, "w": w, "idx": idx, "cost": cost}
     p = {name: None if t is None or name in null else t.data_ptr() for name, t in p.items()}
     rc = getattr(eng.lib, entry)(eng.ctx, dt, B, nb, p["lut"], M, p["obs"], p["w"], *kk, p["idx"], p["cost"], ws.data_ptr(),
@@ -82,6 +90,9 @@ def lut_call(torch, eng, entry, lut, obs, k, w=None, dtype="float32", ws_bytes=N
         assert getattr(eng.lib, family + "_stats")(eng.ctx, dt, B, nb, M, *kk, ws.data_ptr(), *map(ctypes.byref, counts),
                                                    ctypes.byref(word)) == 0
         st = {**{name: c.value for name, c in zip(names, counts)}, scale: word.value}
+    if guard:
+        torch.cuda.synchronize()
+        assert bool((ws[need:] == 0xFF).all()), (entry, dtype, "bytes behind the workspace were written")
     return rc, idx, cost, st
 
 

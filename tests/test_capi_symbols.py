@@ -93,6 +93,29 @@ def test_lut_workspace_bytes_is_zero_exactly_for_refused_sizes(lib_path, name, n
     assert size(0, 2_000_000_000, nb_max, 1_000_000, 256) > 0 and size(1, 1, 1, 1, 1) > 0
 
 
+@pytest.mark.parametrize("dtype", [0, 1])
+@pytest.mark.parametrize("name,nb,chunk", [("spart_lut_topk", 13, 65_536), ("spart_lut_topk_wide", 211, 16_384),
+                                           ("spart_lut_topk_obs_weights", 13, 16_384), ("spart_lut_topk_obs_weights", 211, 16_384),
+                                           ("spart_lut_topk_obs_weights", 2162, None)])
+def test_lut_topk_workspace_grows_by_four_bytes_per_observation_past_the_first_chunk(lib_path, name, nb, chunk, dtype):
+    """the per-chunk buffers are sized for one chunk of observations and reused; only the list of flagged observations
+    (4 bytes each) grows with M.  So past the first chunk the size is that of exactly one chunk + 4 (M - chunk), rounded up to
+    the 256-byte alignment of the fields, and it does not shrink across the boundary."""
+    f = getattr(ctypes.CDLL(lib_path), name + "_workspace_bytes")
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
+    if chunk is None:                                  # 2162 bands: 2 x 2176 operand entries per observation within 256 MiB
+        chunk = 15_360 if dtype == 0 else 7_168
+    for k in (1, 10, 256):
+        at = f(dtype, 20_011, nb, chunk, k)
+        assert at > 0
+        sizes = [f(dtype, 20_011, nb, M, k) for M in (chunk - 1, chunk, chunk + 1, chunk + 37, 2 * chunk, 2 * chunk + 37, 10 * chunk)]
+        assert sizes == sorted(sizes), (k, sizes)
+        for extra in (1, 37, 64, 1000, chunk, chunk + 37, 9 * chunk, 1_000_000):
+            grown = f(dtype, 20_011, nb, chunk + extra, k) - at
+            assert 4 * extra <= grown < 4 * extra + 256, (k, extra, grown)
+
+
 def test_build_id_ties_the_binary_to_its_sources(lib_path, tmp_path):
     """spart_build_id() == the hash of the sources / flags next to the library (build.source_id), read both from the loaded
     code and from the file's bytes; a file without (or with another) id is detected without loading it."""

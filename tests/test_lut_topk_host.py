@@ -108,6 +108,41 @@ def test_brute_force_topk_numpy_and_torch_agree():
             assert (ni[:, 299:] == -1).all() if k > 299 else True          # row 17 (NaN) never appears: 299 rows qualify
 
 
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("nb,seed", [(13, 0), (211, 1)])
+def test_brute_forces_agree_on_hostile_magnitudes(nb, seed, dtype):
+    """the numpy and the torch (CPU) brute forces give the same index and cost, bit for bit, on the cases of
+    tests/test_gpu_lut_magnitudes.py: offsets, band scales and weights over many decades, subnormal and zero costs, one huge
+    entry, rows ruled out by their norm (row_ok) -- and each case is what it claims to be (``holds``)"""
+    from helpers import lut_hostile as H
+    bf = _bf()
+    for case in H.hostile_cases(bf, dtype, nb, seed):
+        ni, nc = H.oracle(bf, case, 10)
+        case.holds(ni, nc)
+        t = [None if a is None else torch.as_tensor(a) for a in (case.lut, case.obs, case.w, case.row_ok)]
+        f = bf.brute_force_topk_obs_weights_torch if case.per_observation else bf.brute_force_topk_torch
+        ti, tc = f(t[0], t[1], 10, t[2], row_ok=t[3])
+        assert np.array_equal(ni, ti.numpy()) and np.array_equal(nc, tc.numpy()), case.name
+        if case.row_ok is not None and case.name.startswith("huge_entry"):       # the plain brute force leaves that row out too
+            pi, pc = bf.brute_force_topk_numpy(case.lut, case.obs, 10, case.w)
+            assert np.array_equal(pi, ni) and np.array_equal(pc, nc), case.name
+        if not case.per_observation:                   # the obs-weights definition with every weight row equal: the same answer
+            W = np.ones_like(case.obs) if case.w is None else np.repeat(case.w[None, :], len(case.obs), axis=0)
+            oi, oc = bf.brute_force_topk_obs_weights_numpy(case.lut, case.obs, 10, W, row_ok=case.row_ok)
+            assert np.array_equal(oi, ni) and np.array_equal(oc, nc), case.name
+
+
+def test_norm_rule_numpy_is_the_kernels_norm():
+    """norm_rule_numpy: finite entries and a finite centred (weighted) norm, the sum taken band by band in the dtype"""
+    bf = _bf()
+    lut = np.array([[1.0, 2.0], [1e20, 0.0], [np.nan, 0.0], [1.8e19, 1.8e19], [1.0, np.inf]], dtype=np.float32)
+    assert bf.norm_rule_numpy(lut, np.zeros(2)).tolist() == [True, False, False, False, False]
+    assert bf.norm_rule_numpy(lut, np.zeros(2), w=np.array([1e-4, 1.0])).tolist() == [True, True, False, True, False]
+    assert bf.norm_rule_numpy(lut, np.zeros(2), w=np.array([-1e-4, 1e-4])).tolist() == [True, True, False, True, False]
+    assert bf.norm_rule_numpy(lut.astype(np.float64), np.zeros(2)).tolist() == [True, True, False, True, False]
+    assert bf.norm_rule_numpy(lut, np.array([-3e19, 0.0])).tolist() == [False] * 5      # a far centre rules out every row
+
+
 def _case(B, nb, M, seed):
     rng = np.random.default_rng(seed)
     lut = rng.uniform(0.0, 0.6, (B, nb)).astype(np.float32)

@@ -77,9 +77,10 @@ def _topk_from_costs_numpy(c, k):
     return idx, cost
 
 
-def brute_force_topk_numpy(lut, obs, k, w=None):
+def brute_force_topk_numpy(lut, obs, k, w=None, row_ok=None):
     """spart_lut_topk's definition: per observation the first k entries of np.argsort(c, kind="stable") after non-finite
-    costs are set to +inf (rows of a non-finite cost never appear; (-1, +inf) pads) -> (idx (M, k) int64, cost (M, k))"""
+    costs are set to +inf (rows of a non-finite cost never appear; (-1, +inf) pads) -> (idx (M, k) int64, cost (M, k)).
+    ``row_ok`` (B,) bool: the rows that count at all (norm_rule_numpy: the overflowing-norm rule); None = every row."""
     lut = np.ascontiguousarray(lut)
     dt = lut.dtype
     obs = np.ascontiguousarray(obs, dtype=dt)
@@ -96,14 +97,16 @@ def brute_force_topk_numpy(lut, obs, k, w=None):
                 d = cols[j] - obs[m, j]
                 t = d if w is None else w[j] * d
                 c = c + t * d
+            if row_ok is not None:
+                c[~np.asarray(row_ok)] = np.inf
             idx[m], cost[m] = _topk_from_costs_numpy(c, k)
     return idx, cost
 
 
-def brute_force_topk_torch(lut, obs, k, w=None, max_elems=1 << 27):
+def brute_force_topk_torch(lut, obs, k, w=None, max_elems=1 << 27, row_ok=None):
     """the same with eager torch ops (one kernel per operation: no contraction), in blocks of observations: tensors of one
     dtype on one device -> (idx (M, k) int64, cost (M, k)).  The (cost, row) order is a stable sort by cost of the rows in
-    ascending order, i.e. the lowest row first among equal costs."""
+    ascending order, i.e. the lowest row first among equal costs.  ``row_ok`` (B,) bool tensor or None, as above."""
     import torch
     B, nb = lut.shape
     M = obs.shape[0]
@@ -120,13 +123,32 @@ def brute_force_topk_torch(lut, obs, k, w=None, max_elems=1 << 27):
             d = cols[j][None, :] - o[:, j][:, None]
             t = d if w is None else w[j] * d
             c = c + t * d
-        c = torch.where(torch.isfinite(c), c, torch.full_like(c, inf))
+        fin = torch.isfinite(c) if row_ok is None else torch.isfinite(c) & row_ok[None, :]
+        c = torch.where(fin, c, torch.full_like(c, inf))
         s, order = torch.sort(c, dim=1, stable=True)
         s, order = s[:, :kk], order[:, :kk]
         ok = s < inf
         idx[m0:m0 + mb, :kk] = torch.where(ok, order, torch.full_like(order, -1))
         cost[m0:m0 + mb, :kk] = s
     return idx, cost
+
+
+def norm_rule_numpy(lut, centre, w=None):
+    """The row rule of every search (include/spart_hip.h): a row counts only if all its entries are finite and its centred
+    norm  n = 0; for j ascending: xc = lut[b, j] - centre[j]; n = n + (|w_j| * xc) * xc  is finite in the LUT's dtype.  The
+    verdict depends on the centres only for entries near the square root of the largest finite number; ``centre`` (nb,) is
+    the caller's stand-in for the device's column centres (any value between a column's moderate entries gives the same
+    verdict on a LUT whose other entries are moderate).  The obs-weights search applies it without weights (w = None).
+    -> row_ok (B,) bool, the ``row_ok`` argument of the brute forces below."""
+    lut = np.ascontiguousarray(lut)
+    dt = lut.dtype
+    centre = np.asarray(centre, dtype=dt)
+    n = np.zeros(lut.shape[0], dtype=dt)
+    with np.errstate(all="ignore"):
+        for j in range(lut.shape[1]):
+            xc = lut[:, j] - centre[j]
+            n = n + ((xc if w is None else abs(dt.type(w[j])) * xc) * xc)
+    return np.isfinite(lut).all(axis=1) & np.isfinite(n)
 
 
 def _obs_weights_checks(lut, obs, w):
@@ -137,12 +159,13 @@ def _obs_weights_checks(lut, obs, w):
     return row_ok, obs_ok
 
 
-def brute_force_topk_obs_weights_numpy(lut, obs, k, w):
+def brute_force_topk_obs_weights_numpy(lut, obs, k, w, row_ok=None):
     """spart_lut_topk_obs_weights' definition, literally: per observation m
         c = 0;  for j: if w[m, j] == 0: skip;  d = lut[:, j] - obs[m, j];  c = c + (w[m, j] * d) * d
     then the first k of the stable argsort (non-finite costs as +inf), padded with (-1, +inf).  lut (B, nb), obs and w (M, nb)
-    of one float dtype -> (idx (M, k) int64, cost (M, k)).  The rule on rows whose centred norm overflows depends on the
-    device's column centres and is not modelled: keep test LUTs far from overflow."""
+    of one float dtype -> (idx (M, k) int64, cost (M, k)).  ``row_ok`` (B,) bool: the rows whose UNWEIGHTED centred norm is
+    finite (norm_rule_numpy(lut, centre)): the search's row rule, which does not depend on the observation; it is applied on
+    top of the finite-entries rule.  None = no norm near overflow."""
     lut = np.ascontiguousarray(lut)
     dt = lut.dtype
     obs = np.ascontiguousarray(obs, dtype=dt)
@@ -151,7 +174,8 @@ def brute_force_topk_obs_weights_numpy(lut, obs, k, w):
     M = obs.shape[0]
     idx = np.full((M, k), -1, dtype=np.int64)
     cost = np.full((M, k), np.inf, dtype=dt)
-    row_ok, obs_ok = _obs_weights_checks(lut, obs, w)
+    fin_ok, obs_ok = _obs_weights_checks(lut, obs, w)
+    row_ok = fin_ok if row_ok is None else fin_ok & np.asarray(row_ok)
     cols = [np.ascontiguousarray(lut[:, j]) for j in range(nb)]
     with np.errstate(all="ignore"):
         for m in range(M):
@@ -168,7 +192,7 @@ def brute_force_topk_obs_weights_numpy(lut, obs, k, w):
     return idx, cost
 
 
-def brute_force_topk_obs_weights_torch(lut, obs, k, w, max_elems=1 << 27):
+def brute_force_topk_obs_weights_torch(lut, obs, k, w, max_elems=1 << 27, row_ok=None):
     """the same with eager torch ops, in blocks of observations; a masked band keeps the running cost as it is
     (torch.where), which is the skip.  Tensors of one dtype on one device -> (idx (M, k) int64, cost (M, k))"""
     import torch
@@ -176,7 +200,7 @@ def brute_force_topk_obs_weights_torch(lut, obs, k, w, max_elems=1 << 27):
     M = obs.shape[0]
     inf = float("inf")
     cols = [lut[:, j].contiguous() for j in range(nb)]
-    row_ok = torch.isfinite(lut).all(dim=1)
+    row_ok = torch.isfinite(lut).all(dim=1) if row_ok is None else torch.isfinite(lut).all(dim=1) & row_ok
     obs_ok = ((w >= 0) & torch.isfinite(w) & ((w == 0) | torch.isfinite(obs))).all(dim=1)
     idx = torch.full((M, k), -1, dtype=torch.int64, device=lut.device)
     cost = torch.full((M, k), inf, dtype=lut.dtype, device=lut.device)
