@@ -303,7 +303,8 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
   // and land in LDS after it, so a workgroup meets ONE barrier per 32 samples and never waits for memory on its critical
   // path (single buffer: barrier, load, wait, barrier).  Five more VGPRs per lane (float32) while the loop runs.
   constexpr bool PINGPONG = sizeof(T) == 4 && MAT == 0;
-  __shared__ __attribute__((aligned(16))) T lds_all[(PINGPONG ? 2 : 1) * SUB * NCONST];
+  // (PINGPONG: one sample's worth of padding, see AHEAD below -- the look-ahead read of a stage's last sample stays inside)
+  __shared__ __attribute__((aligned(16))) T lds_all[(PINGPONG ? 2 : 1) * SUB * NCONST + (PINGPONG ? NCONST : 0)];
   T stg[NCONST * SUB / TILE];
   int cur = 0;
   if (PINGPONG) {
@@ -340,6 +341,18 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
   // prefetch every iteration starts by waiting for its own LDS reads).  Not in the materialising variants: there the
   // nine registers cost a wave of occupancy (109 VGPRs).
   constexpr bool AHEAD = MAT == 0 && sizeof(T) == 4;   // (float64: the 18 registers are missed elsewhere, +0.4 %)
+  static_assert(AHEAD == PINGPONG, "the look-ahead read relies on the padding of lds_all");
+  // AHEAD: the sample's LDS address lives in ONE VGPR that advances by a sample per iteration, and every read -- the next
+  // sample's leaf constants included -- is an immediate offset from it.  A wave-uniform address would sit in an SGPR and be
+  // copied into a VGPR in front of every group of reads (three v_mov per sample, plus the scalar clamp of the look-ahead
+  // index).  `lane0` is a zero the compiler cannot see through (a multiple of four, so that the 16-byte alignment of the
+  // reads stays provable).  The look-ahead of a stage's last sample reads the slot behind it (the other buffer's first
+  // sample or the padding); those nine values are dropped when the next stage reloads lc[].
+  int lane0 = 0;
+  if (AHEAD) {
+    SPART_KEEP_BRANCH(lane0);
+    lane0 &= ~3;
+  }
   T lc[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) lc[i] = lds_c[i];
@@ -358,11 +371,22 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
     common = __all(cl[C_FILM2L] == lds_c[C_FILM2L] && cl[C_CBC] == T(0) && cl[C_PROT] == T(0)) != 0;   // (NaN: general body)
     if (common) tw1c = soil_tw1<T>(tb, lds_c[C_FILM2L]);
   }
+  // One more fact of a sample that every band shares is voted on once per stage (lane l: sample l) and reaches the sample
+  // loop as a scalar bit: whether a J2 of SAILH can take its Taylor side at all (sail_j2_possible).  If not, the two
+  // products, compares and branches around it are skipped.  The bit only skips work whose outcome it already proves: a
+  // sample's numbers do not depend on its stage mates.
+  constexpr bool VOTES = sizeof(T) == 4 && MAT == 0;
+  unsigned long long j2_mask = ~0ull;
+  if constexpr (VOTES) {
+    const int l = threadIdx.x & 63;
+    const T* cl = lds_c + (l < nsub ? l : 0) * NCONST;
+    j2_mask = __ballot(sail_j2_possible(cl[C_KSL], cl[C_LAI]) || sail_j2_possible(cl[C_KOL], cl[C_LAI]));
+  }
   auto sample_loop = [&](auto common_tag) __attribute__((always_inline)) {
   constexpr bool FAST = decltype(common_tag)::value;
   for (int si = 0; si < nsub; ++si) {
     const int64_t s = sb + si;
-    const T* c = lds_c + si * NCONST;                  // uniform LDS address -> broadcast ds_read into VGPRs
+    const T* c = lds_c + si * NCONST + lane0;          // the same LDS address in every lane -> broadcast ds_read into VGPRs
     T refl, tran, absb, K;
     static_assert(C_CAB == 0 && C_NM1 == 8, "lc[] = constants 0..8 in leaf_band's argument order");
     if (!AHEAD) {
@@ -371,7 +395,7 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
     }
     leaf_band<T, !FAST>(tb, lc[0], lc[1], lc[2], lc[3], lc[4], lc[5], lc[6], lc[7], lc[8], refl, tran, absb, K);
     if (AHEAD) {
-      const T* cn = lds_c + ((si + 1 < nsub) ? si + 1 : si) * NCONST;   // next sample's leaf constants, in flight early
+      const T* cn = c + NCONST;                        // next sample's leaf constants, in flight early
 #pragma unroll
       for (int i = 0; i < 9; ++i) lc[i] = cn[i];
     }
@@ -391,18 +415,14 @@ void k_bands(const T* __restrict__ tab, const T* __restrict__ cst, int64_t Bp, i
     // order: leaf -> canopy solve for the leaf alone -> soil -> coupling with the soil background.  The soil model
     // sits between the two canopy parts because that schedule measured fastest (interleaved A/B of four orders).
     const CanopyPar<T> cp = load_canopy<T>(c);
-    const CanopyCore<T> core = canopy_core_l<T>(cp, rho, tau, ab, c[C_KSL], c[C_KOL]);
+    const CanopyCore<T> core = canopy_core_l<T>(cp, rho, tau, ab, c[C_KSL], c[C_KOL], !VOTES || ((j2_mask >> si) & 1) != 0);
     T rdry = (MAT == 2) ? mat.rdry_in[s * mat.po + ti] : soil_dry<T>(tb, c[C_F1], c[C_F2], c[C_F3]);
     T fm[7] = {c[C_FM0], c[C_FM1], c[C_FM2], c[C_FM3], c[C_FM4], c[C_FM5], c[C_FM6]};
-    T rwet;
-    if (FAST) {
-      soil_band_tw<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1c, rwet);
-    } else if (HOIST_FILM) {
-      const T tw1 = film_same ? tw1s : soil_tw1<T>(tb, c[C_FILM2L]);      // (wave-uniform choice)
-      soil_band_tw<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1, rwet);
-    } else {
-      soil_band<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], c[C_FILM2L], rwet);
-    }
+    T rwet, tw1;
+    if (FAST) tw1 = tw1c;
+    else if (HOIST_FILM && film_same) tw1 = tw1s;                          // (wave-uniform choice)
+    else tw1 = soil_tw1<T>(tb, c[C_FILM2L]);
+    soil_band_tw<T>(tb, rdry, c[C_WET], fm, c[C_FMSUM], tw1, rwet);
     if (MAT && active) {
       if (mat.soil_refl) store_row<NT>(mat.soil_refl, off_f, rwet);
       if (!thermal && mat.soil_dry) store_row<NT>(mat.soil_dry, off_o, rdry);

@@ -439,15 +439,26 @@ template <typename T> SPART_HD T sail_j1_a(T L, T tk, T e1, T d, T ia) {
 }
 // J2 = (1 - tk e1)/(k + m), kpm = k + m > 0, ikpm = 1/kpm; (k + m) L < THRESH selects L phi((k + m) L) -- rare, and
 // the Taylor side is only issued when some lane of the wave needs it
-template <typename T> SPART_HD T sail_j2_d(T L, T tk, T e1, T kpm, T ikpm) {
-  T d = kpm * L;
+// maybe_small = false is the caller's proof that no band of this sample has (k + m) L < THRESH (sail_j2_possible); the
+// product, the test and the branch are then not issued.  It never changes a value: where it is false the test fails anyway.
+template <typename T> SPART_HD T sail_j2_d(T L, T tk, T e1, T kpm, T ikpm, bool maybe_small = true) {
   T v = (T(1) - tk * e1) * ikpm;
-  if (SPART_WAVE_ANY(d < SailJ<T>::THRESH)) {
-    SPART_KEEP_BRANCH(d);
-    v = (d < SailJ<T>::THRESH) ? L * SailJ<T>::poly(d) : v;
+  if (maybe_small) {
+    T d = kpm * L;
+    if (SPART_WAVE_ANY(d < SailJ<T>::THRESH)) {
+      SPART_KEEP_BRANCH(d);
+      v = (d < SailJ<T>::THRESH) ? L * SailJ<T>::poly(d) : v;
+    }
   }
   return v;
 }
+// Can (k + m) L < THRESH hold in some band of a sample whose constant rows hold kl = k L and L?  With m >= 0 and L > 0,
+// fl(fl(k + m) L) >= fl(k L) (rounding is monotone), so it cannot once k L clears the threshold.  kl is the prelude's
+// float64 product rounded to T, not the kernel's own product of the rounded factors (a few ulp apart): the test leaves a
+// guard band above THRESH (float32, the only caller: 0.07 against 0.06).  Anything else -- L <= 0, a NaN in either --
+// answers yes.
+constexpr float SAIL_J2_GUARD_F32 = 0.07f;
+SPART_HD bool sail_j2_possible(float kl, float L) { return !(kl >= SAIL_J2_GUARD_F32) || !(L > 0.0f); }
 
 // ------------------------------------------------------------------------------------------
 // tau(K) = (1-K) exp(-K) + K^2 E1(K) = 2 E3(K)           (prospect_5d.py:183-196)
@@ -698,6 +709,14 @@ SPART_HD void leaf_band(const BandTab<T>& tb, T cab, T cca, T cdm, T cw, T cs, T
 // the film thickness only, so a kernel may evaluate it once for a run of samples that share the film thickness
 template <typename T> SPART_HD T soil_tw1(const BandTab<T>& tb, T film2l) { return Mx<T>::exp2(-film2l * tb.kw); }
 
+// float32: p tw1^k, k = 1..6 -- the part of the film series' y_k = p tw1^k rbac that depends on the band and the film only.
+// In a sample loop whose tw1 is fixed (the common-case body of k_bands) the compiler forms the six once per stage.
+SPART_HD void soil_film_powers(float pw, float tw1, float ptw[6]) {
+  ptw[0] = pw * tw1;
+#pragma unroll
+  for (int k = 1; k < 6; ++k) ptw[k] = ptw[k - 1] * tw1;
+}
+
 template <typename T>
 SPART_HD void soil_band_tw(const BandTab<T>& tb, T rdry, T wet, const T fm[7], T fmsum16, T tw1, T& rwet) {
   if constexpr (sizeof(T) == 4) {
@@ -705,20 +724,21 @@ SPART_HD void soil_band_tw(const BandTab<T>& tb, T rdry, T wet, const T fm[7], T
     // constants).  With y_k = p x_k and d_k = 1 - y_k, x_k / d_k = (1 / d_k - 1) / p, so
     //   sum_k f_k x_k / d_k = (sum_k f_k / d_k - F) / p,   F = sum_{k>=1} f_k = fmsum16,
     // and sum_k f_k / d_k is ONE fraction N / D built up term by term (N <- N d_k + f_k D, D <- D d_k: every term and
-    // factor is positive, 0 < d_k <= 1) -- 5 instructions per term and one reciprocal; (1 - Rw)(1 - p) / p is a band
+    // factor is positive, 0 < d_k <= 1) -- 4 instructions per term (5 where p tw1^k is not hoisted) and one reciprocal; (1 - Rw)(1 - p) / p is a band
     // constant.  N / D - F cancels where p x_k is small, but there the whole film term is small next to Rw F:
     // the absolute error is a few ulp of F (tests/test_f32_forms.py bounds it over all bands).
     const T cb = T(1) - tb.cbac;
     const T c2 = (T(1) - tb.rw) * (T(1) - tb.pw) * Mx<T>::rcp(tb.pw);
     T rbac = rdry * (cb * (T(1) - rdry) + T(1));                  // :110-112
-    T y = rbac * (tb.pw * tw1);
-    T D = T(1) - y;
+    T ptw[6];
+    soil_film_powers(tb.pw, tw1, ptw);
+    T D = __builtin_fmaf(-rbac, ptw[0], T(1));                    // d_k = 1 - rbac p tw1^k: one FMA per term
     T N = fm[1];
 #pragma unroll
     for (int k = 1; k < 6; ++k) {
-      y *= tw1;
-      const T d = T(1) - y;
-      N = N * d + fm[k + 1] * D;
+      const T d = __builtin_fmaf(-rbac, ptw[k], T(1));
+      N = __builtin_fmaf(fm[k + 1], D, N * d);                    // (spelled out: left to the compiler, which of the two products
+                                                                  //  of N d + f D is fused differed between the two bodies of k_bands)
       D *= d;
     }
     T v = rdry * fm[0] + tb.rw * fmsum16 + c2 * (N * Mx<T>::rcp(D) - fmsum16);
@@ -775,8 +795,10 @@ template <typename T> struct CanopyCore {
 
 // ksl = ks LAI, kol = ko LAI (constant rows C_KSL / C_KOL in the band kernels): float32 forms (m - k) L as m L - k L,
 // one FMA each; float64 keeps (m - k) L and does not read them
+// j2_possible = false: the caller has shown that neither J2 can take its Taylor side in any band of this sample
+// (sail_j2_possible of ksl and of kol); see sail_j2_d
 template <typename T>
-SPART_HD CanopyCore<T> canopy_core_l(const CanopyPar<T>& c, T rho, T tau, T absb, T ksl, T kol) {
+SPART_HD CanopyCore<T> canopy_core_l(const CanopyPar<T>& c, T rho, T tau, T absb, T ksl, T kol, bool j2_possible = true) {
   // scattering coefficients (:142-148).  With sdb/sdf = (k +- bf)/2, ddb/ddf = (1 +- bf)/2, dob/dof = (K +- bf)/2
   // (:100-105) they are P, k P, K P plus/minus Mn, where P = (rho + tau)/2 and Mn = bf (rho - tau)/2:
   //   sigb = P + Mn, sigf = P - Mn, sb/sf = k P +- Mn, vb/vf = K P +- Mn
@@ -826,8 +848,8 @@ SPART_HD CanopyCore<T> canopy_core_l(const CanopyPar<T>& c, T rho, T tau, T absb
     J1k = sail_j1_d<T>(L, c.tss, e1, d1, idd * d2s);
     J1K = sail_j1_d<T>(L, c.too, e1, d2, idd * d1s);
   }
-  T J2k = sail_j2_d<T>(L, c.tss, e1, ksm, iks);
-  T J2K = sail_j2_d<T>(L, c.too, e1, kom, iko);
+  T J2k = sail_j2_d<T>(L, c.tss, e1, ksm, iks, j2_possible);
+  T J2K = sail_j2_d<T>(L, c.too, e1, kom, iko, j2_possible);
   T ome2 = T(1) - e1 * e1;
   T re = rinf * e1;
   T i1 = Mx<T>::rcp(omr2 * (T(1) + rinf2));  // sic: 1/(1 - rinf2**2) (:189)
