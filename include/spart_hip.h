@@ -60,8 +60,9 @@ extern "C" {
  *   8: spart_lut_topk, spart_lut_topk_workspace_bytes, spart_lut_topk_stats
  *   9: spart_lut_topk_wide, spart_lut_topk_wide_workspace_bytes, spart_lut_topk_wide_stats; sensors of up to SPART_NWLS bands
  *  10: spart_lut_topk_obs_weights, spart_lut_topk_obs_weights_workspace_bytes, spart_lut_topk_obs_weights_stats
- *  11: spart_lut_summarise */
-#define SPART_ABI_VERSION 11
+ *  11: spart_lut_summarise
+ *  12: spart_srf_support; spart_materialize.R_TOC_srf ... rdd_srf */
+#define SPART_ABI_VERSION 12
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -147,6 +148,33 @@ typedef struct spart_materialize {
   int32_t nlayers;             /* canopy.nlayers (sailh.py:48): 0 = the default 60.  It enters the model only as dx = 1 / nlayers,
                                   the width of the stretch below the canopy that Pso[nlayers] averages (:131-135, 219); one value
                                   per call.  1 ... SPART_MAX_NLAYERS */
+  /* SRF-convolved sensor columns, (B,nb) in `dtype`, each optional.  R_TOC / R_TOA / L_TOA above sample the canopy at the
+     np.interp support of the band CENTRE (SPART.py:219-223); a real band integrates its spectral response function.  These
+     seven apply the reference's own convolution, calculate_spectral_convolution (SPART.py:358-396), to the four canopy
+     spectra on the model grid wlS -- 2162 points: 400..2400 nm by 1, 2500..15000 by 100, 16000..50000 by 1000 -- with the
+     context's wl_srf / p_srf (the tables k_econv already convolves the irradiance with):
+       idx[i,j] = the grid point nearest to wl_srf[i,j] in exact arithmetic; ties to the lower index (2450 nm -> index 2000);
+                  NaN -> 0.  This is the reference's np.argmin(np.abs(wlS - w)) for every |w| < 1e15; beyond that the
+                  reference's float64 subtraction no longer tells the grid points apart and it returns 0, where this library
+                  keeps the nearest point (index 0 for a huge negative w, as the reference; the last one for a huge positive
+                  w).  The packaged tables hold such wavelengths only with weights <= 7e-310, and one of them is positive:
+                  Sentinel-2B band 4 has a sample at +9.1e306 nm, which goes to the thermal evaluation here and to index 0
+                  in the reference, so that band's support has one entry more (963 in all, where the literal argmin
+                  gives 962).
+       ev = min(idx, 2001): the 161 thermal pad bands are the one thermal evaluation, as everywhere in this library.
+       For band j: E_j = the ascending list of distinct ev; q_e = the sum of p_srf[i,j] over the samples that map to e and
+       Q_j = sum_i p_srf[i,j], both summed in float64 in i order on the host (spart_srf_support).  Weights are used as given
+       (negative ones included); zero-weight entries stay, so a NaN spectrum value propagates; a Q_j of 0 or non-finite
+       propagates as the reference's division does.
+       x_srf[s,j] = (sum over e in E_j, ascending, of q_e x[s,e]) / Q_j        for x = rso, rdo, rsd, rdd, all float64
+     (fused multiply-adds, one accumulator per value: ONE order of summation whatever the batch).  SMAC and TOC -> TOA
+     (SPART.py:243-252) then run on these four values in place of the interpolated ones, and L_TOA_srf = La R_TOA_srf with
+     the La of the `La` member.  The outputs are the float64 column path rounded once to `dtype` in every mode (pruned or
+     not, f32_bands, lidf_in, nlayers, rdry_in); with f32_columns they are refused (SPART_ERR_INVALID).  With all seven NULL
+     nothing is launched for them.  The library does what the tables say: whether a band's SRF column belongs to its
+     centre and SMAC coefficients is the caller's business (spart_amd.check_srf / align_srf). */
+  void *R_TOC_srf, *R_TOA_srf, *L_TOA_srf;
+  void *rso_srf, *rdo_srf, *rsd_srf, *rdd_srf;
 } spart_materialize;
 
 int spart_ctx_create(spart_ctx **out, int device, const spart_tables *tables);
@@ -175,6 +203,13 @@ int spart_ctx_set_row_pitch(spart_ctx *ctx, int64_t pitch_full, int64_t pitch_op
  * the library derives its interface tables from in spart_ctx_create, exported so that the
  * Python mirror of the reference function runs the same arithmetic. */
 int spart_calculate_tav(double alpha_deg, const double *nr, int64_t n, double *out);
+
+/* The compressed SRF support behind spart_materialize's *_srf outputs (defined there).  HOST function on host pointers, no
+ * context and no GPU: the routine spart_ctx_create itself calls.  wl_srf, p_srf: (nsrf, nb) row-major as in spart_tables.
+ * start (nb + 1): band j owns entries start[j] ... start[j + 1] - 1; ev / q (start[nb]): E_j ascending and the q_e; Q (nb).
+ * With ev = q = NULL only start is filled (the size query; Q is not touched).  Every band has at least one entry. */
+int spart_srf_support(const double *wl_srf, const double *p_srf, int32_t nsrf, int32_t nb, int32_t *start, int32_t *ev,
+                      double *q, double *Q);
 
 /* Bytes of scratch the batched entry points need for B samples (the prelude's per-sample constants, ~0.9 KB per
  * sample, + the band sums of the full-band kernel).  The same buffer may be reused by successive calls

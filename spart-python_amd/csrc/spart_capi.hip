@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -48,6 +49,12 @@ struct spart_ctx {
   double* frac = nullptr;    // (nb)
   double* coef = nullptr;    // (48, nb)
   double* econv = nullptr;   // (nb)
+  // compressed SRF support of every band (spart_srf_support) and the deal of the bands to k_columns_srf's waves
+  int* srf_start = nullptr;  // (nb + 1)
+  int* srf_ev = nullptr;     // (srf_start[nb]) evaluation indices, ascending within a band
+  double* srf_q = nullptr;   // (srf_start[nb]) summed weight of each
+  double* srf_Q = nullptr;   // (nb) sum of the band's weights
+  int* srf_deal = nullptr;   // (nb rounded up to a multiple of COL_WAVES): srf_deal()
   std::vector<double> econv_host;
   // Everything below is mutable per-call state, guarded by `mu`: an entry point holds it while it checks the workspace
   // and issues its launches (microseconds; the GPU work itself stays asynchronous), so calls on ONE context may come from
@@ -342,6 +349,11 @@ hipError_t launch_bands(bool nt, dim3 grid, hipStream_t st, const T* tab, const 
 
 }  // namespace
 
+// any of the seven SRF-convolved (B, nb) outputs is asked for
+static bool wants_srf(const spart_materialize* opt) {
+  return opt && (opt->R_TOC_srf || opt->R_TOA_srf || opt->L_TOA_srf || opt->rso_srf || opt->rdo_srf || opt->rsd_srf || opt->rdd_srf);
+}
+
 // T = dtype of the full-band kernel (band sums, materialised spectra); TG = dtype of the column path: the prelude's
 // constants and the canopy model inside the column kernel (double, except spart_materialize.f32_columns); TO = dtype
 // of the (B, nb) outputs.  <double,double,double> = float64 mode; <float,double,float> = the default float32 mode;
@@ -376,6 +388,7 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
   }
   if ((mat || mp.rdry_in) && !chunk_fits_32bit(ws.chunk, ctx->pf, sizeof(T)))
     return fail(SPART_ERR_INVALID, "batch too large for materialised spectra in one call (chunk %d rows x pitch %d)", ws.chunk, ctx->pf);
+  const bool srf = wants_srf(opt);               // (refused with f32_columns by spart_run_batch)
   const bool full = !(opt && opt->prune_unused_bands);
   if (opt && opt->band_mean && !full)
     return fail(SPART_ERR_INVALID, "spart_run_batch: band_mean needs prune_unused_bands = 0");
@@ -411,6 +424,18 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
                        (const TO*)(opt ? opt->rdry_in : nullptr), ctx->po, B, (TO*)R_TOC,
                        (TO*)R_TOA, (TO*)L_TOA, (TO*)(opt ? opt->rsoil : nullptr), (TO*)(opt ? opt->La : nullptr));
     HIP_TRY(hipGetLastError());
+    // the SRF-convolved columns: the same stream, behind k_columns (whose constants and atmosphere rows it re-reads)
+    if constexpr (sizeof(TG) == 8) {
+      if (srf) {
+        hipLaunchKernelGGL((k_columns_srf<TO, TO>), dim3((unsigned)((B + 63) / 64), (unsigned)((ctx->nb + COL_WAVES - 1) / COL_WAVES)),
+                           dim3(64 * COL_WAVES), 0, s2, (const double*)ctx->tabD, (const double*)cstD, (const double*)atm, Bp, (const int*)ctx->srf_deal,
+                           (const int*)ctx->srf_start, (const int*)ctx->srf_ev, (const double*)ctx->srf_q,
+                           (const double*)ctx->srf_Q, (const double*)ctx->coef, (const double*)ctx->econv, ctx->nb,
+                           (const TO*)opt->rdry_in, ctx->po, B, (TO*)opt->R_TOC_srf, (TO*)opt->R_TOA_srf, (TO*)opt->L_TOA_srf,
+                           (TO*)opt->rso_srf, (TO*)opt->rdo_srf, (TO*)opt->rsd_srf, (TO*)opt->rdd_srf);
+        HIP_TRY(hipGetLastError());
+      }
+    }
     if (prof) HIP_TRY(hipEventRecord(ev[3], s2));
     return SPART_OK;
   };
@@ -981,6 +1006,35 @@ static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t 
   return SPART_OK;
 }
 
+// ---- SRF support (include/spart_hip.h: spart_srf_support)
+// The grid point of wlS (400..2400 by 1, 2500..15000 by 100, 16000..50000 by 1000) nearest to w in exact arithmetic: ties to
+// the lower index, NaN -> 0.  With g[i] <= w <= g[i + 1] <= 2 g[i] both differences below are exact (Sterbenz), so the
+// comparison is the exact one.
+static int srf_grid_index(double w) {
+  static const std::vector<double> g = [] {
+    std::vector<double> v;
+    for (int i = 0; i < NWL; ++i) v.push_back(400.0 + i);
+    for (int i = 0; i <= 125; ++i) v.push_back(2500.0 + 100.0 * i);
+    for (int i = 0; i <= 34; ++i) v.push_back(16000.0 + 1000.0 * i);
+    return v;
+  }();
+  static_assert(NWL + 126 + 35 == NWLS, "the model grid");
+  if (!(w > g.front())) return 0;                       // (NaN included)
+  if (w >= g.back()) return NWLS - 1;
+  const int i = (int)(std::upper_bound(g.begin(), g.end(), w) - g.begin()) - 1;      // g[i] <= w < g[i + 1]
+  return (g[i + 1] - w) < (w - g[i]) ? i + 1 : i;
+}
+
+// Bands to the waves of k_columns_srf: sorted by support size, longest first (ties: the lower band), in groups of COL_WAVES;
+// deal[COL_WAVES g + w] = the band of wave w of group g, the last group padded with -1.
+static std::vector<int> srf_deal(const std::vector<int>& start, int nb) {
+  std::vector<int> deal(nb);
+  for (int j = 0; j < nb; ++j) deal[j] = j;
+  std::stable_sort(deal.begin(), deal.end(), [&](int a, int b) { return start[a + 1] - start[a] > start[b + 1] - start[b]; });
+  deal.resize((size_t)(nb + COL_WAVES - 1) / COL_WAVES * COL_WAVES, -1);
+  return deal;
+}
+
 #ifndef SPART_BUILD_ID
 #define SPART_BUILD_ID "unidentified"     // built outside spart-python_amd/build.py
 #endif
@@ -1022,6 +1076,8 @@ int spart_ctx_destroy(spart_ctx* ctx) {
   (void)hipFree(ctx->tabF); (void)hipFree(ctx->tabD); (void)hipFree(ctx->Ea);
   (void)hipFree(ctx->band0); (void)hipFree(ctx->band1); (void)hipFree(ctx->frac); (void)hipFree(ctx->coef);
   (void)hipFree(ctx->econv);
+  (void)hipFree(ctx->srf_start); (void)hipFree(ctx->srf_ev); (void)hipFree(ctx->srf_q); (void)hipFree(ctx->srf_Q);
+  (void)hipFree(ctx->srf_deal);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   for (SideLane& l : ctx->lanes) {
     (void)hipEventDestroy(l.fork);
@@ -1098,6 +1154,15 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
         (rc = upload(&ctx->coef, coef)) || (rc = upload(&ctx->econv, ec)) || (rc = upload(&own.d_w, wsrf)) ||
         (rc = upload(&own.d_p, psrf)))
       return rc;
+    // compressed SRF support of the bands, for k_columns_srf
+    std::vector<int> sst(t->nb + 1);
+    if ((rc = spart_srf_support(t->wl_srf, t->p_srf, t->nsrf, t->nb, sst.data(), nullptr, nullptr, nullptr))) return rc;
+    std::vector<int> sev(sst[t->nb]);
+    std::vector<double> sq(sst[t->nb]), sQ(t->nb);
+    if ((rc = spart_srf_support(t->wl_srf, t->p_srf, t->nsrf, t->nb, sst.data(), sev.data(), sq.data(), sQ.data()))) return rc;
+    if ((rc = upload(&ctx->srf_start, sst)) || (rc = upload(&ctx->srf_ev, sev)) || (rc = upload(&ctx->srf_q, sq)) ||
+        (rc = upload(&ctx->srf_Q, sQ)) || (rc = upload(&ctx->srf_deal, srf_deal(sst, t->nb))))
+      return rc;
     // SRF convolution of the ET irradiance: one wave per sensor band (SPART.py:358-396)
     hipLaunchKernelGGL(k_econv, dim3(t->nb), dim3(64), 0, 0, ctx->Ea, own.d_w, own.d_p, t->nsrf, t->nb, ctx->econv);
     hipError_t e = hipGetLastError();
@@ -1170,6 +1235,37 @@ int spart_profile_read(spart_ctx* ctx, double* total_ms, int* ncalls) {
 int spart_calculate_tav(double alpha_deg, const double* nr, int64_t n, double* out) {
   if (!nr || !out || n < 0) return fail(SPART_ERR_INVALID, "spart_calculate_tav: null pointer or negative length");
   for (int64_t i = 0; i < n; ++i) out[i] = calculate_tav(alpha_deg, nr[i]);
+  return SPART_OK;
+}
+
+int spart_srf_support(const double* wl_srf, const double* p_srf, int32_t nsrf, int32_t nb, int32_t* start, int32_t* ev,
+                      double* q, double* Q) {
+  if (!wl_srf || !p_srf || !start || nsrf <= 0 || nb <= 0 || (ev == nullptr) != (q == nullptr))
+    return fail(SPART_ERR_INVALID, "spart_srf_support: null pointer, a size <= 0, or only one of ev / q given");
+  std::vector<double> acc(NEVAL);
+  std::vector<char> seen(NEVAL);
+  int32_t n = 0;
+  for (int32_t j = 0; j < nb; ++j) {
+    std::fill(acc.begin(), acc.end(), 0.0);
+    std::fill(seen.begin(), seen.end(), 0);
+    double tot = 0.0;
+    for (int32_t i = 0; i < nsrf; ++i) {
+      const double p = p_srf[(size_t)i * nb + j];
+      const int g = srf_grid_index(wl_srf[(size_t)i * nb + j]);
+      const int e = g < NWL ? g : NWL;                  // the 161 thermal pad bands are ONE evaluation
+      acc[e] += p;
+      seen[e] = 1;
+      tot += p;
+    }
+    start[j] = n;
+    for (int e = 0; e < NEVAL; ++e) {
+      if (!seen[e]) continue;
+      if (ev) { ev[n] = e; q[n] = acc[e]; }
+      ++n;
+    }
+    if (Q && ev) Q[j] = tot;
+  }
+  start[nb] = n;
   return SPART_OK;
 }
 
@@ -1300,6 +1396,8 @@ int spart_run_batch(spart_ctx* ctx, int dtype, int64_t B, const double* const pa
     // float64 columns (identical to the float64 mode's) over a float32 full-band pass: nothing the float32 kernel
     // would have to write in float64 may be requested
     return fail(SPART_ERR_INVALID, "%s: f32_bands goes with the sensor columns (and rsoil / La) only", who);
+  if (wants_srf(opt) && opt->f32_columns)
+    return fail(SPART_ERR_INVALID, "%s: the SRF-convolved outputs come from the float64 column path; they do not go with f32_columns", who);
   return guarded(ctx, who, workspace, ws.total, stream, [&](hipStream_t st) {
     char* wsp = (char*)workspace;
     if (dtype == SPART_F64 && opt && opt->f32_bands)

@@ -608,6 +608,101 @@ __global__ __launch_bounds__(64 * COL_WAVES, COLUMNS_SIMD_WAVES) void k_columns(
   }
 }
 
+// K3s: THE SRF COLUMN KERNEL.  k_columns samples the canopy at the band centre; a real band integrates its spectral
+// response function.  For sensor band j this kernel evaluates the canopy model at every evaluation index of the band's
+// compressed SRF support E_j (spart_srf_support: the distinct model evaluations the band's SRF samples map to, ascending,
+// with the summed weight q_e of each) and forms, per sample and for x in rso, rdo, rsd, rdd,
+//     x_srf = (sum over e in E_j, ascending, of q_e x[e]) / Q_j
+// -- calculate_spectral_convolution (SPART.py:358-396) applied to the canopy spectra on wlS -- then runs SMAC and
+// TOC -> TOA (SPART.py:243-252) with these four values in place of the interpolated ones.  Always float64 arithmetic.
+// Mapping: k_columns' -- 64 samples per workgroup, lane = sample, constants and atmosphere scalars in LDS -- so the band
+// and the (ev, q) entry in flight are wave-uniform: tables and weights arrive by scalar loads, the four accumulators
+// stay in the lane (four FMAs per entry, no cross-lane reduction), and a band's sum has ONE order whatever the batch.
+// Dealing: a wave owns ONE band of one 64-sample block -- grid.y walks groups of COL_WAVES bands, deal[4 g + w] = the band
+// of wave w in group g (-1: none).  Supports range from a dozen to 319 entries, so the host sorts the bands by support
+// size, longest first (srf_deal): the waves of a workgroup finish together, and the long groups are dispatched first.
+// With the band loop outside the kernel the SMAC tail follows the entry loop instead of enclosing it: as an enclosing loop
+// it had its three dozen exp / log literals hoisted across the entry loop and spilled.
+template <typename TO, typename TR>
+__global__ __launch_bounds__(64 * COL_WAVES, COLUMNS_SIMD_WAVES) void k_columns_srf(
+    const double* __restrict__ tab, const double* __restrict__ cst, const double* __restrict__ atm, int64_t Bp,
+    const int* __restrict__ deal, const int* __restrict__ sup_start, const int* __restrict__ sup_ev,
+    const double* __restrict__ sup_q, const double* __restrict__ sup_Q, const double* __restrict__ coef,
+    const double* __restrict__ econv, int nb, const TR* __restrict__ rdry_in, int po, int64_t B, TO* __restrict__ R_TOC,
+    TO* __restrict__ R_TOA, TO* __restrict__ L_TOA, TO* __restrict__ o_rso, TO* __restrict__ o_rdo, TO* __restrict__ o_rsd,
+    TO* __restrict__ o_rdd) {
+  __shared__ double lds_c[NCONST_USED * 64];
+  __shared__ double lds_a[NATM_USED * 64];
+  __shared__ double lds_k[COL_WAVES * 64];              // per wave: the 48 SMAC coefficients of its band
+  stage_f64_tables();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t s = (int64_t)blockIdx.x * 64 + lane;
+  const bool ok = s < B;
+  const int64_t sc = ok ? s : B - 1;                    // (lanes past the end repeat the last sample and store nothing)
+  for (int i = wave; i < NCONST_USED; i += COL_WAVES) lds_c[i * 64 + lane] = cst[(int64_t)i * Bp + sc];
+  for (int i = wave; i < NATM_USED; i += COL_WAVES) lds_a[i * 64 + lane] = atm[(int64_t)i * Bp + sc];
+  __syncthreads();
+  const int j = deal[blockIdx.y * COL_WAVES + wave];
+  if (j < 0) return;                                    // (wave-uniform; no barrier follows)
+  const int e0 = sup_start[j], e1 = sup_start[j + 1];
+  double acc_so = 0.0, acc_do = 0.0, acc_sd = 0.0, acc_dd = 0.0;
+#pragma unroll 1
+  for (int e = e0; e < e1; ++e) {
+    // The sample's constants are read from LDS inside the loop, entry by entry, through an offset the compiler cannot see
+    // through: hoisted out of the loop as invariants they would be 70 live registers and a spilled loop.
+    int lo = lane;
+    SPART_KEEP_BRANCH(lo);
+    const LdsCol<double> c{lds_c + lo};
+    const int band = sup_ev[e];                         // 0..2000 = 400..2400 nm, 2001 = the thermal evaluation
+    const double q = sup_q[e];
+    const bool thermal = band == NWL;
+    const int ti = band < NWL ? band : NWL - 1;         // thermal soil = soil at 2400 nm (SPART.py:440)
+    const BandTab<double> tb = load_tab(tab, ti);
+    double refl, tran, absb, K;
+    leaf_band<double>(tb, c[C_CAB], c[C_CCA], c[C_CDM], c[C_CW], c[C_CS], c[C_CANT], c[C_CBC], c[C_PROT], c[C_NM1], refl,
+                      tran, absb, K);
+    const double rho = thermal ? c[C_RHO_TH] : refl;    // SPART.py:463-466
+    const double tau = thermal ? c[C_TAU_TH] : tran;
+    const double ab = thermal ? (1.0 - c[C_RHO_TH] - c[C_TAU_TH]) : absb;
+    const CanopyPar<double> cp = load_canopy<double>(c);        // (same order of the parts as in k_columns)
+    const CanopyCore<double> core = canopy_core<double>(cp, rho, tau, ab);
+    const double rdry = rdry_in ? (double)rdry_in[sc * po + ti] : soil_dry<double>(tb, c[C_F1], c[C_F2], c[C_F3]);
+    double fm[7] = {c[C_FM0], c[C_FM1], c[C_FM2], c[C_FM3], c[C_FM4], c[C_FM5], c[C_FM6]};
+    double rwet;
+    soil_band<double>(tb, rdry, c[C_WET], fm, c[C_FMSUM], c[C_FILM2L], rwet);
+    double rso, rdo, rsd, rdd;
+    canopy_soil<double>(cp, core, rwet, rso, rdo, rsd, rdd);
+    acc_so = __builtin_fma(q, rso, acc_so);
+    acc_do = __builtin_fma(q, rdo, acc_do);
+    acc_sd = __builtin_fma(q, rsd, acc_sd);
+    acc_dd = __builtin_fma(q, rdd, acc_dd);
+  }
+  const LdsCol<double> a{lds_a + lane};
+  const double Q = sup_Q[j];                            // (0 or non-finite: propagates as the reference's division does)
+  const double v_so = acc_so / Q, v_do = acc_do / Q, v_sd = acc_sd / Q, v_dd = acc_dd / Q;
+  // the band's 48 SMAC coefficients: one vector load (lane r fetches row r) parked in the wave's LDS row, as in k_columns
+  double* kw = lds_k + wave * 64;
+  kw[lane] = coef[(size_t)(lane < NCOEF ? lane : NCOEF - 1) * nb + j];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const SmacOut so = smac_band_c(a, [kw](int r) { return kw[r]; });
+  const double La = a[A_LAF] * econv[j];                 // SPART.py:353, 394
+  double rtoc, rtoa, ltoa;
+  toc_to_toa(so, v_so, v_do, v_dd, v_sd, La, rtoc, rtoa, ltoa);
+  if (ok) {
+    const int64_t o = s * nb + j;
+    if (R_TOC) R_TOC[o] = (TO)rtoc;
+    if (R_TOA) R_TOA[o] = (TO)rtoa;
+    if (L_TOA) L_TOA[o] = (TO)ltoa;
+    if (o_rso) o_rso[o] = (TO)v_so;
+    if (o_rdo) o_rdo[o] = (TO)v_do;
+    if (o_rsd) o_rsd[o] = (TO)v_sd;
+    if (o_rdd) o_rdd[o] = (TO)v_dd;
+  }
+}
+
 // batch-mean canopy spectra from the per-chunk band sums: out (4, 2162) = mean over samples of rso, rdo, rsd, rdd
 template <typename T>
 __global__ __launch_bounds__(256) void k_bandmean(const T* __restrict__ bandsum, int64_t nchunk, int64_t B,

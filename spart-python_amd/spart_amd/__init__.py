@@ -9,6 +9,7 @@ from .api import (BSM, PROSPECT_5D, SAILH, SMAC, SPART, Angles, AtmosphericOptic
                   load_optical_parameters, load_sensor_info, set_leaf_refl_trans_assumptions,
                   set_soil_refl_trans_assumptions)
 from .engine import Engine, get_engine  # noqa: F401
+from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401
 from .lut import generate_lut, invert_lut, load_lut, lut_to_parquet, noise_weights, retrieve, retrieve_stream  # noqa: F401

@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 11        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 12        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -28,7 +28,8 @@ class SpartMaterialize(ctypes.Structure):
                                                                                           ("f32_bands", ctypes.c_int32),
                                                                                           ("fast_prelude", ctypes.c_int32),
                                                                                           ("lidf_in", vp),
-                                                                                          ("nlayers", ctypes.c_int32)]
+                                                                                          ("nlayers", ctypes.c_int32)] + [
+        (n, vp) for n in ("R_TOC_srf", "R_TOA_srf", "L_TOA_srf", "rso_srf", "rdo_srf", "rsd_srf", "rdd_srf")]
 
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
@@ -48,6 +49,8 @@ SIGNATURES = {
     "spart_ctx_econv": (ctypes.c_int, [vp, c_dp]),
     "spart_ctx_set_row_pitch": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64]),
     "spart_calculate_tav": (ctypes.c_int, [ctypes.c_double, c_dp, ctypes.c_int64, c_dp]),
+    "spart_srf_support": (ctypes.c_int, [c_dp, c_dp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_int32), c_dp, c_dp]),
     "spart_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int, ctypes.c_int64]),
     "spart_workspace_bandsum": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t),
                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),

@@ -9,12 +9,14 @@ import threading
 import numpy as np
 
 from . import _lib, tables
+from .srf import check_srf
 
 DTYPES = {"float32": _lib.SPART_F32, "fp32": _lib.SPART_F32, "f32": _lib.SPART_F32,
           "float64": _lib.SPART_F64, "fp64": _lib.SPART_F64, "f64": _lib.SPART_F64}
 SMAC_FIELDS = ["Ta_s", "Ta_o", "Tg", "Ra_dd", "Ra_so", "Ta_ss", "Ta_sd", "Ta_oo", "Ta_do"]   # smac.py:209-211
 MATERIALIZE_FIELDS = ["leaf_refl", "leaf_tran", "leaf_kchl", "soil_refl", "soil_refl_dry", "rso", "rdo", "rsd",
-                      "rdd", "rsoil", "La", "band_mean"]
+                      "rdd", "rsoil", "La", "band_mean", "R_TOC_srf", "R_TOA_srf", "L_TOA_srf", "rso_srf", "rdo_srf", "rsd_srf",
+                      "rdd_srf"]
 _MAT_WIDTH = dict(leaf_refl=_lib.NWLS, leaf_tran=_lib.NWLS, leaf_kchl=_lib.NWL, soil_refl=_lib.NWLS,
                   soil_refl_dry=_lib.NWL, rso=_lib.NWLS, rdo=_lib.NWLS, rsd=_lib.NWLS, rdd=_lib.NWLS)
 
@@ -269,6 +271,7 @@ class Engine:
         for k, v in keep.items():
             setattr(t, k, _dp(v))
         self.nb = 0
+        self.srf_aligned = np.zeros(0, dtype=bool)        # no sensor: no bands
         if sensor is not None or sensor_info is not None:
             si = sensor_info if sensor_info is not None else tables.load_sensor_info(sensor)
             self.sensor_info = si
@@ -280,6 +283,9 @@ class Engine:
             self.nb = int(wl.shape[0])
             self.wl_smac = np.asarray(si["wl_smac"]).reshape(-1)
             self.band_id = list(si["band_id_smac"]) if "band_id_smac" in si else [""] * self.nb
+            # per band: the centre lies inside the extent of its SRF column's weighted samples (srf.check_srf).  The *_srf
+            # outputs are what the tables say either way; api.SPART.run / generate_lut(band_model="srf") insist on all true
+            self.srf_aligned = check_srf(si)
         self._keep = keep
         ctx = _lib.vp()
         rc = self.lib.spart_ctx_create(ctypes.byref(ctx), device, ctypes.byref(t))
@@ -475,7 +481,9 @@ class Engine:
 
         params : (27, B) float64 device tensor (rows = spart_amd.workloads.PARAM_NAMES) or a list of 27
                  scalars / arrays.
-        materialize : iterable of names from MATERIALIZE_FIELDS to also return (full spectra etc.)
+        materialize : iterable of names from MATERIALIZE_FIELDS to also return (full spectra etc.; the seven ``*_srf`` names
+              are the SRF-convolved sensor columns, (B, nb): the band's spectral response function applied to the canopy
+              spectra instead of a sample at the band centre -- float64 column path in every mode, not with f32_columns)
         out : optional dict with preallocated 'R_TOC','R_TOA','L_TOA' (B,nb) tensors and / or preallocated tensors for
               names in ``materialize`` (spectrum arrays on this engine's row pitch, e.g. a previous call's results)
         prune : False (default) evaluates all 2162 bands of every sample; True lets the kernel skip bands

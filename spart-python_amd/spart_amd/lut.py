@@ -4,7 +4,7 @@ own HIP streams beside the kernels (double-buffered device buffers, no host stag
 (216 B in + 3*nb*4 B out per spectrum) hides behind the evaluation whenever the link keeps up.
 
 On-disk layout (a directory):
-    meta.json                  sensor, band ids, band centres, dtype, parameter names, number of rows
+    meta.json                  sensor, band ids, band centres, dtype, parameter names, number of rows, band model
     params.npy   (B, 27) f64   the parameter table (workloads.PARAM_NAMES order)
     R_TOC.npy / R_TOA.npy / L_TOA.npy   (B, nb) in the chosen dtype
 All .npy files are plain numpy arrays (np.load(..., mmap_mode="r") works for tables larger than RAM).
@@ -115,7 +115,7 @@ def _run_pipeline(nchunks, upload, launch, download, ahead=None):
 
 
 def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, device=None, prune=True, fault_threads=8,
-                 f32_bands=False, shard=False, group=None, out=None, sensor_info=None):
+                 f32_bands=False, shard=False, group=None, out=None, sensor_info=None, band_model="centre"):
     """params: (B, 27) array-like on the HOST (numpy / memmap).  Returns dict of host arrays (np.memmap when
     ``path`` is given).
 
@@ -133,6 +133,12 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     up to 2162 bands, e.g. a hyperspectral imager) instead of a packaged sensor: the engine is then
     get_engine(sensor, device, sensor_info=sensor_info), and meta.json records ``sensor`` as given with that dict's bands and
     centres.
+    ``band_model``: "centre" (default: the canopy spectra sampled at the band centre, like the reference) or "srf": the
+    columns R_TOC / R_TOA / L_TOA hold the SRF-convolved values (Engine.run's R_TOC_srf ...; the band's spectral response
+    function applied to the canopy spectra); meta.json records it.  ValueError for a sensor whose SRF columns are not in the
+    order of its band centres (packaged MODIS, OLCI): pass ``sensor_info=spart_amd.align_srf(load_sensor_info(sensor))``.
+    The C ABI always writes the centre columns, so "srf" costs one more (3, chunk, nb) device block that receives them and is
+    never downloaded: their kernel time and stores are spent for nothing in this mode.
     ``out``: optional dict of caller-owned host arrays for the three columns (this rank's rows), e.g. a previous call's result:
     their pages are already resident.  Fresh arrays cost 1.25 GB of first-touch page faults per 8M spectra even with the helper
     threads -- 8M pruned: 57 ms fresh, 40 ms reused (2.0e8 spectra/s; the two PCIe directions alone need 33 ms);
@@ -164,6 +170,8 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     lo0, hi0 = shard_bounds(Btot, world, rank)
     eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
     nb = eng.nb
+    from .api import _SRF_COLUMNS, _band_model
+    srf = _band_model(band_model, eng)
     npdt = np.float32 if dtype in ("float32", "fp32", "f32") else np.float64
     tdt = torch.float32 if npdt is np.float32 else torch.float64
     if path is not None and out is not None:
@@ -194,6 +202,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     drow = [torch.empty((chunk, workloads.NPARAM), dtype=torch.float64, device=dev) for _ in range(2)]   # as on the host
     dsoa = [torch.empty((workloads.NPARAM, chunk), dtype=torch.float64, device=dev) for _ in range(2)]   # kernel layout
     dout = [torch.empty((3, chunk, nb), dtype=tdt, device=dev) for _ in range(2)]
+    dctr = torch.empty((3, chunk, nb), dtype=tdt, device=dev) if srf else None     # band_model="srf": the centre columns, not kept
     ev_in = [torch.cuda.Event() for _ in range(2)]
     ev_done = [torch.cuda.Event() for _ in range(2)]
     nchunks = (B + chunk - 1) // chunk
@@ -230,7 +239,11 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
         compute.wait_event(ev_in[j])
         res = dout[j][:, :n]
         Pd = dsoa[j] if n == chunk else dsoa[j][:, :n].contiguous()
-        eng.run(Pd, dtype, out={"R_TOC": res[0], "R_TOA": res[1], "L_TOA": res[2]}, prune=prune, f32_bands=f32_bands)
+        if srf:
+            eng.run(Pd, dtype, out={**{k: dctr[q, :n] for q, k in enumerate(COLUMNS)}, **{k: res[q] for q, k in enumerate(_SRF_COLUMNS)}},
+                    materialize=_SRF_COLUMNS, prune=prune, f32_bands=f32_bands)
+        else:
+            eng.run(Pd, dtype, out={"R_TOC": res[0], "R_TOA": res[1], "L_TOA": res[2]}, prune=prune, f32_bands=f32_bands)
         ev_done[j].record(compute)
 
     fault_threads = max(0, int(fault_threads))
@@ -277,7 +290,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
         if rank == 0:
             meta = {"sensor": sensor, "bands": [str(b) for b in eng.band_id], "wavelengths": [float(w) for w in eng.wl_smac],
                     "dtype": np.dtype(npdt).name, "rows": int(Btot), "param_names": workloads.PARAM_NAMES,
-                    "columns": list(COLUMNS), "pruned": bool(prune)}
+                    "columns": list(COLUMNS), "pruned": bool(prune), "band_model": band_model}
             with open(os.path.join(path, "meta.json"), "w") as f:
                 json.dump(meta, f, indent=1)
     res = LutBlock(full_out if full_out is not None else out)
