@@ -36,7 +36,8 @@ def tab(hm, tables):
     return t
 
 
-def run_chain(hm, tab, oracle, tables, P, sensor, dtype, lidf_in=None, nlayers=0):
+def chain_bands(hm, tab, P, dtype, lidf_in=None, nlayers=0):
+    """the prelude and all 2002 band evaluations of P: (out (B, 2002, 10), atm (B, 16), lidf (B, 13))"""
     P = np.ascontiguousarray(P, dtype=np.float64)
     B = P.shape[0]
     out = np.zeros((B, 2002, 10))
@@ -48,6 +49,12 @@ def run_chain(hm, tab, oracle, tables, P, sensor, dtype, lidf_in=None, nlayers=0
         li = None if lidf_in is None else np.ascontiguousarray(np.broadcast_to(lidf_in, (B, 13)), dtype=np.float64)
         hm.hm_bands_state(ctypes.c_int(dtype), ctypes.c_int64(B), dp(tab), dp(P), dp(li) if li is not None else None,
                           ctypes.c_int(int(nlayers)), dp(out), dp(atm), dp(lidf))
+    return out, atm, lidf
+
+
+def chain_sensor(hm, oracle, tables, out, atm, sensor):
+    """a sensor's step on chain_bands' arrays: interpolation at the band centres, SMAC, TOC -> TOA: (sm (B, nb, 9), toa (B, nb, 3))"""
+    B = out.shape[0]
     se = oracle.sensor_tables(tables, sensor)
     nb = se["coef"].shape[1]
     i0, i1, fr = oracle.interp_weights(se["wl_smac"])
@@ -59,6 +66,12 @@ def run_chain(hm, tab, oracle, tables, P, sensor, dtype, lidf_in=None, nlayers=0
     sm = np.zeros((B, nb, 9))
     toa = np.zeros((B, nb, 3))
     hm.hm_sensor(ctypes.c_int64(B), ctypes.c_int(nb), dp(atm), dp(coef), dp(econv), dp(rv), dp(sm), dp(toa))
+    return sm, toa
+
+
+def run_chain(hm, tab, oracle, tables, P, sensor, dtype, lidf_in=None, nlayers=0):
+    out, atm, lidf = chain_bands(hm, tab, P, dtype, lidf_in, nlayers)
+    sm, toa = chain_sensor(hm, oracle, tables, out, atm, sensor)
     return out, lidf, sm, toa
 
 
