@@ -19,6 +19,7 @@
 #include "spart_bands_f32.h"
 #include "spart_kernels.h"
 #include "spart_lut.h"
+#include "spart_refine.h"
 
 using namespace spart;
 
@@ -1006,6 +1007,84 @@ static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t 
   return SPART_OK;
 }
 
+// ---- spart_refine (csrc/spart_refine.h): the workspace of a call and the chunk loop.  The workspace is sized by ONE chunk
+// -- min(M, REFINE_ROWS / (F + 1)) observations -- whatever M is: the parameter table, the three column blocks of the forward
+// call, the optimiser's state and the forward call's own workspace.
+struct RefineLayout {
+  int64_t mcap;                 // observations per chunk
+  size_t table, cols[3], t, A, lam, na, cfg, cfg_free, fwd, total;
+};
+static RefineLayout refine_layout(int nb, int64_t M, int F) {
+  RefineLayout l;
+  l.mcap = std::min<int64_t>(M, REFINE_ROWS / (F + 1));
+  const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(F + 1);
+  Carver c;
+  l.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.t = c.take(mc * F * 8);
+  l.A = c.take(mc * (size_t)(refine_ntri(F) + F) * 8);
+  l.lam = c.take(mc * 8);
+  l.na = c.take(mc * 4);
+  l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
+  l.cfg_free = c.take(REFINE_MAXF * 4);
+  // the forward call of a full chunk and of the last, shorter one (the band-sum rows of carve() follow pick_chunk, which is
+  // not monotonic in the batch)
+  size_t fwd = carve(SPART_F64, (int64_t)rows).total;
+  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (F + 1)).total);
+  l.fwd = c.take(fwd);
+  l.total = c.o;
+  return l;
+}
+
+static bool refine_sizes_ok(const spart_ctx* ctx, int64_t M, int F) {
+  return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF;
+}
+
+// spart_refine once its arguments are checked
+static int refine_impl(spart_ctx* ctx, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
+                       const spart_refine_opt& o, double lambda0, const RefineOut& out, char* wsp, const RefineLayout& l,
+                       hipStream_t st) {
+  const int nb = ctx->nb, W = refine_group(F);
+  const size_t lds = refine_lds_bytes(F, W);
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* table = (double*)(wsp + l.table);
+  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
+  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
+  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
+  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
+    const int64_t rows = (int64_t)mc * (F + 1);
+    RefineOut oc = out;
+    oc.x += m0 * F;
+    oc.cost += m0;
+    if (oc.cost0) oc.cost0 += m0;
+    if (oc.sdev) oc.sdev += m0 * F;
+    if (oc.n_accept) oc.n_accept += m0;
+    if (oc.y) oc.y += m0 * nb;
+    hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, lambda0, table, oc.x, t,
+                       lam, na, dcfg, dfree);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    for (int it = 0; it <= o.n_iter; ++it) {
+      if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
+                                                    wsp + l.fwd, ws, st))
+        return rc;
+      hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
+                         obs + m0 * nb, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
+                         o.weights_per_obs ? 1 : 0, (const double*)dcfg, (const int32_t*)dfree, table, mc, F, nb, W, it,
+                         it == o.n_iter ? 1 : 0, t, A, lam, na, oc);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return SPART_OK;
+}
+
 // ---- SRF support (include/spart_hip.h: spart_srf_support)
 // The grid point of wlS (400..2400 by 1, 2500..15000 by 100, 16000..50000 by 1000) nearest to w in exact arithmetic: ties to
 // the lower index, NaN -> 0.  With g[i] <= w <= g[i + 1] <= 2 g[i] both differences below are exact (Sterbenz), so the
@@ -1180,6 +1259,59 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
   *out = ctx;
   own.ctx = nullptr;                                              // (the caller's now)
   return SPART_OK;
+}
+
+size_t spart_refine_workspace_bytes(const spart_ctx* ctx, int64_t M, int F) {
+  return refine_sizes_ok(ctx, M, F) ? refine_layout(ctx->nb, M, F).total : 0;
+}
+
+int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                 const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
+                 double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  const char* who = "spart_refine";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  spart_refine_opt o = *opt;
+  if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
+  if (o.n_iter < 0 || o.n_iter > REFINE_MAX_ITER)
+    return fail(SPART_ERR_INVALID, "%s: n_iter = %d, expected 0 ... %d", who, o.n_iter, REFINE_MAX_ITER);
+  if (o.nlayers < 0 || o.nlayers > SPART_MAX_NLAYERS)
+    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
+  if (!(o.rel_step >= 0.0) || !(o.lambda0 >= 0.0) || std::isinf(o.rel_step) || std::isinf(o.lambda0))
+    return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
+  if (o.rel_step == 0.0) o.rel_step = 1e-3;
+  if (o.lambda0 == 0.0) o.lambda0 = 1e-2;
+  RefineCfg cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  for (int f = 0; f < F; ++f) {
+    const int c = free_cols[f];
+    if (c < 0 || c >= SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, SPART_NPARAM - 1);
+    if (cfg.is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
+    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
+      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
+    cfg.is_free[c] = 1;
+    cfg.free_col[f] = c;
+    cfg.lo[f] = lo[f];
+    cfg.hi[f] = hi[f];
+    cfg.h[f] = o.rel_step * (hi[f] - lo[f]);
+  }
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  if (!obs || !x || !cost) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
+  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
+  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
+  const RefineLayout l = refine_layout(ctx->nb, M, F);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
+  const RefineOut out = {x, cost, cost0, sdev, n_accept, y};
+  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
+    return refine_impl(ctx, M, cfg, F, obs, weights, o, o.lambda0, out, (char*)workspace, l, st);
+  });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

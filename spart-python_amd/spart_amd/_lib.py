@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 12        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 13        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -31,6 +31,14 @@ class SpartMaterialize(ctypes.Structure):
                                                                                           ("nlayers", ctypes.c_int32)] + [
         (n, vp) for n in ("R_TOC_srf", "R_TOA_srf", "L_TOA_srf", "rso_srf", "rdo_srf", "rsd_srf", "rdd_srf")]
 
+
+class SpartRefineOpt(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("column", "n_iter", "weights_per_obs", "fast_prelude", "nlayers")] + [
+        ("rel_step", ctypes.c_double), ("lambda0", ctypes.c_double)]
+
+
+REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
+REFINE_MAXF, REFINE_MAX_ITER = 16, 100
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -73,6 +81,9 @@ SIGNATURES = {
                            ("", (ctypes.c_int, _LUT_TOPK_CALL)),
                            ("_stats", (ctypes.c_int, _LUT_TOPK_STATS)))},
     "spart_lut_summarise": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "spart_refine_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
+    "spart_refine": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp,
+                                    vp, vp, ctypes.POINTER(SpartRefineOpt), vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

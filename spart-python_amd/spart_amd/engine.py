@@ -8,7 +8,7 @@ import threading
 
 import numpy as np
 
-from . import _lib, tables
+from . import _lib, tables, workloads
 from .srf import check_srf
 
 DTYPES = {"float32": _lib.SPART_F32, "fp32": _lib.SPART_F32, "f32": _lib.SPART_F32,
@@ -107,6 +107,44 @@ def lut_weights_kind(shape, M, nb):
     if shape == (M, nb):
         return "per_observation"
     raise ValueError(f"weights has shape {shape}, expected (nb,) = ({nb},) or (M, nb) = ({M}, {nb})")
+
+
+def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=None):
+    """The host-side argument checks of Engine.refine / spart_refine, none of which needs a device.  ``free``: names from
+    workloads.PARAM_NAMES, 1 ... 16 of them, each once; ``bounds``: {name: (lo, hi)} for free names only, finite with lo < hi,
+    the others from ``default_ranges`` (None = workloads.RANGES; a name with neither is a ValueError).
+    -> dict: names, cols (int32), lo, hi (float64), column (0 / 1 / 2), n_iter, rel_step, lambda0."""
+    names = [str(n) for n in free]
+    unknown = [n for n in names if n not in workloads.PARAM_NAMES]
+    if unknown:
+        raise ValueError(f"free: unknown parameter name(s) {unknown}; expected names from {list(workloads.PARAM_NAMES)}")
+    if not 1 <= len(names) <= _lib.REFINE_MAXF:
+        raise ValueError(f"free: {len(names)} names, expected 1 ... {_lib.REFINE_MAXF}")
+    twice = sorted({n for n in names if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"free: {twice} named twice")
+    bounds = dict(bounds or {})
+    stray = [n for n in bounds if n not in names]
+    if stray:
+        raise ValueError(f"bounds: {stray} not free")
+    ranges = workloads.RANGES if default_ranges is None else default_ranges
+    lo, hi = np.empty(len(names)), np.empty(len(names))
+    for i, n in enumerate(names):
+        if n not in bounds and n not in ranges:
+            raise ValueError(f"free: {n!r} has no range and no bound was given for it (bounds={{{n!r}: (lo, hi)}})")
+        lo[i], hi[i] = (float(v) for v in (bounds[n] if n in bounds else ranges[n]))
+        if not (np.isfinite(lo[i]) and np.isfinite(hi[i]) and lo[i] < hi[i]):
+            raise ValueError(f"bounds of {n!r}: ({lo[i]}, {hi[i]}); finite lo < hi expected")
+    if column not in _lib.REFINE_COLUMNS:
+        raise ValueError(f"column = {column!r}, expected one of {_lib.REFINE_COLUMNS}")
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 0 <= int(n_iter) <= _lib.REFINE_MAX_ITER:
+        raise ValueError(f"n_iter = {n_iter!r}, expected an integer 0 ... {_lib.REFINE_MAX_ITER}")
+    for what, v in (("rel_step", rel_step), ("lambda0", lambda0)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{what} = {v!r}, expected a finite value > 0")
+    return {"names": names, "cols": np.array([workloads.PARAM_NAMES.index(n) for n in names], dtype=np.int32), "lo": lo, "hi": hi,
+            "column": _lib.REFINE_COLUMNS.index(column), "n_iter": int(n_iter), "rel_step": float(rel_step),
+            "lambda0": float(lambda0)}
 
 
 # ---- the static tables a context is built from (spart_tables): the reference reads them from the dicts it is HANDED at call
@@ -738,6 +776,71 @@ class Engine:
                                           res["median"].data_ptr(), res["std"].data_ptr(), res["count"].data_ptr(),
                                           self._stream())
         _lib.check(self.lib, self.ctx, rc)
+        return res
+
+    def refine(self, params, obs, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
+               lidf="literal", nlayers=None, _plan=None):
+        """Bounded Levenberg-Marquardt refinement of the ``free`` parameters of every start row against its observation, on the
+        device (include/spart_hip.h: spart_refine, which defines every sum and solve; tools/refine_defined.py is the numpy form).
+        params : the start rows, as for run(): a (27, M) float64 device tensor or a list of 27 scalars / arrays (each 1 or M values)
+        obs : (M, nb) observed ``column`` (R_TOC / R_TOA / L_TOA) of this engine's sensor
+        free : names from workloads.PARAM_NAMES (1 ... 16); the other parameters stay at their start values
+        bounds : {name: (lo, hi)} for some or all free names; the default is workloads.RANGES[name]
+        weights : None, (nb,) or (M, nb); a weight of exactly 0 skips the band (obs may be NaN there); 1 / sigma^2 makes
+                  ``std`` the linearised 1-sigma uncertainty
+        n_iter : proposals (0 ... 100): n_iter + 1 forward evaluations of (F + 1) M rows; there is no early exit
+        lidf, nlayers : as for run()
+        -> dict of device tensors x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: the start could not be
+        evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names."""
+        plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0)
+        if lidf not in ("literal", "newton"):
+            raise ValueError("lidf must be 'literal' or 'newton'")
+        nl = self._nlayers(nlayers)
+        import torch
+        oshape = tuple(obs.shape) if hasattr(obs, "shape") else np.shape(obs)
+        if len(oshape) != 2 or oshape[1] != self.nb:
+            raise ValueError(f"obs has shape {oshape}, expected (M, nb) = (M, {self.nb})")
+        M, nb = int(oshape[0]), int(oshape[1])
+        block = torch.is_tensor(params) and params.dim() == 2
+        if block:
+            if params.shape[0] != _lib.NPARAM:
+                raise ValueError("params must be (27, M)")
+            if int(params.shape[1]) not in (1, M):
+                raise ValueError(f"params of {int(params.shape[1])} rows do not broadcast to the {M} rows of obs")
+        else:
+            if len(params) != _lib.NPARAM:
+                raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+            plist = fill_nulls(params)
+            batch_size(plist, B=M)
+        kind = lut_weights_kind(None if weights is None else (tuple(weights.shape) if hasattr(weights, "shape") else np.shape(weights)), M, nb)
+        # ---- the device from here on
+        torch = self.torch
+        F = len(plan["names"])
+        if block:
+            P = params.to(device=self.device, dtype=torch.float64)
+            cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
+        else:
+            cols, _ = self.columns(plist, M)
+        o = torch.as_tensor(obs).to(device=self.device, dtype=torch.float64).contiguous()
+        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
+        res = {"x": torch.empty((M, F), dtype=torch.float64, device=self.device),
+               "cost": torch.empty((M,), dtype=torch.float64, device=self.device),
+               "cost0": torch.empty((M,), dtype=torch.float64, device=self.device),
+               "std": torch.empty((M, F), dtype=torch.float64, device=self.device),
+               "n_accept": torch.empty((M,), dtype=torch.int32, device=self.device),
+               "y": torch.empty((M, nb), dtype=torch.float64, device=self.device)}
+        opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=1 if kind == "per_observation" else 0,
+                                  fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
+                                  lambda0=plan["lambda0"])
+        nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_refine"] += 1
+        rc = self.lib.spart_refine(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
+                                   ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
+                                   ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        res["names"] = list(plan["names"])
         return res
 
     def profile(self, max_calls):

@@ -445,8 +445,102 @@ def _np_dtype(name):
     return np.float32 if name in ("float32", "fp32", "f32") else np.float64
 
 
+def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
+           lidf="literal", nlayers=None, sensor_info=None, device=None):
+    """The host form of Engine.refine: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays (run()'s
+    conventions), ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``, a sensorinfo dict).
+    -> dict of numpy arrays x, cost, cost0, std, n_accept, y and the list ``names``.  Every argument check that needs no
+    device runs before one is asked for."""
+    from .engine import refine_plan
+    plan = refine_plan(free, bounds, n_iter, column, rel_step, lambda0)
+    if lidf not in ("literal", "newton"):
+        raise ValueError("lidf must be 'literal' or 'newton'")
+    o = np.asarray(obs, dtype=np.float64)
+    if o.ndim != 2:
+        raise ValueError(f"obs has shape {o.shape}, expected (M, nb)")
+    if not isinstance(params, (list, tuple)):
+        params = np.asarray(params, dtype=np.float64)
+        if params.ndim != 2 or params.shape[0] != workloads.NPARAM:
+            raise ValueError(f"params must be (27, M) or a list of 27 columns, got shape {params.shape}")
+        params = list(params)
+    elif len(params) != workloads.NPARAM:
+        raise ValueError(f"params must have 27 entries, got {len(params)}")
+    for c in params:
+        if c is not None and np.size(c) not in (1, o.shape[0]):
+            raise ValueError(f"a params column of {np.size(c)} values does not broadcast to the {o.shape[0]} rows of obs")
+    if weights is not None:
+        from .engine import lut_weights_kind
+        lut_weights_kind(np.shape(weights), o.shape[0], o.shape[1])
+    eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
+    res = eng.refine(params, o, free, weights=weights, lidf=lidf, nlayers=nlayers, _plan=plan)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers")
+
+
+def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
+    """retrieve(refine=...): everything that can be refused from the LUT directory alone -> (plan, options, sensor, sensor_info)"""
+    from .engine import refine_plan
+    opts = dict(refine_opts or {})
+    stray = [n for n in opts if n not in REFINE_OPTS]
+    if stray:
+        raise ValueError(f"refine_opts: unknown option(s) {stray}; expected some of {REFINE_OPTS}")
+    if refine is None:
+        if opts:
+            raise ValueError("refine_opts without refine=[names]")
+        return None
+    meta, params, _ = load_lut(lut_dir)
+    if meta.get("band_model", "centre") == "srf":
+        raise ValueError('retrieve(refine=...) on a band_model="srf" LUT: the refinement fits the band-centre columns '
+                         "(SRF columns as the fitted quantity are not built yet)")
+    if _group_info(shard, group)[0] > 1:
+        raise ValueError("retrieve(refine=...) does not take shard=True under a process group of more than one rank "
+                         "(sharded refinement is not built yet)")
+    if sensor_info is None and not isinstance(meta.get("sensor"), str):
+        raise ValueError("retrieve(refine=...): meta.json names no packaged sensor; pass the LUT's sensor_info=")
+    names, cols = _param_columns(list(refine))
+    P = np.asarray(params)
+    ranges = {}
+    for n, c in zip(names, cols):                     # the LUT's own extent of every free column
+        lo, hi = (float(P[:, c].min()), float(P[:, c].max())) if P.shape[0] else (np.nan, np.nan)
+        if lo < hi:
+            ranges[n] = (lo, hi)
+        elif n not in (opts.get("bounds") or {}):
+            raise ValueError(f"retrieve(refine=...): column {n!r} is constant in the LUT ({lo}); give refine_opts="
+                             f"{{'bounds': {{{n!r}: (lo, hi)}}}} or leave it out")
+    plan = refine_plan(names, opts.get("bounds"), opts.get("n_iter", 10), "R_TOC", opts.get("rel_step", 1e-3),
+                       opts.get("lambda0", 1e-2), default_ranges=ranges)
+    return plan, opts, meta.get("sensor"), sensor_info
+
+
+def _refine_rows(setup, lut_dir, obs, idx, column, weights, device):
+    """the refinement of retrieve(): start = params.npy[idx[:, 0]]; observations without a row get NaN and -1"""
+    plan, opts, sensor, sensor_info = setup
+    _, params, _ = load_lut(lut_dir)
+    F, M = len(plan["names"]), idx.shape[0]
+    out = {"refined": np.full((M, F), np.nan), "refined_cost": np.full(M, np.nan), "refined_cost0": np.full(M, np.nan),
+           "refined_std": np.full((M, F), np.nan), "refined_accepts": np.full(M, -1, dtype=np.int32),
+           "refined_names": list(plan["names"])}
+    ok = np.flatnonzero(idx[:, 0] >= 0)
+    if ok.size:
+        rows, inv = np.unique(idx[ok, 0], return_inverse=True)
+        start = np.asarray(params[rows], dtype=np.float64)[inv]           # (sorted unique rows: a memmap reads only those)
+        w = None if weights is None else np.asarray(weights, dtype=np.float64)
+        if w is not None and w.ndim == 2:
+            w = w[ok]
+        eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
+        plan = dict(plan, column=("R_TOC", "R_TOA", "L_TOA").index(column))
+        r = eng.refine(list(np.ascontiguousarray(start.T)), np.asarray(obs, dtype=np.float64)[ok], plan["names"], weights=w,
+                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), _plan=plan)
+        for key, name in (("refined", "x"), ("refined_cost", "cost"), ("refined_cost0", "cost0"), ("refined_std", "std"),
+                          ("refined_accepts", "n_accept")):
+            out[key][ok] = r[name].cpu().numpy()
+    return out
+
+
 def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None, summary="host",
-             params_cols=None):
+             params_cols=None, refine=None, refine_opts=None, sensor_info=None):
     """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
     mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
     ``weights`` as for invert_lut: (nb,) or (M, nb), e.g. noise_weights(obs, rel_sigma=0.02).
@@ -459,10 +553,29 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     parameter VALUES; the device definition propagates them.  LUT parameter tables hold no NaN, so the two agree on every real
     table.  ``summary="device"`` with ``shard=True`` under a process group of more than one rank raises ValueError: each rank
     holds only its own rows (the sharded summary is not built yet).
-    -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, P) float64, names (the P parameter names)."""
+    -> dict: idx (M, k) int64, cost (M, k), mean / median / std (M, P) float64, names (the P parameter names).
+
+    ``refine``: a list of names from workloads.PARAM_NAMES.  The best row of every observation (params.npy[idx[:, 0]]) then
+    starts a bounded Levenberg-Marquardt fit of those parameters against the observation, the others held at the row's values
+    (Engine.refine / spart_refine); the keys above are unchanged, bit for bit, and the result gains ``refined`` (M, F),
+    ``refined_cost``, ``refined_cost0`` (the cost at the start: cost[:, 0] of a float64 LUT bit for bit), ``refined_std``
+    (M, F), ``refined_accepts`` (M,) int32 and ``refined_names``; observations without a row (idx -1) get NaN and -1.
+    ``refine_opts``: bounds / n_iter / rel_step / lambda0 / lidf / nlayers of Engine.refine; the default bounds are the LUT's
+    own minimum and maximum of every free column (a constant column without a bound is a ValueError).  The sensor is
+    meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band_model="srf" LUT and for
+    ``shard=True`` under a process group of more than one rank (neither is built yet)."""
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
+    setup = _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info)
+    out = _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, summary, params_cols, names, cols)
+    if setup is not None:
+        out.update(_refine_rows(setup, lut_dir, obs, out["idx"], column, weights, device))
+    return out
+
+
+def _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, summary, params_cols, names, cols):
+    """retrieve() without the refinement"""
     if summary == "host":
         idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
         _, params, _ = load_lut(lut_dir)
