@@ -3,18 +3,8 @@
 The band kernel's speed depends on resident waves per SIMD (512 VGPRs / wave budget): 5 for the float32 kernels
 (<= 96 VGPRs, no scratch), 3 for the float64 ones (<= 168).  A change that silently pushes a kernel over the edge
 would only show up as a slower benchmark; this test makes it a failure on the build machine."""
-import os
-import shutil
 
-import pytest
-
-
-@pytest.fixture(scope="module")
-def kernel_meta():
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
-    return compiled()
+from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 
 def _find(meta, fragment):

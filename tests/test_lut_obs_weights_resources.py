@@ -1,17 +1,9 @@
 """Resource guard of the per-observation-weights LUT search (no GPU: hipcc cross-compiles): its K = 2 nb MFMA scan and
 collect kernels keep everything in registers and LDS -- no scratch, no spills -- in both dtypes."""
-import os
-import shutil
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def kernel_meta():
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
-    return compiled()
+from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 
 @pytest.mark.parametrize("frag", ["k_lutow_gemmIfLb0E", "k_lutow_gemmIfLb1E", "k_lutow_gemmIdLb0E", "k_lutow_gemmIdLb1E",

@@ -4,19 +4,9 @@ LDS (static + the dynamic size its launcher requests, LUT_SUM_SMALL_LDS_BYTES of
 fit a CU's 160 KiB."""
 import os
 import re
-import shutil
-
-import pytest
 
 from conftest import ROOT
-
-
-@pytest.fixture(scope="module")
-def kernel_meta():
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
-    return compiled()
+from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 
 def launcher_constants():

@@ -1,17 +1,9 @@
 """Resource guard of the wide LUT search (no GPU: hipcc cross-compiles): the K-streamed MFMA scan and collect kernels of
 spart_lut_topk_wide keep everything in registers and LDS -- no scratch, no spills -- in both dtypes."""
-import os
-import shutil
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def kernel_meta():
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
-    return compiled()
+from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 
 @pytest.mark.parametrize("frag", ["k_lutw_gemmIfLb0E", "k_lutw_gemmIfLb1E", "k_lutw_gemmIdLb0E", "k_lutw_gemmIdLb1E"])

@@ -1,18 +1,7 @@
 """Register, scratch and LDS budget of k_columns_srf, the SRF-convolved column kernel (no GPU needed: device assembly
 metadata).  It runs beside k_columns at the same four waves per SIMD: at most 128 VGPRs, nothing spilled, no scratch, and
 no more LDS than the float64 k_columns itself."""
-import os
-import shutil
-
-import pytest
-
-
-@pytest.fixture(scope="module")
-def kernel_meta():
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_meta import kernel_meta as compiled      # memoised: one device compile per pytest process
-    return compiled()
+from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 
 def _find(meta, fragment):
@@ -32,12 +21,8 @@ def test_srf_column_kernel_fits_four_waves_without_spills(kernel_meta):
         assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, (name, k)
 
 
-def test_srf_column_kernel_uses_no_more_lds_than_k_columns():
-    """(the LDS figure comes from each kernel's own descriptor block: helpers/kernel_lds.py)"""
-    if not any(c and os.path.exists(c) for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc"))):
-        pytest.skip("hipcc not available")
-    from helpers.kernel_lds import kernel_lds
-    lds = kernel_lds()
+def test_srf_column_kernel_uses_no_more_lds_than_k_columns(kernel_meta):
+    lds = {n: k["group_segment_fixed_size"] for n, k in kernel_meta.items()}
     base = [v for n, v in lds.items() if "k_columnsId" in n]              # the float64 column kernels
     srf = {n: v for n, v in lds.items() if "k_columns_srfI" in n}
     assert base and srf

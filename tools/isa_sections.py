@@ -151,13 +151,17 @@ def budget(lines, frag, secmap, k0, k1, rank=0):
     return name, counts, sum(1 for l in body if l.strip().startswith("v_"))
 
 
+def valu_count(lines, frag):
+    """VALU instructions of the whole kernel, from its unit's assembly as a list of lines"""
+    return sum(1 for l in kernel_body(lines, frag)[1] if l.strip().startswith("v_"))
+
+
 def product_valu_count(src, frag):
     with tempfile.TemporaryDirectory() as d:
         o = os.path.join(d, "k.s")
         subprocess.check_call([build.hipcc(), *build.tu_flags(src), "-DSPART_FAST_MATH=1", "-S", "--cuda-device-only", "-o", o, src],
                               stderr=subprocess.DEVNULL)
-        _, body = kernel_body(open(o).read().split("\n"), frag)
-    return sum(1 for l in body if l.strip().startswith("v_"))
+        return valu_count(open(o).read().split("\n"), frag)
 
 
 def main():

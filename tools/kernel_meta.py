@@ -17,4 +17,4 @@ if __name__ == "__main__":
     for d, (k, v) in zip(dem, names.items()):
         d = re.sub(r"\(.*", "", d).replace("void spart::", "")
         print(f"{d:60s} vgpr {v['vgpr_count']:4d} sgpr {v['sgpr_count']:4d} scratch {v['private_segment_fixed_size']:5d} "
-              f"lds {v.get('group_segment_fixed_size', 0):6d} spill v{v['vgpr_spill_count']} s{v['sgpr_spill_count']}")
+              f"lds {v['group_segment_fixed_size']:6d} spill v{v['vgpr_spill_count']} s{v['sgpr_spill_count']}")
