@@ -40,4 +40,11 @@ print("  refined        :", np.round(err_fit, 4), " median 1-sigma / range:", np
 print("cost went down for", float((res["refined_cost"] < res["refined_cost0"]).mean()) * 100, "% of the spectra; median cost ratio",
       float(np.median(res["refined_cost"] / res["refined_cost0"])))
 assert (res["refined_cost"] <= res["refined_cost0"]).all()
+
+# the same fit as optimal estimation: the mean and spread of the k rows found become a Gaussian prior on the four parameters
+# (knn_prior), the cost gains its term and refined_std is the linearised posterior 1-sigma
+oe = retrieve(out, obs, 10, refine=names, refine_opts={"n_iter": 8, "prior": "knn"})
+err_oe = np.median(np.abs(oe["refined"] - truth[:, cols]) / span, axis=0)
+print("  with knn prior :", np.round(err_oe, 4), " median 1-sigma / range:", np.round(np.nanmedian(oe["refined_std"], axis=0) / span, 4))
+assert (oe["refined_cost"] <= oe["refined_cost0"]).all()
 print("refined", len(names), "parameters of", obs.shape[0], "spectra")

@@ -62,8 +62,9 @@ extern "C" {
  *  10: spart_lut_topk_obs_weights, spart_lut_topk_obs_weights_workspace_bytes, spart_lut_topk_obs_weights_stats
  *  11: spart_lut_summarise
  *  12: spart_srf_support; spart_materialize.R_TOC_srf ... rdd_srf
- *  13: spart_refine, spart_refine_workspace_bytes, spart_refine_opt */
-#define SPART_ABI_VERSION 13
+ *  13: spart_refine, spart_refine_workspace_bytes, spart_refine_opt
+ *  14: spart_refine_opt.prior_per_obs, prior_mean, prior_weight */
+#define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
 #define SPART_F64 1
@@ -393,6 +394,9 @@ int spart_lut_summarise(spart_ctx *ctx, int64_t B, int P, const double *params, 
  *   free_cols HOST (F,): the distinct columns 0 ... 26 that are fitted, 1 <= F <= 16;  lo, hi HOST (F,): finite, lo < hi
  *   obs (M, nb), weights NULL / (nb,) / (M, nb) (opt->weights_per_obs = 1): device memory, float64.  A weight of exactly 0
  *             skips its band and obs may be NaN there (the mask rule of spart_lut_topk_obs_weights)
+ *   opt->prior_mean, opt->prior_weight  both NULL (no prior), or a Gaussian prior on the free parameters (optimal estimation):
+ *             mu_f and p_f = 1 / sigma_f^2, (F,) or (M, F) row-major (opt->prior_per_obs = 1), device memory, float64.  A weight
+ *             of exactly 0 puts no prior on that parameter and mu_f may be NaN there
  *   x (M, F), cost (M,): required.  cost0 (M,), std (M, F), n_accept (M,) int32, y (M, nb): each may be NULL
  * Definition (tools/refine_defined.py is the same text in numpy; float64, no FMA contraction, IEEE division and sqrt; every
  * sum and solve in one order, so the result is one defined number whatever the batch):
@@ -401,28 +405,33 @@ int spart_lut_summarise(spart_ctx *ctx, int64_t B, int P, const double *params, 
  *   for it = 0 ... n_iter (n_iter + 1 forward calls; call 0 evaluates the start):
  *     rows    p_0 = base with the free columns set to t; p_f = p_0 with column free[f-1] set to t_f + s_f h_f, s_f = +1 if
  *             t_f + h_f <= hi_f else -1;  Y_0 ... Y_F = the chosen sensor column of the rows
- *     cost    c_t = 0; for j ascending: w_j == 0 skips the band, else d_j = Y_0j - obs_j, c_t = c_t + (w_j d_j) d_j
+ *     cost    c_t = 0; for j ascending: w_j == 0 skips the band, else d_j = Y_0j - obs_j, c_t = c_t + (w_j d_j) d_j;
+ *             then, with a prior, for f ascending: p_f == 0 skips, else e_f = t_f - mu_f, c_t = c_t + (p_f e_f) e_f
  *     decide  accept iff c_t < c (a NaN never is).  If the START is not accepted (cost0 not finite, or any negative / NaN /
- *             infinite weight) the observation is dead: x = the clipped start, cost = cost0 = c_t, n_accept = -1, std = NaN,
+ *             infinite band or prior weight) the observation is dead: x = the clipped start, cost = cost0 = c_t, n_accept = -1, std = NaN,
  *             y = Y_0, and nothing about it changes afterwards.
  *             accept: x = t, c = c_t, r_j = d_j, J_jf = (Y_fj - Y_0j) / (s_f h_f), y = Y_0; for it > 0 also
  *             lambda = max(lambda / 10, 1e-12), n_accept += 1.  reject: lambda = min(lambda 10, 1e12).
  *     propose (not after it = n_iter) with bands of weight 0 skipped in every sum:
  *             A_ab = sum_j (w_j J_ja) J_jb for a >= b (the lower triangle; j ascending), g_a = sum_j (w_j J_ja) r_j,
+ *             then, with a prior, for a ascending with p_a != 0: A_aa = A_aa + p_a, g_a = g_a + p_a e_a (e of the trial just
+ *             accepted); these augmented sums are the state of the accepted point (what a rejection restores),
  *             D_a = A_aa if A_aa > 0 else 1, B = A with B_aa = A_aa + lambda D_a;  B delta = -g by Cholesky B = L L^T in
  *             textbook row order (sums over k ascending), forward and back substitution; a pivot !(s > 0) or a non-finite
  *             delta_f gives delta = 0;  t = clip(x + delta).  A delta of 0 re-evaluates x, is not accepted and raises lambda:
  *             the intended handling of singular systems.  There is no early exit: converged observations keep proposing.
  *   std     from the undamped A of the last accepted point: A = L L^T; for each f solve L z = e_f; var_f = sum_{k >= f} z_k^2
  *           (k ascending), std_f = sqrt(var_f); all NaN when the factorisation fails.  With weights = 1 / sigma^2 this is the
- *           linearised 1-sigma uncertainty of the retrieved parameter.
+ *           linearised 1-sigma uncertainty of the retrieved parameter; with a prior A is J^T W J + S_a^-1, so std is the
+ *           linearised posterior 1-sigma.  cost and cost0 include the prior's term; y, r and J do not know of it.
  * So cost <= cost0, and the state after n_iter = k is a prefix of n_iter = k + 1.
  * Observations go in chunks of (1 << 19) / (F + 1), so the workspace is bounded whatever M is: the parameter table
  * (27, (F + 1) Mc), three column blocks, the optimiser's state and spart_workspace_bytes(SPART_F64, (F + 1) Mc) for
  * Mc = min(M, chunk).  spart_refine_workspace_bytes is 0 for sizes the call refuses.
  * Refused before anything is launched or written: SPART_ERR_INVALID for F outside 1 ... 16, a free column outside 0 ... 26 or a
  * duplicate, lo >= hi or a non-finite bound, n_iter outside 0 ... 100, column outside 0 ... 2, a negative or non-finite rel_step /
- * lambda0, a NULL required pointer, M < 0 or M > 2e9; SPART_ERR_NOSENSOR for a context without sensor; SPART_ERR_WORKSPACE for
+ * lambda0, a NULL required pointer, exactly one of prior_mean / prior_weight NULL, prior_per_obs outside 0 / 1, M < 0 or
+ * M > 2e9; SPART_ERR_NOSENSOR for a context without sensor; SPART_ERR_WORKSPACE for
  * a workspace that is missing or too small.  M = 0 launches nothing. */
 typedef struct spart_refine_opt {
   int32_t column;          /* 0 R_TOC, 1 R_TOA, 2 L_TOA */
@@ -432,6 +441,9 @@ typedef struct spart_refine_opt {
   int32_t nlayers;         /* as spart_materialize.nlayers, 0 = 60 */
   double rel_step;         /* 0 = 1e-3 */
   double lambda0;          /* 0 = 1e-2 */
+  int32_t prior_per_obs;        /* 0: prior_mean / prior_weight are (F,); 1: (M, F) row-major */
+  const double *prior_mean;     /* device memory, float64; NULL with prior_weight NULL = no prior */
+  const double *prior_weight;   /* device memory, float64: 1 / sigma_f^2; exactly 0 = no prior on that parameter */
 } spart_refine_opt;
 size_t spart_refine_workspace_bytes(const spart_ctx *ctx, int64_t M, int F);
 int spart_refine(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,

@@ -1078,7 +1078,10 @@ static int refine_impl(spart_ctx* ctx, int64_t M, const RefineCfg& cfg, int F, c
       hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
                          obs + m0 * nb, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
                          o.weights_per_obs ? 1 : 0, (const double*)dcfg, (const int32_t*)dfree, table, mc, F, nb, W, it,
-                         it == o.n_iter ? 1 : 0, t, A, lam, na, oc);
+                         it == o.n_iter ? 1 : 0, t, A, lam, na, oc,
+                         o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * F : o.prior_mean) : nullptr,
+                         o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * F : o.prior_weight) : nullptr,
+                         o.prior_per_obs ? 1 : 0);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -1282,6 +1285,10 @@ int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARA
     return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
   if (!(o.rel_step >= 0.0) || !(o.lambda0 >= 0.0) || std::isinf(o.rel_step) || std::isinf(o.lambda0))
     return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
+  if (o.prior_per_obs != 0 && o.prior_per_obs != 1)
+    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: (F,), 1: (M, F))", who, o.prior_per_obs);
+  if (!o.prior_mean != !o.prior_weight)
+    return fail(SPART_ERR_INVALID, "%s: prior_mean and prior_weight come together (both NULL = no prior)", who);
   if (o.rel_step == 0.0) o.rel_step = 1e-3;
   if (o.lambda0 == 0.0) o.lambda0 = 1e-2;
   RefineCfg cfg;

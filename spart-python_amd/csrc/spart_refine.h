@@ -63,6 +63,19 @@ SPART_HD double refine_mac(double acc, double w, double a, double b) {
   return acc + (w * a) * b;
 }
 
+// one free parameter of the prior's part of the trial cost: c + (p e) e with e = t - mu; the caller skips parameters of weight 0
+SPART_HD double refine_prior_cost(double c, double p, double t, double mu) {
+  SPART_NO_CONTRACT
+  const double e = t - mu;
+  return c + (p * e) * e;
+}
+
+// one free parameter of the prior's part of g: acc + p e (e = refine_residual(t, mu)); its part of A_aa is the plain sum A_aa + p
+SPART_HD double refine_prior_gain(double acc, double p, double e) {
+  SPART_NO_CONTRACT
+  return acc + p * e;
+}
+
 SPART_HD double refine_lambda(double lam, bool accept) {
   SPART_NO_CONTRACT
   if (accept) {
@@ -165,10 +178,13 @@ SPART_HD void refine_std(int F, const double* A, int SA, double* L, int SL, doub
 // W nb doubles, so a tile of REFINE_JT bands is staged through LDS with band-contiguous lanes and then read one column per
 // lane.  Everything indexed by the run-time F lives in LDS at [k][o], row stride W + 1 doubles (lane o touches column o only;
 // the odd stride spreads the band-contiguous staging stores over the banks): no register array is indexed by a run-time
-// value, so nothing goes to scratch.
-//   pass 1   lane o < W: the trial cost of observation o from block 0, bands ascending, then the decision;
+// value, so nothing goes to scratch.  The prior (pmu / ppw, NULL without one) has no LDS rows: lane o reads its observation's
+// at most 2 F doubles from global memory in the two per-observation phases that use them.
+//   pass 1   lane o < W: the trial cost of observation o from block 0, bands ascending, then the prior's terms (f ascending),
+//            then the decision;
 //   pass 2   (only for accepted or newly dead observations) all F + 1 blocks: y, r_j, J_jf in place of Y_f, then the
-//            P = F (F + 1) / 2 + F sums of an observation dealt to its 64 / W lanes, each one sequential in j;
+//            P = F (F + 1) / 2 + F sums of an observation dealt to its 64 / W lanes, each one sequential in j; then lane
+//            o < W adds the prior's p_a to A_aa and p_a e_a to g_a, so the state holds the augmented sums;
 //   finish   lane o < W: lambda, then either the damped solve and the F (F + 1) new table entries, or (last call) std.
 // The per-entry order is the definition's whatever W is, so the mapping is free of the result.
 constexpr int REFINE_JT = 16;                // bands per LDS tile (128 B of a row)
@@ -248,13 +264,15 @@ struct RefineOut {
 };
 
 // Once per iteration `it` (last: it == n_iter).  obs / wts are the chunk's rows ((Mc, nb); wts NULL, or (nb,) with
-// wper == 0, or the chunk's rows with wper == 1).
+// wper == 0, or the chunk's rows with wper == 1).  pmu / ppw: both NULL (no prior), or the prior's mean and weight, (F,) with
+// pper == 0 or the chunk's rows of (M, F) with pper == 1.
 __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ cols, const double* __restrict__ obs,
                                                     const double* __restrict__ wts, int wper, const double* __restrict__ cfg,
                                                     const int32_t* __restrict__ cfg_free, double* __restrict__ table, int Mc, int F,
                                                     int nb, int W, int it, int last, double* __restrict__ st,
                                                     double* __restrict__ sA, double* __restrict__ slam, int32_t* __restrict__ sna,
-                                                    RefineOut out) {
+                                                    RefineOut out, const double* __restrict__ pmu,
+                                                    const double* __restrict__ ppw, int pper) {
   SPART_NO_CONTRACT
   extern __shared__ __attribute__((aligned(16))) char refine_smem[];
   constexpr int JT = REFINE_JT;
@@ -278,6 +296,8 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
   const int64_t R = (int64_t)(F + 1) * Mc;
   const double* obs_g = obs + (int64_t)g0 * nb;
   const double* wts_g = wts ? (wper ? wts + (int64_t)g0 * nb : wts) : nullptr;
+  const bool prior = ppw != nullptr;                     // (kernel-uniform)
+  const int64_t pm = pper && mine ? (int64_t)m * F : 0;  // (lanes < W) where this lane's prior starts
 
   // the weight and observation tile of bands j0 .. j0 + JT - 1: lanes run along the bands (out of range: weight 0)
   auto stage_obs = [&](int j0) {
@@ -314,6 +334,13 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
         ct = refine_cost_band(ct, w, Yl[jj * WP + lane], rl[jj * WP + lane]);
       }
   }
+  if (prior && mine)
+    for (int f = 0; f < F; ++f) {
+      const double p = ppw[pm + f];
+      if (refine_bad_weight(p)) bad = true;
+      if (p == 0.0) continue;
+      ct = refine_prior_cost(ct, p, st[(int64_t)m * F + f], pmu[pm + f]);
+    }
   // ---- the decision
   int code = 0, na = 0;
   double lam = 0.0;
@@ -408,6 +435,18 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
       }
     }
     __syncthreads();
+    if (prior) {
+      if (mine && code == 1)
+        for (int a = 0; a < F; ++a) {
+          const double p = ppw[pm + a];
+          if (p == 0.0) continue;
+          double* Aaa = Al + refine_tri(a, a) * WP + lane;
+          double* ga = Al + (nt + a) * WP + lane;
+          *Aaa = *Aaa + p;
+          *ga = refine_prior_gain(*ga, p, refine_residual(xl[a * WP + lane], pmu[pm + a]));
+        }
+      __syncthreads();
+    }
   }
   // accepted: the new sums become the state; rejected: the state's sums come back
   {

@@ -8,7 +8,7 @@ from .api import (BSM, PROSPECT_5D, SAILH, SMAC, SPART, Angles, AtmosphericOptic
                   calculate_leafangles, calculate_spectral_convolution, calculate_tav, soilwat, load_ET_parameters,
                   load_optical_parameters, load_sensor_info, set_leaf_refl_trans_assumptions,
                   set_soil_refl_trans_assumptions)
-from .engine import Engine, get_engine  # noqa: F401
+from .engine import Engine, get_engine, knn_prior  # noqa: F401
 from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401

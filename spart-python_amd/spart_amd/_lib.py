@@ -9,7 +9,7 @@ LIB_PATH = os.path.normpath(os.path.join(HERE, "..", "libspart_hip.so"))
 SPART_F32, SPART_F64 = 0, 1
 NPARAM, NCOEF, NWL, NWLS, NLINCL = 27, 48, 2001, 2162, 13
 NLAYERS = 60            # SPART_NLAYERS: CanopyStructure's default (sailh.py:345)
-ABI_VERSION = 13        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
+ABI_VERSION = 14        # SPART_ABI_VERSION of include/spart_hip.h this binding was written against
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 vp = ctypes.c_void_p
@@ -34,7 +34,8 @@ class SpartMaterialize(ctypes.Structure):
 
 class SpartRefineOpt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("column", "n_iter", "weights_per_obs", "fast_prelude", "nlayers")] + [
-        ("rel_step", ctypes.c_double), ("lambda0", ctypes.c_double)]
+        ("rel_step", ctypes.c_double), ("lambda0", ctypes.c_double), ("prior_per_obs", ctypes.c_int32), ("prior_mean", vp),
+        ("prior_weight", vp)]
 
 
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column

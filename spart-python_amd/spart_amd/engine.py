@@ -109,11 +109,89 @@ def lut_weights_kind(shape, M, nb):
     raise ValueError(f"weights has shape {shape}, expected (nb,) = ({nb},) or (M, nb) = ({M}, {nb})")
 
 
-def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=None):
+def _prior_plan(names, prior):
+    """refine_plan's prior checks: {name: (mean, sigma)} -> {"mean", "weight": F arrays, each () or (n,); "rows": n or None}"""
+    if not isinstance(prior, dict):
+        raise ValueError(f"prior = {prior!r}, expected a dict {{name: (mean, sigma)}}")
+    stray = [n for n in prior if n not in names]
+    if stray:
+        raise ValueError(f"prior: {stray} not free")
+    mean, weight, rows = [np.float64(0.0)] * len(names), [np.float64(0.0)] * len(names), None
+    for n, entry in prior.items():
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"prior[{n!r}]: expected (mean, sigma)")
+        mu, sigma = (np.asarray(v, dtype=np.float64) for v in entry)
+        if not (np.all(sigma > 0) and not np.isnan(sigma).any()):
+            raise ValueError(f"prior[{n!r}]: sigma must be > 0 (finite, or inf for no prior), got {entry[1]!r}")
+        for what, v in (("mean", mu), ("sigma", sigma)):
+            if v.ndim > 1 or (v.ndim == 1 and rows not in (None, v.shape[0])):
+                raise ValueError(f"prior[{n!r}]: {what} has shape {v.shape}, expected a scalar or (M,)" +
+                                 (f" = ({rows},)" if rows is not None else ""))
+            if v.ndim == 1:
+                rows = int(v.shape[0])
+        with np.errstate(over="ignore"):
+            w = 1.0 / (sigma * sigma)
+        i = names.index(n)
+        mean[i], weight[i] = mu, w
+    return {"mean": mean, "weight": weight, "rows": rows}
+
+
+def prior_arrays(plan_prior, M):
+    """the prior of a refine_plan for M observations -> (mean, weight) float64, (F,) or, with any array-valued entry, (M, F)"""
+    rows = plan_prior["rows"]
+    if rows is None:
+        return np.array(plan_prior["mean"], dtype=np.float64), np.array(plan_prior["weight"], dtype=np.float64)
+    if rows != M:
+        raise ValueError(f"prior: arrays of {rows} values for {M} observations; expected scalars or (M,) = ({M},)")
+    return tuple(np.ascontiguousarray(np.stack([np.broadcast_to(v, (M,)) for v in plan_prior[k]], axis=1), dtype=np.float64)
+                 for k in ("mean", "weight"))
+
+
+def _prior_tensor_shapes(prior_mean, prior_weight, M, F):
+    """the ready-made form of a prior: both given, both (F,) or both (M, F) -> 1 for (M, F), else 0"""
+    if prior_mean is None or prior_weight is None:
+        raise ValueError("prior_mean and prior_weight come together")
+    sm, sw = (tuple(int(n) for n in (v.shape if hasattr(v, "shape") else np.shape(v))) for v in (prior_mean, prior_weight))
+    if sm != sw or sm not in ((F,), (M, F)):
+        raise ValueError(f"prior_mean {sm} and prior_weight {sw}: expected both (F,) = ({F},) or both (M, F) = ({M}, {F})")
+    return int(len(sm) == 2)
+
+
+def knn_prior(mean, std, lo, hi, floor=0.05):
+    """A Gaussian prior for Engine.refine from the summary of the k nearest LUT rows (Engine.lut_summarise / retrieve's mean and
+    std of the free columns): sigma = maximum(std, floor * (hi - lo)), weight = 1.0 / (sigma * sigma), each one rounded
+    operation in float64, so numpy arrays and torch tensors give the same bits.  ``mean``, ``std`` (M, F) (numpy or torch);
+    ``lo``, ``hi`` (F,) the bounds of the free parameters.  ``floor`` (default 0.05: a twentieth of the range) is an option, not
+    a tolerance: it keeps a set of k identical rows (std = 0) from pinning the parameter.  An observation without rows (a NaN
+    mean or std) gets weight 0 and mean 0: no prior.  -> (prior_mean, prior_weight), like the inputs."""
+    floor = float(floor)
+    if not (np.isfinite(floor) and floor >= 0):
+        raise ValueError(f"floor = {floor!r}, expected a finite value >= 0")
+    width = floor * (np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64))
+    if hasattr(mean, "device") and not isinstance(mean, np.ndarray):            # torch tensors
+        import torch
+        mean, std = mean.to(torch.float64), torch.as_tensor(std).to(device=mean.device, dtype=torch.float64)
+        sigma = torch.maximum(std, torch.as_tensor(width, device=mean.device).expand_as(std))
+        weight = 1.0 / (sigma * sigma)
+        none = torch.isnan(mean) | torch.isnan(std)
+        zero = torch.zeros((), dtype=torch.float64, device=mean.device)
+        return torch.where(none, zero, mean), torch.where(none, zero, weight)
+    mean, std = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        sigma = np.maximum(std, width)
+        weight = 1.0 / (sigma * sigma)
+    none = np.isnan(mean) | np.isnan(std)
+    return np.where(none, 0.0, mean), np.where(none, 0.0, weight)
+
+
+def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=None, prior=None):
     """The host-side argument checks of Engine.refine / spart_refine, none of which needs a device.  ``free``: names from
     workloads.PARAM_NAMES, 1 ... 16 of them, each once; ``bounds``: {name: (lo, hi)} for free names only, finite with lo < hi,
-    the others from ``default_ranges`` (None = workloads.RANGES; a name with neither is a ValueError).
-    -> dict: names, cols (int32), lo, hi (float64), column (0 / 1 / 2), n_iter, rel_step, lambda0."""
+    the others from ``default_ranges`` (None = workloads.RANGES; a name with neither is a ValueError).  ``prior``:
+    {name: (mean, sigma)} for free names only, each a scalar or an (M,) array (any array makes the prior per-observation);
+    sigma > 0, finite or np.inf (no prior on that name, like a name that is not listed); the weight is 1.0 / (sigma * sigma).
+    -> dict: names, cols (int32), lo, hi (float64), column (0 / 1 / 2), n_iter, rel_step, lambda0, prior (None, or what
+    prior_arrays turns into (mean, weight) once M is known)."""
     names = [str(n) for n in free]
     unknown = [n for n in names if n not in workloads.PARAM_NAMES]
     if unknown:
@@ -144,7 +222,7 @@ def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=
             raise ValueError(f"{what} = {v!r}, expected a finite value > 0")
     return {"names": names, "cols": np.array([workloads.PARAM_NAMES.index(n) for n in names], dtype=np.int32), "lo": lo, "hi": hi,
             "column": _lib.REFINE_COLUMNS.index(column), "n_iter": int(n_iter), "rel_step": float(rel_step),
-            "lambda0": float(lambda0)}
+            "lambda0": float(lambda0), "prior": None if prior is None else _prior_plan(names, prior)}
 
 
 # ---- the static tables a context is built from (spart_tables): the reference reads them from the dicts it is HANDED at call
@@ -779,7 +857,7 @@ class Engine:
         return res
 
     def refine(self, params, obs, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
-               lidf="literal", nlayers=None, _plan=None):
+               lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, _plan=None):
         """Bounded Levenberg-Marquardt refinement of the ``free`` parameters of every start row against its observation, on the
         device (include/spart_hip.h: spart_refine, which defines every sum and solve; tools/refine_defined.py is the numpy form).
         params : the start rows, as for run(): a (27, M) float64 device tensor or a list of 27 scalars / arrays (each 1 or M values)
@@ -790,9 +868,18 @@ class Engine:
                   ``std`` the linearised 1-sigma uncertainty
         n_iter : proposals (0 ... 100): n_iter + 1 forward evaluations of (F + 1) M rows; there is no early exit
         lidf, nlayers : as for run()
+        prior : {name: (mean, sigma)} for some free names, scalars or (M,) arrays: a Gaussian prior (optimal estimation); the cost
+                gains sum_f (t_f - mean_f)^2 / sigma_f^2, and ``std`` becomes the linearised posterior 1-sigma
+        prior_mean, prior_weight : the same prior ready-made, (F,) or (M, F) float64 (weight = 1 / sigma^2, exactly 0 = none;
+                e.g. knn_prior's); tensors already on the device are used where they are.  Not together with ``prior``
         -> dict of device tensors x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: the start could not be
         evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names."""
-        plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0)
+        ready = prior_mean is not None or prior_weight is not None
+        if prior is not None and ready:
+            raise ValueError("prior and prior_mean / prior_weight exclude each other")
+        plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
+        if plan.get("prior") is not None and ready:
+            raise ValueError("prior and prior_mean / prior_weight exclude each other")
         if lidf not in ("literal", "newton"):
             raise ValueError("lidf must be 'literal' or 'newton'")
         nl = self._nlayers(nlayers)
@@ -813,9 +900,15 @@ class Engine:
             plist = fill_nulls(params)
             batch_size(plist, B=M)
         kind = lut_weights_kind(None if weights is None else (tuple(weights.shape) if hasattr(weights, "shape") else np.shape(weights)), M, nb)
+        F = len(plan["names"])
+        per_obs = 0
+        if ready:
+            per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, F)
+        elif plan.get("prior") is not None:
+            prior_mean, prior_weight = prior_arrays(plan["prior"], M)
+            per_obs = int(prior_mean.ndim == 2)
         # ---- the device from here on
         torch = self.torch
-        F = len(plan["names"])
         if block:
             P = params.to(device=self.device, dtype=torch.float64)
             cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
@@ -832,6 +925,9 @@ class Engine:
         opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=1 if kind == "per_observation" else 0,
                                   fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
                                   lambda0=plan["lambda0"])
+        if prior_mean is not None:
+            pm, pw = (torch.as_tensor(v).to(device=self.device, dtype=torch.float64).contiguous() for v in (prior_mean, prior_weight))
+            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
         nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.calls["spart_refine"] += 1

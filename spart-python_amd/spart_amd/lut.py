@@ -446,13 +446,17 @@ def _np_dtype(name):
 
 
 def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
-           lidf="literal", nlayers=None, sensor_info=None, device=None):
+           lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None, prior_weight=None):
     """The host form of Engine.refine: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays (run()'s
-    conventions), ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``, a sensorinfo dict).
+    conventions), ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``, a sensorinfo dict);
+    ``prior`` or ``prior_mean`` / ``prior_weight`` as for Engine.refine.
     -> dict of numpy arrays x, cost, cost0, std, n_accept, y and the list ``names``.  Every argument check that needs no
     device runs before one is asked for."""
-    from .engine import refine_plan
-    plan = refine_plan(free, bounds, n_iter, column, rel_step, lambda0)
+    from .engine import _prior_tensor_shapes, prior_arrays, refine_plan
+    ready = prior_mean is not None or prior_weight is not None
+    if prior is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    plan = refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
     if lidf not in ("literal", "newton"):
         raise ValueError("lidf must be 'literal' or 'newton'")
     o = np.asarray(obs, dtype=np.float64)
@@ -471,12 +475,18 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
     if weights is not None:
         from .engine import lut_weights_kind
         lut_weights_kind(np.shape(weights), o.shape[0], o.shape[1])
+    if ready:
+        _prior_tensor_shapes(prior_mean, prior_weight, o.shape[0], len(plan["names"]))
+    elif plan["prior"] is not None:
+        prior_arrays(plan["prior"], o.shape[0])
     eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
-    res = eng.refine(params, o, free, weights=weights, lidf=lidf, nlayers=nlayers, _plan=plan)
+    res = eng.refine(params, o, free, weights=weights, lidf=lidf, nlayers=nlayers, prior_mean=prior_mean, prior_weight=prior_weight,
+                     _plan=plan)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
-REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers")
+REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor")
+REFINE_KEYS = {"refined": "x", "refined_std": "std", "refined_cost": "cost", "refined_cost0": "cost0", "refined_accepts": "n_accept"}
 
 
 def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
@@ -500,6 +510,14 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     if sensor_info is None and not isinstance(meta.get("sensor"), str):
         raise ValueError("retrieve(refine=...): meta.json names no packaged sensor; pass the LUT's sensor_info=")
     names, cols = _param_columns(list(refine))
+    prior = opts.get("prior")
+    if not (prior is None or isinstance(prior, dict) or (isinstance(prior, str) and prior == "knn")):
+        raise ValueError(f'refine_opts["prior"] = {prior!r}, expected a dict {{name: (mean, sigma)}} or "knn"')
+    if "prior_floor" in opts:
+        from .engine import knn_prior
+        if not (isinstance(prior, str) and prior == "knn"):
+            raise ValueError('refine_opts["prior_floor"] goes with "prior": "knn"')
+        knn_prior(np.zeros((0, 1)), np.zeros((0, 1)), [0.0], [1.0], floor=opts["prior_floor"])      # (its own check of floor)
     P = np.asarray(params)
     ranges = {}
     for n, c in zip(names, cols):                     # the LUT's own extent of every free column
@@ -510,15 +528,18 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
             raise ValueError(f"retrieve(refine=...): column {n!r} is constant in the LUT ({lo}); give refine_opts="
                              f"{{'bounds': {{{n!r}: (lo, hi)}}}} or leave it out")
     plan = refine_plan(names, opts.get("bounds"), opts.get("n_iter", 10), "R_TOC", opts.get("rel_step", 1e-3),
-                       opts.get("lambda0", 1e-2), default_ranges=ranges)
+                       opts.get("lambda0", 1e-2), default_ranges=ranges, prior=prior if isinstance(prior, dict) else None)
     return plan, opts, meta.get("sensor"), sensor_info
 
 
 def _refine_rows(setup, lut_dir, obs, idx, column, weights, device):
-    """the refinement of retrieve(): start = params.npy[idx[:, 0]]; observations without a row get NaN and -1"""
+    """the refinement of retrieve(): start = params.npy[idx[:, 0]]; observations without a row get NaN and -1.  The "knn" prior
+    is knn_prior of Engine.lut_summarise on the free columns of the rows found, whatever summarised the other keys."""
+    from .engine import knn_prior, prior_arrays
     plan, opts, sensor, sensor_info = setup
     _, params, _ = load_lut(lut_dir)
     F, M = len(plan["names"]), idx.shape[0]
+    dict_prior = None if plan["prior"] is None else prior_arrays(plan["prior"], M)
     out = {"refined": np.full((M, F), np.nan), "refined_cost": np.full(M, np.nan), "refined_cost0": np.full(M, np.nan),
            "refined_std": np.full((M, F), np.nan), "refined_accepts": np.full(M, -1, dtype=np.int32),
            "refined_names": list(plan["names"])}
@@ -530,11 +551,18 @@ def _refine_rows(setup, lut_dir, obs, idx, column, weights, device):
         if w is not None and w.ndim == 2:
             w = w[ok]
         eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
-        plan = dict(plan, column=("R_TOC", "R_TOA", "L_TOA").index(column))
+        plan = dict(plan, column=("R_TOC", "R_TOA", "L_TOA").index(column), prior=None)
+        pm = pw = None
+        if dict_prior is not None:
+            pm, pw = (a[ok] if a.ndim == 2 else a for a in dict_prior)
+        elif opts.get("prior") == "knn":
+            import torch
+            free = np.ascontiguousarray(np.asarray(params)[:, plan["cols"]], dtype=np.float64)
+            near = eng.lut_summarise(torch.as_tensor(free).to(eng.device), torch.as_tensor(np.ascontiguousarray(idx[ok])).to(eng.device))
+            pm, pw = knn_prior(near["mean"], near["std"], plan["lo"], plan["hi"], floor=opts.get("prior_floor", 0.05))
         r = eng.refine(list(np.ascontiguousarray(start.T)), np.asarray(obs, dtype=np.float64)[ok], plan["names"], weights=w,
-                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), _plan=plan)
-        for key, name in (("refined", "x"), ("refined_cost", "cost"), ("refined_cost0", "cost0"), ("refined_std", "std"),
-                          ("refined_accepts", "n_accept")):
+                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw, _plan=plan)
+        for key, name in REFINE_KEYS.items():
             out[key][ok] = r[name].cpu().numpy()
     return out
 
@@ -561,13 +589,19 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     ``refined_cost``, ``refined_cost0`` (the cost at the start: cost[:, 0] of a float64 LUT bit for bit), ``refined_std``
     (M, F), ``refined_accepts`` (M,) int32 and ``refined_names``; observations without a row (idx -1) get NaN and -1.
     ``refine_opts``: bounds / n_iter / rel_step / lambda0 / lidf / nlayers of Engine.refine; the default bounds are the LUT's
-    own minimum and maximum of every free column (a constant column without a bound is a ValueError).  The sensor is
+    own minimum and maximum of every free column (a constant column without a bound is a ValueError).  ``"prior"``: a dict
+    {name: (mean, sigma)} as for Engine.refine, or ``"knn"``: knn_prior of the mean and std of the free columns of the k rows
+    found (Engine.lut_summarise, whatever ``summary`` says: that summary is one defined number), with the plan's bounds and
+    ``"prior_floor"`` (default 0.05); ``refined_std`` is then the linearised posterior 1-sigma.  The sensor is
     meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band_model="srf" LUT and for
     ``shard=True`` under a process group of more than one rank (neither is built yet)."""
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
     setup = _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info)
+    if setup is not None and setup[0]["prior"] is not None:
+        from .engine import prior_arrays
+        prior_arrays(setup[0]["prior"], np.shape(obs)[0])                # (an array that is not (M,): refused before the search)
     out = _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, summary, params_cols, names, cols)
     if setup is not None:
         out.update(_refine_rows(setup, lut_dir, obs, out["idx"], column, weights, device))
@@ -616,7 +650,7 @@ class _DeviceStage:
     """The device side of retrieve_stream: the LUT column and the parameter columns, uploaded once; two sets of chunk
     buffers; three streams.  upload / launch / download are what _run_pipeline calls for buffer j = chunk number % 2."""
 
-    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights):
+    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights, refine=None):
         import torch
         self.torch, self.eng, self.lut, self.par, self.k, self.dtype = torch, eng, lut_t, par_t, k, dtype
         dev = self.dev = eng.device
@@ -631,21 +665,32 @@ class _DeviceStage:
         self.used = [False, False]
         self.keep = [None, None]        # host sources of the upload in flight on buffer j
         self.res = [None, None]         # device results of the chunk in buffer j, until its download is done
+        # retrieve_stream(refine=...): a _StreamRefine.  The fit runs in float64: a float32 LUT's chunks go up a second time,
+        # as float64 (obs64 / w64), so that it sees the numbers retrieve() hands to Engine.refine
+        self.refine = refine
+        self.wide = refine is not None and lut_t.dtype != torch.float64
+        if self.wide:
+            self.obs64 = [torch.empty((chunk, nb), dtype=torch.float64, device=dev) for _ in range(2)]
+            self.w64 = [torch.empty((chunk, nb), dtype=torch.float64, device=dev) for _ in range(2)] if per_obs_weights else None
 
     def _tensor(self, a):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")          # read-only inputs (memmaps opened "r") are only read
             return self.torch.from_numpy(a)
 
-    def upload(self, j, obs, w):
+    def upload(self, j, obs, w, obs64=None, w64=None):
         n = obs.shape[0]
         with self.torch.cuda.stream(self.h2d):
             if self.used[j]:
                 self.h2d.wait_event(self.ev_done[j])               # the kernels that read buffer j last have run
-            self.keep[j] = (obs, w)
+            self.keep[j] = (obs, w, obs64, w64)
             self.obs[j][:n].copy_(self._tensor(obs), non_blocking=True)
             if w is not None:
                 self.w[j][:n].copy_(self._tensor(w), non_blocking=True)
+            if self.wide:
+                self.obs64[j][:n].copy_(self._tensor(obs64), non_blocking=True)
+                if w64 is not None:
+                    self.w64[j][:n].copy_(self._tensor(w64), non_blocking=True)
             self.ev_in[j].record(self.h2d)
         self.used[j] = True
 
@@ -655,6 +700,10 @@ class _DeviceStage:
         idx, cost = self.eng.lut_topk(self.lut, self.obs[j][:n], self.k, weights=w, dtype=self.dtype)
         res = self.eng.lut_summarise(self.par, idx)
         res["best_cost"] = cost[:, 0].contiguous()
+        if self.refine is not None:
+            o64 = self.obs64[j][:n] if self.wide else self.obs[j][:n]
+            w64 = (self.w64[j][:n] if self.wide else w) if self.w is not None else self.refine.shared
+            res.update(self.refine.run(idx, o64, w64))
         self.res[j] = res
         self.ev_done[j].record(self.compute)
 
@@ -666,7 +715,49 @@ class _DeviceStage:
             self.d2h.synchronize()                                 # res[j] may be replaced by chunk i + 2
 
 
-def _stream_chunks(obs, weights, chunk, out, stage, npdt):
+class _StreamRefine:
+    """The refinement of one chunk of retrieve_stream, on the engine's current stream with nothing going through the host:
+    start rows gathered from the whole parameter table on the device, the "knn" prior from the chunk's own summary of the
+    free columns, Engine.refine in its device-tensor form, rows without a match overwritten with NaN / -1."""
+
+    def __init__(self, setup, eng, params, column, shared, dict_prior):
+        import torch
+        self.eng = eng                                 # the sensor's engine (the searches run on the stage's, which needs none)
+        self.plan, self.opts, _, _ = setup
+        self.plan = dict(self.plan, column=("R_TOC", "R_TOA", "L_TOA").index(column), prior=None)
+        P = np.ascontiguousarray(np.asarray(params), dtype=np.float64)
+        self.table = torch.as_tensor(P).to(eng.device)                                   # (B, 27): 216 B per row
+        self.free = self.table[:, torch.as_tensor(self.plan["cols"].astype(np.int64)).to(eng.device)].contiguous()
+        self.shared = None if shared is None else torch.as_tensor(np.ascontiguousarray(shared, dtype=np.float64)).to(eng.device)
+        self.prior = None if dict_prior is None else tuple(torch.as_tensor(a).to(eng.device) for a in dict_prior)
+        self.lo = 0                                                                      # first observation of the next chunk
+
+    def run(self, idx, obs, w):
+        import torch
+        eng = self.eng
+        from .engine import knn_prior
+        n, best = idx.shape[0], idx[:, 0]
+        start = self.table.index_select(0, best.clamp(min=0)).t().contiguous()           # (27, n)
+        pm = pw = None
+        if self.prior is not None:
+            pm, pw = (a[self.lo:self.lo + n] if a.dim() == 2 else a for a in self.prior)
+        elif self.opts.get("prior") == "knn":
+            near = eng.lut_summarise(self.free, idx)
+            pm, pw = knn_prior(near["mean"], near["std"], self.plan["lo"], self.plan["hi"], floor=self.opts.get("prior_floor", 0.05))
+        self.lo += n
+        r = eng.refine(start, obs, self.plan["names"], weights=w, lidf=self.opts.get("lidf", "literal"),
+                       nlayers=self.opts.get("nlayers"), prior_mean=pm, prior_weight=pw, _plan=self.plan)
+        none = best < 0
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=idx.device)
+        out = {}
+        for key, name in REFINE_KEYS.items():
+            v = r[name]
+            miss = none[:, None] if v.dim() == 2 else none
+            out[key] = torch.where(miss, torch.full((), -1, dtype=torch.int32, device=idx.device) if name == "n_accept" else nan, v)
+        return out
+
+
+def _stream_chunks(obs, weights, chunk, out, stage, npdt, wide=False):
     """retrieve_stream's chunk arithmetic: observations lo ... lo + n of chunk i go up as C-contiguous ``npdt`` arrays (with
     their own rows of (M, nb) ``weights``; None otherwise), and the stage's results land in rows lo ... lo + n of every array
     of ``out``.  ``stage``: upload(j, obs, w), launch(j, n), download(j, n, dest) for buffer j = i % 2 (_DeviceStage)."""
@@ -680,8 +771,9 @@ def _stream_chunks(obs, weights, chunk, out, stage, npdt):
 
     def upload(i):
         lo, n = bounds(i)
-        stage.upload(i % 2, np.ascontiguousarray(obs[lo:lo + n], dtype=npdt),
-                     None if weights is None else np.ascontiguousarray(weights[lo:lo + n], dtype=npdt))
+        o, w = obs[lo:lo + n], None if weights is None else weights[lo:lo + n]
+        more = (np.ascontiguousarray(o, dtype=np.float64), None if w is None else np.ascontiguousarray(w, dtype=np.float64)) if wide else ()
+        stage.upload(i % 2, np.ascontiguousarray(o, dtype=npdt), None if w is None else np.ascontiguousarray(w, dtype=npdt), *more)
 
     def launch(i):
         stage.launch(i % 2, bounds(i)[1])
@@ -694,7 +786,7 @@ def _stream_chunks(obs, weights, chunk, out, stage, npdt):
 
 
 def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=None, chunk=1 << 16, device=None, out=None,
-                    _stage=None):
+                    refine=None, refine_opts=None, sensor_info=None, _stage=None):
     """A scene in, parameter maps out: retrieve(summary="device") for any number of observations, in chunks.
     ``obs`` (M, nb) on the HOST (array or memmap; any M, also 0); ``weights`` None, (nb,) or (M, nb) (sliced with the chunks),
     as for invert_lut; ``params_cols`` as for retrieve.  The LUT column and the chosen parameter columns are uploaded ONCE;
@@ -704,7 +796,16 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     the nearest row, the usual quality flag), and names.  The (M, k) indices are not returned: at scene size they are the bulk
     of the download and the summary replaces them.  A pixel that matches nothing (a NaN observation without a mask, a negative
     weight) comes back with count 0 and NaN maps (best_cost +inf).  Every array equals retrieve(summary="device")'s bit for
-    bit, whatever the chunk size.  ``out``: caller-owned arrays of those shapes and dtypes (e.g. a previous call's result)."""
+    bit, whatever the chunk size.  ``out``: caller-owned arrays of those shapes and dtypes (e.g. a previous call's result).
+
+    ``refine`` / ``refine_opts`` / ``sensor_info`` as for retrieve (the same refusals): refined maps.  The WHOLE 27-column
+    parameter table is then uploaded once as well (216 B per row), and per chunk everything after the top-k stays on the
+    device and on the compute stream: the start rows are gathered from it by idx[:, 0], the "knn" prior comes from the chunk's
+    own summary of the free columns, Engine.refine takes both as device tensors.  The result (and ``out``) gains ``refined``,
+    ``refined_std`` (M, F), ``refined_cost``, ``refined_cost0`` (M,), ``refined_accepts`` (M,) int32 and ``refined_names``, each
+    equal to retrieve(summary="device", refine=...)'s bit for bit whatever the chunk size; a pixel without a row gets NaN
+    and -1.  A per-observation prior dict goes up once too, as its (M, F) float64 mean and weight."""
+    setup = _refine_setup(lut_dir, refine, refine_opts, False, None, sensor_info)
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
     names, cols = _param_columns(params_cols)
@@ -722,6 +823,14 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
         weights = np.asarray(weights)
     kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
     shapes = {**{n: ((M, P), np.float64) for n in STREAM_MAPS}, "count": ((M,), np.int32), "best_cost": ((M,), npdt)}
+    dict_prior = None
+    if setup is not None:
+        F = len(setup[0]["names"])
+        shapes.update({"refined": ((M, F), np.float64), "refined_std": ((M, F), np.float64), "refined_cost": ((M,), np.float64),
+                       "refined_cost0": ((M,), np.float64), "refined_accepts": ((M,), np.int32)})
+        if setup[0]["prior"] is not None:
+            from .engine import prior_arrays
+            dict_prior = prior_arrays(setup[0]["prior"], M)
     if out is None:
         res = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
     else:
@@ -735,6 +844,9 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
             res[n][...] = np.nan
         res["count"][...] = 0
         res["best_cost"][...] = np.inf
+        for n in res:
+            if n.startswith("refined"):
+                res[n][...] = -1 if n == "refined_accepts" else np.nan
     elif M > 0:
         stage = _stage
         if stage is None:
@@ -744,9 +856,18 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
             lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=td)      # (a copy: memmaps opened read-only)
             par_t = torch.as_tensor(np.ascontiguousarray(np.asarray(params)[:, cols], dtype=np.float64)).to(eng.device)
             shared = None if kind != "shared" else torch.as_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
-            stage = _DeviceStage(eng, lut_t, par_t, k, meta["dtype"], max(1, min(int(chunk), M)), kind == "per_observation", shared)
-        _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt)
+            fit = None
+            if setup is not None:
+                _, _, sensor, sinfo = setup
+                fit_eng = get_engine(sensor, device, sensor_info=sinfo) if sinfo is not None else get_engine(sensor, device)
+                fit = _StreamRefine(setup, fit_eng, params, column, weights if kind == "shared" else None, dict_prior)
+            stage = _DeviceStage(eng, lut_t, par_t, k, meta["dtype"], max(1, min(int(chunk), M)), kind == "per_observation", shared,
+                                 refine=fit)
+        _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt,
+                       wide=bool(getattr(stage, "wide", False)))
     res["names"] = names
+    if setup is not None:
+        res["refined_names"] = list(setup[0]["names"])
     return res
 
 

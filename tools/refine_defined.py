@@ -5,6 +5,9 @@ build of the step functions (tests/test_refine_host.py) and the kernels (tests/t
 bit.  numpy rounds every ufunc once and never fuses a multiply with an add, which is the arithmetic the definition asks for
 (float64, no FMA contraction, IEEE division and square root).
 
+The optional Gaussian prior on the free parameters (prior_mean, prior_weight = 1 / sigma^2; optimal estimation) adds its terms
+after the band sums: prior_cost_defined to the trial cost, prior_normal_defined to the diagonal of A and to g.
+
 Index conventions.  A is symmetric and only its LOWER triangle is ever formed: entry (a, b), a >= b, is
 sum_j (w_j J_ja) J_jb -- the weight multiplies the factor with the LARGER column number.  PACKED(F) lists the pairs in the
 order a(a + 1)/2 + b; the packed vector of an observation is those F(F + 1)/2 sums followed by g_0 ... g_{F-1}.
@@ -154,9 +157,48 @@ def step_sign(t, h, hi):
         return np.where(t + h <= hi, 1.0, -1.0)
 
 
-def refine_defined(base, free, lo, hi, obs, forward, weights=None, n_iter=10, rel_step=1e-3, lambda0=1e-2, history=None):
+def prior_defined(prior_mean, prior_weight, M, F):
+    """none / (F,) / (M, F) -> (mu, p), both (M, F) float64, or (None, None) without a prior"""
+    if prior_mean is None and prior_weight is None:
+        return None, None
+    if prior_mean is None or prior_weight is None:
+        raise ValueError("prior_mean and prior_weight come together")
+    mu, p = np.asarray(prior_mean, dtype=np.float64), np.asarray(prior_weight, dtype=np.float64)
+    if mu.shape != p.shape or mu.shape not in ((F,), (M, F)):
+        raise ValueError(f"prior_mean {mu.shape} and prior_weight {p.shape}: expected both ({F},) or both ({M}, {F})")
+    return np.array(np.broadcast_to(mu, (M, F)), order="C"), np.array(np.broadcast_to(p, (M, F)), order="C")
+
+
+def prior_cost_defined(c, t, mu, p):
+    """the prior's part of step 3: for f ascending: skip p_f == 0 (mu_f may be NaN), else e_f = t_f - mu_f,
+    c = c + (p_f e_f) e_f.  -> (c (M,), e (M, F))"""
+    with np.errstate(all="ignore"):
+        e = t - mu
+        for f in range(t.shape[1]):
+            c = np.where(p[:, f] == 0.0, c, c + (p[:, f] * e[:, f]) * e[:, f])
+    return c, e
+
+
+def prior_normal_defined(packed, e, p):
+    """the prior's part of step 6, after the band sums: for a ascending with p_a != 0: A_aa = A_aa + p_a,
+    g_a = g_a + p_a e_a.  -> a new packed (M, P)"""
+    F = e.shape[1]
+    nt = F * (F + 1) // 2
+    out = np.array(packed, dtype=np.float64, copy=True)
+    with np.errstate(all="ignore"):
+        for a in range(F):
+            skip = p[:, a] == 0.0
+            out[:, tri(a, a)] = np.where(skip, out[:, tri(a, a)], out[:, tri(a, a)] + p[:, a])
+            out[:, nt + a] = np.where(skip, out[:, nt + a], out[:, nt + a] + p[:, a] * e[:, a])
+    return out
+
+
+def refine_defined(base, free, lo, hi, obs, forward, weights=None, n_iter=10, rel_step=1e-3, lambda0=1e-2, history=None,
+                   prior_mean=None, prior_weight=None):
     """base (M, 27) start rows; free: F distinct column numbers; lo, hi (F,); obs (M, nb); weights None, (nb,) or (M, nb) (a
     weight of exactly 0 skips the band); forward(rows (R, 27)) -> (R, nb) float64, the chosen sensor column of the model.
+    prior_mean, prior_weight: None, or both (F,) or both (M, F): a Gaussian prior on the free parameters, weight = 1 / sigma^2
+    (exactly 0: no prior on that parameter, the mean may then be NaN; negative, NaN or infinite: a dead observation).
     -> dict x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: a dead observation), y (M, nb).
     ``history``: an optional list that receives (x, cost) after every decision (the prefix property)."""
     base = np.ascontiguousarray(base, dtype=np.float64)
@@ -172,6 +214,9 @@ def refine_defined(base, free, lo, hi, obs, forward, weights=None, n_iter=10, re
         raise ValueError("n_iter: 0 ... 100")
     w = weights_defined(weights, M, nb)
     bad = bad_weights_defined(w)
+    mu, pw = prior_defined(prior_mean, prior_weight, M, F)
+    if pw is not None:
+        bad = bad | bad_weights_defined(pw)
     h = rel_step * (hi - lo)
     x = clip_defined(base[:, free], lo, hi)
     t = x.copy()
@@ -191,6 +236,8 @@ def refine_defined(base, free, lo, hi, obs, forward, weights=None, n_iter=10, re
                 rows[f + 1, :, free[f]] = t[:, f] + sh[:, f]
         Y = np.asarray(forward(rows.reshape(-1, base.shape[1])), dtype=np.float64).reshape(F + 1, M, nb)
         ct, d = cost_defined(Y[0], obs, w)
+        if pw is not None:
+            ct, e = prior_cost_defined(ct, t, mu, pw)
         with np.errstate(all="ignore"):
             accept = (ct < c) & ~dead & ~bad
         if it == 0:
@@ -202,7 +249,10 @@ def refine_defined(base, free, lo, hi, obs, forward, weights=None, n_iter=10, re
         if accept.any():
             with np.errstate(all="ignore"):
                 J = np.moveaxis((Y[1:] - Y[0][None]) / sh.T[:, :, None], 0, 2)       # (M, nb, F)
-            packed = np.where(accept[:, None], normal_defined(J, d, w), packed)
+            new = normal_defined(J, d, w)
+            if pw is not None:
+                new = prior_normal_defined(new, e, pw)
+            packed = np.where(accept[:, None], new, packed)
         x = np.where(accept[:, None], t, x)
         c = np.where(accept, ct, c)
         y = np.where(accept[:, None], Y[0], y)

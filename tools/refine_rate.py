@@ -1,6 +1,7 @@
 """Rates of the device-resident refinement (spart_refine) against the forward evaluations it is built around.
 
-    python tools/refine_rate.py [--obs 262144] [--free 6] [--iters 10] [--reps 20] [--out profiles/refine_rate.txt]
+    python tools/refine_rate.py [--obs 262144] [--free 6] [--iters 10] [--reps 20] [--prior none|shared|per_obs]
+                                [--out profiles/refine_rate.txt]
 
 Workload: Sentinel-2A (nb = 13), M LHS rows as the truth, the free parameters started 10 % of their range away, float64.
   a  the whole spart_refine call (Engine.refine: k_refine_init, n_iter + 1 forward calls, n_iter + 1 step kernels);
@@ -9,6 +10,8 @@ Workload: Sentinel-2A (nb = 13), M LHS rows as the truth, the free parameters st
   c  the step kernel's own time per iteration, two ways: (a - b) / (n_iter + 1) by device events (it also holds the init
      kernel and the forward calls' chunking), and k_refine_step's row of `rocprofv3 --kernel-trace --stats` from a separate run
      in a child process.
+``--prior``: the Gaussian prior of the call -- none (the default), shared ((F,) mean and weight) or per_obs ((M, F)); the means
+are the truth, sigma a tenth of the range.
 The goal is c <= a quarter of one forward call.  Device events, medians after two warm-up calls; every figure in the report is
 measured in this run.
 """
@@ -48,6 +51,21 @@ def event_ms(torch, f, reps, warm=2):
     return ts
 
 
+def prior_of(torch, eng, M, F, kind):
+    """keywords of Engine.refine for --prior: device tensors, the truth of workload() as the mean, sigma = 10 % of the range"""
+    if kind == "none":
+        return {}
+    from spart_amd import workloads
+    names = NAMES[:F]
+    cols = [workloads.PARAM_NAMES.index(n) for n in names]
+    lo, hi = (np.array([workloads.RANGES[n][i] for n in names]) for i in (0, 1))
+    truth = workloads.lhs_params(M, "full", seed=77)[:, cols]
+    sigma = 0.1 * (hi - lo)
+    mean = np.ascontiguousarray(truth) if kind == "per_obs" else 0.5 * (lo + hi)
+    weight = np.broadcast_to(1.0 / (sigma * sigma), mean.shape).copy()
+    return {"prior_mean": torch.as_tensor(mean, device=eng.device), "prior_weight": torch.as_tensor(weight, device=eng.device)}
+
+
 def workload(torch, eng, M, F):
     """(start (27, M) device tensor, obs (M, nb) device tensor, names)"""
     from spart_amd import workloads
@@ -67,8 +85,9 @@ def child(a):
     from spart_amd import get_engine
     eng = get_engine(SENSOR, 0)
     start, obs, names = workload(torch, eng, a.obs, a.free)
+    prior = prior_of(torch, eng, a.obs, a.free, a.prior)
     for _ in range(3):
-        eng.refine(start, obs, names, n_iter=a.iters)
+        eng.refine(start, obs, names, n_iter=a.iters, **prior)
     torch.cuda.synchronize()
 
 
@@ -76,7 +95,7 @@ def kernel_lines(a):
     """--child under rocprofv3 --kernel-trace --stats in a fresh process group -> ({kernel: (calls, average ms, min, max)}, note)"""
     d = a.trace_dir or tempfile.mkdtemp(prefix="refine_trace_")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-           "--child", "--obs", str(a.obs), "--free", str(a.free), "--iters", str(a.iters)]
+           "--child", "--obs", str(a.obs), "--free", str(a.free), "--iters", str(a.iters), "--prior", a.prior]
     try:
         proc = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
     except OSError as e:
@@ -104,6 +123,7 @@ def main():
     ap.add_argument("--free", type=int, default=6)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--prior", choices=("none", "shared", "per_obs"), default="none")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-dir", default=None)
     ap.add_argument("--no-trace", action="store_true")
@@ -125,16 +145,17 @@ def main():
     eng = get_engine(SENSOR, 0)
     M, F, nb, calls = a.obs, a.free, eng.nb, a.iters + 1
     start, obs, names = workload(torch, eng, M, F)
+    prior = prior_of(torch, eng, M, F, a.prior)
     rows = (F + 1) * M
     chunk = (1 << 19) // (F + 1)
     say(f"spart_refine on MI355X (one GCD), tools/refine_rate.py: {SENSOR}, nb = {nb}, M = {M} observations, F = {F} free parameters "
-        f"{names}, n_iter = {a.iters} ({calls} forward calls of {rows} rows, in chunks of {chunk} observations), float64; device "
+        f"{names}, prior = {a.prior}, n_iter = {a.iters} ({calls} forward calls of {rows} rows, in chunks of {chunk} observations), float64; device "
         f"events, medians of {a.reps} after 2 warm-up calls.")
     say()
     res = {}
 
     def call_a():
-        res.update(eng.refine(start, obs, names, n_iter=a.iters))
+        res.update(eng.refine(start, obs, names, n_iter=a.iters, **prior))
     Pf = torch.as_tensor(np.ascontiguousarray(np.tile(start.cpu().numpy(), (1, F + 1))), device=eng.device)
     out = {k: torch.empty((rows, nb), dtype=torch.float64, device=eng.device) for k in ("R_TOC", "R_TOA", "L_TOA")}
 
