@@ -63,7 +63,9 @@ extern "C" {
  *  11: spart_lut_summarise
  *  12: spart_srf_support; spart_materialize.R_TOC_srf ... rdd_srf
  *  13: spart_refine, spart_refine_workspace_bytes, spart_refine_opt
- *  14: spart_refine_opt.prior_per_obs, prior_mean, prior_weight */
+ *  14: spart_refine_opt.prior_per_obs, prior_mean, prior_weight
+ * spart_refine_srf was added WITHOUT a new number: it is one more symbol, no struct layout or argument list changed, so every
+ * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -427,7 +429,7 @@ int spart_lut_summarise(spart_ctx *ctx, int64_t B, int P, const double *params, 
  * So cost <= cost0, and the state after n_iter = k is a prefix of n_iter = k + 1.
  * Observations go in chunks of (1 << 19) / (F + 1), so the workspace is bounded whatever M is: the parameter table
  * (27, (F + 1) Mc), three column blocks, the optimiser's state and spart_workspace_bytes(SPART_F64, (F + 1) Mc) for
- * Mc = min(M, chunk).  spart_refine_workspace_bytes is 0 for sizes the call refuses.
+ * Mc = min(M, chunk).  spart_refine_workspace_bytes is 0 for sizes the call refuses; it sizes spart_refine_srf's workspace too.
  * Refused before anything is launched or written: SPART_ERR_INVALID for F outside 1 ... 16, a free column outside 0 ... 26 or a
  * duplicate, lo >= hi or a non-finite bound, n_iter outside 0 ... 100, column outside 0 ... 2, a negative or non-finite rel_step /
  * lambda0, a NULL required pointer, exactly one of prior_mean / prior_weight NULL, prior_per_obs outside 0 / 1, M < 0 or
@@ -450,6 +452,22 @@ int spart_refine(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARA
                  const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
                  const spart_refine_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
                  double *y, void *workspace, size_t workspace_bytes, void *stream);
+
+/* spart_refine with the SRF-convolved columns as the fitted quantity (what a sensor measures, and what a LUT of *_srf columns
+ * stores).  Argument for argument spart_refine's list, and its definition word for word with ONE substitution: Y_0 ... Y_F are
+ * the chosen SRF-convolved column of the rows -- spart_materialize.R_TOC_srf, R_TOA_srf or L_TOA_srf for opt->column 0, 1 or
+ * 2: bit for bit what spart_run_batch(SPART_F64, prune_unused_bands = 1) returns for those rows, with the thermal inputs at
+ * their defaults, no rdry_in / lidf_in, opt->fast_prelude and opt->nlayers honoured -- and y is that column at x.  Start, cost,
+ * decision, propose and std rules, prior, dead observations, chunking, refusals and their order, SPART_ERR_NOSENSOR, M = 0 and
+ * the stream rule are spart_refine's.  The workspace is spart_refine's too: spart_refine_workspace_bytes serves both calls.
+ * As for the *_srf outputs the library does what the sensor tables say (see spart_srf_support): a sensor whose SRF samples
+ * are not aligned with the model grid is the caller's business.
+ * Cost: an iteration evaluates every entry of the compressed SRF support of every band for (F + 1) rows per observation (968
+ * model bands per row for Sentinel-2A) where spart_refine evaluates <= 2 nb; the centre column kernel is not launched. */
+int spart_refine_srf(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                     const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
+                     const spart_refine_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
+                     double *y, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -361,10 +361,12 @@ static bool wants_srf(const spart_materialize* opt) {
 // <float,double,double> = f32_bands; <float,float,float> = f32_columns.
 // In EVERY mode the columns come from prelude -> k_columns<TG, TO>, i.e. from the <= 2 nb bands they depend on; the
 // full-band kernel runs beside that on the caller's stream whenever full spectra are asked for (opt = NULL: band sums).
+// centre = false (spart_refine_srf's forward call only): k_columns is not launched and R_TOC / R_TOA / L_TOA are not touched;
+// the call's result is the *_srf outputs of opt alone.
 template <typename T, typename TG, typename TO = T>
 static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_NPARAM], const double* rho_th,
                     const double* tau_th, void* R_TOC, void* R_TOA, void* L_TOA, const spart_materialize* opt, char* wsp,
-                    const Workspace& ws, hipStream_t st) {
+                    const Workspace& ws, hipStream_t st, bool centre = true) {
   ParamPtrs pp = param_slice(0, params, NPARAM);
   pp.rho_th = rho_th;
   pp.tau_th = tau_th;
@@ -418,14 +420,16 @@ static int run_impl(spart_ctx* ctx, int64_t B, const double* const params[SPART_
   const bool fork = lane != nullptr;
   hipStream_t s2 = fork ? lane->side : st;
   auto columns = [&]() -> int {                // the column kernel, on s2
-    hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, s2, table<TG>(ctx),
-                       (const TG*)constants<TG>(wsp, ws),
-                       (const double*)atm, Bp, (const int*)ctx->band0, (const int*)ctx->band1, (const double*)ctx->frac,
-                       (const double*)ctx->coef, (const double*)ctx->econv, ctx->nb,
-                       (const TO*)(opt ? opt->rdry_in : nullptr), ctx->po, B, (TO*)R_TOC,
-                       (TO*)R_TOA, (TO*)L_TOA, (TO*)(opt ? opt->rsoil : nullptr), (TO*)(opt ? opt->La : nullptr));
-    HIP_TRY(hipGetLastError());
-    // the SRF-convolved columns: the same stream, behind k_columns (whose constants and atmosphere rows it re-reads)
+    if (centre) {
+      hipLaunchKernelGGL((k_columns<TG, TO, TO>), dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, s2, table<TG>(ctx),
+                         (const TG*)constants<TG>(wsp, ws),
+                         (const double*)atm, Bp, (const int*)ctx->band0, (const int*)ctx->band1, (const double*)ctx->frac,
+                         (const double*)ctx->coef, (const double*)ctx->econv, ctx->nb,
+                         (const TO*)(opt ? opt->rdry_in : nullptr), ctx->po, B, (TO*)R_TOC,
+                         (TO*)R_TOA, (TO*)L_TOA, (TO*)(opt ? opt->rsoil : nullptr), (TO*)(opt ? opt->La : nullptr));
+      HIP_TRY(hipGetLastError());
+    }
+    // the SRF-convolved columns: the same stream, behind k_columns (like it they read the prelude's constants and atmosphere rows)
     if constexpr (sizeof(TG) == 8) {
       if (srf) {
         hipLaunchKernelGGL((k_columns_srf<TO, TO>), dim3((unsigned)((B + 63) / 64), (unsigned)((ctx->nb + COL_WAVES - 1) / COL_WAVES)),
@@ -1040,8 +1044,10 @@ static bool refine_sizes_ok(const spart_ctx* ctx, int64_t M, int F) {
   return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF;
 }
 
-// spart_refine once its arguments are checked
-static int refine_impl(spart_ctx* ctx, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
+// spart_refine (srf = false) / spart_refine_srf (srf = true) once the arguments are checked.  The band model decides what
+// the forward call writes into the column block the step kernel reads: k_columns' three centre columns, or the ONE
+// *_srf output of k_columns_srf the fit is about (k_columns is then not launched at all).
+static int refine_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
                        const spart_refine_opt& o, double lambda0, const RefineOut& out, char* wsp, const RefineLayout& l,
                        hipStream_t st) {
   const int nb = ctx->nb, W = refine_group(F);
@@ -1055,6 +1061,7 @@ static int refine_impl(spart_ctx* ctx, int64_t M, const RefineCfg& cfg, int F, c
   double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
   double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
   int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
+  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
   for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
     const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
     const int64_t rows = (int64_t)mc * (F + 1);
@@ -1073,7 +1080,7 @@ static int refine_impl(spart_ctx* ctx, int64_t M, const RefineCfg& cfg, int F, c
     const Workspace ws = carve(SPART_F64, rows);
     for (int it = 0; it <= o.n_iter; ++it) {
       if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
-                                                    wsp + l.fwd, ws, st))
+                                                    wsp + l.fwd, ws, st, !srf))
         return rc;
       hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
                          obs + m0 * nb, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
@@ -1268,11 +1275,11 @@ size_t spart_refine_workspace_bytes(const spart_ctx* ctx, int64_t M, int F) {
   return refine_sizes_ok(ctx, M, F) ? refine_layout(ctx->nb, M, F).total : 0;
 }
 
-int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
-                 const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
-                 double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-  const char* who = "spart_refine";
+// spart_refine and spart_refine_srf: one argument check, one refusal order
+static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F,
+                       const int32_t* free_cols, const double* lo, const double* hi, const double* obs, const double* weights,
+                       const spart_refine_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
+                       double* y, void* workspace, size_t workspace_bytes, void* stream) {
   if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
   if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
   if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
@@ -1317,8 +1324,24 @@ int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARA
     return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
   const RefineOut out = {x, cost, cost0, sdev, n_accept, y};
   return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
-    return refine_impl(ctx, M, cfg, F, obs, weights, o, o.lambda0, out, (char*)workspace, l, st);
+    return refine_impl(ctx, srf, M, cfg, F, obs, weights, o, o.lambda0, out, (char*)workspace, l, st);
   });
+}
+
+int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                 const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
+                 double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  return refine_call("spart_refine", false, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept, y,
+                     workspace, workspace_bytes, stream);
+}
+
+int spart_refine_srf(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                     const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
+                     double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  return refine_call("spart_refine_srf", true, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept,
+                     y, workspace, workspace_bytes, stream);
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

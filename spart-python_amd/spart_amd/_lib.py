@@ -47,6 +47,10 @@ _LUT_SIZES = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]
 _LUT_TOPK_CALL = [vp] + _LUT_SIZES[:3] + [vp, ctypes.c_int64, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]
 _LUT_TOPK_STATS = [vp] + _LUT_SIZES + [ctypes.c_int, vp, c_i64p, c_i64p, c_i64p, c_dp]
 
+# spart_refine and spart_refine_srf: one argument list
+_REFINE_CALL = [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp,
+                vp, vp, ctypes.POINTER(SpartRefineOpt), vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+
 # name -> (restype, argtypes): every symbol include/spart_hip.h declares
 SIGNATURES = {
     "spart_ctx_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(SpartTables)]),
@@ -83,8 +87,8 @@ SIGNATURES = {
                            ("_stats", (ctypes.c_int, _LUT_TOPK_STATS)))},
     "spart_lut_summarise": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "spart_refine_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
-    "spart_refine": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp,
-                                    vp, vp, ctypes.POINTER(SpartRefineOpt), vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "spart_refine": (ctypes.c_int, _REFINE_CALL),
+    "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
@@ -171,7 +175,13 @@ def load(path=None):
                            f", this binding needs {ABI_VERSION} (include/spart_hip.h: SPART_ABI_VERSION); rebuild it with "
                            "`python spart-python_amd/build.py`")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # symbols can be added without a new interface version (include/spart_hip.h: spart_refine_srf), so the number
+            # alone does not say that a foreign library has them all
+            raise RuntimeError(f"{path} implements interface version {have_abi} but does not export {name}, which this binding "
+                               "needs (include/spart_hip.h); rebuild it with `python spart-python_amd/build.py`") from None
         fn.restype = res
         fn.argtypes = args
     if in_tree and want is not None and lib.spart_build_id().decode() != want:      # (what the loaded code says, not what the file's bytes said)

@@ -857,7 +857,7 @@ class Engine:
         return res
 
     def refine(self, params, obs, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
-               lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, _plan=None):
+               lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, band_model="centre", _plan=None):
         """Bounded Levenberg-Marquardt refinement of the ``free`` parameters of every start row against its observation, on the
         device (include/spart_hip.h: spart_refine, which defines every sum and solve; tools/refine_defined.py is the numpy form).
         params : the start rows, as for run(): a (27, M) float64 device tensor or a list of 27 scalars / arrays (each 1 or M values)
@@ -872,11 +872,18 @@ class Engine:
                 gains sum_f (t_f - mean_f)^2 / sigma_f^2, and ``std`` becomes the linearised posterior 1-sigma
         prior_mean, prior_weight : the same prior ready-made, (F,) or (M, F) float64 (weight = 1 / sigma^2, exactly 0 = none;
                 e.g. knn_prior's); tensors already on the device are used where they are.  Not together with ``prior``
+        band_model : "centre" (default: the model sampled at the band centres, spart_refine) or "srf": ``obs`` and the fitted model
+                are the SRF-convolved column (run()'s R_TOC_srf / R_TOA_srf / L_TOA_srf; spart_refine_srf) -- what a sensor measures
+                and what generate_lut(band_model="srf") stores.  An iteration then evaluates the whole SRF support of every band
+                (968 model bands per row for Sentinel-2A against 13).  ValueError for a sensor whose SRF columns are not in
+                the order of its band centres (align_srf mends it)
         -> dict of device tensors x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: the start could not be
         evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names."""
         ready = prior_mean is not None or prior_weight is not None
         if prior is not None and ready:
             raise ValueError("prior and prior_mean / prior_weight exclude each other")
+        from .api import _band_model
+        entry = "spart_refine_srf" if _band_model(band_model, self) else "spart_refine"
         plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
         if plan.get("prior") is not None and ready:
             raise ValueError("prior and prior_mean / prior_weight exclude each other")
@@ -930,11 +937,11 @@ class Engine:
             opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
         nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.calls["spart_refine"] += 1
-        rc = self.lib.spart_refine(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                   _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
-                                   ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
-                                   ws.data_ptr(), nbytes, self._stream())
+        self.calls[entry] += 1
+        rc = getattr(self.lib, entry)(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                      _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
+                                      ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
+                                      ws.data_ptr(), nbytes, self._stream())
         _lib.check(self.lib, self.ctx, rc)
         res["names"] = list(plan["names"])
         return res

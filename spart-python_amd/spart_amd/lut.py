@@ -446,16 +446,19 @@ def _np_dtype(name):
 
 
 def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
-           lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None, prior_weight=None):
+           lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None, prior_weight=None,
+           band_model="centre"):
     """The host form of Engine.refine: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays (run()'s
     conventions), ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``, a sensorinfo dict);
-    ``prior`` or ``prior_mean`` / ``prior_weight`` as for Engine.refine.
+    ``prior`` or ``prior_mean`` / ``prior_weight`` and ``band_model`` as for Engine.refine.
     -> dict of numpy arrays x, cost, cost0, std, n_accept, y and the list ``names``.  Every argument check that needs no
     device runs before one is asked for."""
     from .engine import _prior_tensor_shapes, prior_arrays, refine_plan
     ready = prior_mean is not None or prior_weight is not None
     if prior is not None and ready:
         raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    if band_model not in BAND_MODELS:
+        raise ValueError(f"band_model must be 'centre' or 'srf', got {band_model!r}")
     plan = refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
     if lidf not in ("literal", "newton"):
         raise ValueError("lidf must be 'literal' or 'newton'")
@@ -481,16 +484,20 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
         prior_arrays(plan["prior"], o.shape[0])
     eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
     res = eng.refine(params, o, free, weights=weights, lidf=lidf, nlayers=nlayers, prior_mean=prior_mean, prior_weight=prior_weight,
-                     _plan=plan)
+                     band_model=band_model, _plan=plan)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
-REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor")
+BAND_MODELS = ("centre", "srf")
+REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor", "band_model")
 REFINE_KEYS = {"refined": "x", "refined_std": "std", "refined_cost": "cost", "refined_cost0": "cost0", "refined_accepts": "n_accept"}
 
 
 def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
-    """retrieve(refine=...): everything that can be refused from the LUT directory alone -> (plan, options, sensor, sensor_info)"""
+    """retrieve(refine=...): everything that can be refused from the LUT directory alone -> (plan, options, sensor, sensor_info).
+    options["band_model"] is then set: the fit's band model, which must be the LUT's.  It is never taken from meta.json
+    silently: an SRF iteration evaluates the whole SRF support of every band (968 model bands per row for Sentinel-2A, 13 for
+    the centre model), so the caller says so."""
     from .engine import refine_plan
     opts = dict(refine_opts or {})
     stray = [n for n in opts if n not in REFINE_OPTS]
@@ -501,9 +508,13 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
             raise ValueError("refine_opts without refine=[names]")
         return None
     meta, params, _ = load_lut(lut_dir)
-    if meta.get("band_model", "centre") == "srf":
-        raise ValueError('retrieve(refine=...) on a band_model="srf" LUT: the refinement fits the band-centre columns '
-                         "(SRF columns as the fitted quantity are not built yet)")
+    have, want = meta.get("band_model", "centre"), opts.setdefault("band_model", "centre")
+    if want not in BAND_MODELS:
+        raise ValueError(f'refine_opts["band_model"] = {want!r}, expected "centre" or "srf"')
+    if want != have:
+        raise ValueError(f'retrieve(refine=...): the LUT holds band_model="{have}" columns and the fit was asked for "{want}"; the '
+                         f'fit uses the band model the LUT was generated with: pass refine_opts={{"band_model": "{have}"}}'
+                         + (" (an srf iteration evaluates the whole SRF support of every band)" if have == "srf" else ""))
     if _group_info(shard, group)[0] > 1:
         raise ValueError("retrieve(refine=...) does not take shard=True under a process group of more than one rank "
                          "(sharded refinement is not built yet)")
@@ -561,7 +572,8 @@ def _refine_rows(setup, lut_dir, obs, idx, column, weights, device):
             near = eng.lut_summarise(torch.as_tensor(free).to(eng.device), torch.as_tensor(np.ascontiguousarray(idx[ok])).to(eng.device))
             pm, pw = knn_prior(near["mean"], near["std"], plan["lo"], plan["hi"], floor=opts.get("prior_floor", 0.05))
         r = eng.refine(list(np.ascontiguousarray(start.T)), np.asarray(obs, dtype=np.float64)[ok], plan["names"], weights=w,
-                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw, _plan=plan)
+                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw,
+                       band_model=opts["band_model"], _plan=plan)
         for key, name in REFINE_KEYS.items():
             out[key][ok] = r[name].cpu().numpy()
     return out
@@ -588,13 +600,16 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     (Engine.refine / spart_refine); the keys above are unchanged, bit for bit, and the result gains ``refined`` (M, F),
     ``refined_cost``, ``refined_cost0`` (the cost at the start: cost[:, 0] of a float64 LUT bit for bit), ``refined_std``
     (M, F), ``refined_accepts`` (M,) int32 and ``refined_names``; observations without a row (idx -1) get NaN and -1.
-    ``refine_opts``: bounds / n_iter / rel_step / lambda0 / lidf / nlayers of Engine.refine; the default bounds are the LUT's
-    own minimum and maximum of every free column (a constant column without a bound is a ValueError).  ``"prior"``: a dict
+    ``refine_opts``: bounds / n_iter / rel_step / lambda0 / lidf / nlayers / band_model of Engine.refine; the default bounds are the
+    LUT's own minimum and maximum of every free column (a constant column without a bound is a ValueError).  ``"band_model"``
+    (default "centre") must be the LUT's own (meta.json): a generate_lut(band_model="srf") LUT is refined with
+    refine_opts={"band_model": "srf"} (spart_refine_srf: the SRF-convolved column is the fitted quantity), and only so.
+    ``"prior"``: a dict
     {name: (mean, sigma)} as for Engine.refine, or ``"knn"``: knn_prior of the mean and std of the free columns of the k rows
     found (Engine.lut_summarise, whatever ``summary`` says: that summary is one defined number), with the plan's bounds and
     ``"prior_floor"`` (default 0.05); ``refined_std`` is then the linearised posterior 1-sigma.  The sensor is
-    meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band_model="srf" LUT and for
-    ``shard=True`` under a process group of more than one rank (neither is built yet)."""
+    meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band model other than the
+    LUT's and for ``shard=True`` under a process group of more than one rank (sharded refinement is not built yet)."""
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
@@ -746,7 +761,8 @@ class _StreamRefine:
             pm, pw = knn_prior(near["mean"], near["std"], self.plan["lo"], self.plan["hi"], floor=self.opts.get("prior_floor", 0.05))
         self.lo += n
         r = eng.refine(start, obs, self.plan["names"], weights=w, lidf=self.opts.get("lidf", "literal"),
-                       nlayers=self.opts.get("nlayers"), prior_mean=pm, prior_weight=pw, _plan=self.plan)
+                       nlayers=self.opts.get("nlayers"), prior_mean=pm, prior_weight=pw, band_model=self.opts["band_model"],
+                       _plan=self.plan)
         none = best < 0
         nan = torch.full((), float("nan"), dtype=torch.float64, device=idx.device)
         out = {}
