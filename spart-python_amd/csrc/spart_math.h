@@ -102,10 +102,12 @@ template <> struct Mx<float> {
     return 1.0f / x;
 #endif
   }
-  // log1p for x >= 0 (the only use: ln b, b >= 1): 2 atanh(x/(2+x)) series below 0.5, log(1+x) above
+  // log1p for x >= 0 (ln b, b >= 1): 2 atanh(x/(2+x)) series below 0.5, log(1+x) above.  No kernel calls it any more (the
+  // float32 N-layer chain runs in base 2, log2_1p below), so the quotient is a true division: with v_rcp_f32 the series
+  // side reached 4.2 * 2^-24 on the device, past the 4 * 2^-24 it is held to (tests/test_gpu_devmath.py)
   static SPART_HD float log1p(float x) {
 #if defined(SPART_FAST_MATH)
-    float s = x * rcp(2.0f + x);
+    float s = x / (2.0f + x);
     float s2 = s * s;
     float p = 2.0f * s * (1.0f + s2 * (0.333333333f + s2 * (0.2f + s2 * (0.142857143f + s2 * 0.111111111f))));
     return (x < 0.5f) ? p : log(1.0f + x);
@@ -140,7 +142,8 @@ template <> struct Mx<float> {
   }
   // The same two in base 2 (the float32 N-layer chain of leaf_band: log2 -> times N-1 -> exp2 with no ln 2 / log2(e)
   // factors in between).  log2(1 + x), x >= 0: the series above times log2(e) below 0.5 (the factor rides on the 2 s
-  // multiply), v_log_f32 above.
+  // multiply), v_log_f32 above.  On the device the series side carries v_rcp_f32's error (1.6 * 2^-24) through five more
+  // roundings: 4.9 * 2^-24 = 2.9e-7 relative at worst (tests/test_gpu_devmath.py), against 1e-4 for the model
   static SPART_HD float log2_1p(float x) {
 #if defined(SPART_FAST_MATH)
     float s = x * rcp(2.0f + x);
@@ -223,7 +226,8 @@ __device__ __forceinline__ double spart_horner(double p, double x, double c_unif
 //    exp(x) is 0 below x = -745 (including -inf); log is only called with positive finite normal arguments.  Neither
 //    propagates a NaN argument by itself: in leaf_band / soil_band / canopy_core every result of exp / log is multiplied
 //    with terms that are NaN when the argument is (test_nan_and_nonphysical_inputs_do_not_crash).  Relative error <= 3e-16 (exp), absolute <= 3e-16 / relative <= 2e-15 away from
-//    x = 1 (log).
+//    x = 1 (log); measured on an MI355X, element by element against long double (tests/test_gpu_devmath.py): 2.4e-16 (exp,
+//    exp2), 1.5e-16 (exp_poly), 1.3e-16 absolute / 1.9e-16 relative (log).
 static __device__ __constant__ double c_EXP_F64[12] = {1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320,
                                                 1.0 / 362880, 1.0 / 3628800, 1.0 / 39916800, 1.0 / 479001600, 1.0 / 6227020800.0};
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -308,12 +312,18 @@ template <> struct Mx<double> {
   static SPART_HD double exp2(double x) { return ::exp2(x); }
   static SPART_HD double log(double x) { return ::log(x); }
 #endif
-  // square root: v_rsq_f64 (4.6e-8 relative) refined by ONE Newton step, sqrt x = g (1 + e/2 + O(e^2)), g = x y0,
-  // e = 1 - g y0: relative error 3 e^2 / 8 < 1e-15 in 5 instructions (the library's sequence: ~14).  The argument of the
+  // square root: v_rsq_f64 (5.2e-8 relative, measured by tests/test_gpu_devmath.py)
+  // refined by ONE Newton step, sqrt x = g (1 + e/2 + O(e^2)), g = x y0, e = 1 - g y0: relative error 3 e^2 / 8 in 5
+  // instructions (the library's sequence: ~14).  e is TWICE the seed's error d (g y0 = x y0^2), so that is 3 d^2 / 2 = 4.1e-15,
+  // 4.2e-15 with the roundings (measured 4.06e-15; exact squares do not all give exact roots).  An earlier "< 1e-15" here took
+  // e for the seed's error.  No caller needs more: the float64 model is held to 1e-6 ... 4e-9 of the oracle.  The argument of the
   // rsq is kept away from 0 by ADDING 1e-300 (x = 0 -> 0 * rsq(1e-300) = 0 instead of 0 * inf; x + 1e-300 == x for every
-  // normal x): a negative x <= -1e-300 gives NaN like np.sqrt (a max() here returned finite garbage), a NaN x
-  // stays NaN.  Outside that: -1e-300 < x < 0 returns a tiny negative finite value (|result| < 1e-150) instead of NaN, and a
-  // positive x below 1e-300 returns x * 1e150 (too small); no quantity of the model comes near either range.
+  // x >= 1e-284): a negative x < -1e-300 gives NaN like np.sqrt (a max() here returned finite garbage; x = -1e-300
+  // itself gives -inf), a NaN x stays NaN.  Outside that: -1e-300 < x < 0 returns a tiny negative finite value (|result| < 1e-150) instead of NaN, a
+  // positive x below 1e-300 returns x * 1e150 (too small), and from 1e-300 to 1e-292 the added 1e-300 shows: with
+  // d = 1e-300 / x the result is (1 + 3 d / 2) (1 + d)^-3/2 of the root, 3 d^2 / 8 low (12 % at x = 1e-300).  One quantity of
+  // the model comes there: leaf_band's D when K <= 0 (plate_tau clamps K to 1e-300, so a1 ~ 1e-300); D then outweighs a1 in
+  // a - 1 and b - 1 alike, and only their ratio survives into the zero-absorption limit of the Stokes terms.
   static SPART_HD double sqrt(double x) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(SPART_FAST_MATH)
     const double y0 = __builtin_amdgcn_rsq(x + 1e-300);
@@ -324,8 +334,9 @@ template <> struct Mx<double> {
     return ::sqrt(x);
 #endif
   }
-  // reciprocal: v_rcp_f64 (4.6e-8 relative, tools/ubench/rcp64_probe) refined by ONE Newton step r (2 - x r):
-  // relative error e^2 = 2e-15 in 3 instructions (the IEEE division sequence: ~12); the host build divides
+  // reciprocal: v_rcp_f64 (4.6e-8 relative, tests/test_gpu_devmath.py) refined by ONE Newton step r (2 - x r):
+  // relative error e^2 + 2^-53 = 2.3e-15 (measured 2.2e-15; powers of two are exact) in 3 instructions (the IEEE division
+  // sequence: ~12); the host build divides
   static SPART_HD double rcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(SPART_FAST_MATH)
     const double r = __builtin_amdgcn_rcp(x);
@@ -335,7 +346,7 @@ template <> struct Mx<double> {
 #endif
   }
   // ln(1+x), x >= 0: 2 atanh(x/(2+x)) series below 0.1 (s <= 0.048, s^15/15 < 1e-21), log(1+x) above
-  // (whose rounding of 1+x costs at most 1e-16/0.1 relative)
+  // (whose rounding of 1+x costs at most 1e-16/0.1 relative; measured on the device: 1.2e-15)
   static SPART_HD double log1p(double x) {
 #if defined(SPART_FAST_MATH)
     if (x < 0.1) {
@@ -353,7 +364,8 @@ template <> struct Mx<double> {
     return ::log1p(x);
 #endif
   }
-  // 1 - e^-z: Taylor for |z| below 0.02 (z^9/9! < 2e-21), direct otherwise (cancellation <= 1e-16/0.02 relative)
+  // 1 - e^-z: Taylor for |z| below 0.02 (z^9/9! < 2e-21), direct otherwise: e^-z carries its own 3e-16 into the difference,
+  // (3e-16 + 2^-53) / (1 - e^-0.02) = 2.1e-14 relative at the switch point (measured: 9.1e-15 with exp, 5.6e-15 with exp_poly)
   static SPART_HD double omen_taylor(double z) {
     double p = -1.0 / 40320.0;
     p = p * z + 1.0 / 5040.0;
@@ -1198,7 +1210,7 @@ SPART_HD void volscatt1(double sin_tts, double cos_tts, double sin_tto, double c
   double As = ::fmax(Ss, Cs), Ao = ::fmax(So, Co);
   double cbs = -Cs / As, cbo = -Co / Ao;                         // cos bts, cos bto
   double bts = ::acos(cbs), bto = ::acos(cbo);
-  using Md = Mx<double>;           // (device: v_rsq_f64 + one Newton step, 1e-15; the two divisions above stay IEEE: -Cs / As must be
+  using Md = Mx<double>;           // (device: v_rsq_f64 + one Newton step, 4.2e-15; the two divisions above stay IEEE: -Cs / As must be
                                    //  EXACTLY -1 when As = Cs, acos magnifies anything less near +-1)
   double sbs = Md::sqrt(::fmax(0.0, 1.0 - cbs * cbs)), sbo = Md::sqrt(::fmax(0.0, 1.0 - cbo * cbo));
   chi_o = 2.0 / PI * ((bto - PI / 2) * Co + sbo * So);
@@ -1651,7 +1663,7 @@ template <typename A> SPART_HD SmacOut smac_band(const A& atm, const double* coe
 SPART_HD void toc_to_toa(const SmacOut& a, double rv_so, double rv_do, double rv_dd, double rv_sd, double La,
                          double& R_TOC, double& R_TOA, double& L_TOA) {
   using Md = Mx<double>;
-  const double imr = Md::rcp(1.0 - rv_dd * a.Ra_dd);          // (device: v_rcp_f64 + one Newton step, 2e-15 relative)
+  const double imr = Md::rcp(1.0 - rv_dd * a.Ra_dd);          // (device: v_rcp_f64 + one Newton step, 2.3e-15 relative)
   double rtoa0 = a.Ra_so + a.Ta_ss * rv_so * a.Ta_oo;
   double rtoa1 = (a.Ta_sd * rv_do + a.Ta_ss * rv_sd * a.Ra_dd * rv_do) * a.Ta_oo * imr;
   double rtoa2 = (a.Ta_ss * rv_sd + a.Ta_sd * rv_dd) * a.Ta_do * imr;
