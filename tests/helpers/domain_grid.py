@@ -146,9 +146,19 @@ def oracle_grid(oracle, tables, P, rho, tau, block=256):
     return out
 
 
+_GRID = []             # build_grid's result: the oracle runs once per process, every test module reads the same arrays
+
+
 def build_grid(oracle, tables):
     """the grid with the oracle's values: dict P, kind, rho, tau, inside (bool), common (bool) and oracle_grid's arrays.
-    Rows where the oracle is non-finite in any band are dropped (DROPPED of them)."""
+    Rows where the oracle is non-finite in any band are dropped (DROPPED of them).  Built once per process (the oracle and
+    its packaged tables are fixed); callers read the arrays and do not write to them."""
+    if not _GRID:
+        _GRID.append(_build_grid(oracle, tables))
+    return _GRID[0]
+
+
+def _build_grid(oracle, tables):
     P, kind = grid_params()
     rho, tau = thermal_draw(len(P), 73)
     ref = oracle_grid(oracle, tables, P, rho, tau)

@@ -122,7 +122,9 @@ def test_convolution_of_the_engines_own_spectra(torch_mod, rows):
 
 
 def test_one_unit_sample_at_the_centre_gives_the_centre_columns(torch_mod, rows):
-    """a synthetic sensor whose SRF is ONE sample of weight 1 at each (integer) band centre: the convolution is the sample"""
+    """a synthetic sensor whose SRF is ONE sample of weight 1 at each (integer) band centre: the convolution is the sample --
+    the four canopy columns, R_TOA and L_TOA bit for bit; R_TOC within the float64 contract (a
+    quotient in one kernel against a reciprocal product in the other)"""
     from spart_amd import get_engine, tables as tb
     si = dict(tb.load_sensor_info("Sentinel2A-MSI"))
     centres = np.asarray(si["wl_smac"], dtype=np.float64).reshape(-1)
@@ -137,6 +139,10 @@ def test_one_unit_sample_at_the_centre_gives_the_centre_columns(torch_mod, rows)
     err.update({x: S.rel_err(got[x + "_srf"], spectra[x][:, at]) for x in CANOPY})
     print({k: f"{v:.2e}" for k, v in err.items()})
     assert max(err.values()) <= F64, err
+    for x in CANOPY:
+        assert np.array_equal(got[x + "_srf"], spectra[x][:, at], equal_nan=True), x
+    for k in ("R_TOA", "L_TOA"):
+        assert np.array_equal(got[k + "_srf"], got[k], equal_nan=True), k
 
 
 # ------------------------------------------------------------------ 4. shapes and modes

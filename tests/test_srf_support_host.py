@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import srf_numpy
+from helpers.srf_exact import hostile_table
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 # sum_j |E_j| (and the largest |E_j|) of the packaged tables.  Sentinel-2B: 962 with the literal argmin; the definition's exact
@@ -78,26 +79,6 @@ def test_hyperspectral_fixture_support(lib):
     got = library_support(lib, z["si/wl_srf"], z["si/p_srf"])
     assert_support_equal(got, srf_numpy.support(z["si/wl_srf"], z["si/p_srf"]))
     assert got[0].shape == (212,) and (got[1] == srf_numpy.NWL).any()      # centres up to 2500 nm reach the thermal pad
-
-
-def hostile_table():
-    """(nsrf, 3): NaN, +-tiny, negative, x.5 ties, the 2400 / 2500 gap (2450 and just above), thermal-pad ties, 60000, zero,
-    negative and duplicated weights -- every |w| < 1e15, where the literal argmin is the definition"""
-    tiny = np.nextafter(0.0, 1.0)
-    col0 = [np.nan, tiny, -tiny, -5.0, 0.0, 399.5, 400.0, 400.5, 401.5, 401.5, 1000.5, 1000.4999999999999, 1000.5000000000001,
-            2399.5, 2400.0, 2400.5, 2450.0, 2450.01, np.nextafter(2450.0, 3000.0), np.nextafter(2450.0, 0.0), 2499.9, 2500.0]
-    col1 = [2550.0, 2550.0000001, 2549.9999, 14950.0, 15000.0, 15500.0, 15500.0001, 16000.0, 16500.0, 16500.5, 49500.0, 49501.0,
-            50000.0, 60000.0, 1e14, -1e14, np.nan, np.nan, 700.0, 700.0, 700.2, 699.8]
-    col2 = [np.nan] * 21 + [865.0]
-    w = np.array([col0, col1, col2], dtype=np.float64).T
-    rng = np.random.default_rng(7)
-    p = rng.uniform(-1.0, 1.0, w.shape)
-    p[0, 0] = 0.0                                          # a zero weight on the NaN wavelength: the entry stays
-    p[4, 0] = -0.0
-    p[5:8, 0] = [0.25, -0.25, 1e-300]
-    p[16, 1], p[17, 1] = 0.0, 0.0
-    p[:21, 2] = 0.0                                        # band 2: Q from one sample, index 0 entry of weight 0 kept
-    return w, p
 
 
 def test_hostile_table_support(lib):
