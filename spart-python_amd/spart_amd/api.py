@@ -620,7 +620,7 @@ class SPART:
         if not (np.shape(wls) == _WLS_DEFAULT.shape and np.array_equal(wls, _WLS_DEFAULT)):
             raise ValueError("SPART.spectral.wlS differs from the reference's 2162-point grid (SPART.py:303-310): not supported")
         eng, wl, bands, wl_index, bands_arr = self._engine()
-        srf = _band_model(band_model, eng)
+        srf = _engine._band_model(band_model, eng)
         cols = self._columns()
         rdry = self.soilpar.rdry if getattr(self.soilpar, "rdry_set", False) else None
         th = (self.leafbio.rho_thermal, self.leafbio.tau_thermal)
@@ -639,7 +639,7 @@ class SPART:
             if materialize:
                 fields += _SPECTRA
             if srf:
-                fields += _SRF_COLUMNS
+                fields += _engine._SRF_COLUMNS
             # the (B, nb) results share ONE device block, so that they come back in one device-to-host copy
             B = _engine.batch_size(cols + list(th), [(rdry, _lib.NWL), (clidf, _lib.NLINCL)])
             td = torch.float32 if _engine.DTYPES[self.dtype] == 0 else torch.float64
@@ -648,7 +648,7 @@ class SPART:
                           prune=not materialize, out={k: blk[i] for i, k in enumerate(ncol)}, canopy_lidf=clidf, nlayers=nlay)
             host = _np(blk)
             out = {k: (host[ncol.index(k)] if k in ncol else _np(v)) for k, v in res.items()}
-            for k in _SRF_COLUMNS if srf else ():
+            for k in _engine._SRF_COLUMNS if srf else ():
                 out[k[:-4]] = out.pop(k)                    # R_TOC / R_TOA / L_TOA are the SRF-convolved columns
             scalar = _is_scalar(*[c for c in cols if c is not None]) and out["R_TOC"].shape[0] == 1
         # attributes documented at SPART.py:66-81
@@ -694,24 +694,6 @@ class SPART:
                 self._set_spectra({k: _np(res[k]) for k in _SPECTRA}, last["scalar"])
             return self.__dict__[name]
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
-
-
-_SRF_COLUMNS = ["R_TOC_srf", "R_TOA_srf", "L_TOA_srf"]
-
-
-def _band_model(band_model, eng):
-    """band_model= of SPART.run / generate_lut -> True for "srf"; ValueError for anything but "centre" / "srf", and for "srf"
-    on an engine whose SRF columns do not belong to its band centres"""
-    if band_model not in ("centre", "srf"):
-        raise ValueError(f"band_model must be 'centre' or 'srf', got {band_model!r}")
-    if band_model == "srf" and eng.nb == 0:
-        raise ValueError("band_model='srf' needs a sensor: this engine was made without one")
-    if band_model == "srf" and not np.all(eng.srf_aligned):
-        off = np.flatnonzero(~np.asarray(eng.srf_aligned)).tolist()
-        raise ValueError(f"band_model='srf': the centres of bands {off} lie outside the wavelength extent of their SRF columns -- "
-                         "this sensor's wl_srf_smac / p_srf_smac are in another band order than wl_smac / SMAC_coef; pass "
-                         "a sensorinfo mended by spart_amd.align_srf")
-    return band_model == "srf"
 
 
 _SPECTRA = ["leaf_refl", "leaf_tran", "leaf_kchl", "soil_refl", "soil_refl_dry", "rso", "rdo", "rsd", "rdd"]

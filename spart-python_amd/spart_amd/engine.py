@@ -17,6 +17,7 @@ SMAC_FIELDS = ["Ta_s", "Ta_o", "Tg", "Ra_dd", "Ra_so", "Ta_ss", "Ta_sd", "Ta_oo"
 MATERIALIZE_FIELDS = ["leaf_refl", "leaf_tran", "leaf_kchl", "soil_refl", "soil_refl_dry", "rso", "rdo", "rsd",
                       "rdd", "rsoil", "La", "band_mean", "R_TOC_srf", "R_TOA_srf", "L_TOA_srf", "rso_srf", "rdo_srf", "rsd_srf",
                       "rdd_srf"]
+_SRF_COLUMNS = ["R_TOC_srf", "R_TOA_srf", "L_TOA_srf"]      # what band_model="srf" returns as R_TOC / R_TOA / L_TOA
 _MAT_WIDTH = dict(leaf_refl=_lib.NWLS, leaf_tran=_lib.NWLS, leaf_kchl=_lib.NWL, soil_refl=_lib.NWLS,
                   soil_refl_dry=_lib.NWL, rso=_lib.NWLS, rdo=_lib.NWLS, rsd=_lib.NWLS, rdd=_lib.NWLS)
 
@@ -223,6 +224,73 @@ def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=
     return {"names": names, "cols": np.array([workloads.PARAM_NAMES.index(n) for n in names], dtype=np.int32), "lo": lo, "hi": hi,
             "column": _lib.REFINE_COLUMNS.index(column), "n_iter": int(n_iter), "rel_step": float(rel_step),
             "lambda0": float(lambda0), "prior": None if prior is None else _prior_plan(names, prior)}
+
+
+def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean, prior_weight,
+                band_model, nb=None, _plan=None):
+    """Every argument check of spart_amd.refine and Engine.refine that needs no device: prior exclusivity, the band model's
+    name, refine_plan (unless ``_plan`` is one), lidf, and the shapes of obs ((M, nb); ``nb`` given: that nb), params (a (27, M)
+    block or 27 columns of 1 or M values), weights and the prior.
+    -> (plan, params, M, weights kind, prior_mean, prior_weight, prior per observation 0 / 1); ``params`` comes back as the
+    2-D tensor it was, else as a list of 27 columns; a plan's prior comes back as its prior_arrays."""
+    import torch
+    ready = prior_mean is not None or prior_weight is not None
+    if prior is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    _band_model(band_model)
+    plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
+    if plan.get("prior") is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    if lidf not in ("literal", "newton"):
+        raise ValueError("lidf must be 'literal' or 'newton'")
+    oshape = tuple(int(n) for n in np.shape(obs))
+    if len(oshape) != 2 or (nb is not None and oshape[1] != nb):
+        raise ValueError(f"obs has shape {oshape}, expected (M, nb)" + ("" if nb is None else f" = (M, {nb})"))
+    M = oshape[0]
+    if not isinstance(params, (list, tuple)):
+        if not torch.is_tensor(params):
+            params = np.asarray(params, dtype=np.float64)
+        if len(params.shape) != 2 or params.shape[0] != _lib.NPARAM:
+            raise ValueError(f"params must be (27, M) or a list of 27 columns, got shape {tuple(params.shape)}")
+        counts = [int(params.shape[1])]
+        if not torch.is_tensor(params):
+            params = list(params)
+    else:
+        if len(params) != _lib.NPARAM:
+            raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+        params = fill_nulls(params)
+        counts = [math.prod(np.shape(c)) for c in params]
+    for n in counts:
+        if n not in (1, M):
+            raise ValueError(f"a params column of {n} values does not broadcast to the {M} rows of obs")
+    kind = lut_weights_kind(None if weights is None else np.shape(weights), M, oshape[1])
+    per_obs = 0
+    if ready:
+        per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, len(plan["names"]))
+    elif plan.get("prior") is not None:
+        prior_mean, prior_weight = prior_arrays(plan["prior"], M)
+        per_obs = int(prior_mean.ndim == 2)
+    return plan, params, M, kind, prior_mean, prior_weight, per_obs
+
+
+BAND_MODELS = ("centre", "srf")
+
+
+def _band_model(band_model, eng=None):
+    """band_model= of SPART.run / generate_lut / refine -> True for "srf"; ValueError for anything but "centre" / "srf", and,
+    given the engine, for "srf" on one whose SRF columns do not belong to its band centres"""
+    if band_model not in BAND_MODELS:
+        raise ValueError(f"band_model must be 'centre' or 'srf', got {band_model!r}")
+    if eng is None:
+        return band_model == "srf"
+    if band_model == "srf" and eng.nb == 0:
+        raise ValueError("band_model='srf' needs a sensor: this engine was made without one")
+    if band_model == "srf" and not np.all(eng.srf_aligned):
+        off = np.flatnonzero(~np.asarray(eng.srf_aligned)).tolist()
+        raise ValueError(f"band_model='srf': the centres of bands {off} lie outside the wavelength extent of their SRF columns -- "
+                         "this sensor's wl_srf_smac / p_srf_smac are in another band order than wl_smac / SMAC_coef; pass "
+                         "a sensorinfo mended by spart_amd.align_srf")
+    return band_model == "srf"
 
 
 # ---- the static tables a context is built from (spart_tables): the reference reads them from the dicts it is HANDED at call
@@ -879,48 +947,19 @@ class Engine:
                 the order of its band centres (align_srf mends it)
         -> dict of device tensors x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: the start could not be
         evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names."""
-        ready = prior_mean is not None or prior_weight is not None
-        if prior is not None and ready:
-            raise ValueError("prior and prior_mean / prior_weight exclude each other")
-        from .api import _band_model
+        plan, params, M, kind, prior_mean, prior_weight, per_obs = refine_args(
+            params, obs, free, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean, prior_weight, band_model,
+            nb=self.nb, _plan=_plan)
         entry = "spart_refine_srf" if _band_model(band_model, self) else "spart_refine"
-        plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
-        if plan.get("prior") is not None and ready:
-            raise ValueError("prior and prior_mean / prior_weight exclude each other")
-        if lidf not in ("literal", "newton"):
-            raise ValueError("lidf must be 'literal' or 'newton'")
         nl = self._nlayers(nlayers)
-        import torch
-        oshape = tuple(obs.shape) if hasattr(obs, "shape") else np.shape(obs)
-        if len(oshape) != 2 or oshape[1] != self.nb:
-            raise ValueError(f"obs has shape {oshape}, expected (M, nb) = (M, {self.nb})")
-        M, nb = int(oshape[0]), int(oshape[1])
-        block = torch.is_tensor(params) and params.dim() == 2
-        if block:
-            if params.shape[0] != _lib.NPARAM:
-                raise ValueError("params must be (27, M)")
-            if int(params.shape[1]) not in (1, M):
-                raise ValueError(f"params of {int(params.shape[1])} rows do not broadcast to the {M} rows of obs")
-        else:
-            if len(params) != _lib.NPARAM:
-                raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
-            plist = fill_nulls(params)
-            batch_size(plist, B=M)
-        kind = lut_weights_kind(None if weights is None else (tuple(weights.shape) if hasattr(weights, "shape") else np.shape(weights)), M, nb)
-        F = len(plan["names"])
-        per_obs = 0
-        if ready:
-            per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, F)
-        elif plan.get("prior") is not None:
-            prior_mean, prior_weight = prior_arrays(plan["prior"], M)
-            per_obs = int(prior_mean.ndim == 2)
+        nb, F = self.nb, len(plan["names"])
         # ---- the device from here on
         torch = self.torch
-        if block:
+        if torch.is_tensor(params):
             P = params.to(device=self.device, dtype=torch.float64)
             cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
         else:
-            cols, _ = self.columns(plist, M)
+            cols, _ = self.columns(params, M)
         o = torch.as_tensor(obs).to(device=self.device, dtype=torch.float64).contiguous()
         w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
         res = {"x": torch.empty((M, F), dtype=torch.float64, device=self.device),

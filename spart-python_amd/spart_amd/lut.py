@@ -16,10 +16,46 @@ import warnings
 
 import numpy as np
 
-from . import workloads
-from .engine import get_engine
+from . import _lib, workloads
+from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, prior_arrays,
+                     refine_args, refine_plan)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
+LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
+
+
+def _np_dtype(name):
+    """the numpy dtype of a LUT's columns (meta.json "dtype", one of engine.DTYPES' names), which is the dtype its searches run in"""
+    return np.float32 if DTYPES.get(name, _lib.SPART_F64) == _lib.SPART_F32 else np.float64
+
+
+def _torch_dtype(npdt):
+    import torch
+    return getattr(torch, np.dtype(npdt).name)
+
+
+def _host_tensor(a):
+    """the numpy array ``a`` as a CPU tensor over the same memory"""
+    import torch
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")          # read-only inputs (memmaps opened "r") are only read
+        return torch.from_numpy(a)
+
+
+def _check_out(out, shapes):
+    """out= of generate_lut / retrieve_stream: ``shapes`` {name: (shape, dtype)} -> {name: out[name]}, each checked"""
+    for n, (s, d) in shapes.items():
+        a = out.get(n)
+        if not isinstance(a, np.ndarray) or a.shape != s or a.dtype != d or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"out[{n!r}] must be a writable C-contiguous {s} {np.dtype(d).name} array")
+    return {n: out[n] for n in shapes}
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= LUT_MAX_K:
+        raise ValueError(f"k = {k}, expected 1 <= k <= {LUT_MAX_K}")
+    return int(k)
+
 
 _MADV_POPULATE_WRITE = 23          # linux/mman.h (Linux >= 5.14): fault the range in, writable, inside ONE system call
 _libc = None
@@ -156,7 +192,6 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     that the per-chunk launch / copy overheads win).
     The copies block the HOST thread (pageable memory) but not the GPU, which stays busy as long as the two copies
     of a chunk (372 B per spectrum, ~7 ms per 1M at PCIe Gen5 rates) take less than its kernels (12 ms per 1M)."""
-    import warnings
     from concurrent.futures import ThreadPoolExecutor
 
     import torch
@@ -168,12 +203,11 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     Btot = P.shape[0]
     world, rank = _group_info(shard, group)
     lo0, hi0 = shard_bounds(Btot, world, rank)
-    eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
     nb = eng.nb
-    from .api import _SRF_COLUMNS, _band_model
     srf = _band_model(band_model, eng)
-    npdt = np.float32 if dtype in ("float32", "fp32", "f32") else np.float64
-    tdt = torch.float32 if npdt is np.float32 else torch.float64
+    npdt = _np_dtype(dtype)
+    tdt = _torch_dtype(npdt)
     if path is not None and out is not None:
         raise ValueError("generate_lut: give `path` (results land in the directory's .npy files) or `out` (caller-owned arrays), not both")
     if path is not None:
@@ -185,11 +219,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
     else:
         full_out = None
         if out is not None:                                    # caller-owned destination (reused between tables: its pages are resident)
-            for k in COLUMNS:
-                a = out.get(k)
-                if not isinstance(a, np.ndarray) or a.shape != (hi0 - lo0, nb) or a.dtype != npdt or not a.flags.c_contiguous or not a.flags.writeable:
-                    raise ValueError(f"out[{k!r}] must be a writable C-contiguous ({hi0 - lo0}, {nb}) {np.dtype(npdt).name} array")
-            out = {k: out[k] for k in COLUMNS}
+            out = _check_out(out, {k: ((int(hi0 - lo0), int(nb)), npdt) for k in COLUMNS})
         else:
             out = {k: np.empty((hi0 - lo0, nb), dtype=npdt) for k in COLUMNS}
         pm = None
@@ -212,11 +242,6 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
         lo = i * chunk
         return lo, min(chunk, B - lo)
 
-    def as_tensor(a):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")          # read-only inputs (memmaps opened "r") are only read
-            return torch.from_numpy(a)
-
     def upload(i):
         j = i % 2
         lo, n = bounds(i)
@@ -227,7 +252,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
             if i >= 2:
                 h2d.wait_event(ev_done[j])                         # dsoa[j] is free once chunk i-2's kernels ran
             keep[j] = src
-            drow[j][:n].copy_(as_tensor(src), non_blocking=True)
+            drow[j][:n].copy_(_host_tensor(src), non_blocking=True)
             dsoa[j][:, :n].copy_(drow[j][:n].t())                  # -> structure of arrays (27, n)
             ev_in[j].record(h2d)
         if pm is not None:
@@ -269,7 +294,7 @@ def generate_lut(params, sensor, path=None, dtype="float32", chunk=1 << 18, devi
         with torch.cuda.device(dev), torch.cuda.stream(d2h):
             d2h.wait_event(ev_done[j])
             for q, k in enumerate(COLUMNS):
-                as_tensor(out[k][lo:lo + n]).copy_(dout[j][q, :n], non_blocking=True)
+                _host_tensor(out[k][lo:lo + n]).copy_(dout[j][q, :n], non_blocking=True)
             d2h.synchronize()                                      # dout[j] may be overwritten by chunk i+2
 
     # downloads (which also take the first-touch page faults of the destination) run on the pipeline's helper thread so
@@ -334,7 +359,7 @@ def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, 
     world, rank = _group_info(shard, group)
     lo, hi = shard_bounds(table.shape[0], world, rank)
     eng = get_engine(None, device)
-    td = torch.float32 if dtype in ("float32", "fp32", "f32") else torch.float64
+    td = _torch_dtype(_np_dtype(dtype))
     local = torch.as_tensor(np.array(table[lo:hi])).to(device=eng.device, dtype=td)      # (a copy: memmaps opened read-only)
     o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=td)
     info = {}
@@ -363,8 +388,8 @@ def invert_lut(lut, obs, column="R_TOC", weights=None, dtype=None, shard=False, 
         if local.shape[0] > 0 and M > 0:
             idx, cost = nearest(local, o) if k is None else topk(local, o, int(k))
         else:
-            if k is not None and not 1 <= int(k) <= 256:
-                raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+            if k is not None:
+                _check_k(k)
             idx = torch.full(shape, -1, dtype=torch.int64)
             cost = torch.full(shape, float("inf"), dtype=td)
     out = (idx.cpu().numpy(), cost.cpu().numpy())
@@ -440,11 +465,6 @@ def _param_columns(params_cols):
     return names, [workloads.PARAM_NAMES.index(n) for n in names]
 
 
-def _np_dtype(name):
-    """the numpy dtype of a LUT's columns (meta.json "dtype"), which is the dtype its searches run in"""
-    return np.float32 if name in ("float32", "fp32", "f32") else np.float64
-
-
 def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
            lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None, prior_weight=None,
            band_model="centre"):
@@ -453,42 +473,14 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
     ``prior`` or ``prior_mean`` / ``prior_weight`` and ``band_model`` as for Engine.refine.
     -> dict of numpy arrays x, cost, cost0, std, n_accept, y and the list ``names``.  Every argument check that needs no
     device runs before one is asked for."""
-    from .engine import _prior_tensor_shapes, prior_arrays, refine_plan
-    ready = prior_mean is not None or prior_weight is not None
-    if prior is not None and ready:
-        raise ValueError("prior and prior_mean / prior_weight exclude each other")
-    if band_model not in BAND_MODELS:
-        raise ValueError(f"band_model must be 'centre' or 'srf', got {band_model!r}")
-    plan = refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
-    if lidf not in ("literal", "newton"):
-        raise ValueError("lidf must be 'literal' or 'newton'")
-    o = np.asarray(obs, dtype=np.float64)
-    if o.ndim != 2:
-        raise ValueError(f"obs has shape {o.shape}, expected (M, nb)")
-    if not isinstance(params, (list, tuple)):
-        params = np.asarray(params, dtype=np.float64)
-        if params.ndim != 2 or params.shape[0] != workloads.NPARAM:
-            raise ValueError(f"params must be (27, M) or a list of 27 columns, got shape {params.shape}")
-        params = list(params)
-    elif len(params) != workloads.NPARAM:
-        raise ValueError(f"params must have 27 entries, got {len(params)}")
-    for c in params:
-        if c is not None and np.size(c) not in (1, o.shape[0]):
-            raise ValueError(f"a params column of {np.size(c)} values does not broadcast to the {o.shape[0]} rows of obs")
-    if weights is not None:
-        from .engine import lut_weights_kind
-        lut_weights_kind(np.shape(weights), o.shape[0], o.shape[1])
-    if ready:
-        _prior_tensor_shapes(prior_mean, prior_weight, o.shape[0], len(plan["names"]))
-    elif plan["prior"] is not None:
-        prior_arrays(plan["prior"], o.shape[0])
-    eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
-    res = eng.refine(params, o, free, weights=weights, lidf=lidf, nlayers=nlayers, prior_mean=prior_mean, prior_weight=prior_weight,
-                     band_model=band_model, _plan=plan)
+    plan, params = refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean,
+                               prior_weight, band_model)[:2]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.refine(params, np.asarray(obs, dtype=np.float64), free, weights=weights, lidf=lidf, nlayers=nlayers,
+                     prior_mean=prior_mean, prior_weight=prior_weight, band_model=band_model, _plan=plan)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
-BAND_MODELS = ("centre", "srf")
 REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor", "band_model")
 REFINE_KEYS = {"refined": "x", "refined_std": "std", "refined_cost": "cost", "refined_cost0": "cost0", "refined_accepts": "n_accept"}
 
@@ -498,7 +490,6 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     options["band_model"] is then set: the fit's band model, which must be the LUT's.  It is never taken from meta.json
     silently: an SRF iteration evaluates the whole SRF support of every band (968 model bands per row for Sentinel-2A, 13 for
     the centre model), so the caller says so."""
-    from .engine import refine_plan
     opts = dict(refine_opts or {})
     stray = [n for n in opts if n not in REFINE_OPTS]
     if stray:
@@ -525,7 +516,6 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     if not (prior is None or isinstance(prior, dict) or (isinstance(prior, str) and prior == "knn")):
         raise ValueError(f'refine_opts["prior"] = {prior!r}, expected a dict {{name: (mean, sigma)}} or "knn"')
     if "prior_floor" in opts:
-        from .engine import knn_prior
         if not (isinstance(prior, str) and prior == "knn"):
             raise ValueError('refine_opts["prior_floor"] goes with "prior": "knn"')
         knn_prior(np.zeros((0, 1)), np.zeros((0, 1)), [0.0], [1.0], floor=opts["prior_floor"])      # (its own check of floor)
@@ -543,39 +533,90 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     return plan, opts, meta.get("sensor"), sensor_info
 
 
-def _refine_rows(setup, lut_dir, obs, idx, column, weights, device):
-    """the refinement of retrieve(): start = params.npy[idx[:, 0]]; observations without a row get NaN and -1.  The "knn" prior
-    is knn_prior of Engine.lut_summarise on the free columns of the rows found, whatever summarised the other keys."""
-    from .engine import knn_prior, prior_arrays
-    plan, opts, sensor, sensor_info = setup
-    _, params, _ = load_lut(lut_dir)
-    F, M = len(plan["names"]), idx.shape[0]
-    dict_prior = None if plan["prior"] is None else prior_arrays(plan["prior"], M)
-    out = {"refined": np.full((M, F), np.nan), "refined_cost": np.full(M, np.nan), "refined_cost0": np.full(M, np.nan),
-           "refined_std": np.full((M, F), np.nan), "refined_accepts": np.full(M, -1, dtype=np.int32),
-           "refined_names": list(plan["names"])}
-    ok = np.flatnonzero(idx[:, 0] >= 0)
-    if ok.size:
-        rows, inv = np.unique(idx[ok, 0], return_inverse=True)
-        start = np.asarray(params[rows], dtype=np.float64)[inv]           # (sorted unique rows: a memmap reads only those)
-        w = None if weights is None else np.asarray(weights, dtype=np.float64)
-        if w is not None and w.ndim == 2:
-            w = w[ok]
-        eng = get_engine(sensor, device, sensor_info=sensor_info) if sensor_info is not None else get_engine(sensor, device)
-        plan = dict(plan, column=("R_TOC", "R_TOA", "L_TOA").index(column), prior=None)
+# what an observation that matches nothing gets, by output name (retrieve, retrieve_stream and the fit)
+_EMPTY = {"idx": -1, "cost": np.inf, "best_cost": np.inf, "mean": np.nan, "median": np.nan, "std": np.nan, "count": 0,
+          "refined": np.nan, "refined_std": np.nan, "refined_cost": np.nan, "refined_cost0": np.nan, "refined_accepts": -1}
+
+
+def _summary_shapes(M, P):
+    return {**{n: ((M, P), np.float64) for n in STREAM_MAPS}, "count": ((M,), np.int32)}
+
+
+def _refined_shapes(M, F):
+    return {"refined": ((M, F), np.float64), "refined_std": ((M, F), np.float64), "refined_cost": ((M,), np.float64),
+            "refined_cost0": ((M,), np.float64), "refined_accepts": ((M,), np.int32)}
+
+
+def _unmatched(shapes):
+    """host arrays {name: (shape, dtype)} in which nothing matched"""
+    return {n: np.full(s, _EMPTY[n], dtype=d) for n, (s, d) in shapes.items()}
+
+
+def _dict_prior(setup, M):
+    """the (mean, weight) arrays of refine_opts["prior"] = {name: (mean, sigma)} for M observations, else None"""
+    return None if setup is None or setup[0]["prior"] is None else prior_arrays(setup[0]["prior"], M)
+
+
+def _f64_tensor(a, device):
+    return _host_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+
+
+class _Fit:
+    """The join of search, summary, prior and fit, built once per call of retrieve / retrieve_stream from _refine_setup's
+    result: the sensor's engine (the searches run on one that needs no sensor); the plan with ``column`` re-indexed and its
+    prior taken out; a dict prior (_dict_prior) as device (mean, weight), with the row offset of the next run(); for the "knn"
+    prior the free columns of the parameter table on the device; the shared (nb,) weights as float64."""
+
+    def __init__(self, setup, params, column, shared, dict_prior, device):
+        plan, self.opts, sensor, sensor_info = setup
+        self.eng = get_engine(sensor, device, sensor_info=sensor_info)
+        dev = self.eng.device
+        self.plan = dict(plan, column=COLUMNS.index(column), prior=None)
+        self.prior = None if dict_prior is None else tuple(_f64_tensor(a, dev) for a in dict_prior)
+        self.lo = 0                                                                      # first observation of the next run()
+        self.free = _f64_tensor(np.asarray(params)[:, plan["cols"]], dev) if self.opts.get("prior") == "knn" else None
+        self.shared = None if shared is None else _f64_tensor(shared, dev)
+
+    def run(self, start, idx, obs64, w64):
+        """Engine.refine of the next n observations, all on the engine's device and its current stream: ``start`` (27, n) the
+        rows the fit starts from, ``idx`` (n, k) lut_topk's (the "knn" prior is knn_prior of Engine.lut_summarise of the free
+        columns of those rows), ``obs64`` (n, nb) float64, ``w64`` (n, nb) float64 or None (then the shared weights, if any).
+        -> the REFINE_KEYS tensors; an observation without a row (idx[:, 0] < 0) is fitted like the others and overwritten."""
+        import torch
+        n, plan, opts = idx.shape[0], self.plan, self.opts
         pm = pw = None
-        if dict_prior is not None:
-            pm, pw = (a[ok] if a.ndim == 2 else a for a in dict_prior)
-        elif opts.get("prior") == "knn":
-            import torch
-            free = np.ascontiguousarray(np.asarray(params)[:, plan["cols"]], dtype=np.float64)
-            near = eng.lut_summarise(torch.as_tensor(free).to(eng.device), torch.as_tensor(np.ascontiguousarray(idx[ok])).to(eng.device))
+        if self.prior is not None:
+            pm, pw = (a[self.lo:self.lo + n] if a.dim() == 2 else a for a in self.prior)
+        elif self.free is not None:
+            near = self.eng.lut_summarise(self.free, idx)
             pm, pw = knn_prior(near["mean"], near["std"], plan["lo"], plan["hi"], floor=opts.get("prior_floor", 0.05))
-        r = eng.refine(list(np.ascontiguousarray(start.T)), np.asarray(obs, dtype=np.float64)[ok], plan["names"], weights=w,
-                       lidf=opts.get("lidf", "literal"), nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw,
-                       band_model=opts["band_model"], _plan=plan)
+        self.lo += n
+        r = self.eng.refine(start, obs64, plan["names"], weights=self.shared if w64 is None else w64, lidf=opts.get("lidf", "literal"),
+                            nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw, band_model=opts["band_model"], _plan=plan)
+        none = idx[:, 0] < 0
+        out = {}
         for key, name in REFINE_KEYS.items():
-            out[key][ok] = r[name].cpu().numpy()
+            v = r[name]
+            out[key] = torch.where(none[:, None] if v.dim() == 2 else none, torch.full((), _EMPTY[key], dtype=v.dtype, device=v.device), v)
+        return out
+
+
+def _refine_best(setup, dict_prior, lut_dir, obs, idx, column, weights, device):
+    """the refinement of retrieve(): start = params.npy[idx[:, 0]], gathered on the host (a memmap reads only the rows it needs),
+    one _Fit.run for all M observations; no engine is asked for when no observation has a row"""
+    plan = setup[0]
+    out = _unmatched(_refined_shapes(idx.shape[0], len(plan["names"])))
+    if (idx[:, :1] >= 0).any():
+        _, params, _ = load_lut(lut_dir)
+        shared = weights if weights is not None and np.ndim(weights) == 1 else None
+        fit = _Fit(setup, params, column, shared, dict_prior, device)
+        dev = fit.eng.device
+        rows, inv = np.unique(np.maximum(idx[:, 0], 0), return_inverse=True)
+        start = np.asarray(params[rows], dtype=np.float64)[inv]           # (sorted unique rows: a memmap reads only those)
+        w64 = None if weights is None or shared is not None else _f64_tensor(weights, dev)
+        r = fit.run(_f64_tensor(start.T, dev), _host_tensor(np.ascontiguousarray(idx)).to(dev), _f64_tensor(obs, dev), w64)
+        out = {key: v.cpu().numpy() for key, v in r.items()}
+    out["refined_names"] = list(plan["names"])
     return out
 
 
@@ -614,12 +655,10 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
     setup = _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info)
-    if setup is not None and setup[0]["prior"] is not None:
-        from .engine import prior_arrays
-        prior_arrays(setup[0]["prior"], np.shape(obs)[0])                # (an array that is not (M,): refused before the search)
+    dict_prior = _dict_prior(setup, np.shape(obs)[0])                    # (an array that is not (M,): refused before the search)
     out = _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, summary, params_cols, names, cols)
     if setup is not None:
-        out.update(_refine_rows(setup, lut_dir, obs, out["idx"], column, weights, device))
+        out.update(_refine_best(setup, dict_prior, lut_dir, obs, out["idx"], column, weights, device))
     return out
 
 
@@ -639,33 +678,38 @@ def _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, su
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
     npdt = _np_dtype(meta["dtype"])
-    td = torch.float32 if npdt is np.float32 else torch.float64
-    k = int(k)
-    if not 1 <= k <= 256:
-        raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+    k = _check_k(int(k))
     eng = get_engine(None, device)
-    o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=td)
-    M, B, P = o.shape[0], table.shape[0], len(cols)
+    o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=_torch_dtype(npdt))
+    M, B = o.shape[0], table.shape[0]
     if B > 0 and M > 0:
-        lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=td)          # (a copy: memmaps opened read-only)
-        par_t = torch.as_tensor(np.ascontiguousarray(np.asarray(params)[:, cols], dtype=np.float64)).to(eng.device)
-        idx_t, cost_t = eng.lut_topk(lut_t, o, k, weights=weights, dtype=meta["dtype"])
-        res = eng.lut_summarise(par_t, idx_t)                                             # idx never left the device
-        out = {"idx": idx_t.cpu().numpy(), "cost": cost_t.cpu().numpy()}
-        out.update({n: res[n].cpu().numpy() for n in STREAM_MAPS + ("count",)})
+        idx, cost, res = _topk_summary(eng, *_upload_lut(eng, table, params, cols, npdt), o, k, weights, meta["dtype"])
+        out = {n: v.cpu().numpy() for n, v in {"idx": idx, "cost": cost, **res}.items()}
     else:
-        out = {"idx": np.full((M, k), -1, dtype=np.int64), "cost": np.full((M, k), np.inf, dtype=npdt)}
-        out.update({n: np.full((M, P), np.nan) for n in STREAM_MAPS})
-        out["count"] = np.zeros(M, dtype=np.int32)
+        out = _unmatched({"idx": ((M, k), np.int64), "cost": ((M, k), npdt), **_summary_shapes(M, len(cols))})
     out["names"] = names
     return out
+
+
+def _upload_lut(eng, table, params, cols, npdt):
+    """the LUT column in its own dtype and the chosen parameter columns as float64, on the engine's device"""
+    import torch
+    lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=_torch_dtype(npdt))     # (a copy: memmaps opened read-only)
+    return lut_t, _f64_tensor(np.asarray(params)[:, cols], eng.device)
+
+
+def _topk_summary(eng, lut_t, par_t, obs_t, k, weights, dtype):
+    """Engine.lut_topk, then Engine.lut_summarise of the rows found: the indices never leave the device
+    -> (idx (n, k), cost (n, k), {mean, median, std, count})"""
+    idx, cost = eng.lut_topk(lut_t, obs_t, k, weights=weights, dtype=dtype)
+    return idx, cost, eng.lut_summarise(par_t, idx)
 
 
 class _DeviceStage:
     """The device side of retrieve_stream: the LUT column and the parameter columns, uploaded once; two sets of chunk
     buffers; three streams.  upload / launch / download are what _run_pipeline calls for buffer j = chunk number % 2."""
 
-    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights, refine=None):
+    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights, fit=None, params=None):
         import torch
         self.torch, self.eng, self.lut, self.par, self.k, self.dtype = torch, eng, lut_t, par_t, k, dtype
         dev = self.dev = eng.device
@@ -680,18 +724,15 @@ class _DeviceStage:
         self.used = [False, False]
         self.keep = [None, None]        # host sources of the upload in flight on buffer j
         self.res = [None, None]         # device results of the chunk in buffer j, until its download is done
-        # retrieve_stream(refine=...): a _StreamRefine.  The fit runs in float64: a float32 LUT's chunks go up a second time,
-        # as float64 (obs64 / w64), so that it sees the numbers retrieve() hands to Engine.refine
-        self.refine = refine
-        self.wide = refine is not None and lut_t.dtype != torch.float64
+        # retrieve_stream(refine=...): a _Fit and the WHOLE parameter table, (B, 27): 216 B per row, which the start rows are
+        # gathered from.  The fit runs in float64: a float32 LUT's chunks go up a second time, as float64 (obs64 / w64), so that
+        # it sees the numbers retrieve() hands to it
+        self.fit = fit
+        self.table = None if fit is None else _f64_tensor(np.asarray(params), dev)
+        self.wide = fit is not None and lut_t.dtype != torch.float64
         if self.wide:
             self.obs64 = [torch.empty((chunk, nb), dtype=torch.float64, device=dev) for _ in range(2)]
             self.w64 = [torch.empty((chunk, nb), dtype=torch.float64, device=dev) for _ in range(2)] if per_obs_weights else None
-
-    def _tensor(self, a):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")          # read-only inputs (memmaps opened "r") are only read
-            return self.torch.from_numpy(a)
 
     def upload(self, j, obs, w, obs64=None, w64=None):
         n = obs.shape[0]
@@ -699,26 +740,26 @@ class _DeviceStage:
             if self.used[j]:
                 self.h2d.wait_event(self.ev_done[j])               # the kernels that read buffer j last have run
             self.keep[j] = (obs, w, obs64, w64)
-            self.obs[j][:n].copy_(self._tensor(obs), non_blocking=True)
+            self.obs[j][:n].copy_(_host_tensor(obs), non_blocking=True)
             if w is not None:
-                self.w[j][:n].copy_(self._tensor(w), non_blocking=True)
+                self.w[j][:n].copy_(_host_tensor(w), non_blocking=True)
             if self.wide:
-                self.obs64[j][:n].copy_(self._tensor(obs64), non_blocking=True)
+                self.obs64[j][:n].copy_(_host_tensor(obs64), non_blocking=True)
                 if w64 is not None:
-                    self.w64[j][:n].copy_(self._tensor(w64), non_blocking=True)
+                    self.w64[j][:n].copy_(_host_tensor(w64), non_blocking=True)
             self.ev_in[j].record(self.h2d)
         self.used[j] = True
 
     def launch(self, j, n):
         self.compute.wait_event(self.ev_in[j])
         w = self.w[j][:n] if self.w is not None else self.shared
-        idx, cost = self.eng.lut_topk(self.lut, self.obs[j][:n], self.k, weights=w, dtype=self.dtype)
-        res = self.eng.lut_summarise(self.par, idx)
+        idx, cost, res = _topk_summary(self.eng, self.lut, self.par, self.obs[j][:n], self.k, w, self.dtype)
         res["best_cost"] = cost[:, 0].contiguous()
-        if self.refine is not None:
+        if self.fit is not None:
+            start = self.table.index_select(0, idx[:, 0].clamp(min=0)).t().contiguous()      # (27, n)
             o64 = self.obs64[j][:n] if self.wide else self.obs[j][:n]
-            w64 = (self.w64[j][:n] if self.wide else w) if self.w is not None else self.refine.shared
-            res.update(self.refine.run(idx, o64, w64))
+            w64 = None if self.w is None else (self.w64[j][:n] if self.wide else w)
+            res.update(self.fit.run(start, idx, o64, w64))
         self.res[j] = res
         self.ev_done[j].record(self.compute)
 
@@ -726,51 +767,8 @@ class _DeviceStage:
         with self.torch.cuda.device(self.dev), self.torch.cuda.stream(self.d2h):
             self.d2h.wait_event(self.ev_done[j])
             for name, a in dest.items():
-                self._tensor(a).copy_(self.res[j][name], non_blocking=True)
+                _host_tensor(a).copy_(self.res[j][name], non_blocking=True)
             self.d2h.synchronize()                                 # res[j] may be replaced by chunk i + 2
-
-
-class _StreamRefine:
-    """The refinement of one chunk of retrieve_stream, on the engine's current stream with nothing going through the host:
-    start rows gathered from the whole parameter table on the device, the "knn" prior from the chunk's own summary of the
-    free columns, Engine.refine in its device-tensor form, rows without a match overwritten with NaN / -1."""
-
-    def __init__(self, setup, eng, params, column, shared, dict_prior):
-        import torch
-        self.eng = eng                                 # the sensor's engine (the searches run on the stage's, which needs none)
-        self.plan, self.opts, _, _ = setup
-        self.plan = dict(self.plan, column=("R_TOC", "R_TOA", "L_TOA").index(column), prior=None)
-        P = np.ascontiguousarray(np.asarray(params), dtype=np.float64)
-        self.table = torch.as_tensor(P).to(eng.device)                                   # (B, 27): 216 B per row
-        self.free = self.table[:, torch.as_tensor(self.plan["cols"].astype(np.int64)).to(eng.device)].contiguous()
-        self.shared = None if shared is None else torch.as_tensor(np.ascontiguousarray(shared, dtype=np.float64)).to(eng.device)
-        self.prior = None if dict_prior is None else tuple(torch.as_tensor(a).to(eng.device) for a in dict_prior)
-        self.lo = 0                                                                      # first observation of the next chunk
-
-    def run(self, idx, obs, w):
-        import torch
-        eng = self.eng
-        from .engine import knn_prior
-        n, best = idx.shape[0], idx[:, 0]
-        start = self.table.index_select(0, best.clamp(min=0)).t().contiguous()           # (27, n)
-        pm = pw = None
-        if self.prior is not None:
-            pm, pw = (a[self.lo:self.lo + n] if a.dim() == 2 else a for a in self.prior)
-        elif self.opts.get("prior") == "knn":
-            near = eng.lut_summarise(self.free, idx)
-            pm, pw = knn_prior(near["mean"], near["std"], self.plan["lo"], self.plan["hi"], floor=self.opts.get("prior_floor", 0.05))
-        self.lo += n
-        r = eng.refine(start, obs, self.plan["names"], weights=w, lidf=self.opts.get("lidf", "literal"),
-                       nlayers=self.opts.get("nlayers"), prior_mean=pm, prior_weight=pw, band_model=self.opts["band_model"],
-                       _plan=self.plan)
-        none = best < 0
-        nan = torch.full((), float("nan"), dtype=torch.float64, device=idx.device)
-        out = {}
-        for key, name in REFINE_KEYS.items():
-            v = r[name]
-            miss = none[:, None] if v.dim() == 2 else none
-            out[key] = torch.where(miss, torch.full((), -1, dtype=torch.int32, device=idx.device) if name == "n_accept" else nan, v)
-        return out
 
 
 def _stream_chunks(obs, weights, chunk, out, stage, npdt, wide=False):
@@ -825,60 +823,34 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
     names, cols = _param_columns(params_cols)
-    k = int(k)
-    if not 1 <= k <= 256:
-        raise ValueError(f"k = {k}, expected 1 <= k <= 256")
+    k = _check_k(int(k))
     B, nb = table.shape
     npdt = _np_dtype(meta["dtype"])
     obs = obs if isinstance(obs, np.memmap) else np.asarray(obs)
     if obs.ndim != 2 or obs.shape[1] != nb:
         raise ValueError(f"obs must be (M, {nb}), got shape {obs.shape}")
-    M, P = obs.shape[0], len(cols)
-    from .engine import lut_weights_kind
+    M = obs.shape[0]
     if weights is not None and not isinstance(weights, np.memmap):
         weights = np.asarray(weights)
     kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
-    shapes = {**{n: ((M, P), np.float64) for n in STREAM_MAPS}, "count": ((M,), np.int32), "best_cost": ((M,), npdt)}
-    dict_prior = None
+    shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt)}
     if setup is not None:
-        F = len(setup[0]["names"])
-        shapes.update({"refined": ((M, F), np.float64), "refined_std": ((M, F), np.float64), "refined_cost": ((M,), np.float64),
-                       "refined_cost0": ((M,), np.float64), "refined_accepts": ((M,), np.int32)})
-        if setup[0]["prior"] is not None:
-            from .engine import prior_arrays
-            dict_prior = prior_arrays(setup[0]["prior"], M)
-    if out is None:
-        res = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()}
-    else:
-        for n, (s, d) in shapes.items():
-            a = out.get(n)
-            if not isinstance(a, np.ndarray) or a.shape != s or a.dtype != d or not a.flags.c_contiguous or not a.flags.writeable:
-                raise ValueError(f"out[{n!r}] must be a writable C-contiguous {s} {np.dtype(d).name} array")
-        res = {n: out[n] for n in shapes}
+        shapes.update(_refined_shapes(M, len(setup[0]["names"])))
+    dict_prior = _dict_prior(setup, M)
+    res = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()} if out is None else _check_out(out, shapes)
     if B == 0:                                                     # an empty table matches nothing
-        for n in STREAM_MAPS:
-            res[n][...] = np.nan
-        res["count"][...] = 0
-        res["best_cost"][...] = np.inf
-        for n in res:
-            if n.startswith("refined"):
-                res[n][...] = -1 if n == "refined_accepts" else np.nan
+        for n, a in res.items():
+            a[...] = _EMPTY[n]
     elif M > 0:
         stage = _stage
         if stage is None:
-            import torch
             eng = get_engine(None, device)
-            td = torch.float32 if npdt is np.float32 else torch.float64
-            lut_t = torch.as_tensor(np.array(table)).to(device=eng.device, dtype=td)      # (a copy: memmaps opened read-only)
-            par_t = torch.as_tensor(np.ascontiguousarray(np.asarray(params)[:, cols], dtype=np.float64)).to(eng.device)
-            shared = None if kind != "shared" else torch.as_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
-            fit = None
-            if setup is not None:
-                _, _, sensor, sinfo = setup
-                fit_eng = get_engine(sensor, device, sensor_info=sinfo) if sinfo is not None else get_engine(sensor, device)
-                fit = _StreamRefine(setup, fit_eng, params, column, weights if kind == "shared" else None, dict_prior)
-            stage = _DeviceStage(eng, lut_t, par_t, k, meta["dtype"], max(1, min(int(chunk), M)), kind == "per_observation", shared,
-                                 refine=fit)
+            shared = weights if kind == "shared" else None
+            fit = None if setup is None else _Fit(setup, params, column, shared, dict_prior, device)
+            if shared is not None:
+                shared = _host_tensor(np.ascontiguousarray(shared, dtype=npdt)).to(eng.device)
+            stage = _DeviceStage(eng, *_upload_lut(eng, table, params, cols, npdt), k, meta["dtype"], max(1, min(int(chunk), M)),
+                                 kind == "per_observation", shared, fit=fit, params=params)
         _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt,
                        wide=bool(getattr(stage, "wide", False)))
     res["names"] = names

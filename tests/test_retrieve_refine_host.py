@@ -1,7 +1,8 @@
 """retrieve_stream(refine=...) without a GPU: the chunk arithmetic of a float32 LUT -- every chunk goes up twice, in the LUT's
 dtype for the search and as float64 of the caller's arrays for the fit -- with an injected stage that records what it is handed
 and answers with the definition tests/helpers/retrieve_defined.py over a toy forward model; that definition's own invariants;
-and the edges of retrieve_stream(refine=...) that are settled before a device is asked for."""
+the edges of retrieve_stream(refine=...) that are settled before a device is asked for; and retrieve(refine=...) itself, the
+join of search, summary, prior and fit, over a stand-in engine that answers with the definitions under tools/."""
 import json
 import os
 
@@ -98,6 +99,15 @@ class WideStage:
             a[...] = self.res[j][name]
 
 
+def rounded_numbers_end_elsewhere(params, table, obs, w, lo, hi, fit, want):
+    """the float64 copies matter: with the rounded numbers the definition ends elsewhere"""
+    rounded = retrieve_defined(params, table, obs.astype(np.float32), K, w, NAMES, lo, hi, forward, **fit)
+    assert same(rounded["idx"], want["idx"]) and not same(rounded["refined"], want["refined"])
+    if w is not None and w.ndim == 2:
+        rounded = retrieve_defined(params, table, obs, K, w.astype(np.float32), NAMES, lo, hi, forward, **fit)
+        assert same(rounded["idx"], want["idx"]) and not same(rounded["refined"], want["refined"])
+
+
 @pytest.fixture(scope="module")
 def toy_lut(tmp_path_factory):
     params = np.random.default_rng(5).uniform(0.0, 1.0, (B, 27))
@@ -123,12 +133,7 @@ def test_a_float32_lut_sends_every_chunk_up_twice(toy_lut, weights, prior):
     assert (want["refined_accepts"][matched] >= 0).mean() > 0.5 and (want["refined_accepts"] >= 1).any()
     assert not same(want["refined"], want["start"])
     assert np.isnan(want["refined"][~matched]).all() and (want["refined_accepts"][~matched] == -1).all()
-    # the float64 copies matter: with the rounded numbers the definition ends elsewhere
-    rounded = retrieve_defined(params, table, obs.astype(np.float32), K, w, NAMES, lo, hi, forward, **fit)
-    assert same(rounded["idx"], want["idx"]) and not same(rounded["refined"], want["refined"])
-    if weights == "per_observation":
-        rounded = retrieve_defined(params, table, obs, K, w.astype(np.float32), NAMES, lo, hi, forward, **fit)
-        assert same(rounded["idx"], want["idx"]) and not same(rounded["refined"], want["refined"])
+    rounded_numbers_end_elsewhere(params, table, obs, w, lo, hi, fit, want)
     scene = np.asfortranarray(obs)                                   # (not C-contiguous: the chunks must be made so)
     for chunk, sizes in ((1, [1] * M), (7, [7, 7, 7, 2]), (M, [M]), (M + 1, [M])):
         stage = WideStage(params, table, scene, w, lo, hi, **fit)
@@ -275,3 +280,108 @@ def test_stream_edges_that_need_no_device(toy_lut, tmp_path):
     want = retrieve_defined(flat, tc, obs, K, None, NAMES, l2, h2, forward, n_iter=2)
     assert all(same(got[k], want[k]) for k in REFINED) and (want["refined_accepts"] >= 1).any()
     assert not same(want["refined"][:, 2], want["start"][:, 2])     # the bounded constant column moves
+
+
+class HostEngine:
+    """Engine's part in retrieve(refine=...) on the host: lut_topk, lut_summarise and refine answer with the definitions under
+    tools/ wrapped in CPU tensors (the fit over the toy forward model, whatever the column), and ``fits`` records what every
+    refine call was handed"""
+    device = "cpu"
+
+    def __init__(self):
+        self.fits = []
+
+    def lut_topk(self, lut, obs, k, weights=None, dtype="float32", stats=False):
+        import torch
+        from helpers.retrieve_defined import bf
+        lut = np.ascontiguousarray(np.asarray(lut))
+        assert lut.dtype == np.dtype(dtype) and not stats
+        o = np.ascontiguousarray(np.asarray(obs), dtype=lut.dtype)
+        w = None if weights is None else np.ascontiguousarray(np.asarray(weights), dtype=lut.dtype)
+        search = bf.brute_force_topk_obs_weights_numpy if w is not None and w.ndim == 2 else bf.brute_force_topk_numpy
+        return tuple(torch.as_tensor(a) for a in search(lut, o, k, w))
+
+    def lut_summarise(self, params, idx):
+        import torch
+        from helpers.retrieve_defined import bf
+        res = bf.summarise_defined(np.asarray(params), np.asarray(idx))
+        return {n: torch.as_tensor(a) for n, a in zip(("mean", "median", "std", "count"), res)}
+
+    def refine(self, params, obs, free, **kw):
+        import torch
+        from helpers.retrieve_defined import rd
+        plan = kw["_plan"]
+        assert list(free) == plan["names"] and plan["prior"] is None and all(torch.is_tensor(t) for t in (params, obs))
+        num = lambda t: None if t is None else t.numpy().copy()      # noqa: E731
+        self.fits.append(dict(kw, params=num(params), obs=num(obs), weights=num(kw["weights"])))
+        r = rd.refine_defined(num(params).T, plan["cols"], plan["lo"], plan["hi"], num(obs), forward, weights=num(kw["weights"]),
+                              n_iter=plan["n_iter"], rel_step=plan["rel_step"], lambda0=plan["lambda0"],
+                              prior_mean=num(kw["prior_mean"]), prior_weight=num(kw["prior_weight"]))
+        return dict({n: torch.as_tensor(r[n]) for n in ("x", "cost", "cost0", "std", "n_accept", "y")}, names=list(free))
+
+
+@pytest.fixture()
+def host_engine(monkeypatch):
+    """spart_amd.lut.get_engine answers with ONE HostEngine; ``asked`` lists (sensor, keyword arguments) of every call"""
+    from spart_amd import lut
+    eng = HostEngine()
+    eng.asked = []
+
+    def get_engine(sensor=None, device=None, **kw):
+        eng.asked.append((sensor, kw))
+        return eng
+    monkeypatch.setattr(lut, "get_engine", get_engine)
+    return eng
+
+
+@pytest.mark.parametrize("prior", [None, "knn", "dict"])
+@pytest.mark.parametrize("weights", ["none", "shared", "per_observation"])
+def test_retrieve_joins_search_summary_prior_and_fit_as_defined(toy_lut, host_engine, tmp_path, weights, prior):
+    """retrieve(refine=...) on the host and on the device summary against retrieve_defined, bit for bit, with what the fit
+    was handed: the column's number, lidf, nlayers, the band model, the sensor_info, and float64 of the caller's arrays"""
+    from spart_amd import retrieve
+    _, params, table = toy_lut
+    d, _ = write_lut(tmp_path / "lut", params, "float32", columns=["R_TOC", "L_TOA"])
+    np.save(os.path.join(d, "L_TOA.npy"), table)
+    obs, w = toy_scene(weights)
+    lo, hi = free_bounds(params)
+    if prior == "dict":
+        prior = {"LAI": (np.linspace(0.2, 0.8, M), 0.1), "Cab": (0.5, 0.2)}
+    fit = dict(n_iter=3, rel_step=2e-3, lambda0=0.1, prior=prior, prior_floor=0.1 if prior == "knn" else 0.05)
+    opts = {k: v for k, v in fit.items() if k != "prior_floor" and v is not None}
+    if prior == "knn":
+        opts["prior_floor"] = 0.1
+    opts.update(lidf="newton", nlayers=30)
+    want = retrieve_defined(params, table, obs, K, w, NAMES, lo, hi, forward, **fit)
+    matched = want["idx"][:, 0] >= 0
+    assert not matched[8] and matched.sum() >= M - 3 and (want["refined_accepts"] >= 1).any()
+    assert np.isnan(want["refined"][~matched]).all() and (want["refined_accepts"][~matched] == -1).all()
+    rounded_numbers_end_elsewhere(params, table, obs, w, lo, hi, fit, want)
+    sinfo = {"a sensorinfo": "handed on as it is"}
+    for summary in ("host", "device"):
+        del host_engine.fits[:], host_engine.asked[:]
+        got = retrieve(d, obs, K, column="L_TOA", weights=w, summary=summary, refine=NAMES, refine_opts=opts, sensor_info=sinfo)
+        assert got["refined_names"] == NAMES and same(got["idx"], want["idx"]) and same(got["cost"], want["cost"])
+        for name in REFINED:
+            assert same(got[name], want[name]), (summary, name)
+        assert [a for a in host_engine.asked if a[0] is not None] == [("Sentinel2A-MSI", {"sensor_info": sinfo})]
+        (seen,) = host_engine.fits                                       # one call for all M observations
+        assert seen["_plan"]["column"] == 2 and seen["lidf"] == "newton" and seen["nlayers"] == 30 and seen["band_model"] == "centre"
+        assert same(seen["obs"], np.asarray(obs, dtype=np.float64)) and seen["params"].shape == (27, M)
+        assert same(seen["params"][:, matched], np.ascontiguousarray(params[want["idx"][matched, 0]].T))
+        assert (seen["weights"] is None) if w is None else (same(seen["weights"], w) and not same(seen["weights"], w.astype(np.float32).astype(np.float64)))
+
+
+def test_retrieve_without_a_row_or_an_observation_asks_for_no_fit(toy_lut, host_engine, tmp_path):
+    from spart_amd import retrieve
+    d32, params, table = toy_lut
+    dn, _ = write_lut(tmp_path / "nan", params, "float32", table=np.full((B, NB), np.nan))
+    obs, w = toy_scene("per_observation")
+    for d, o, ww, m in ((dn, obs, w, M), (d32, np.empty((0, NB)), None, 0)):
+        for summary in ("host", "device"):
+            got = retrieve(d, o, K, weights=ww, summary=summary, refine=NAMES, refine_opts={"prior": "knn"})
+            assert host_engine.fits == [] and all(a[0] is None for a in host_engine.asked) and got["refined_names"] == NAMES
+            assert got["idx"].shape == (m, K) and (got["idx"] == -1).all() and np.isinf(got["cost"]).all()
+            assert got["refined"].shape == got["refined_std"].shape == (m, 4) and got["refined_accepts"].dtype == np.int32
+            assert all(np.isnan(got[k]).all() for k in REFINED[:4]) and (got["refined_accepts"] == -1).all()
+            assert all(got[k].shape == (m,) and got[k].dtype == np.float64 for k in ("refined_cost", "refined_cost0"))
