@@ -65,7 +65,9 @@ extern "C" {
  *  13: spart_refine, spart_refine_workspace_bytes, spart_refine_opt
  *  14: spart_refine_opt.prior_per_obs, prior_mean, prior_weight
  * spart_refine_srf was added WITHOUT a new number: it is one more symbol, no struct layout or argument list changed, so every
- * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library. */
+ * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library.
+ * spart_refine_views, spart_views_workspace_bytes and spart_refine_views_opt were added by the same rule: new symbols
+ * and a new struct that embeds spart_refine_opt unchanged. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -468,6 +470,51 @@ int spart_refine_srf(spart_ctx *ctx, int64_t M, const double *const base[SPART_N
                      const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
                      const spart_refine_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
                      double *y, void *workspace, size_t workspace_bytes, void *stream);
+
+/* spart_refine for several observations of the SAME surface (the cameras of a multi-angle instrument, a few overpasses, a short
+ * time series): per pixel ONE unknown vector is fitted against V observations ("views"), each with its own fixed parameters.
+ * The first Fs = opt->n_shared entries of free_cols are SHARED (one value for all views), the other Fl = F - Fs are LOCAL (one
+ * value per view): n = Fs + V Fl unknowns per pixel, 1 <= n <= 16.  Unknown a < Fs is shared name a; unknown Fs + v Fl + l is
+ * local name Fs + l in view v.  With V = 1 the call is spart_refine (band_model 0) / spart_refine_srf (band_model 1) bit for bit.
+ *   base[27]  each (V, M) view-major float64 device memory: element [v M + m] is view v of pixel m.  The entries of a shared
+ *             column in views 1 ... V-1 are never read (they may be NaN)
+ *   free_cols, lo, hi  HOST (F,): one bound pair per NAME
+ *   obs, y    (M, V, nb) row-major;  weights NULL, (nb,) applied to every view, or (M, V, nb) (opt->fit.weights_per_obs = 1)
+ *   opt->fit  spart_refine's options; prior_mean / prior_weight are (n,) or (M, n) (prior_per_obs = 1), per unknown
+ *   x, std    (M, n);  cost, cost0, n_accept (M,)
+ * Definition (tools/refine_views_defined.py is the same text in numpy).  Virtual band u = v nb + j; unknown a is ACTIVE in view
+ * v if it is shared or a local of view v.
+ *   start   shared z_a = base[free[a]] of view 0, clipped; local z_(v,l) = base[free[Fs + l]] of view v, clipped; h_a =
+ *           rel_step (hi - lo) of the name
+ *   rows    each iteration and view evaluates F + 1 rows: p_(v,0) = view v's base with the free columns taken from the trial
+ *           (the shared values and that view's locals); p_(v,f) = p_(v,0) with column free[f-1] moved by s_a h_a of the unknown
+ *           it belongs to, s_a by spart_refine's rule on t_a.  One forward call evaluates V (F + 1) rows per pixel
+ *   cost    spart_refine's band loop over u ascending (w_u == 0 skips the band), then the prior over the n unknowns ascending
+ *   J       J_ua = (Y_f(a)[v, j] - Y_0[v, j]) / (s_a h_a) where a is active in v; elsewhere the entry is structurally absent.
+ *           A_ab (a >= b) and g_a are spart_refine's sums over u ascending restricted to the u where a (and b) are active and
+ *           w_u != 0: an absent entry is SKIPPED, never multiplied in, so local pairs of different views are exactly 0 and a NaN
+ *           in one view's column cannot leak into another view's unknowns
+ *   everything else is spart_refine's text with F read as n: decision, dead observations (a pixel is dead as a whole), lambda
+ *   and its clamps, the prior's additions, D, Cholesky and its failure rule, clip, std, no early exit, the prefix property,
+ *   cost <= cost0.
+ * Consequences: a view whose weights are all zero leaves its locals at their clipped start (delta = 0 exactly); without a prior
+ * on those locals the undamped A is singular and the pixel's whole std row is NaN; with a prior weight on them std is finite.
+ * Pixels go in chunks of max(1, (1 << 19) / ((F + 1) V)); the workspace is bounded by one chunk like spart_refine's.
+ * Refused before anything is launched or written: spart_refine's list in its order, with -- after the NULL check of base,
+ * free_cols, lo, hi, opt -- V outside 1 ... 64, n_shared outside 0 ... F, n outside 1 ... 16, band_model outside 0 / 1.
+ * spart_views_workspace_bytes is 0 exactly for refused sizes (spart_refine_workspace_bytes stays the one size query of
+ * spart_refine and spart_refine_srf: this call has its own, named apart). */
+typedef struct spart_refine_views_opt {
+  spart_refine_opt fit;    /* column, n_iter, weights_per_obs, fast_prelude, nlayers, rel_step, lambda0, the prior */
+  int32_t V;               /* views per pixel, 1 ... 64 */
+  int32_t n_shared;        /* Fs: the first Fs entries of free_cols are shared, the other F - Fs local */
+  int32_t band_model;      /* 0: centre columns (spart_refine's forward call), 1: SRF columns (spart_refine_srf's) */
+} spart_refine_views_opt;
+size_t spart_views_workspace_bytes(const spart_ctx *ctx, int64_t M, int V, int F, int n_shared);
+int spart_refine_views(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                       const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
+                       const spart_refine_views_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
+                       double *y, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

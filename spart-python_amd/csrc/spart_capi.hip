@@ -20,6 +20,7 @@
 #include "spart_kernels.h"
 #include "spart_lut.h"
 #include "spart_refine.h"
+#include "spart_refine_views.h"
 
 using namespace spart;
 
@@ -1275,16 +1276,10 @@ size_t spart_refine_workspace_bytes(const spart_ctx* ctx, int64_t M, int F) {
   return refine_sizes_ok(ctx, M, F) ? refine_layout(ctx->nb, M, F).total : 0;
 }
 
-// spart_refine and spart_refine_srf: one argument check, one refusal order
-static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F,
-                       const int32_t* free_cols, const double* lo, const double* hi, const double* obs, const double* weights,
-                       const spart_refine_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
-                       double* y, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  spart_refine_opt o = *opt;
+// What spart_refine, spart_refine_srf and spart_refine_views check about the fit itself, in one order: the options (with the
+// defaults that 0 stands for filled in), then every free column with its bounds, which become `cfg`.
+static int refine_check_fit(const char* who, spart_refine_opt& o, int F, const int32_t* free_cols, const double* lo,
+                            const double* hi, RefineCfg& cfg) {
   if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
   if (o.n_iter < 0 || o.n_iter > REFINE_MAX_ITER)
     return fail(SPART_ERR_INVALID, "%s: n_iter = %d, expected 0 ... %d", who, o.n_iter, REFINE_MAX_ITER);
@@ -1293,12 +1288,11 @@ static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, con
   if (!(o.rel_step >= 0.0) || !(o.lambda0 >= 0.0) || std::isinf(o.rel_step) || std::isinf(o.lambda0))
     return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
   if (o.prior_per_obs != 0 && o.prior_per_obs != 1)
-    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: (F,), 1: (M, F))", who, o.prior_per_obs);
+    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: one row for all, 1: one row per observation)", who, o.prior_per_obs);
   if (!o.prior_mean != !o.prior_weight)
     return fail(SPART_ERR_INVALID, "%s: prior_mean and prior_weight come together (both NULL = no prior)", who);
   if (o.rel_step == 0.0) o.rel_step = 1e-3;
   if (o.lambda0 == 0.0) o.lambda0 = 1e-2;
-  RefineCfg cfg;
   std::memset(&cfg, 0, sizeof(cfg));
   for (int f = 0; f < F; ++f) {
     const int c = free_cols[f];
@@ -1312,6 +1306,21 @@ static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, con
     cfg.hi[f] = hi[f];
     cfg.h[f] = o.rel_step * (hi[f] - lo[f]);
   }
+  return SPART_OK;
+}
+
+// spart_refine and spart_refine_srf: one argument check, one refusal order
+static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F,
+                       const int32_t* free_cols, const double* lo, const double* hi, const double* obs, const double* weights,
+                       const spart_refine_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
+                       double* y, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  spart_refine_opt o = *opt;
+  RefineCfg cfg;
+  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
   if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
   if (M == 0) return SPART_OK;
   if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
@@ -1342,6 +1351,134 @@ int spart_refine_srf(spart_ctx* ctx, int64_t M, const double* const base[SPART_N
                      size_t workspace_bytes, void* stream) {
   return refine_call("spart_refine_srf", true, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept,
                      y, workspace, workspace_bytes, stream);
+}
+
+// ---- spart_refine_views (csrc/spart_refine_views.h).  The workspace is spart_refine's, sized by ONE chunk of
+// views_chunk(V, F) pixels: V (F + 1) table rows per pixel, the state per unknown.
+static RefineLayout views_layout(int nb, int64_t M, int V, int F, int n) {
+  RefineLayout l;
+  l.mcap = std::min<int64_t>(M, views_chunk(V, F));
+  const size_t mc = (size_t)l.mcap, per = (size_t)(F + 1) * V, rows = mc * per;
+  Carver c;
+  l.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.t = c.take(mc * n * 8);
+  l.A = c.take(mc * (size_t)(refine_ntri(n) + n) * 8);
+  l.lam = c.take(mc * 8);
+  l.na = c.take(mc * 4);
+  l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
+  l.cfg_free = c.take(REFINE_MAXF * 4);
+  size_t fwd = carve(SPART_F64, (int64_t)rows).total;         // (a full chunk and the last, shorter one: see refine_layout)
+  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (int64_t)per).total);
+  l.fwd = c.take(fwd);
+  l.total = c.o;
+  return l;
+}
+
+static bool views_sizes_ok(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
+  if (!refine_sizes_ok(ctx, M, F) || V < 1 || V > VIEWS_MAXV || n_shared < 0 || n_shared > F) return false;
+  const int n = n_shared + V * (F - n_shared);
+  return n >= 1 && n <= REFINE_MAXF;
+}
+
+size_t spart_views_workspace_bytes(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
+  return views_sizes_ok(ctx, M, V, F, n_shared) ? views_layout(ctx->nb, M, V, F, n_shared + V * (F - n_shared)).total : 0;
+}
+
+// refine_impl's chunk loop with the view-major table and the joint step kernel; o.prior_* are per unknown
+static int views_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int V, int F, int Fs, const double* obs,
+                      const double* weights, const spart_refine_opt& o, const RefineOut& out, char* wsp, const RefineLayout& l,
+                      hipStream_t st) {
+  const int nb = ctx->nb, n = Fs + V * (F - Fs), W = views_group(F, n);
+  const int64_t U = (int64_t)V * nb;
+  const size_t lds = views_lds_bytes(F, n, W);
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* table = (double*)(wsp + l.table);
+  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
+  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
+  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
+  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
+    const int64_t rows = (int64_t)mc * (F + 1) * V;
+    RefineOut oc = out;
+    oc.x += m0 * n;
+    oc.cost += m0;
+    if (oc.cost0) oc.cost0 += m0;
+    if (oc.sdev) oc.sdev += m0 * n;
+    if (oc.n_accept) oc.n_accept += m0;
+    if (oc.y) oc.y += m0 * U;
+    hipLaunchKernelGGL(k_refine_views_init, dim3((unsigned)(((int64_t)mc * V + 255) / 256)), dim3(256), 0, st, cfg, M, m0, mc, V, F,
+                       Fs, o.lambda0, table, oc.x, t, lam, na, dcfg, dfree);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    for (int it = 0; it <= o.n_iter; ++it) {
+      if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
+                                                    wsp + l.fwd, ws, st, !srf))
+        return rc;
+      ViewsStep a;
+      a.cols = cols[o.column];
+      a.obs = obs + m0 * U;
+      a.wts = weights ? (o.weights_per_obs ? weights + m0 * U : weights) : nullptr;
+      a.cfg = dcfg;
+      a.cfg_free = dfree;
+      a.table = table;
+      a.Mc = mc, a.V = V, a.F = F, a.Fs = Fs, a.nb = nb, a.it = it, a.last = it == o.n_iter ? 1 : 0;
+      a.wper = o.weights_per_obs ? 1 : 0, a.pper = o.prior_per_obs ? 1 : 0;
+      a.st = t, a.sA = A, a.slam = lam, a.sna = na;
+      a.out = oc;
+      a.pmu = o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * n : o.prior_mean) : nullptr;
+      a.ppw = o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * n : o.prior_weight) : nullptr;
+      hipLaunchKernelGGL(W == 8 ? k_refine_views_step<8> : k_refine_views_step<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds,
+                         st, a);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return SPART_OK;
+}
+
+int spart_refine_views(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                       const double* lo, const double* hi, const double* obs, const double* weights,
+                       const spart_refine_views_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
+                       double* y, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_refine_views";
+  // refine_call's list and order, the new sizes after the arguments they are read from
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  const int V = opt->V, Fs = opt->n_shared;
+  if (V < 1 || V > VIEWS_MAXV) return fail(SPART_ERR_INVALID, "%s: V = %d, expected 1 <= V <= %d", who, V, VIEWS_MAXV);
+  if (Fs < 0 || Fs > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, Fs, F);
+  const int n = Fs + V * (F - Fs);
+  if (n < 1 || n > REFINE_MAXF)
+    return fail(SPART_ERR_INVALID, "%s: n_shared + V (F - n_shared) = %d unknowns per pixel, expected 1 ... %d", who, n, REFINE_MAXF);
+  if (opt->band_model != 0 && opt->band_model != 1)
+    return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, opt->band_model);
+  spart_refine_opt o = opt->fit;
+  RefineCfg cfg;
+  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  if (!obs || !x || !cost) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
+  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
+  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
+  const RefineLayout l = views_layout(ctx->nb, M, V, F, n);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
+  const RefineOut out = {x, cost, cost0, sdev, n_accept, y};
+  const bool srf = opt->band_model == 1;
+  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
+    return views_impl(ctx, srf, M, cfg, V, F, Fs, obs, weights, o, out, (char*)workspace, l, st);
+  });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

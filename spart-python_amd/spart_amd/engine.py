@@ -273,6 +273,102 @@ def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, la
     return plan, params, M, kind, prior_mean, prior_weight, per_obs
 
 
+def _views_prior(names, Fs, V, prior):
+    """refine_views' prior: {name: (mean, sigma)} -> (mean, weight) per UNKNOWN, (n,) or -- when any value has a pixel axis --
+    (M, n), with M read from the values.  A shared name takes a scalar or (M,); a local name a scalar, (V,) or (M, V)."""
+    if not isinstance(prior, dict):
+        raise ValueError(f"prior = {prior!r}, expected a dict {{name: (mean, sigma)}}")
+    stray = [k for k in prior if k not in names]
+    if stray:
+        raise ValueError(f"prior: {stray} not free")
+    Fl = len(names) - Fs
+    n, rows = Fs + V * Fl, None
+    parts = {}
+    for name, entry in prior.items():
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"prior[{name!r}]: expected (mean, sigma)")
+        mu, sigma = (np.asarray(v, dtype=np.float64) for v in entry)
+        if not (np.all(sigma > 0) and not np.isnan(sigma).any()):
+            raise ValueError(f"prior[{name!r}]: sigma must be > 0 (finite, or inf for no prior), got {entry[1]!r}")
+        local = names.index(name) >= Fs
+        for what, v in (("mean", mu), ("sigma", sigma)):
+            ok = v.ndim == 0 or (v.ndim == 1 and (not local or v.shape[0] == V)) or (local and v.ndim == 2 and v.shape[1] == V)
+            m = v.shape[0] if (v.ndim == 2 or (v.ndim == 1 and not local)) else None
+            if not ok or (m is not None and rows not in (None, m)):
+                raise ValueError(f"prior[{name!r}]: {what} has shape {v.shape}, expected a scalar, " +
+                                 (f"(V,) = ({V},) or (M, V)" if local else "or (M,)"))
+            rows = m if m is not None else rows
+        with np.errstate(over="ignore"):
+            parts[name] = (mu, 1.0 / (sigma * sigma))
+    R = 1 if rows is None else rows
+    mean, weight = np.zeros((R, n)), np.zeros((R, n))
+    for name, (mu, w) in parts.items():
+        f = names.index(name)
+        for out, v in ((mean, mu), (weight, w)):
+            if f < Fs:
+                out[:, f] = v
+            else:
+                out[:, Fs + (f - Fs):n:Fl] = np.broadcast_to(v, (R, V))
+    return (mean[0], weight[0]) if rows is None else (mean, weight)
+
+
+def refine_views_args(params, obs, shared, local, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean,
+                      prior_weight, band_model, nb=None):
+    """Every argument check of spart_amd.refine_views and Engine.refine_views that needs no device: refine_plan on the names
+    shared + local, then the shapes -- obs (M, V, nb) with 1 <= V <= 64, n = Fs + V Fl in 1 ... 16, params a (27, V, M) block or
+    27 entries each broadcastable to (V, M), weights None / (nb,) / (M, V, nb), the prior per unknown.
+    -> (plan, params, (M, V, Fs, n), weights per observation 0 / 1, prior_mean, prior_weight, prior per observation 0 / 1)"""
+    import torch
+    ready = prior_mean is not None or prior_weight is not None
+    if prior is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    _band_model(band_model)
+    shared, local = [str(s) for s in shared], [str(s) for s in local]
+    plan = refine_plan(shared + local, bounds, n_iter, column, rel_step, lambda0)
+    if lidf not in ("literal", "newton"):
+        raise ValueError("lidf must be 'literal' or 'newton'")
+    oshape = tuple(int(k) for k in np.shape(obs))
+    if len(oshape) != 3 or (nb is not None and oshape[2] != nb):
+        raise ValueError(f"obs has shape {oshape}, expected (M, V, nb)" + ("" if nb is None else f" = (M, V, {nb})"))
+    M, V, Fs = oshape[0], oshape[1], len(shared)
+    if not 1 <= V <= _lib.REFINE_MAXV:
+        raise ValueError(f"obs has V = {V} views, expected 1 ... {_lib.REFINE_MAXV}")
+    n = Fs + V * len(local)
+    if not 1 <= n <= _lib.REFINE_MAXF:
+        raise ValueError(f"{Fs} shared + {V} views x {len(local)} local = {n} unknowns per pixel, expected 1 ... {_lib.REFINE_MAXF}")
+    if not isinstance(params, (list, tuple)):
+        if not torch.is_tensor(params):
+            params = np.asarray(params, dtype=np.float64)
+        if len(params.shape) != 3 or tuple(params.shape) != (_lib.NPARAM, V, M):
+            raise ValueError(f"params must be (27, V, M) = (27, {V}, {M}) or a list of 27 entries, got shape {tuple(params.shape)}")
+    else:
+        if len(params) != _lib.NPARAM:
+            raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+        for i, c in enumerate(fill_nulls(params)):
+            try:
+                np.broadcast_shapes(tuple(np.shape(c)), (V, M))
+            except ValueError:
+                raise ValueError(f"params[{i}] of shape {tuple(np.shape(c))} does not broadcast to (V, M) = ({V}, {M})") from None
+            if len(np.shape(c)) > 2:
+                raise ValueError(f"params[{i}] of shape {tuple(np.shape(c))} does not broadcast to (V, M) = ({V}, {M})")
+        params = fill_nulls(params)
+    wper = 0
+    if weights is not None:
+        ws = tuple(int(k) for k in np.shape(weights))
+        if ws not in ((oshape[2],), oshape):
+            raise ValueError(f"weights has shape {ws}, expected (nb,) = ({oshape[2]},) or (M, V, nb) = {oshape}")
+        wper = int(len(ws) == 3)
+    per_obs = 0
+    if ready:
+        per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, n)
+    elif prior is not None:
+        prior_mean, prior_weight = _views_prior(plan["names"], Fs, V, prior)
+        per_obs = int(prior_mean.ndim == 2)
+        if per_obs and prior_mean.shape[0] != M:
+            raise ValueError(f"prior: arrays of {prior_mean.shape[0]} pixels for the {M} of obs")
+    return plan, params, (M, V, Fs, n), wper, prior_mean, prior_weight, per_obs
+
+
 BAND_MODELS = ("centre", "srf")
 
 
@@ -982,6 +1078,67 @@ class Engine:
                                       ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
                                       ws.data_ptr(), nbytes, self._stream())
         _lib.check(self.lib, self.ctx, rc)
+        res["names"] = list(plan["names"])
+        return res
+
+    def refine_views(self, params, obs, shared, local=(), bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3,
+                     lambda0=1e-2, lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None,
+                     band_model="centre"):
+        """refine() for V observations ("views") of the same pixels at once: per pixel ONE unknown vector -- the ``shared``
+        parameters, one value for all views, and the ``local`` ones, one value per view -- is fitted against all V observations
+        (include/spart_hip.h: spart_refine_views; tools/refine_views_defined.py is the numpy form).  Every view has its own fixed
+        parameters (geometry, atmosphere, DOY ...).
+        params : a (27, V, M) float64 device tensor, or 27 entries each broadcastable to (V, M) (scalar, (M,), (V, 1), (V, M)).
+                 A shared parameter starts from view 0's value
+        obs : (M, V, nb);  weights : None, (nb,) for every view, or (M, V, nb) (exactly 0 skips the band; a view of zeros is masked:
+              its locals stay at their start, and without a prior on them the pixel's ``std`` is NaN)
+        shared, local : names from workloads.PARAM_NAMES; n = len(shared) + V len(local) unknowns per pixel, 1 ... 16
+        bounds : {name: (lo, hi)}, one pair per name; the default is workloads.RANGES[name]
+        prior : {name: (mean, sigma)}: a shared name takes scalars or (M,) arrays, a local name scalars, (V,) or (M, V)
+        prior_mean, prior_weight : the same ready-made per unknown, (n,) or (M, n); not together with ``prior``
+        column, n_iter, rel_step, lambda0, lidf, nlayers, band_model : as for refine()
+        -> dict of device tensors x, std (M, n) -- unknown a < Fs is shared[a], unknown Fs + v Fl + l is local[l] in view v --
+        cost, cost0 (M,), n_accept (M,) int32 (-1: a dead pixel), y (M, V, nb); the slices shared / shared_std (M, Fs) and
+        local / local_std (M, V, Fl) of x / std; and ``names`` = shared + local.
+        A LUT search across views is another feature: retrieve / retrieve_stream do not call this."""
+        plan, params, (M, V, Fs, n), wper, prior_mean, prior_weight, per_obs = refine_views_args(
+            params, obs, shared, local, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean, prior_weight,
+            band_model, nb=self.nb)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        nb, F = self.nb, len(plan["names"])
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if torch.is_tensor(params):
+            cols = list(params.to(**f64).contiguous())
+        else:
+            host = np.stack([np.broadcast_to(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float64), (V, M)) for c in params])
+            cols = list(torch.as_tensor(host).to(self.device))
+        o = torch.as_tensor(obs).to(**f64).contiguous()
+        w = None if weights is None else torch.as_tensor(weights).to(**f64).contiguous()
+        res = {"x": torch.empty((M, n), **f64), "cost": torch.empty((M,), **f64), "cost0": torch.empty((M,), **f64),
+               "std": torch.empty((M, n), **f64), "n_accept": torch.empty((M,), dtype=torch.int32, device=self.device),
+               "y": torch.empty((M, V, nb), **f64)}
+        opt = _lib.SpartRefineViewsOpt(V=V, n_shared=Fs, band_model=int(srf))
+        opt.fit = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=wper,
+                                      fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
+                                      lambda0=plan["lambda0"])
+        if prior_mean is not None:
+            pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in (prior_mean, prior_weight))
+            opt.fit.prior_per_obs, opt.fit.prior_mean, opt.fit.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
+        nbytes = max(int(self.lib.spart_views_workspace_bytes(self.ctx, M, V, F, Fs)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_refine_views"] += 1
+        rc = self.lib.spart_refine_views(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                         _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
+                                         ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
+                                         ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        for k, src in (("shared", "x"), ("shared_std", "std")):
+            res[k] = res[src][:, :Fs]
+        for k, src in (("local", "x"), ("local_std", "std")):
+            res[k] = res[src][:, Fs:].reshape(M, V, F - Fs)
         res["names"] = list(plan["names"])
         return res
 

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, prior_arrays,
-                     refine_args, refine_plan)
+                     refine_args, refine_plan, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -478,6 +478,24 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
     eng = get_engine(sensor, device, sensor_info=sensor_info)
     res = eng.refine(params, np.asarray(obs, dtype=np.float64), free, weights=weights, lidf=lidf, nlayers=nlayers,
                      prior_mean=prior_mean, prior_weight=prior_weight, band_model=band_model, _plan=plan)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3,
+                 lambda0=1e-2, lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None,
+                 prior_weight=None, band_model="centre"):
+    """The host form of Engine.refine_views: numpy in and out.  ``params`` (27, V, M) or 27 entries each broadcastable to (V, M),
+    ``obs`` (M, V, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``); everything else as for
+    Engine.refine_views.  -> dict of numpy arrays x, std, cost, cost0, n_accept, y, shared, shared_std, local, local_std and the
+    list ``names``.  Every argument check that needs no device runs before one is asked for.  A LUT search across views is
+    another feature: retrieve / retrieve_stream do not call this."""
+    params = refine_views_args(params, obs, shared, local, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior,
+                               prior_mean, prior_weight, band_model)[1]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.refine_views(params if isinstance(params, list) else eng.torch.as_tensor(params), np.asarray(obs, dtype=np.float64),
+                           shared, local, bounds=bounds, weights=weights, column=column, n_iter=n_iter, rel_step=rel_step,
+                           lambda0=lambda0, lidf=lidf, nlayers=nlayers, prior=prior, prior_mean=prior_mean,
+                           prior_weight=prior_weight, band_model=band_model)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
