@@ -10,7 +10,7 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "spart-python_amd"))
-from spart_amd import generate_lut, refine, retrieve, workloads  # noqa: E402
+from spart_amd import generate_lut, noise_weights, refine, retrieve, workloads  # noqa: E402
 
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 200_000
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(tempfile.gettempdir(), "spart_lut_f64")
@@ -47,4 +47,17 @@ oe = retrieve(out, obs, 10, refine=names, refine_opts={"n_iter": 8, "prior": "kn
 err_oe = np.median(np.abs(oe["refined"] - truth[:, cols]) / span, axis=0)
 print("  with knn prior :", np.round(err_oe, 4), " median 1-sigma / range:", np.round(np.nanmedian(oe["refined_std"], axis=0) / span, 4))
 assert (oe["refined_cost"] <= oe["refined_cost0"]).all()
+
+# what the fit knows beyond one sigma per parameter: with the noise model as weights (1 / sigma^2 of the 0.5 % noise),
+# "posterior": True adds the full posterior covariance, the averaging kernel and its trace, the degrees of freedom for signal
+w = noise_weights(obs, 1e-4, 0.005)
+a, b = names.index("LAI"), names.index("Cdm")
+for label, prior in (("no prior ", None), ("knn prior", "knn")):
+    opts = {"n_iter": 8, "posterior": True, **({"prior": prior} if prior else {})}
+    r = retrieve(out, obs, 10, weights=w, refine=names, refine_opts=opts)
+    cov, ok = r["refined_cov"], np.isfinite(r["refined_dfs"])
+    corr = cov[ok, a, b] / np.sqrt(cov[ok, a, a] * cov[ok, b, b])
+    print(f"  {label}: median LAI / Cdm correlation {np.median(corr):+.3f}, degrees of freedom for signal: median "
+          f"{np.median(r['refined_dfs'][ok]):.3f} of {len(names)} (min {r['refined_dfs'][ok].min():.3f})")
+    assert ok.mean() > 0.9 and (np.abs(corr) <= 1 + 1e-9).all() and (r["refined_dfs"][ok] <= len(names) + 1e-6).all()
 print("refined", len(names), "parameters of", obs.shape[0], "spectra")

@@ -67,7 +67,7 @@ extern "C" {
  * spart_refine_srf was added WITHOUT a new number: it is one more symbol, no struct layout or argument list changed, so every
  * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library.
  * spart_refine_views, spart_views_workspace_bytes and spart_refine_views_opt were added by the same rule: new symbols
- * and a new struct that embeds spart_refine_opt unchanged. */
+ * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -515,6 +515,56 @@ int spart_refine_views(spart_ctx *ctx, int64_t M, const double *const base[SPART
                        const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
                        const spart_refine_views_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
                        double *y, void *workspace, size_t workspace_bytes, void *stream);
+
+/* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
+ * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging
+ * kernel A^-1 J^T W J and its trace, the degrees of freedom for signal.  ONE evaluation of the point: k_refine_init's table,
+ * one forward call of (F + 1) rows per observation, one kernel.  base, free_cols, lo, hi, weights and opt are spart_refine's;
+ * obs may be NULL (no measurement: sensitivities and the covariance a measurement WOULD give).  opt->n_iter and opt->lambda0
+ * are checked but not used.  band_model 0 evaluates spart_refine's centre columns, 1 spart_refine_srf's SRF columns.
+ * Definition per observation (tools/refine_posterior_defined.py is the same text in numpy; float64, no FMA contraction, IEEE
+ * division and sqrt):
+ *   point   x = clip(base[free]); h_f, s_f (by spart_refine's rule on x_f) and the rows p_0 ... p_F as in spart_refine;
+ *           Y_0 ... Y_F = the chosen column of the rows
+ *   cost    spart_refine's band loop and prior loop at t = x, same order, same skip rules; with obs == NULL the band loop adds
+ *           nothing (c = 0 before the prior's terms).  nband counts w_j != 0
+ *   dead    status = -1: a band or prior weight negative, NaN or infinite, or a cost that is not < +inf.  x, y = Y_0, cost and
+ *           nband are written; jac, cov, ak, std and dfs are NaN
+ *   J       J_jf = (Y_fj - Y_0j) / (s_f h_f) for EVERY band j, bands of weight 0 included
+ *   K       the data part alone: K_ab = sum_j (w_j J_ja) J_jb for a >= b, j ascending, w_j == 0 skipped.  A = K; then for a
+ *           ascending with p_a != 0: A_aa = A_aa + p_a
+ *   factor  A = L L^T by spart_refine's Cholesky; a pivot !(s > 0) gives status = 1: cov, ak, std and dfs are NaN while x, y,
+ *           jac, cost and nband stay valid
+ *   cov     Z = L^-1, column f by std's recurrence z_k = ((k == f) - sum_{f <= i < k} L_ki z_i) / L_kk (i ascending);
+ *           cov_ab for a >= b is v = 0; for k = a ... F-1: v = v + Z_ka Z_kb, copied to (b, a); std_f = sqrt(cov_ff)
+ *   ak, dfs K mirrored to full; ak_ab = 0; for c = 0 ... F-1: ak_ab = ak_ab + cov_ac K_cb;  dfs = 0; for a ascending:
+ *           dfs = dfs + ak_aa
+ * Consequences.  Called on the rows a fit returned -- base with the free columns set to spart_refine's x, the same bounds,
+ * weights, prior and options -- std, y and cost equal the fit's bit for bit: the columns are a pure function of a row's own 27
+ * parameters, clip(x) = x, and the step signs are those of the accepted trial.  Without a prior ak is the identity up to
+ * rounding and dfs = F.  With all band weights zero and a prior, K = 0: ak and dfs are exactly 0 and cov = diag(1 / p) up to
+ * rounding.
+ * The workspace is spart_refine_workspace_bytes(ctx, M, F); observations go in spart_refine's chunks; jac's offsets are 64-bit.
+ * Refused before anything is launched or written: spart_refine's list in its order (obs is not required), out NULL with the
+ * other NULL arguments, then band_model outside 0 / 1, then all ten output pointers NULL; SPART_ERR_NOSENSOR and
+ * SPART_ERR_WORKSPACE as for spart_refine.  M = 0 launches nothing.  Everything is queued on `stream`; nothing synchronises.
+ * Added WITHOUT a new interface number, by spart_refine_srf's rule: one more symbol and one new struct. */
+typedef struct spart_posterior_out {   /* device memory; each may be NULL, not all of them */
+  double *x;      /* (M, F)      the point: base[free] clipped */
+  double *y;      /* (M, nb)     the chosen column at x */
+  double *jac;    /* (M, nb, F)  J_jf, row-major, EVERY band (weight-0 bands included) */
+  double *cov;    /* (M, F, F)   A^-1, full and exactly symmetric */
+  double *ak;     /* (M, F, F)   averaging kernel A^-1 K (not symmetric) */
+  double *std;    /* (M, F)      sqrt(cov_ff) */
+  double *dfs;    /* (M,)        trace of ak */
+  double *cost;   /* (M,)        spart_refine's cost at x, prior term included */
+  int32_t *nband; /* (M,)        bands with weight != 0 */
+  int32_t *status;/* (M,)        0 ok, 1 A not positive definite, -1 dead */
+} spart_posterior_out;
+int spart_refine_posterior(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                           const double *lo, const double *hi /* HOST, (F,) */, const double *obs /* may be NULL */,
+                           const double *weights, const spart_refine_opt *opt, int band_model /* 0 centre, 1 srf */,
+                           const spart_posterior_out *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -20,6 +20,7 @@
 #include "spart_kernels.h"
 #include "spart_lut.h"
 #include "spart_refine.h"
+#include "spart_refine_posterior.h"
 #include "spart_refine_views.h"
 
 using namespace spart;
@@ -1351,6 +1352,89 @@ int spart_refine_srf(spart_ctx* ctx, int64_t M, const double* const base[SPART_N
                      size_t workspace_bytes, void* stream) {
   return refine_call("spart_refine_srf", true, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept,
                      y, workspace, workspace_bytes, stream);
+}
+
+// ---- spart_refine_posterior (csrc/spart_refine_posterior.h): refine_impl's chunk loop with ONE forward call per chunk and
+// k_refine_posterior in place of k_refine_step.  The optimiser's state of the layout is not used, so its A block takes
+// k_refine_init's x when the caller does not ask for it.
+static int posterior_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
+                          const spart_refine_opt& o, const spart_posterior_out& out, char* wsp, const RefineLayout& l,
+                          hipStream_t st) {
+  const int nb = ctx->nb, W = refine_posterior_group(F);
+  const size_t lds = refine_posterior_lds_bytes(F, W);
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* table = (double*)(wsp + l.table);
+  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
+  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
+  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
+  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
+    const int64_t rows = (int64_t)mc * (F + 1);
+    PosteriorOut oc;
+    oc.y = out.y ? out.y + m0 * nb : nullptr;
+    oc.jac = out.jac ? out.jac + m0 * nb * F : nullptr;
+    oc.cov = out.cov ? out.cov + m0 * F * F : nullptr;
+    oc.ak = out.ak ? out.ak + m0 * F * F : nullptr;
+    oc.sdev = out.std ? out.std + m0 * F : nullptr;
+    oc.dfs = out.dfs ? out.dfs + m0 : nullptr;
+    oc.cost = out.cost ? out.cost + m0 : nullptr;
+    oc.nband = out.nband ? out.nband + m0 : nullptr;
+    oc.status = out.status ? out.status + m0 : nullptr;
+    hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, o.lambda0, table,
+                       out.x ? out.x + m0 * F : A, t, lam, na, dcfg, dfree);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, wsp + l.fwd,
+                                                  ws, st, !srf))
+      return rc;
+    hipLaunchKernelGGL(W == 8 ? k_refine_posterior<8> : k_refine_posterior<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
+                       obs ? obs + m0 * nb : nullptr, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
+                       o.weights_per_obs ? 1 : 0, (const double*)dcfg, mc, F, nb, (const double*)t, oc,
+                       o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * F : o.prior_mean) : nullptr,
+                       o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * F : o.prior_weight) : nullptr,
+                       o.prior_per_obs ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+  }
+  return SPART_OK;
+}
+
+int spart_refine_posterior(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                           const double* lo, const double* hi, const double* obs, const double* weights,
+                           const spart_refine_opt* opt, int band_model, const spart_posterior_out* out, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const char* who = "spart_refine_posterior";
+  // refine_call's list and order; obs may be NULL here, and the outputs come in one struct
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!base || !free_cols || !lo || !hi || !opt || !out) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  spart_refine_opt o = *opt;
+  RefineCfg cfg;
+  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
+  if (band_model != 0 && band_model != 1)
+    return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, band_model);
+  if (!out->x && !out->y && !out->jac && !out->cov && !out->ak && !out->std && !out->dfs && !out->cost && !out->nband && !out->status)
+    return fail(SPART_ERR_INVALID, "%s: every output is null", who);
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
+  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
+  const RefineLayout l = refine_layout(ctx->nb, M, F);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
+  const spart_posterior_out oo = *out;
+  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
+    return posterior_impl(ctx, band_model == 1, M, cfg, F, obs, weights, o, oo, (char*)workspace, l, st);
+  });
 }
 
 // ---- spart_refine_views (csrc/spart_refine_views.h).  The workspace is spart_refine's, sized by ONE chunk of

@@ -12,6 +12,7 @@ from .engine import Engine, get_engine, knn_prior  # noqa: F401
 from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401
-from .lut import generate_lut, invert_lut, load_lut, lut_to_parquet, noise_weights, refine, refine_views, retrieve, retrieve_stream  # noqa: F401
+from .lut import (generate_lut, invert_lut, jacobian, load_lut, lut_to_parquet, noise_weights, posterior, refine, refine_views,  # noqa: F401
+                  retrieve, retrieve_stream)
 
 __version__ = "0.1.0"

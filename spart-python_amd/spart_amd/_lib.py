@@ -42,6 +42,11 @@ class SpartRefineViewsOpt(ctypes.Structure):
     _fields_ = [("fit", SpartRefineOpt), ("V", ctypes.c_int32), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32)]
 
 
+class SpartPosteriorOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("x", "y", "jac", "cov", "ak", "std", "dfs", "cost", "nband", "status")]
+
+
+POSTERIOR_OUTS = tuple(n for n, _ in SpartPosteriorOut._fields_)     # spart_posterior_out, in its order
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
 REFINE_MAXF, REFINE_MAX_ITER = 16, 100
 REFINE_MAXV = 64                                    # spart_refine_views_opt.V
@@ -96,6 +101,7 @@ SIGNATURES = {
     "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),
     "spart_views_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spart_refine_views": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartRefineViewsOpt)] + _REFINE_CALL[10:]),
+    "spart_refine_posterior": (ctypes.c_int, _REFINE_CALL[:10] + [ctypes.c_int, ctypes.POINTER(SpartPosteriorOut)] + _REFINE_CALL[16:]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

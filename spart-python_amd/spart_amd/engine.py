@@ -372,6 +372,17 @@ def refine_views_args(params, obs, shared, local, bounds, weights, column, n_ite
 BAND_MODELS = ("centre", "srf")
 
 
+def params_rows(params):
+    """the number of rows a params argument of refine() / posterior() stands for when no obs says it: the second axis of a
+    (27, M) block, else the largest entry of the list"""
+    if isinstance(params, (list, tuple)):
+        return max([1] + [math.prod(np.shape(c)) for c in params if c is not None])
+    shape = tuple(np.shape(params))
+    if len(shape) != 2:
+        raise ValueError(f"params must be (27, M) or a list of 27 columns, got shape {shape}")
+    return int(shape[1])
+
+
 def _band_model(band_model, eng=None):
     """band_model= of SPART.run / generate_lut / refine -> True for "srf"; ValueError for anything but "centre" / "srf", and,
     given the engine, for "srf" on one whose SRF columns do not belong to its band centres"""
@@ -1021,7 +1032,8 @@ class Engine:
         return res
 
     def refine(self, params, obs, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
-               lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, band_model="centre", _plan=None):
+               lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, band_model="centre", _plan=None,
+               posterior=False):
         """Bounded Levenberg-Marquardt refinement of the ``free`` parameters of every start row against its observation, on the
         device (include/spart_hip.h: spart_refine, which defines every sum and solve; tools/refine_defined.py is the numpy form).
         params : the start rows, as for run(): a (27, M) float64 device tensor or a list of 27 scalars / arrays (each 1 or M values)
@@ -1042,7 +1054,9 @@ class Engine:
                 (968 model bands per row for Sentinel-2A against 13).  ValueError for a sensor whose SRF columns are not in
                 the order of its band centres (align_srf mends it)
         -> dict of device tensors x (M, F), cost, cost0 (M,), std (M, F), n_accept (M,) int32 (-1: the start could not be
-        evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names."""
+        evaluated, x is then the clipped start) and y (M, nb), the model at x; and ``names``, the F names.
+        posterior=True adds cov, corr, ak (M, F, F) and dfs (M,) of posterior() at the fitted rows (one more forward call); every
+        other entry keeps its bits."""
         plan, params, M, kind, prior_mean, prior_weight, per_obs = refine_args(
             params, obs, free, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean, prior_weight, band_model,
             nb=self.nb, _plan=_plan)
@@ -1079,7 +1093,80 @@ class Engine:
                                       ws.data_ptr(), nbytes, self._stream())
         _lib.check(self.lib, self.ctx, rc)
         res["names"] = list(plan["names"])
+        if posterior:
+            # the fitted rows: the start rows with the free columns at x; std, y and cost of that call are the fit's bit for bit
+            fitted = list(cols)
+            for f, c in enumerate(plan["cols"]):
+                fitted[int(c)] = res["x"][:, f].contiguous()
+            post = self.posterior(fitted, o, free, weights=w, lidf=lidf, nlayers=nlayers, prior_mean=prior_mean,
+                                  prior_weight=prior_weight, band_model=band_model, _plan=dict(plan, prior=None))
+            res.update({k: post[k] for k in ("cov", "corr", "ak", "dfs")})
         return res
+
+    def posterior(self, params, obs, free, bounds=None, weights=None, column="R_TOC", rel_step=1e-3, lidf="literal", nlayers=None,
+                  prior=None, prior_mean=None, prior_weight=None, band_model="centre", _plan=None, _outputs=None):
+        """What refine()'s optimal-estimation fit knows about a point, on the device in one call (include/spart_hip.h:
+        spart_refine_posterior, which defines every sum; tools/refine_posterior_defined.py is the numpy form): the Jacobian of the
+        sensor column, the posterior covariance (J^T W J + S_a^-1)^-1, the averaging kernel and the degrees of freedom for signal.
+        params, free, bounds, weights, column, rel_step, lidf, nlayers, prior / prior_mean / prior_weight, band_model : as for
+        refine(); the point is ``params`` with its free columns clipped to the bounds.  With weights = 1 / sigma^2 of the
+        measurement ``cov`` is the linearised posterior covariance
+        obs : (M, nb), or None: no measurement -- ``cost`` is then the prior's term alone, everything else is unchanged
+        -> dict of device tensors x (M, F), y (M, nb), jac (M, nb, F) (every band, weight-0 bands included), cov, ak (M, F, F),
+        std (M, F), dfs, cost (M,), nband (M,) int32 (bands with a weight != 0), status (M,) int32 (0 ok; 1: A is not positive
+        definite, cov / ak / std / dfs are NaN; -1: the point could not be evaluated or a weight is negative or not finite, jac
+        is NaN too), corr (M, F, F) = cov_ab / (std_a std_b); and ``names``.  On the rows a fit returned, with the fit's
+        arguments, std, y and cost are the fit's bit for bit (refine(posterior=True) does that)."""
+        shape_of = obs if obs is not None else np.broadcast_to(np.float64(0.0), (params_rows(params), self.nb))
+        plan, params, M, kind, prior_mean, prior_weight, per_obs = refine_args(
+            params, shape_of, free, bounds, weights, column, 0, rel_step, 1e-2, lidf, prior, prior_mean, prior_weight, band_model,
+            nb=self.nb, _plan=_plan)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        nb, F = self.nb, len(plan["names"])
+        # ---- the device from here on
+        torch = self.torch
+        if torch.is_tensor(params):
+            P = params.to(device=self.device, dtype=torch.float64)
+            cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
+        else:
+            cols, _ = self.columns(params, M)
+        o = None if obs is None else torch.as_tensor(obs).to(device=self.device, dtype=torch.float64).contiguous()
+        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
+        shapes = {"x": (M, F), "y": (M, nb), "jac": (M, nb, F), "cov": (M, F, F), "ak": (M, F, F), "std": (M, F), "dfs": (M,),
+                  "cost": (M,), "nband": (M,), "status": (M,)}
+        want = _lib.POSTERIOR_OUTS if _outputs is None else tuple(_outputs)
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("nband", "status") else torch.float64, device=self.device)
+               for k in _lib.POSTERIOR_OUTS if k in want}
+        out = _lib.SpartPosteriorOut(**{k: v.data_ptr() for k, v in res.items()})
+        opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=0, weights_per_obs=1 if kind == "per_observation" else 0,
+                                  fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"], lambda0=0.0)
+        if prior_mean is not None:
+            pm, pw = (torch.as_tensor(v).to(device=self.device, dtype=torch.float64).contiguous() for v in (prior_mean, prior_weight))
+            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
+        nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_refine_posterior"] += 1
+        rc = self.lib.spart_refine_posterior(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                             _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr() if o is not None else None,
+                                             w.data_ptr() if w is not None else None, ctypes.byref(opt), 1 if srf else 0,
+                                             ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        if "cov" in res and "std" in res:
+            res["corr"] = res["cov"] / (res["std"][:, :, None] * res["std"][:, None, :])
+            d = res["corr"].diagonal(dim1=1, dim2=2)      # sqrt(v) * sqrt(v) need not be v: the diagonal is 1 by definition
+            d.copy_(torch.where(torch.isnan(d), d, torch.ones_like(d)))
+        res["names"] = list(plan["names"])
+        return res
+
+    def jacobian(self, params, free, bounds=None, column="R_TOC", rel_step=1e-3, lidf="literal", nlayers=None, band_model="centre"):
+        """The thin form of posterior(): no observation, no weights, no prior.  -> dict of device tensors y (M, nb), the sensor
+        column at ``params`` (free columns clipped to the bounds), and jac (M, nb, F), its one-sided finite-difference Jacobian
+        with respect to the ``free`` parameters (step rel_step (hi - lo), forward unless that leaves the bounds); and ``names``.
+        A row that cannot be evaluated has a NaN jac."""
+        res = self.posterior(params, None, free, bounds=bounds, column=column, rel_step=rel_step, lidf=lidf, nlayers=nlayers,
+                             band_model=band_model, _outputs=("y", "jac"))
+        return {k: res[k] for k in ("y", "jac", "names")}
 
     def refine_views(self, params, obs, shared, local=(), bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3,
                      lambda0=1e-2, lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None,

@@ -17,8 +17,8 @@ import warnings
 import numpy as np
 
 from . import _lib, workloads
-from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, prior_arrays,
-                     refine_args, refine_plan, refine_views_args)
+from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, params_rows,
+                     prior_arrays, refine_args, refine_plan, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -481,6 +481,33 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
+def posterior(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", rel_step=1e-3, lidf="literal", nlayers=None,
+              sensor_info=None, device=None, prior=None, prior_mean=None, prior_weight=None, band_model="centre"):
+    """The host form of Engine.posterior: numpy in and out.  ``params``, ``sensor`` / ``sensor_info`` as for refine(); ``obs``
+    (M, nb) or None.  -> dict of numpy arrays x, y, jac, cov, ak, std, dfs, cost, nband, status, corr and the list ``names``.
+    Every argument check that needs no device runs before one is asked for."""
+    shape_of = obs
+    if obs is None:
+        nb = 1 if weights is None else int(np.shape(weights)[-1]) if np.ndim(weights) else 1
+        shape_of = np.broadcast_to(np.float64(0.0), (params_rows(params), nb))
+    plan, params = refine_args(params, shape_of, free, bounds, weights, column, 0, rel_step, 1e-2, lidf, prior, prior_mean,
+                               prior_weight, band_model)[:2]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.posterior(params, None if obs is None else np.asarray(obs, dtype=np.float64), free, weights=weights, lidf=lidf,
+                        nlayers=nlayers, prior_mean=prior_mean, prior_weight=prior_weight, band_model=band_model, _plan=plan)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def jacobian(params, sensor, free, bounds=None, column="R_TOC", rel_step=1e-3, lidf="literal", nlayers=None, sensor_info=None,
+             device=None, band_model="centre"):
+    """The host form of Engine.jacobian: -> dict of numpy arrays y (M, nb), jac (M, nb, F) and the list ``names``"""
+    plan, params = refine_args(params, np.broadcast_to(np.float64(0.0), (params_rows(params), 1)), free, bounds, None, column, 0,
+                               rel_step, 1e-2, lidf, None, None, None, band_model)[:2]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.posterior(params, None, free, lidf=lidf, nlayers=nlayers, band_model=band_model, _plan=plan, _outputs=("y", "jac"))
+    return {"y": res["y"].cpu().numpy(), "jac": res["jac"].cpu().numpy(), "names": res["names"]}
+
+
 def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3,
                  lambda0=1e-2, lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None, prior_mean=None,
                  prior_weight=None, band_model="centre"):
@@ -499,8 +526,10 @@ def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=Non
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
-REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor", "band_model")
+REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor", "band_model",
+               "posterior")
 REFINE_KEYS = {"refined": "x", "refined_std": "std", "refined_cost": "cost", "refined_cost0": "cost0", "refined_accepts": "n_accept"}
+POSTERIOR_KEYS = {"refined_cov": "cov", "refined_ak": "ak", "refined_dfs": "dfs"}      # refine_opts={"posterior": True}
 
 
 def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
@@ -530,6 +559,8 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     if sensor_info is None and not isinstance(meta.get("sensor"), str):
         raise ValueError("retrieve(refine=...): meta.json names no packaged sensor; pass the LUT's sensor_info=")
     names, cols = _param_columns(list(refine))
+    if not isinstance(opts.get("posterior", False), (bool, np.bool_)):
+        raise ValueError(f'refine_opts["posterior"] = {opts["posterior"]!r}, expected True or False')
     prior = opts.get("prior")
     if not (prior is None or isinstance(prior, dict) or (isinstance(prior, str) and prior == "knn")):
         raise ValueError(f'refine_opts["prior"] = {prior!r}, expected a dict {{name: (mean, sigma)}} or "knn"')
@@ -553,16 +584,18 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
 
 # what an observation that matches nothing gets, by output name (retrieve, retrieve_stream and the fit)
 _EMPTY = {"idx": -1, "cost": np.inf, "best_cost": np.inf, "mean": np.nan, "median": np.nan, "std": np.nan, "count": 0,
-          "refined": np.nan, "refined_std": np.nan, "refined_cost": np.nan, "refined_cost0": np.nan, "refined_accepts": -1}
+          "refined": np.nan, "refined_std": np.nan, "refined_cost": np.nan, "refined_cost0": np.nan, "refined_accepts": -1,
+          "refined_cov": np.nan, "refined_ak": np.nan, "refined_dfs": np.nan}
 
 
 def _summary_shapes(M, P):
     return {**{n: ((M, P), np.float64) for n in STREAM_MAPS}, "count": ((M,), np.int32)}
 
 
-def _refined_shapes(M, F):
+def _refined_shapes(M, F, posterior=False):
+    more = {"refined_cov": ((M, F, F), np.float64), "refined_ak": ((M, F, F), np.float64), "refined_dfs": ((M,), np.float64)}
     return {"refined": ((M, F), np.float64), "refined_std": ((M, F), np.float64), "refined_cost": ((M,), np.float64),
-            "refined_cost0": ((M,), np.float64), "refined_accepts": ((M,), np.int32)}
+            "refined_cost0": ((M,), np.float64), "refined_accepts": ((M,), np.int32), **(more if posterior else {})}
 
 
 def _unmatched(shapes):
@@ -599,7 +632,8 @@ class _Fit:
         """Engine.refine of the next n observations, all on the engine's device and its current stream: ``start`` (27, n) the
         rows the fit starts from, ``idx`` (n, k) lut_topk's (the "knn" prior is knn_prior of Engine.lut_summarise of the free
         columns of those rows), ``obs64`` (n, nb) float64, ``w64`` (n, nb) float64 or None (then the shared weights, if any).
-        -> the REFINE_KEYS tensors; an observation without a row (idx[:, 0] < 0) is fitted like the others and overwritten."""
+        -> the REFINE_KEYS tensors (with refine_opts["posterior"] the POSTERIOR_KEYS too: Engine.refine(posterior=True), one more
+        forward call at the fitted rows); an observation without a row (idx[:, 0] < 0) is fitted like the others and overwritten."""
         import torch
         n, plan, opts = idx.shape[0], self.plan, self.opts
         pm = pw = None
@@ -610,12 +644,13 @@ class _Fit:
             pm, pw = knn_prior(near["mean"], near["std"], plan["lo"], plan["hi"], floor=opts.get("prior_floor", 0.05))
         self.lo += n
         r = self.eng.refine(start, obs64, plan["names"], weights=self.shared if w64 is None else w64, lidf=opts.get("lidf", "literal"),
-                            nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw, band_model=opts["band_model"], _plan=plan)
+                            nlayers=opts.get("nlayers"), prior_mean=pm, prior_weight=pw, band_model=opts["band_model"], _plan=plan,
+                            posterior=bool(opts.get("posterior", False)))
         none = idx[:, 0] < 0
         out = {}
-        for key, name in REFINE_KEYS.items():
+        for key, name in {**REFINE_KEYS, **(POSTERIOR_KEYS if opts.get("posterior", False) else {})}.items():
             v = r[name]
-            out[key] = torch.where(none[:, None] if v.dim() == 2 else none, torch.full((), _EMPTY[key], dtype=v.dtype, device=v.device), v)
+            out[key] = torch.where(none.reshape((-1,) + (1,) * (v.dim() - 1)), torch.full((), _EMPTY[key], dtype=v.dtype, device=v.device), v)
         return out
 
 
@@ -623,7 +658,7 @@ def _refine_best(setup, dict_prior, lut_dir, obs, idx, column, weights, device):
     """the refinement of retrieve(): start = params.npy[idx[:, 0]], gathered on the host (a memmap reads only the rows it needs),
     one _Fit.run for all M observations; no engine is asked for when no observation has a row"""
     plan = setup[0]
-    out = _unmatched(_refined_shapes(idx.shape[0], len(plan["names"])))
+    out = _unmatched(_refined_shapes(idx.shape[0], len(plan["names"]), bool(setup[1].get("posterior", False))))
     if (idx[:, :1] >= 0).any():
         _, params, _ = load_lut(lut_dir)
         shared = weights if weights is not None and np.ndim(weights) == 1 else None
@@ -666,7 +701,9 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     ``"prior"``: a dict
     {name: (mean, sigma)} as for Engine.refine, or ``"knn"``: knn_prior of the mean and std of the free columns of the k rows
     found (Engine.lut_summarise, whatever ``summary`` says: that summary is one defined number), with the plan's bounds and
-    ``"prior_floor"`` (default 0.05); ``refined_std`` is then the linearised posterior 1-sigma.  The sensor is
+    ``"prior_floor"`` (default 0.05); ``refined_std`` is then the linearised posterior 1-sigma.  ``"posterior": True`` adds
+    ``refined_cov`` (M, F, F), the full posterior covariance, ``refined_ak`` (M, F, F), the averaging kernel, and ``refined_dfs``
+    (M,), its trace, the degrees of freedom for signal (Engine.posterior at the fitted rows; NaN without a row).  The sensor is
     meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band model other than the
     LUT's and for ``shard=True`` under a process group of more than one rank (sharded refinement is not built yet)."""
     if summary not in SUMMARIES:
@@ -836,7 +873,8 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     own summary of the free columns, Engine.refine takes both as device tensors.  The result (and ``out``) gains ``refined``,
     ``refined_std`` (M, F), ``refined_cost``, ``refined_cost0`` (M,), ``refined_accepts`` (M,) int32 and ``refined_names``, each
     equal to retrieve(summary="device", refine=...)'s bit for bit whatever the chunk size; a pixel without a row gets NaN
-    and -1.  A per-observation prior dict goes up once too, as its (M, F) float64 mean and weight."""
+    and -1; with refine_opts={"posterior": True} ``refined_cov``, ``refined_ak`` and ``refined_dfs`` as maps too.  A
+    per-observation prior dict goes up once too, as its (M, F) float64 mean and weight."""
     setup = _refine_setup(lut_dir, refine, refine_opts, False, None, sensor_info)
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
@@ -853,7 +891,7 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
     shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt)}
     if setup is not None:
-        shapes.update(_refined_shapes(M, len(setup[0]["names"])))
+        shapes.update(_refined_shapes(M, len(setup[0]["names"]), bool(setup[1].get("posterior", False))))
     dict_prior = _dict_prior(setup, M)
     res = {n: np.empty(s, dtype=d) for n, (s, d) in shapes.items()} if out is None else _check_out(out, shapes)
     if B == 0:                                                     # an empty table matches nothing
