@@ -1013,22 +1013,30 @@ static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t 
   return SPART_OK;
 }
 
-// ---- spart_refine (csrc/spart_refine.h): the workspace of a call and the chunk loop.  The workspace is sized by ONE chunk
-// -- min(M, REFINE_ROWS / (F + 1)) observations -- whatever M is: the parameter table, the three column blocks of the forward
-// call, the optimiser's state and the forward call's own workspace.
+// ---- The refinement family (csrc/spart_refine.h, spart_refine_views.h, spart_refine_posterior.h): spart_refine,
+// spart_refine_srf, spart_refine_posterior and spart_refine_views share one workspace layout, one chunk loop and one entry
+// check.  A call fits n unknowns per observation from V views of it, F free columns each, the first Fs of them shared by the
+// views; the single-view entries are {1, F, F, F}.
+struct RefineShape {
+  int V, F, Fs, n;
+};
+
+// The workspace is sized by ONE chunk -- min(M, views_chunk(V, F)) observations of V (F + 1) table rows each -- whatever M
+// is: the parameter table, the three column blocks of the forward call, the optimiser's state per unknown and the forward
+// call's own workspace.
 struct RefineLayout {
   int64_t mcap;                 // observations per chunk
   size_t table, cols[3], t, A, lam, na, cfg, cfg_free, fwd, total;
 };
-static RefineLayout refine_layout(int nb, int64_t M, int F) {
+static RefineLayout refine_layout(int nb, int64_t M, int V, int F, int n) {
   RefineLayout l;
-  l.mcap = std::min<int64_t>(M, REFINE_ROWS / (F + 1));
-  const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(F + 1);
+  l.mcap = std::min<int64_t>(M, views_chunk(V, F));
+  const size_t mc = (size_t)l.mcap, per = (size_t)(F + 1) * V, rows = mc * per;
   Carver c;
   l.table = c.take((size_t)NPARAM * rows * 8);
   for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
-  l.t = c.take(mc * F * 8);
-  l.A = c.take(mc * (size_t)(refine_ntri(F) + F) * 8);
+  l.t = c.take(mc * n * 8);
+  l.A = c.take(mc * (size_t)(refine_ntri(n) + n) * 8);
   l.lam = c.take(mc * 8);
   l.na = c.take(mc * 4);
   l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
@@ -1036,65 +1044,251 @@ static RefineLayout refine_layout(int nb, int64_t M, int F) {
   // the forward call of a full chunk and of the last, shorter one (the band-sum rows of carve() follow pick_chunk, which is
   // not monotonic in the batch)
   size_t fwd = carve(SPART_F64, (int64_t)rows).total;
-  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (F + 1)).total);
+  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (int64_t)per).total);
   l.fwd = c.take(fwd);
   l.total = c.o;
   return l;
 }
 
-static bool refine_sizes_ok(const spart_ctx* ctx, int64_t M, int F) {
-  return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF;
+static bool refine_sizes_ok(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
+  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF) return false;
+  if (V < 1 || V > VIEWS_MAXV || n_shared < 0 || n_shared > F) return false;
+  const int n = n_shared + V * (F - n_shared);
+  return n >= 1 && n <= REFINE_MAXF;
 }
 
-// spart_refine (srf = false) / spart_refine_srf (srf = true) once the arguments are checked.  The band model decides what
-// the forward call writes into the column block the step kernel reads: k_columns' three centre columns, or the ONE
-// *_srf output of k_columns_srf the fit is about (k_columns is then not launched at all).
-static int refine_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
-                       const spart_refine_opt& o, double lambda0, const RefineOut& out, char* wsp, const RefineLayout& l,
-                       hipStream_t st) {
-  const int nb = ctx->nb, W = refine_group(F);
-  const size_t lds = refine_lds_bytes(F, W);
+// A checked call, as the chunk loop and the three kernel sequences see it
+struct RefineRun {
+  spart_ctx* ctx;
+  bool srf;                     // the forward call writes the ONE *_srf column of the fit, not k_columns' three
+  int64_t M;
+  RefineShape s;
+  RefineCfg cfg;
+  spart_refine_opt o;           // (the defaults that 0 stands for filled in)
+  const double *obs, *weights;
+  char* wsp;
+  RefineLayout l;
+};
+// the blocks of the workspace; `cols` is the column block the kernel after a forward call reads
+struct RefineWs {
+  double *table, *cols, *t, *A, *lam, *cfg;
+  int32_t *na, *cfg_free;
+};
+
+// The rows of chunk m0 of an optional array of `width` values per observation: NULL stays NULL, an array shared by all
+// observations is itself
+template <typename T> static T* rows_at(T* p, int64_t m0, int64_t width, bool per_obs = true) {
+  return p && per_obs ? p + m0 * width : p;
+}
+static RefineOut rows_at(const RefineOut& o, int64_t m0, const RefineShape& s, int nb) {
+  return {rows_at(o.x, m0, s.n), rows_at(o.cost, m0, 1), rows_at(o.cost0, m0, 1), rows_at(o.sdev, m0, s.n), rows_at(o.n_accept, m0, 1),
+          rows_at(o.y, m0, (int64_t)s.V * nb)};
+}
+
+// the forward call of `rows` table rows into the three column blocks (no template: the float64 forward kernels are instantiated
+// here, ahead of the family's own)
+static int refine_forward(const RefineRun& r, int64_t rows, const double* const* params, double* const* cols,
+                          const spart_materialize& mat, const Workspace& ws, hipStream_t st) {
+  return run_impl<double, double, double>(r.ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, r.wsp + r.l.fwd, ws,
+                                          st, !r.srf);
+}
+
+// The chunk loop.  Per chunk of mc observations from m0: init(w, m0, mc) launches the kernel that writes the table and the
+// start state, then n_fwd times the forward call of the table's rows and after(w, m0, mc, it), the kernel that reads its
+// columns.  The band model decides what the forward call writes into the column block that kernel reads: k_columns' three
+// centre columns, or the ONE *_srf output of k_columns_srf the fit is about (k_columns is then not launched at all).
+template <typename Init, typename After>
+static int refine_loop(const RefineRun& r, int n_fwd, hipStream_t st, Init&& init, After&& after) {
+  const RefineLayout& l = r.l;
   spart_materialize mat;
   std::memset(&mat, 0, sizeof(mat));
   mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* table = (double*)(wsp + l.table);
-  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
-  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
-  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
-  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
-    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
-    const int64_t rows = (int64_t)mc * (F + 1);
-    RefineOut oc = out;
-    oc.x += m0 * F;
-    oc.cost += m0;
-    if (oc.cost0) oc.cost0 += m0;
-    if (oc.sdev) oc.sdev += m0 * F;
-    if (oc.n_accept) oc.n_accept += m0;
-    if (oc.y) oc.y += m0 * nb;
-    hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, lambda0, table, oc.x, t,
-                       lam, na, dcfg, dfree);
+  mat.fast_prelude = r.o.fast_prelude;
+  mat.nlayers = r.o.nlayers;
+  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
+  if (r.srf) (r.o.column == 0 ? mat.R_TOC_srf : r.o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[r.o.column];
+  const RefineWs w = {(double*)(r.wsp + l.table), cols[r.o.column], (double*)(r.wsp + l.t), (double*)(r.wsp + l.A),
+                      (double*)(r.wsp + l.lam), (double*)(r.wsp + l.cfg), (int32_t*)(r.wsp + l.na), (int32_t*)(r.wsp + l.cfg_free)};
+  for (int64_t m0 = 0; m0 < r.M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, r.M - m0);
+    const int64_t rows = (int64_t)mc * (r.s.F + 1) * r.s.V;
+    init(w, m0, mc);
     HIP_TRY(hipGetLastError());
     const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = w.table + (int64_t)p * rows;
     const Workspace ws = carve(SPART_F64, rows);
-    for (int it = 0; it <= o.n_iter; ++it) {
-      if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
-                                                    wsp + l.fwd, ws, st, !srf))
-        return rc;
-      hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
-                         obs + m0 * nb, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
-                         o.weights_per_obs ? 1 : 0, (const double*)dcfg, (const int32_t*)dfree, table, mc, F, nb, W, it,
-                         it == o.n_iter ? 1 : 0, t, A, lam, na, oc,
-                         o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * F : o.prior_mean) : nullptr,
-                         o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * F : o.prior_weight) : nullptr,
-                         o.prior_per_obs ? 1 : 0);
+    for (int it = 0; it < n_fwd; ++it) {
+      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
+      after(w, m0, mc, it);
       HIP_TRY(hipGetLastError());
     }
   }
   return SPART_OK;
+}
+
+// spart_refine / spart_refine_srf: k_refine_init, then n_iter + 1 times the forward call and k_refine_step
+static int refine_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) {
+  const spart_refine_opt& o = r.o;
+  const int nb = r.ctx->nb, F = r.s.F, W = refine_group(F);
+  const size_t lds = refine_lds_bytes(F, W);
+  return refine_loop(
+      r, o.n_iter + 1, st,
+      [&](const RefineWs& w, int64_t m0, int mc) {
+        hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, m0, mc, F, o.lambda0, w.table,
+                           out.x + m0 * F, w.t, w.lam, w.na, w.cfg, w.cfg_free);
+      },
+      [&](const RefineWs& w, int64_t m0, int mc, int it) {
+        hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)w.cols,
+                           r.obs + m0 * nb, rows_at(r.weights, m0, nb, o.weights_per_obs), o.weights_per_obs ? 1 : 0,
+                           (const double*)w.cfg, (const int32_t*)w.cfg_free, w.table, mc, F, nb, W, it, it == o.n_iter ? 1 : 0, w.t,
+                           w.A, w.lam, w.na, rows_at(out, m0, r.s, nb), rows_at(o.prior_mean, m0, F, o.prior_per_obs),
+                           rows_at(o.prior_weight, m0, F, o.prior_per_obs), o.prior_per_obs ? 1 : 0);
+      });
+}
+
+// spart_refine_posterior: k_refine_init, ONE forward call per chunk and k_refine_posterior.  The optimiser's state of the
+// layout is not used, so its A block takes k_refine_init's x when the caller does not ask for it.
+static int posterior_impl(const RefineRun& r, const spart_posterior_out& out, hipStream_t st) {
+  const spart_refine_opt& o = r.o;
+  const int nb = r.ctx->nb, F = r.s.F, W = refine_posterior_group(F);
+  const size_t lds = refine_posterior_lds_bytes(F, W);
+  return refine_loop(
+      r, 1, st,
+      [&](const RefineWs& w, int64_t m0, int mc) {
+        hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, m0, mc, F, o.lambda0, w.table,
+                           out.x ? out.x + m0 * F : w.A, w.t, w.lam, w.na, w.cfg, w.cfg_free);
+      },
+      [&](const RefineWs& w, int64_t m0, int mc, int) {
+        const PosteriorOut oc = {rows_at(out.y, m0, nb),    rows_at(out.jac, m0, (int64_t)nb * F), rows_at(out.cov, m0, F * F),
+                                 rows_at(out.ak, m0, F * F), rows_at(out.std, m0, F),              rows_at(out.dfs, m0, 1),
+                                 rows_at(out.cost, m0, 1),   rows_at(out.nband, m0, 1),            rows_at(out.status, m0, 1)};
+        hipLaunchKernelGGL(W == 8 ? k_refine_posterior<8> : k_refine_posterior<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)w.cols,
+                           rows_at(r.obs, m0, nb), rows_at(r.weights, m0, nb, o.weights_per_obs), o.weights_per_obs ? 1 : 0,
+                           (const double*)w.cfg, mc, F, nb, (const double*)w.t, oc, rows_at(o.prior_mean, m0, F, o.prior_per_obs),
+                           rows_at(o.prior_weight, m0, F, o.prior_per_obs), o.prior_per_obs ? 1 : 0);
+      });
+}
+
+// spart_refine_views: the view-major table of k_refine_views_init, then n_iter + 1 times the forward call and the joint step
+// kernel; o.prior_* are per unknown
+static int views_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) {
+  const spart_refine_opt& o = r.o;
+  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, W = views_group(F, n);
+  const int64_t U = (int64_t)V * nb;
+  const size_t lds = views_lds_bytes(F, n, W);
+  return refine_loop(
+      r, o.n_iter + 1, st,
+      [&](const RefineWs& w, int64_t m0, int mc) {
+        hipLaunchKernelGGL(k_refine_views_init, dim3((unsigned)(((int64_t)mc * V + 255) / 256)), dim3(256), 0, st, r.cfg, r.M, m0, mc, V,
+                           F, Fs, o.lambda0, w.table, out.x + m0 * n, w.t, w.lam, w.na, w.cfg, w.cfg_free);
+      },
+      [&](const RefineWs& w, int64_t m0, int mc, int it) {
+        ViewsStep a;
+        a.cols = w.cols;
+        a.obs = r.obs + m0 * U;
+        a.wts = rows_at(r.weights, m0, U, o.weights_per_obs);
+        a.cfg = w.cfg;
+        a.cfg_free = w.cfg_free;
+        a.table = w.table;
+        a.Mc = mc, a.V = V, a.F = F, a.Fs = Fs, a.nb = nb, a.it = it, a.last = it == o.n_iter ? 1 : 0;
+        a.wper = o.weights_per_obs ? 1 : 0, a.pper = o.prior_per_obs ? 1 : 0;
+        a.st = w.t, a.sA = w.A, a.slam = w.lam, a.sna = w.na;
+        a.out = rows_at(out, m0, r.s, nb);
+        a.pmu = rows_at(o.prior_mean, m0, n, o.prior_per_obs);
+        a.ppw = rows_at(o.prior_weight, m0, n, o.prior_per_obs);
+        hipLaunchKernelGGL(W == 8 ? k_refine_views_step<8> : k_refine_views_step<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds,
+                           st, a);
+      });
+}
+
+// What every entry point checks about the fit itself, in one order: the options (with the defaults that 0 stands for filled
+// in), then every free column with its bounds, which become `cfg`.
+static int refine_check_fit(const char* who, spart_refine_opt& o, int F, const int32_t* free_cols, const double* lo,
+                            const double* hi, RefineCfg& cfg) {
+  if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
+  if (o.n_iter < 0 || o.n_iter > REFINE_MAX_ITER)
+    return fail(SPART_ERR_INVALID, "%s: n_iter = %d, expected 0 ... %d", who, o.n_iter, REFINE_MAX_ITER);
+  if (o.nlayers < 0 || o.nlayers > SPART_MAX_NLAYERS)
+    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
+  if (!(o.rel_step >= 0.0) || !(o.lambda0 >= 0.0) || std::isinf(o.rel_step) || std::isinf(o.lambda0))
+    return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
+  if (o.prior_per_obs != 0 && o.prior_per_obs != 1)
+    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: one row for all, 1: one row per observation)", who, o.prior_per_obs);
+  if (!o.prior_mean != !o.prior_weight)
+    return fail(SPART_ERR_INVALID, "%s: prior_mean and prior_weight come together (both NULL = no prior)", who);
+  if (o.rel_step == 0.0) o.rel_step = 1e-3;
+  if (o.lambda0 == 0.0) o.lambda0 = 1e-2;
+  std::memset(&cfg, 0, sizeof(cfg));
+  for (int f = 0; f < F; ++f) {
+    const int c = free_cols[f];
+    if (c < 0 || c >= SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, SPART_NPARAM - 1);
+    if (cfg.is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
+    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
+      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
+    cfg.is_free[c] = 1;
+    cfg.free_col[f] = c;
+    cfg.lo[f] = lo[f];
+    cfg.hi[f] = hi[f];
+    cfg.h[f] = o.rel_step * (hi[f] - lo[f]);
+  }
+  return SPART_OK;
+}
+
+static int refine_check_band_model(const char* who, int band_model) {
+  if (band_model == 0 || band_model == 1) return SPART_OK;
+  return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, band_model);
+}
+
+// the arguments the four entry points share
+struct RefineArgs {
+  spart_ctx* ctx;
+  int64_t M;
+  const double* const* base;
+  int F;
+  const int32_t* free_cols;
+  const double *lo, *hi, *obs, *weights;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// The one argument check and refusal order of the family.  `have_opt`: the entry's own option and output structs are there;
+// `have_data`: so are the obs, x and cost it requires.  before(r) reads the options into r.o, r.s and r.srf once they are
+// known to be there and may refuse; after() may refuse once the fit is checked; run(r, st) queues the checked call.
+template <typename Before, typename After, typename Run>
+static int refine_entry(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after, Run&& run) {
+  if (!a.ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (a.M < 0 || a.M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)a.M);
+  if (a.F < 1 || a.F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, a.F, REFINE_MAXF);
+  if (!a.base || !a.free_cols || !a.lo || !a.hi || !have_opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  RefineRun r;
+  r.ctx = a.ctx, r.M = a.M, r.obs = a.obs, r.weights = a.weights, r.wsp = (char*)a.workspace;
+  r.s = {1, a.F, a.F, a.F};
+  if (int rc = before(r)) return rc;
+  if (int rc = refine_check_fit(who, r.o, a.F, a.free_cols, a.lo, a.hi, r.cfg)) return rc;
+  if (int rc = after()) return rc;
+  if (a.ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (a.M == 0) return SPART_OK;
+  if (int i = first_null(a.base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  if (!have_data) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
+  if (r.o.weights_per_obs && !a.weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+  for (int p = 0; p < SPART_NPARAM; ++p) r.cfg.base[p] = a.base[p];
+  for (int f = 0; f < a.F; ++f) r.cfg.freebase[f] = a.base[r.cfg.free_col[f]];
+  r.l = refine_layout(a.ctx->nb, a.M, r.s.V, r.s.F, r.s.n);
+  if (!a.workspace || a.workspace_bytes < r.l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, r.l.total, a.workspace_bytes);
+  return guarded(a.ctx, who, a.workspace, r.l.total, a.stream, [&](hipStream_t st) { return run(r, st); });
+}
+static int refine_no_check() { return SPART_OK; }
+
+static int refine_call(const char* who, bool srf, const RefineArgs& a, const spart_refine_opt* opt, const RefineOut& out) {
+  return refine_entry(
+      who, a, opt, a.obs && out.x && out.cost,
+      [&](RefineRun& r) {
+        r.o = *opt, r.srf = srf;
+        return SPART_OK;
+      },
+      refine_no_check, [&](const RefineRun& r, hipStream_t st) { return refine_impl(r, out, st); });
 }
 
 // ---- SRF support (include/spart_hip.h: spart_srf_support)
@@ -1274,295 +1468,71 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
 }
 
 size_t spart_refine_workspace_bytes(const spart_ctx* ctx, int64_t M, int F) {
-  return refine_sizes_ok(ctx, M, F) ? refine_layout(ctx->nb, M, F).total : 0;
+  return refine_sizes_ok(ctx, M, 1, F, F) ? refine_layout(ctx->nb, M, 1, F, F).total : 0;
 }
 
-// What spart_refine, spart_refine_srf and spart_refine_views check about the fit itself, in one order: the options (with the
-// defaults that 0 stands for filled in), then every free column with its bounds, which become `cfg`.
-static int refine_check_fit(const char* who, spart_refine_opt& o, int F, const int32_t* free_cols, const double* lo,
-                            const double* hi, RefineCfg& cfg) {
-  if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
-  if (o.n_iter < 0 || o.n_iter > REFINE_MAX_ITER)
-    return fail(SPART_ERR_INVALID, "%s: n_iter = %d, expected 0 ... %d", who, o.n_iter, REFINE_MAX_ITER);
-  if (o.nlayers < 0 || o.nlayers > SPART_MAX_NLAYERS)
-    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
-  if (!(o.rel_step >= 0.0) || !(o.lambda0 >= 0.0) || std::isinf(o.rel_step) || std::isinf(o.lambda0))
-    return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
-  if (o.prior_per_obs != 0 && o.prior_per_obs != 1)
-    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: one row for all, 1: one row per observation)", who, o.prior_per_obs);
-  if (!o.prior_mean != !o.prior_weight)
-    return fail(SPART_ERR_INVALID, "%s: prior_mean and prior_weight come together (both NULL = no prior)", who);
-  if (o.rel_step == 0.0) o.rel_step = 1e-3;
-  if (o.lambda0 == 0.0) o.lambda0 = 1e-2;
-  std::memset(&cfg, 0, sizeof(cfg));
-  for (int f = 0; f < F; ++f) {
-    const int c = free_cols[f];
-    if (c < 0 || c >= SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, SPART_NPARAM - 1);
-    if (cfg.is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
-    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
-      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
-    cfg.is_free[c] = 1;
-    cfg.free_col[f] = c;
-    cfg.lo[f] = lo[f];
-    cfg.hi[f] = hi[f];
-    cfg.h[f] = o.rel_step * (hi[f] - lo[f]);
-  }
-  return SPART_OK;
-}
-
-// spart_refine and spart_refine_srf: one argument check, one refusal order
-static int refine_call(const char* who, bool srf, spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F,
-                       const int32_t* free_cols, const double* lo, const double* hi, const double* obs, const double* weights,
-                       const spart_refine_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
-                       double* y, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  spart_refine_opt o = *opt;
-  RefineCfg cfg;
-  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
-  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (M == 0) return SPART_OK;
-  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
-  if (!obs || !x || !cost) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
-  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
-  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
-  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
-  const RefineLayout l = refine_layout(ctx->nb, M, F);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
-  const RefineOut out = {x, cost, cost0, sdev, n_accept, y};
-  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
-    return refine_impl(ctx, srf, M, cfg, F, obs, weights, o, o.lambda0, out, (char*)workspace, l, st);
-  });
+size_t spart_views_workspace_bytes(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
+  return refine_sizes_ok(ctx, M, V, F, n_shared) ? refine_layout(ctx->nb, M, V, F, n_shared + V * (F - n_shared)).total : 0;
 }
 
 int spart_refine(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
                  const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
                  double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
                  size_t workspace_bytes, void* stream) {
-  return refine_call("spart_refine", false, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept, y,
-                     workspace, workspace_bytes, stream);
+  return refine_call("spart_refine", false, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt,
+                     {x, cost, cost0, sdev, n_accept, y});
 }
 
 int spart_refine_srf(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
                      const double* lo, const double* hi, const double* obs, const double* weights, const spart_refine_opt* opt,
                      double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept, double* y, void* workspace,
                      size_t workspace_bytes, void* stream) {
-  return refine_call("spart_refine_srf", true, ctx, M, base, F, free_cols, lo, hi, obs, weights, opt, x, cost, cost0, sdev, n_accept,
-                     y, workspace, workspace_bytes, stream);
+  return refine_call("spart_refine_srf", true, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream},
+                     opt, {x, cost, cost0, sdev, n_accept, y});
 }
 
-// ---- spart_refine_posterior (csrc/spart_refine_posterior.h): refine_impl's chunk loop with ONE forward call per chunk and
-// k_refine_posterior in place of k_refine_step.  The optimiser's state of the layout is not used, so its A block takes
-// k_refine_init's x when the caller does not ask for it.
-static int posterior_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int F, const double* obs, const double* weights,
-                          const spart_refine_opt& o, const spart_posterior_out& out, char* wsp, const RefineLayout& l,
-                          hipStream_t st) {
-  const int nb = ctx->nb, W = refine_posterior_group(F);
-  const size_t lds = refine_posterior_lds_bytes(F, W);
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* table = (double*)(wsp + l.table);
-  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
-  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
-  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
-  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
-    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
-    const int64_t rows = (int64_t)mc * (F + 1);
-    PosteriorOut oc;
-    oc.y = out.y ? out.y + m0 * nb : nullptr;
-    oc.jac = out.jac ? out.jac + m0 * nb * F : nullptr;
-    oc.cov = out.cov ? out.cov + m0 * F * F : nullptr;
-    oc.ak = out.ak ? out.ak + m0 * F * F : nullptr;
-    oc.sdev = out.std ? out.std + m0 * F : nullptr;
-    oc.dfs = out.dfs ? out.dfs + m0 : nullptr;
-    oc.cost = out.cost ? out.cost + m0 : nullptr;
-    oc.nband = out.nband ? out.nband + m0 : nullptr;
-    oc.status = out.status ? out.status + m0 : nullptr;
-    hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, o.lambda0, table,
-                       out.x ? out.x + m0 * F : A, t, lam, na, dcfg, dfree);
-    HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
-    if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, wsp + l.fwd,
-                                                  ws, st, !srf))
-      return rc;
-    hipLaunchKernelGGL(W == 8 ? k_refine_posterior<8> : k_refine_posterior<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)cols[o.column],
-                       obs ? obs + m0 * nb : nullptr, weights ? (o.weights_per_obs ? weights + m0 * nb : weights) : nullptr,
-                       o.weights_per_obs ? 1 : 0, (const double*)dcfg, mc, F, nb, (const double*)t, oc,
-                       o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * F : o.prior_mean) : nullptr,
-                       o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * F : o.prior_weight) : nullptr,
-                       o.prior_per_obs ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-  }
-  return SPART_OK;
-}
-
+// obs may be NULL here, and the outputs come in one struct, of which one at least is asked for
 int spart_refine_posterior(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
                            const double* lo, const double* hi, const double* obs, const double* weights,
                            const spart_refine_opt* opt, int band_model, const spart_posterior_out* out, void* workspace,
                            size_t workspace_bytes, void* stream) {
   const char* who = "spart_refine_posterior";
-  // refine_call's list and order; obs may be NULL here, and the outputs come in one struct
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!base || !free_cols || !lo || !hi || !opt || !out) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  spart_refine_opt o = *opt;
-  RefineCfg cfg;
-  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
-  if (band_model != 0 && band_model != 1)
-    return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, band_model);
-  if (!out->x && !out->y && !out->jac && !out->cov && !out->ak && !out->std && !out->dfs && !out->cost && !out->nband && !out->status)
-    return fail(SPART_ERR_INVALID, "%s: every output is null", who);
-  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (M == 0) return SPART_OK;
-  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
-  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
-  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
-  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
-  const RefineLayout l = refine_layout(ctx->nb, M, F);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
-  const spart_posterior_out oo = *out;
-  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
-    return posterior_impl(ctx, band_model == 1, M, cfg, F, obs, weights, o, oo, (char*)workspace, l, st);
-  });
+  spart_posterior_out oo;
+  return refine_entry(
+      who, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt && out, true,
+      [&](RefineRun& r) {
+        r.o = *opt, r.srf = band_model == 1, oo = *out;
+        return SPART_OK;
+      },
+      [&] {
+        if (int rc = refine_check_band_model(who, band_model)) return rc;
+        if (!oo.x && !oo.y && !oo.jac && !oo.cov && !oo.ak && !oo.std && !oo.dfs && !oo.cost && !oo.nband && !oo.status)
+          return fail(SPART_ERR_INVALID, "%s: every output is null", who);
+        return SPART_OK;
+      },
+      [&](const RefineRun& r, hipStream_t st) { return posterior_impl(r, oo, st); });
 }
 
-// ---- spart_refine_views (csrc/spart_refine_views.h).  The workspace is spart_refine's, sized by ONE chunk of
-// views_chunk(V, F) pixels: V (F + 1) table rows per pixel, the state per unknown.
-static RefineLayout views_layout(int nb, int64_t M, int V, int F, int n) {
-  RefineLayout l;
-  l.mcap = std::min<int64_t>(M, views_chunk(V, F));
-  const size_t mc = (size_t)l.mcap, per = (size_t)(F + 1) * V, rows = mc * per;
-  Carver c;
-  l.table = c.take((size_t)NPARAM * rows * 8);
-  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
-  l.t = c.take(mc * n * 8);
-  l.A = c.take(mc * (size_t)(refine_ntri(n) + n) * 8);
-  l.lam = c.take(mc * 8);
-  l.na = c.take(mc * 4);
-  l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
-  l.cfg_free = c.take(REFINE_MAXF * 4);
-  size_t fwd = carve(SPART_F64, (int64_t)rows).total;         // (a full chunk and the last, shorter one: see refine_layout)
-  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (int64_t)per).total);
-  l.fwd = c.take(fwd);
-  l.total = c.o;
-  return l;
-}
-
-static bool views_sizes_ok(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
-  if (!refine_sizes_ok(ctx, M, F) || V < 1 || V > VIEWS_MAXV || n_shared < 0 || n_shared > F) return false;
-  const int n = n_shared + V * (F - n_shared);
-  return n >= 1 && n <= REFINE_MAXF;
-}
-
-size_t spart_views_workspace_bytes(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
-  return views_sizes_ok(ctx, M, V, F, n_shared) ? views_layout(ctx->nb, M, V, F, n_shared + V * (F - n_shared)).total : 0;
-}
-
-// refine_impl's chunk loop with the view-major table and the joint step kernel; o.prior_* are per unknown
-static int views_impl(spart_ctx* ctx, bool srf, int64_t M, const RefineCfg& cfg, int V, int F, int Fs, const double* obs,
-                      const double* weights, const spart_refine_opt& o, const RefineOut& out, char* wsp, const RefineLayout& l,
-                      hipStream_t st) {
-  const int nb = ctx->nb, n = Fs + V * (F - Fs), W = views_group(F, n);
-  const int64_t U = (int64_t)V * nb;
-  const size_t lds = views_lds_bytes(F, n, W);
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* table = (double*)(wsp + l.table);
-  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
-  double *t = (double*)(wsp + l.t), *A = (double*)(wsp + l.A), *lam = (double*)(wsp + l.lam), *dcfg = (double*)(wsp + l.cfg);
-  int32_t *na = (int32_t*)(wsp + l.na), *dfree = (int32_t*)(wsp + l.cfg_free);
-  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
-    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
-    const int64_t rows = (int64_t)mc * (F + 1) * V;
-    RefineOut oc = out;
-    oc.x += m0 * n;
-    oc.cost += m0;
-    if (oc.cost0) oc.cost0 += m0;
-    if (oc.sdev) oc.sdev += m0 * n;
-    if (oc.n_accept) oc.n_accept += m0;
-    if (oc.y) oc.y += m0 * U;
-    hipLaunchKernelGGL(k_refine_views_init, dim3((unsigned)(((int64_t)mc * V + 255) / 256)), dim3(256), 0, st, cfg, M, m0, mc, V, F,
-                       Fs, o.lambda0, table, oc.x, t, lam, na, dcfg, dfree);
-    HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
-    for (int it = 0; it <= o.n_iter; ++it) {
-      if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
-                                                    wsp + l.fwd, ws, st, !srf))
-        return rc;
-      ViewsStep a;
-      a.cols = cols[o.column];
-      a.obs = obs + m0 * U;
-      a.wts = weights ? (o.weights_per_obs ? weights + m0 * U : weights) : nullptr;
-      a.cfg = dcfg;
-      a.cfg_free = dfree;
-      a.table = table;
-      a.Mc = mc, a.V = V, a.F = F, a.Fs = Fs, a.nb = nb, a.it = it, a.last = it == o.n_iter ? 1 : 0;
-      a.wper = o.weights_per_obs ? 1 : 0, a.pper = o.prior_per_obs ? 1 : 0;
-      a.st = t, a.sA = A, a.slam = lam, a.sna = na;
-      a.out = oc;
-      a.pmu = o.prior_mean ? (o.prior_per_obs ? o.prior_mean + m0 * n : o.prior_mean) : nullptr;
-      a.ppw = o.prior_weight ? (o.prior_per_obs ? o.prior_weight + m0 * n : o.prior_weight) : nullptr;
-      hipLaunchKernelGGL(W == 8 ? k_refine_views_step<8> : k_refine_views_step<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds,
-                         st, a);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return SPART_OK;
-}
-
+// the sizes of the views are checked once the options they are read from are known to be there, before the fit
 int spart_refine_views(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
                        const double* lo, const double* hi, const double* obs, const double* weights,
                        const spart_refine_views_opt* opt, double* x, double* cost, double* cost0, double* sdev, int32_t* n_accept,
                        double* y, void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "spart_refine_views";
-  // refine_call's list and order, the new sizes after the arguments they are read from
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!base || !free_cols || !lo || !hi || !opt) return fail(SPART_ERR_INVALID, "%s: null argument", who);
-  const int V = opt->V, Fs = opt->n_shared;
-  if (V < 1 || V > VIEWS_MAXV) return fail(SPART_ERR_INVALID, "%s: V = %d, expected 1 <= V <= %d", who, V, VIEWS_MAXV);
-  if (Fs < 0 || Fs > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, Fs, F);
-  const int n = Fs + V * (F - Fs);
-  if (n < 1 || n > REFINE_MAXF)
-    return fail(SPART_ERR_INVALID, "%s: n_shared + V (F - n_shared) = %d unknowns per pixel, expected 1 ... %d", who, n, REFINE_MAXF);
-  if (opt->band_model != 0 && opt->band_model != 1)
-    return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, opt->band_model);
-  spart_refine_opt o = opt->fit;
-  RefineCfg cfg;
-  if (int rc = refine_check_fit(who, o, F, free_cols, lo, hi, cfg)) return rc;
-  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (M == 0) return SPART_OK;
-  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
-  if (!obs || !x || !cost) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
-  if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
-  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
-  for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]];
-  const RefineLayout l = views_layout(ctx->nb, M, V, F, n);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
   const RefineOut out = {x, cost, cost0, sdev, n_accept, y};
-  const bool srf = opt->band_model == 1;
-  return guarded(ctx, who, workspace, l.total, stream, [&](hipStream_t st) {
-    return views_impl(ctx, srf, M, cfg, V, F, Fs, obs, weights, o, out, (char*)workspace, l, st);
-  });
+  return refine_entry(
+      who, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt, obs && x && cost,
+      [&](RefineRun& r) {
+        const int V = opt->V, Fs = opt->n_shared;
+        if (V < 1 || V > VIEWS_MAXV) return fail(SPART_ERR_INVALID, "%s: V = %d, expected 1 <= V <= %d", who, V, VIEWS_MAXV);
+        if (Fs < 0 || Fs > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, Fs, F);
+        const int n = Fs + V * (F - Fs);
+        if (n < 1 || n > REFINE_MAXF)
+          return fail(SPART_ERR_INVALID, "%s: n_shared + V (F - n_shared) = %d unknowns per pixel, expected 1 ... %d", who, n, REFINE_MAXF);
+        r.o = opt->fit, r.srf = opt->band_model == 1, r.s = {V, F, Fs, n};
+        return refine_check_band_model(who, opt->band_model);
+      },
+      refine_no_check, [&](const RefineRun& r, hipStream_t st) { return views_impl(r, out, st); });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

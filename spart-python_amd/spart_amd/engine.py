@@ -226,6 +226,31 @@ def refine_plan(free, bounds, n_iter, column, rel_step, lambda0, default_ranges=
             "lambda0": float(lambda0), "prior": None if prior is None else _prior_plan(names, prior)}
 
 
+def _refine_head(make_plan, lidf, prior, prior_mean, prior_weight, band_model):
+    """How refine_args and refine_views_args begin: prior exclusivity, the band model's name, the plan ``make_plan()`` gives,
+    lidf -> the plan"""
+    ready = prior_mean is not None or prior_weight is not None
+    if prior is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    _band_model(band_model)
+    plan = make_plan()
+    if plan.get("prior") is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    if lidf not in ("literal", "newton"):
+        raise ValueError("lidf must be 'literal' or 'newton'")
+    return plan
+
+
+def _refine_prior(prior_mean, prior_weight, M, n, made):
+    """How they end: the ready-made prior with its shapes checked for n unknowns, else ``made``, the (mean, weight) arrays of
+    the dict prior or None -> (prior_mean, prior_weight, prior per observation 0 / 1)"""
+    if prior_mean is not None or prior_weight is not None:
+        return prior_mean, prior_weight, _prior_tensor_shapes(prior_mean, prior_weight, M, n)
+    if made is None:
+        return None, None, 0
+    return made[0], made[1], int(made[0].ndim == 2)
+
+
 def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior, prior_mean, prior_weight,
                 band_model, nb=None, _plan=None):
     """Every argument check of spart_amd.refine and Engine.refine that needs no device: prior exclusivity, the band model's
@@ -234,15 +259,8 @@ def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, la
     -> (plan, params, M, weights kind, prior_mean, prior_weight, prior per observation 0 / 1); ``params`` comes back as the
     2-D tensor it was, else as a list of 27 columns; a plan's prior comes back as its prior_arrays."""
     import torch
-    ready = prior_mean is not None or prior_weight is not None
-    if prior is not None and ready:
-        raise ValueError("prior and prior_mean / prior_weight exclude each other")
-    _band_model(band_model)
-    plan = _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior)
-    if plan.get("prior") is not None and ready:
-        raise ValueError("prior and prior_mean / prior_weight exclude each other")
-    if lidf not in ("literal", "newton"):
-        raise ValueError("lidf must be 'literal' or 'newton'")
+    plan = _refine_head(lambda: _plan if _plan is not None else refine_plan(free, bounds, n_iter, column, rel_step, lambda0, prior=prior),
+                        lidf, prior, prior_mean, prior_weight, band_model)
     oshape = tuple(int(n) for n in np.shape(obs))
     if len(oshape) != 2 or (nb is not None and oshape[1] != nb):
         raise ValueError(f"obs has shape {oshape}, expected (M, nb)" + ("" if nb is None else f" = (M, {nb})"))
@@ -264,13 +282,8 @@ def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, la
         if n not in (1, M):
             raise ValueError(f"a params column of {n} values does not broadcast to the {M} rows of obs")
     kind = lut_weights_kind(None if weights is None else np.shape(weights), M, oshape[1])
-    per_obs = 0
-    if ready:
-        per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, len(plan["names"]))
-    elif plan.get("prior") is not None:
-        prior_mean, prior_weight = prior_arrays(plan["prior"], M)
-        per_obs = int(prior_mean.ndim == 2)
-    return plan, params, M, kind, prior_mean, prior_weight, per_obs
+    return (plan, params, M, kind) + _refine_prior(prior_mean, prior_weight, M, len(plan["names"]),
+                                                   None if plan.get("prior") is None else prior_arrays(plan["prior"], M))
 
 
 def _views_prior(names, Fs, V, prior):
@@ -319,14 +332,12 @@ def refine_views_args(params, obs, shared, local, bounds, weights, column, n_ite
     27 entries each broadcastable to (V, M), weights None / (nb,) / (M, V, nb), the prior per unknown.
     -> (plan, params, (M, V, Fs, n), weights per observation 0 / 1, prior_mean, prior_weight, prior per observation 0 / 1)"""
     import torch
-    ready = prior_mean is not None or prior_weight is not None
-    if prior is not None and ready:
-        raise ValueError("prior and prior_mean / prior_weight exclude each other")
-    _band_model(band_model)
-    shared, local = [str(s) for s in shared], [str(s) for s in local]
-    plan = refine_plan(shared + local, bounds, n_iter, column, rel_step, lambda0)
-    if lidf not in ("literal", "newton"):
-        raise ValueError("lidf must be 'literal' or 'newton'")
+
+    def make_plan():
+        nonlocal shared, local
+        shared, local = [str(s) for s in shared], [str(s) for s in local]
+        return refine_plan(shared + local, bounds, n_iter, column, rel_step, lambda0)
+    plan = _refine_head(make_plan, lidf, prior, prior_mean, prior_weight, band_model)
     oshape = tuple(int(k) for k in np.shape(obs))
     if len(oshape) != 3 or (nb is not None and oshape[2] != nb):
         raise ValueError(f"obs has shape {oshape}, expected (M, V, nb)" + ("" if nb is None else f" = (M, V, {nb})"))
@@ -358,18 +369,15 @@ def refine_views_args(params, obs, shared, local, bounds, weights, column, n_ite
         if ws not in ((oshape[2],), oshape):
             raise ValueError(f"weights has shape {ws}, expected (nb,) = ({oshape[2]},) or (M, V, nb) = {oshape}")
         wper = int(len(ws) == 3)
-    per_obs = 0
-    if ready:
-        per_obs = _prior_tensor_shapes(prior_mean, prior_weight, M, n)
-    elif prior is not None:
-        prior_mean, prior_weight = _views_prior(plan["names"], Fs, V, prior)
-        per_obs = int(prior_mean.ndim == 2)
-        if per_obs and prior_mean.shape[0] != M:
-            raise ValueError(f"prior: arrays of {prior_mean.shape[0]} pixels for the {M} of obs")
+    prior_mean, prior_weight, per_obs = _refine_prior(prior_mean, prior_weight, M, n,
+                                                      None if prior is None else _views_prior(plan["names"], Fs, V, prior))
+    if prior is not None and per_obs and prior_mean.shape[0] != M:
+        raise ValueError(f"prior: arrays of {prior_mean.shape[0]} pixels for the {M} of obs")
     return plan, params, (M, V, Fs, n), wper, prior_mean, prior_weight, per_obs
 
 
 BAND_MODELS = ("centre", "srf")
+_FIT_OUTS = ("x", "cost", "cost0", "std", "n_accept", "y")     # of spart_refine / _srf / _views, in the order of their argument lists
 
 
 def params_rows(params):
@@ -1031,6 +1039,52 @@ class Engine:
         _lib.check(self.lib, self.ctx, rc)
         return res
 
+    def _refine_columns(self, params, M):
+        """the start rows of refine() / posterior() as 27 float64 device columns of M values"""
+        if self.torch.is_tensor(params):
+            P = params.to(device=self.device, dtype=self.torch.float64)
+            return list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
+        return self.columns(params, M)[0]
+
+    def _fit_outputs(self, M, n, yshape):
+        """the six outputs of a fit of n unknowns per observation, in the order of the C argument list (_FIT_OUTS)"""
+        torch = self.torch
+        shapes = {"x": (M, n), "cost": (M,), "cost0": (M,), "std": (M, n), "n_accept": (M,), "y": yshape}
+        return {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device) for k in _FIT_OUTS}
+
+    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None):
+        """What every entry point of the refinement family does once its parameter columns ``cols`` and its outputs are on the
+        device: obs and weights as float64 device tensors, spart_refine_opt from the plan, the prior (mean, weight, per
+        observation 0 / 1) hooked up, the workspace, the call count, the C call and its check.  ``outs``: the C arguments between
+        the options and the workspace; ``views`` = (V, Fs, srf) wraps the options in spart_refine_views_opt.
+        -> (obs, weights) as the call got them"""
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        o = None if obs is None else torch.as_tensor(obs).to(**f64).contiguous()
+        w = None if weights is None else torch.as_tensor(weights).to(**f64).contiguous()
+        opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=wper,
+                                  fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
+                                  lambda0=plan["lambda0"])
+        if prior[0] is not None:
+            pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in prior[:2])
+            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = prior[2], pm.data_ptr(), pw.data_ptr()
+        F = len(plan["names"])
+        if views is None:
+            nbytes = int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F))
+        else:
+            V, Fs, srf = views
+            nbytes = int(self.lib.spart_views_workspace_bytes(self.ctx, M, V, F, Fs))
+            opt = _lib.SpartRefineViewsOpt(fit=opt, V=V, n_shared=Fs, band_model=int(srf))
+        nbytes = max(nbytes, 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls[entry] += 1
+        rc = getattr(self.lib, entry)(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                      _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr() if o is not None else None,
+                                      w.data_ptr() if w is not None else None, ctypes.byref(opt), *outs, ws.data_ptr(), nbytes,
+                                      self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        return o, w
+
     def refine(self, params, obs, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
                lidf="literal", nlayers=None, prior=None, prior_mean=None, prior_weight=None, band_model="centre", _plan=None,
                posterior=False):
@@ -1062,36 +1116,11 @@ class Engine:
             nb=self.nb, _plan=_plan)
         entry = "spart_refine_srf" if _band_model(band_model, self) else "spart_refine"
         nl = self._nlayers(nlayers)
-        nb, F = self.nb, len(plan["names"])
         # ---- the device from here on
-        torch = self.torch
-        if torch.is_tensor(params):
-            P = params.to(device=self.device, dtype=torch.float64)
-            cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
-        else:
-            cols, _ = self.columns(params, M)
-        o = torch.as_tensor(obs).to(device=self.device, dtype=torch.float64).contiguous()
-        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
-        res = {"x": torch.empty((M, F), dtype=torch.float64, device=self.device),
-               "cost": torch.empty((M,), dtype=torch.float64, device=self.device),
-               "cost0": torch.empty((M,), dtype=torch.float64, device=self.device),
-               "std": torch.empty((M, F), dtype=torch.float64, device=self.device),
-               "n_accept": torch.empty((M,), dtype=torch.int32, device=self.device),
-               "y": torch.empty((M, nb), dtype=torch.float64, device=self.device)}
-        opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=1 if kind == "per_observation" else 0,
-                                  fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
-                                  lambda0=plan["lambda0"])
-        if prior_mean is not None:
-            pm, pw = (torch.as_tensor(v).to(device=self.device, dtype=torch.float64).contiguous() for v in (prior_mean, prior_weight))
-            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
-        nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.calls[entry] += 1
-        rc = getattr(self.lib, entry)(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                      _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
-                                      ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
-                                      ws.data_ptr(), nbytes, self._stream())
-        _lib.check(self.lib, self.ctx, rc)
+        cols = self._refine_columns(params, M)
+        res = self._fit_outputs(M, len(plan["names"]), (M, self.nb))
+        o, w = self._refine_device(entry, plan, M, cols, obs, weights, 1 if kind == "per_observation" else 0, lidf, nl,
+                                   (prior_mean, prior_weight, per_obs), [res[k].data_ptr() for k in _FIT_OUTS])
         res["names"] = list(plan["names"])
         if posterior:
             # the fitted rows: the start rows with the free columns at x; std, y and cost of that call are the fit's bit for bit
@@ -1126,32 +1155,16 @@ class Engine:
         nb, F = self.nb, len(plan["names"])
         # ---- the device from here on
         torch = self.torch
-        if torch.is_tensor(params):
-            P = params.to(device=self.device, dtype=torch.float64)
-            cols = list(P.expand(_lib.NPARAM, M).contiguous()) if M else list(P)
-        else:
-            cols, _ = self.columns(params, M)
-        o = None if obs is None else torch.as_tensor(obs).to(device=self.device, dtype=torch.float64).contiguous()
-        w = None if weights is None else torch.as_tensor(weights).to(device=self.device, dtype=torch.float64).contiguous()
+        cols = self._refine_columns(params, M)
         shapes = {"x": (M, F), "y": (M, nb), "jac": (M, nb, F), "cov": (M, F, F), "ak": (M, F, F), "std": (M, F), "dfs": (M,),
                   "cost": (M,), "nband": (M,), "status": (M,)}
         want = _lib.POSTERIOR_OUTS if _outputs is None else tuple(_outputs)
         res = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("nband", "status") else torch.float64, device=self.device)
                for k in _lib.POSTERIOR_OUTS if k in want}
         out = _lib.SpartPosteriorOut(**{k: v.data_ptr() for k, v in res.items()})
-        opt = _lib.SpartRefineOpt(column=plan["column"], n_iter=0, weights_per_obs=1 if kind == "per_observation" else 0,
-                                  fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"], lambda0=0.0)
-        if prior_mean is not None:
-            pm, pw = (torch.as_tensor(v).to(device=self.device, dtype=torch.float64).contiguous() for v in (prior_mean, prior_weight))
-            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
-        nbytes = max(int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F)), 256)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.calls["spart_refine_posterior"] += 1
-        rc = self.lib.spart_refine_posterior(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                             _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr() if o is not None else None,
-                                             w.data_ptr() if w is not None else None, ctypes.byref(opt), 1 if srf else 0,
-                                             ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
-        _lib.check(self.lib, self.ctx, rc)
+        self._refine_device("spart_refine_posterior", dict(plan, n_iter=0, lambda0=0.0), M, cols, obs, weights,
+                            1 if kind == "per_observation" else 0, lidf, nl, (prior_mean, prior_weight, per_obs),
+                            [1 if srf else 0, ctypes.byref(out)])
         if "cov" in res and "std" in res:
             res["corr"] = res["cov"] / (res["std"][:, :, None] * res["std"][:, None, :])
             d = res["corr"].diagonal(dim1=1, dim2=2)      # sqrt(v) * sqrt(v) need not be v: the diagonal is 1 by definition
@@ -1196,32 +1209,14 @@ class Engine:
         nb, F = self.nb, len(plan["names"])
         # ---- the device from here on
         torch = self.torch
-        f64 = dict(dtype=torch.float64, device=self.device)
         if torch.is_tensor(params):
-            cols = list(params.to(**f64).contiguous())
+            cols = list(params.to(dtype=torch.float64, device=self.device).contiguous())
         else:
             host = np.stack([np.broadcast_to(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float64), (V, M)) for c in params])
             cols = list(torch.as_tensor(host).to(self.device))
-        o = torch.as_tensor(obs).to(**f64).contiguous()
-        w = None if weights is None else torch.as_tensor(weights).to(**f64).contiguous()
-        res = {"x": torch.empty((M, n), **f64), "cost": torch.empty((M,), **f64), "cost0": torch.empty((M,), **f64),
-               "std": torch.empty((M, n), **f64), "n_accept": torch.empty((M,), dtype=torch.int32, device=self.device),
-               "y": torch.empty((M, V, nb), **f64)}
-        opt = _lib.SpartRefineViewsOpt(V=V, n_shared=Fs, band_model=int(srf))
-        opt.fit = _lib.SpartRefineOpt(column=plan["column"], n_iter=plan["n_iter"], weights_per_obs=wper,
-                                      fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"],
-                                      lambda0=plan["lambda0"])
-        if prior_mean is not None:
-            pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in (prior_mean, prior_weight))
-            opt.fit.prior_per_obs, opt.fit.prior_mean, opt.fit.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
-        nbytes = max(int(self.lib.spart_views_workspace_bytes(self.ctx, M, V, F, Fs)), 256)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.calls["spart_refine_views"] += 1
-        rc = self.lib.spart_refine_views(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                         _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr(), w.data_ptr() if w is not None else None,
-                                         ctypes.byref(opt), *[res[k].data_ptr() for k in ("x", "cost", "cost0", "std", "n_accept", "y")],
-                                         ws.data_ptr(), nbytes, self._stream())
-        _lib.check(self.lib, self.ctx, rc)
+        res = self._fit_outputs(M, n, (M, V, nb))
+        self._refine_device("spart_refine_views", plan, M, cols, obs, weights, wper, lidf, nl, (prior_mean, prior_weight, per_obs),
+                            [res[k].data_ptr() for k in _FIT_OUTS], views=(V, Fs, srf))
         for k, src in (("shared", "x"), ("shared_std", "std")):
             res[k] = res[src][:, :Fs]
         for k, src in (("local", "x"), ("local_std", "std")):

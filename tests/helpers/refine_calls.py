@@ -45,9 +45,10 @@ def cols_of(names):
 
 
 def refine_call(torch, eng, base, free, lo, hi, obs, w=None, column=0, n_iter=3, rel_step=0.0, lambda0=0.0, null=(), ws_bytes=None,
-                guard=False, M=None, F=None, ctx="own", nlayers=0, fast_prelude=0):
-    """One spart_refine through ctypes -> (rc, dict of numpy outputs).  Every output is pre-filled with FILL; ``null``: names
-    of base / free / lo / hi / obs / opt / the outputs to pass as NULL; ``M`` / ``F``: sizes to pass in place of the arrays' own;
+                guard=False, M=None, F=None, ctx="own", nlayers=0, fast_prelude=0, entry="spart_refine"):
+    """One ``entry`` (spart_refine / spart_refine_srf) through ctypes -> (rc, dict of numpy outputs).  Every output is pre-filled
+    with FILL; ``null``: names of base / free / lo / hi / obs / opt / ws / the outputs to pass as NULL, "base[i]" for one NULL
+    column; ``M`` / ``F``: sizes to pass in place of the arrays' own;
     ``ws_bytes``: the workspace size handed in; ``guard``: GUARD bytes of 0xFF behind a correctly sized workspace must survive."""
     from spart_amd import _lib
     dev = eng.device
@@ -74,12 +75,12 @@ def refine_call(torch, eng, base, free, lo, hi, obs, w=None, column=0, n_iter=3,
     fc = np.array(free, dtype=np.int32)
     lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
     ptr = lambda name, v: None if name in null else v     # noqa: E731
-    rc = eng.lib.spart_refine(c, Mx, ptr("base", (_lib.vp * 27)(*[Bt[i].data_ptr() for i in range(27)])), Fx,
-                              ptr("free", fc.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
-                              ptr("lo", lo.ctypes.data_as(_lib.c_dp)), ptr("hi", hi.ctypes.data_as(_lib.c_dp)),
-                              ptr("obs", ot.data_ptr()), None if wt is None else wt.data_ptr(), ptr("opt", ctypes.byref(opt)),
-                              *[ptr(k, out[k].data_ptr()) for k in OUTS], ptr("ws", ws.data_ptr()), ctypes.c_size_t(n),
-                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    rc = getattr(eng.lib, entry)(c, Mx, ptr("base", (_lib.vp * 27)(*[ptr(f"base[{i}]", Bt[i].data_ptr()) for i in range(27)])), Fx,
+                                 ptr("free", fc.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                                 ptr("lo", lo.ctypes.data_as(_lib.c_dp)), ptr("hi", hi.ctypes.data_as(_lib.c_dp)),
+                                 ptr("obs", ot.data_ptr()), None if wt is None else wt.data_ptr(), ptr("opt", ctypes.byref(opt)),
+                                 *[ptr(k, out[k].data_ptr()) for k in OUTS], ptr("ws", ws.data_ptr()), ctypes.c_size_t(n),
+                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     torch.cuda.synchronize()
     if guard:
         assert bool((ws[need:] == 0xFF).all()), "bytes behind the workspace were written"

@@ -184,6 +184,27 @@ def test_refusals_leave_outputs_and_guard_untouched(torch_mod, engines):
     assert rc == 0 and all(same(got[k], ref[k]) for k in OUTS)
 
 
+@pytest.mark.parametrize("entry", ["spart_refine", "spart_refine_srf"])
+def test_the_first_refusal_wins(torch_mod, engines, entry):
+    """calls with two faults: the one that is checked first is the one reported, and nothing is written"""
+    from spart_amd import get_engine
+    eng = engines["s2"]
+    base, free, lo, hi, obs, w = make_case(torch_mod, eng, ["LAI", "Cab", "Cw"], 9, "R_TOC", "per_observation", 4)
+    INVALID = -1
+    bare = get_engine(None, 0).ctx
+    for kw, want, text in [(dict(F=17, null=("free",)), INVALID, "F = 17, expected"),
+                           (dict(M=-1, F=0), INVALID, "M = -1, expected"),
+                           (dict(column=3, ctx=bare), INVALID, "column = 3"),
+                           (dict(n_iter=101, null=("obs",)), INVALID, "n_iter = 101"),
+                           (dict(M=0, null=("obs", "x", "cost", "ws")), 0, None),
+                           (dict(null=("base[3]", "obs")), INVALID, "base[3] is null"),
+                           (dict(null=("obs", "ws")), INVALID, "null argument (obs, x and cost are required)")]:
+        rc, got = refine_call(torch_mod, eng, base, free, lo, hi, obs, w, entry=entry, **kw)
+        msg = eng.lib.spart_last_error(eng.ctx).decode()
+        assert rc == want and (text is None or msg.startswith(f"{entry}: {text}")), (kw, rc, msg)
+        assert all((got[k] == FILL).all() for k in OUTS), kw
+
+
 def test_refine_example_runs(tmp_path):
     """examples/refine.py as a user runs it: its own process, exit code 0, the expected last line"""
     import subprocess

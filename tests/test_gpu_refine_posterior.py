@@ -228,6 +228,24 @@ def test_refusals_leave_every_output_untouched(torch_mod, engines):
     assert rc == 0 and not untouched(got) and (got["status"] == 0).all()
 
 
+def test_the_first_refusal_wins(torch_mod, engines):
+    """calls with two faults: the one that is checked first is the one reported, and nothing is written"""
+    from spart_amd import get_engine, workloads
+    eng, bare = engines[S2], get_engine(None, 0)
+    free, (lo, hi) = cols_of(FREE[2]), bounds_of(FREE[2])
+    base, obs = workloads.lhs_params(8, "full", seed=3), np.full((8, 13), 0.2)
+    for e, kw, text in [(eng, dict(F=17, null=("free",)), "F = 17, expected"),
+                        (eng, dict(M=-1, F=0), "M = -1, expected"),
+                        (eng, dict(band_model=2, n_iter=101), "n_iter = 101"),
+                        (bare, dict(outputs=(), nb=13, ws_bytes=1 << 20), "every output is null")]:
+        rc, got = posterior_call(torch_mod, e, base, free, lo, hi, obs, **kw)
+        msg = e.lib.spart_last_error(e.ctx).decode()
+        assert rc == -1 and msg.startswith(f"spart_refine_posterior: {text}"), (kw, rc, msg)
+        assert untouched(got), kw
+    rc, got = posterior_call(torch_mod, eng, base, free, lo, hi, None)                               # obs is optional here
+    assert rc == 0 and not untouched(got) and (got["status"] == 0).all()
+
+
 def test_engine_posterior_jacobian_and_refine(torch_mod, engines):
     import spart_amd
     eng, F, M = engines[S2], 6, 70

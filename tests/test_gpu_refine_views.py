@@ -174,6 +174,36 @@ def test_refusals_leave_outputs_untouched(torch_mod, engines):
     assert size(v=64, f=16, fs=16) > 0 and size(v=16, f=1, fs=0) > 0 and size(v=1, f=16, fs=0) > 0 and size(v=64, f=1, fs=1) > 0
 
 
+def test_the_first_refusal_wins(torch_mod, engines):
+    """calls with two faults: the one that is checked first is the one reported, and nothing is written"""
+    eng = engines["s2"]
+    case = make_views_case(torch_mod, eng, ["LAI", "Cab"], ["aot550"], 9, 3, "R_TOC", "per_pixel", "none", 2)
+    a = (case["base"], case["shared"], case["local"], case["lo"], case["hi"], case["obs"], case["w"])
+    twice = (case["base"], case["shared"], case["shared"][:1], case["lo"], case["hi"], case["obs"], case["w"])     # F = 3, column 0 twice
+    for args, kw, text in [(a, dict(F=17, null=("free",)), "F = 17, expected"),
+                           (a, dict(M=-1, F=0), "M = -1, expected"),
+                           (a, dict(V=0, column=3), "V = 0, expected"),
+                           (a, dict(band_model=2, n_iter=101), "band_model = 2"),
+                           (twice, dict(n_shared=4), "n_shared = 4, expected")]:
+        rc, got = views_call(torch_mod, eng, *args, **kw)
+        msg = eng.lib.spart_last_error(eng.ctx).decode()
+        assert rc == -1 and msg.startswith(f"spart_refine_views: {text}"), (kw, rc, msg)
+        assert all((got[k] == FILL).all() for k in OUTS), kw
+
+
+@pytest.mark.parametrize("sensor", ["s2", "hyper"])
+def test_one_view_is_sized_like_spart_refine(engines, sensor):
+    """V = 1 carves spart_refine's workspace: the same bytes for every M around the chunk and for either n_shared"""
+    eng = engines[sensor]
+    for F in (1, 7, 16):
+        c = (1 << 19) // (F + 1)
+        for M in (1, c - 1, c, c + 1, 2_000_000_000):
+            one = int(eng.lib.spart_refine_workspace_bytes(eng.ctx, M, F))
+            assert one > 0, (F, M)
+            for n_shared in (F, 0):
+                assert int(eng.lib.spart_views_workspace_bytes(eng.ctx, M, 1, F, n_shared)) == one, (F, M, n_shared)
+
+
 def test_refine_views_example_runs():
     """examples/refine_views.py as a user runs it: its own process, exit code 0, the expected last line"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "refine_views.py"), "256"], capture_output=True, text=True, timeout=600)
