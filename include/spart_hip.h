@@ -67,7 +67,8 @@ extern "C" {
  * spart_refine_srf was added WITHOUT a new number: it is one more symbol, no struct layout or argument list changed, so every
  * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library.
  * spart_refine_views, spart_views_workspace_bytes and spart_refine_views_opt were added by the same rule: new symbols
- * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise. */
+ * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise, and
+ * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -364,6 +365,68 @@ int spart_lut_topk_obs_weights(spart_ctx *ctx, int dtype, int64_t B, int nb, con
  * Nbound_m = sum_j w[m,j] max_b (lut[b,j] - centre_j)^2, the scale of the rounding bound. */
 int spart_lut_topk_obs_weights_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, int k, const void *workspace,
                                      int64_t *n_brute_force, int64_t *n_candidates, int64_t *max_candidates, double *nbound);
+
+/* The likelihood-weighted (Bayesian / GLUE) LUT estimate: what the LUT AS A WHOLE says about an observation given its noise
+ * (no reference counterpart).  Every row b within `cut` of the best one gets the weight exp(-chi^2_b / 2); the outputs are the
+ * weighted mean and spread of the parameter rows and the effective sample size, the one number that tells whether the LUT is
+ * dense enough for the noise level.  lut (B, nb), obs and weights (M, nb) in `dtype`; weights is required; params (B, P)
+ * float64 row-major; all device memory.  T is the dtype.
+ * Definition, per observation m.  The cost c_T(b, m), the row acceptance rule and the observation validity rule are
+ * spart_lut_topk_obs_weights', word for word: the cost is evaluated in T with every operation rounded and no FMA, a band of
+ * weight exactly zero is skipped (obs may be NaN or inf there), a row with a non-finite entry or an overflowing unweighted
+ * centred norm is never accepted, and an observation with a negative, NaN or infinite weight, or a non-finite value in a band of
+ * non-zero weight, is invalid.
+ *   E          the accepted rows with a finite c_T.  If the observation is invalid or E is empty: count 0, best_idx -1,
+ *              best_cost +inf, sum_w 0, ess / mean / std NaN.
+ *   c*         the minimum of c_T over E; best_idx the lowest row attaining it.  best_idx and best_cost equal
+ *              spart_lut_topk_obs_weights(k = 1) bit for bit.
+ *   e_b        (double)c_T(b) - (double)c*
+ *   S          {b in E : e_b <= cut}, taken in ascending row order; count = |S|
+ *   omega_b    exp(-(e_b / (2 tau))) in float64, tau the temperature; 2 tau is formed first, the division is IEEE, the
+ *              exponential is the library's (relative error <= 3e-16; exactly 1 at e_b = 0)
+ *   sums       float64, sequential over S ascending from 0, no FMA contraction:
+ *              sum_w  = sum omega_b
+ *              s2     = sum omega_b omega_b,        ess = (sum_w * sum_w) / s2
+ *              mean_p = (sum (omega_b x_bp)) / sum_w,               x_bp = params[b, p]
+ *              var_p  = (sum ((omega_b d) d)) / sum_w with d = x_bp - mean_p,     std_p = sqrt(var_p)
+ * Consequences:
+ *   - cut = 0 and a unique minimum: count = 1, ess = 1, std = 0 and mean = params[best_idx] exactly.
+ *   - all weights of an observation zero and cut >= 0: S is every accepted row and omega = 1; mean and std are then
+ *     spart_lut_summarise's sums over all accepted rows in order.
+ *   - the result is the same bit for bit with brute_force 0 or 1, whatever else is in the batch, and whichever chunk the
+ *     observation falls in.
+ * Refused before anything is launched or written, SPART_ERR_INVALID: a dtype outside 0 / 1; nb outside 1 ... SPART_NWLS; P
+ * outside 1 ... 64; B or M < 0 or > 2e9; a NULL opt or out; a NaN or negative cut; a negative, NaN or infinite temperature;
+ * brute_force outside 0 / 1; with M > 0 all seven outputs NULL (the outputs of an empty batch have no address); with M > 0
+ * and B > 0 a NULL lut, params, obs or weights.
+ * SPART_ERR_WORKSPACE as for the searches.  M = 0 launches nothing; B = 0 with M > 0 launches no search and writes the
+ * empty-observation outputs (no workspace needed).  spart_lut_bayes_workspace_bytes is 0 exactly for the sizes the call
+ * refuses or has no search for (B = 0, M = 0); past the first chunk of observations it grows by 4 bytes per observation (the
+ * flag list), like the searches'.
+ * How (csrc/spart_lut.h, "likelihood-weighted posterior", derives the threshold): the per-observation-weights filter on the
+ * matrix cores with the radius threshold U + cut + Delta(cut) in place of the top-k one, at most 1088 candidate tiles per
+ * observation; one wave per observation then sorts its tiles and runs three passes over their rows (minimum; weights and
+ * first moments; second moments).  An observation whose candidate list overflows, whose threshold is not finite (cut = +inf),
+ * or any observation under brute_force = 1, takes the same three passes over every row of the LUT. */
+typedef struct spart_lut_bayes_opt {
+  double cut;          /* >= 0 or +inf: rows with e_b <= cut take part */
+  double temperature;  /* 0 = 1.0; else finite > 0 */
+  int32_t brute_force; /* 0 auto; 1: every observation by the brute-force kernel (same result bit for bit) */
+} spart_lut_bayes_opt;
+typedef struct spart_lut_bayes_out { /* device memory, each may be NULL, not all */
+  double *mean, *std;                /* (M, P) */
+  double *sum_w, *ess;               /* (M,)   */
+  int64_t *count, *best_idx;         /* (M,)   */
+  void *best_cost;                   /* (M,) in dtype */
+} spart_lut_bayes_out;
+size_t spart_lut_bayes_workspace_bytes(int dtype, int64_t B, int nb, int64_t M);
+int spart_lut_bayes(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut, int P, const double *params, int64_t M,
+                    const void *obs, const void *weights, const spart_lut_bayes_opt *opt, const spart_lut_bayes_out *out,
+                    void *workspace, size_t workspace_bytes, void *stream);
+/* Diagnostics of the LAST spart_lut_bayes call that used `workspace` (same dtype, B, nb, M), as
+ * spart_lut_topk_obs_weights_stats: brute-forced observations, candidate tiles (sum and maximum) and the largest Nbound_m. */
+int spart_lut_bayes_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, const void *workspace, int64_t *n_brute_force,
+                          int64_t *n_candidates, int64_t *max_candidates, double *nbound);
 
 /* Parameter summaries of the rows a top-k search selected (what a LUT retrieval reports: maps of LAI, Cab, ... with a spread;
  * no reference counterpart).  params (B, P) float64 row-major, the LUT's parameter table; idx (M, k) int64, the output of any

@@ -782,12 +782,39 @@ static LutWideLayout lut_wide_layout(int dtype, int64_t B, int nb, int64_t M, in
   return L;
 }
 
-// OBSW: per-observation weights (csrc/spart_lut.h, "per-observation weights") -- the same pipeline with K = 2 nbp: its own
-// observation pass, GEMM and bound, a per-band pass k_lutow_q before the chunks, and the select's OBSW flag.
+// The exact top-k over the candidate rows (brute = false: the chunk m0 .. m0 + mc) and over every row for the flagged
+// observations (brute = true, after the last chunk): the consumer of lut_wide_impl for the two wide top-k searches
 template <typename T, bool OBSW>
-static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int k,
-                         int64_t* idx, void* cost, char* wsp, hipStream_t st) {
-  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, k, OBSW);
+static auto lutw_topk_consumer(const T* lut, const T* obs, const T* w, int nb, int64_t B, int64_t M, int k, int64_t* idx, void* cost) {
+  return [=](bool brute, int64_t m0, int64_t mc, const LutWideLayout& L, char* wsp, hipStream_t st) {
+    constexpr int ROWS = LutWide<T>::ROWS;
+    const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
+    unsigned long long* ctl = (unsigned long long*)(wsp + L.ctl);
+    int* flags = (int*)(wsp + L.flags);
+    const T* norm = (const T*)(wsp + L.norm);
+    if (!brute)
+      hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, OBSW>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
+                         k, (const T*)(wsp + L.thr), (const int*)(wsp + L.cn), (const int*)(wsp + L.cand), L.cap, ctl, flags, idx,
+                         (T*)cost, norm);
+    else   // (fixed grid; the kernel reads the count on the device)
+      hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, OBSW>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
+                         (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx,
+                         (T*)cost, norm);
+    return SPART_OK;
+  };
+}
+
+// OBSW: per-observation weights (csrc/spart_lut.h, "per-observation weights") -- the same pipeline with K = 2 nbp: its own
+// observation pass, GEMM and bound, a per-band pass k_lutow_q before the chunks, and the consumer's OBSW flag.
+// kcap sizes the layout (the candidate capacity is lut_topk_cap(kcap) tiles); U is the kth smallest partial value and the
+// threshold admits every row within `cut` of the kth best (OBSW only; the top-k searches pass kcap = kth = k and cut = 0.0).
+// filter = false queues the row pass only (centres and norms), no GEMM: a consumer that flags every observation itself.
+// consume(brute, m0, mc, layout, workspace, stream) queues what reads the candidate lists: once per chunk with brute =
+// false, and once after the last chunk with brute = true for the flagged observations of every chunk.
+template <typename T, bool OBSW, typename Consume>
+static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t M, const void* obs_, const void* weights, int kcap,
+                         int kth, double cut, bool filter, char* wsp, hipStream_t st, Consume&& consume) {
+  const LutWideLayout L = lut_wide_layout(dtype, B, nb, M, kcap, OBSW);
   constexpr int ROWS = LutWide<T>::ROWS;
   constexpr int OWG = 2 * LUTW_TB * ROWS;
   constexpr auto gemm_scan = OBSW ? k_lutow_gemm<T, false> : k_lutw_gemm<T, false>;
@@ -803,7 +830,6 @@ static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
   T* thr = (T*)(wsp + L.thr);
   int* cn = (int*)(wsp + L.cn);
   int* cand = (int*)(wsp + L.cand);
-  int* flags = (int*)(wsp + L.flags);
   unsigned long long* qb = (unsigned long long*)(wsp + L.q);       // OBSW only: the per-band Q_j
   // the coefficients of Delta (spart_lut.h, wide top-k and per-observation weights), with the 1 % slack
   const double u = (double)LutNum<T>::u;
@@ -820,41 +846,71 @@ static int lut_wide_impl(int dtype, int64_t B, int nb, const void* lut_, int64_t
                      (const T*)centre, nb, B, norm, ctl + (OBSW ? LUT_TOPK_CTL_WORDS : 0));
   HIP_TRY(hipGetLastError());
   if constexpr (OBSW) {
-    const int64_t qy = (B + 3) / 4;
-    hipLaunchKernelGGL((k_lutow_q<T>), dim3((unsigned)((nb + 63) / 64), (unsigned)(qy < 1024 ? qy : 1024)), dim3(256), 0, st, lut,
-                       (const T*)norm, (const T*)centre, nb, B, qb);
-    HIP_TRY(hipGetLastError());
+    if (filter) {
+      const int64_t qy = (B + 3) / 4;
+      hipLaunchKernelGGL((k_lutow_q<T>), dim3((unsigned)((nb + 63) / 64), (unsigned)(qy < 1024 ? qy : 1024)), dim3(256), 0, st, lut,
+                         (const T*)norm, (const T*)centre, nb, B, qb);
+      HIP_TRY(hipGetLastError());
+    }
   }
-  const size_t sel_lds = (size_t)LUT_TOPK_BUF * 12 + 2 * (size_t)nb * sizeof(T);
   for (int64_t m0 = 0; m0 < M; m0 += L.mc) {
     const int64_t mc = M - m0 < L.mc ? M - m0 : L.mc;
     const T* ob = obs + m0 * nb;
     const unsigned gx = (unsigned)((mc + OWG - 1) / OWG), gobs = (unsigned)((mc + 3) / 4);
-    if constexpr (OBSW)
-      hipLaunchKernelGGL((k_lutow_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w + m0 * nb, (const T*)centre,
-                         (const unsigned long long*)qb, nb, L.nbp, mc, bq, (double*)ya, ctl);
-    else
-      hipLaunchKernelGGL((k_lutw_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w, (const T*)centre, nb, L.nbp, mc, bq, (T*)ya);
-    hipLaunchKernelGGL(gemm_scan, dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
-                       (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr, (int*)nullptr);
-    if constexpr (OBSW)
-      hipLaunchKernelGGL((k_lutow_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const double*)ya, nb, mc,
-                         L.npart, k, ce, cf, thr, cn);
-    else
-      hipLaunchKernelGGL((k_lutw_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const T*)ya, w, nb, mc,
-                         L.npart, k, ce, cf, cw, (const unsigned long long*)ctl, thr, cn);
-    hipLaunchKernelGGL(gemm_collect, dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
-                       (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap, cn, cand);
-    hipLaunchKernelGGL((k_lutw_select<T, ROWS, false, OBSW>), dim3((unsigned)mc), dim3(64), sel_lds, st, lut, obs, w, nb, B, m0, mc,
-                       k, (const T*)thr, (const int*)cn, (const int*)cand, L.cap, ctl, flags, idx, (T*)cost, (const T*)norm);
+    if (filter) {
+      if constexpr (OBSW)
+        hipLaunchKernelGGL((k_lutow_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w + m0 * nb, (const T*)centre,
+                           (const unsigned long long*)qb, nb, L.nbp, mc, bq, (double*)ya, ctl);
+      else
+        hipLaunchKernelGGL((k_lutw_obs<T>), dim3(gobs), dim3(256), 0, st, ob, w, (const T*)centre, nb, L.nbp, mc, bq, (T*)ya);
+      hipLaunchKernelGGL(gemm_scan, dim3(gx, (unsigned)L.nslice), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
+                         (const T*)bq, L.nbp, mc, L.nslice, pc, ps, (const T*)nullptr, 0, (int*)nullptr, (int*)nullptr);
+      if constexpr (OBSW)
+        hipLaunchKernelGGL((k_lutow_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const double*)ya, nb, mc,
+                           L.npart, kth, ce, cf, cut, thr, cn);
+      else
+        hipLaunchKernelGGL((k_lutw_bound<T>), dim3(gobs), dim3(256), 0, st, (const T*)pc, (const T*)ps, (const T*)ya, w, nb, mc,
+                           L.npart, kth, ce, cf, cw, (const unsigned long long*)ctl, thr, cn);
+      hipLaunchKernelGGL(gemm_collect, dim3(gx, (unsigned)L.nslice2), dim3(256), 0, st, lut, (const T*)norm, (const T*)centre, nb, B,
+                         (const T*)bq, L.nbp, mc, L.nslice2, (T*)nullptr, (T*)nullptr, (const T*)thr, L.cap, cn, cand);
+    }
+    const int rc = consume(false, m0, mc, L, wsp, st);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
   }
-  // the flagged observations of every chunk (fixed grid; the kernel reads the count on the device)
-  hipLaunchKernelGGL((k_lutw_select<T, ROWS, true, OBSW>), dim3(LUTW_SELECT_BLOCKS), dim3(64), sel_lds, st, lut, obs, w, nb, B,
-                     (int64_t)0, M, k, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr, L.cap, ctl, flags, idx, (T*)cost,
-                     (const T*)norm);
+  const int rc = consume(true, (int64_t)0, M, L, wsp, st);             // the flagged observations of every chunk
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SPART_OK;
+}
+
+// spart_lut_bayes once its arguments are checked (csrc/spart_lut.h, "likelihood-weighted posterior"): the per-observation-
+// weights pipeline with k = 1 and the radius threshold, k_lut_bayes as its consumer.  opt->brute_force skips the filter.
+template <typename T>
+static int lut_bayes_impl(int dtype, int64_t B, int nb, const void* lut_, int P, const double* params, int64_t M, const void* obs_,
+                          const void* weights, const spart_lut_bayes_opt& opt, const LutBayesOut& out, char* wsp, hipStream_t st) {
+  constexpr int ROWS = LutWide<T>::ROWS;
+  const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
+  const double two_tau = 2.0 * (opt.temperature == 0.0 ? 1.0 : opt.temperature);
+  const double cut = opt.cut;
+  const int force = opt.brute_force;
+  const size_t lds = lut_bayes_lds_bytes(nb, sizeof(T));
+  return lut_wide_impl<T, true>(
+      dtype, B, nb, lut_, M, obs_, weights, LUT_BAYES_CAPK, 1, cut * (1.0 + 0x1p-50), force == 0, wsp, st,
+      [=](bool brute, int64_t m0, int64_t mc, const LutWideLayout& L, char* ws, hipStream_t s) {
+        unsigned long long* ctl = (unsigned long long*)(ws + L.ctl);
+        int* flags = (int*)(ws + L.flags);
+        const T* norm = (const T*)(ws + L.norm);
+        if (!brute)
+          hipLaunchKernelGGL((k_lut_bayes<T, ROWS, false>), dim3((unsigned)mc), dim3(64), lds, s, lut, obs, w, norm, params, nb, B, P,
+                             m0, mc, cut, two_tau, force, (const T*)(ws + L.thr), (const int*)(ws + L.cn),
+                             (const int*)(ws + L.cand), L.cap, ctl, flags, out);
+        else
+          hipLaunchKernelGGL((k_lut_bayes<T, ROWS, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), lds, s, lut, obs, w, norm, params, nb,
+                             B, P, (int64_t)0, M, cut, two_tau, force, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                             L.cap, ctl, flags, out);
+        return SPART_OK;
+      });
 }
 
 // The checks every batched entry point over B samples starts with, in this order (the LUT searches have lut_search's).
@@ -1811,7 +1867,10 @@ int spart_lut_topk_wide(spart_ctx* ctx, int dtype, int64_t B, int nb, const void
                         void* stream) {
   return lut_search(ctx, LUT_WIDE, dtype, B, nb, lut, M, obs, weights, k, idx, cost, workspace, workspace_bytes,
                     spart_lut_topk_wide_workspace_bytes(dtype, B, nb, M, k), stream, [&](auto t, char* wsp, hipStream_t st) {
-                      return lut_wide_impl<decltype(t), false>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, wsp, st);
+                      using T = decltype(t);
+                      return lut_wide_impl<T, false>(dtype, B, nb, lut, M, obs, weights, k, k, 0.0, true, wsp, st,
+                                                    lutw_topk_consumer<T, false>((const T*)lut, (const T*)obs, (const T*)weights,
+                                                                                nb, B, M, k, idx, cost));
                     });
 }
 
@@ -1832,7 +1891,10 @@ int spart_lut_topk_obs_weights(spart_ctx* ctx, int dtype, int64_t B, int nb, con
                                void* stream) {
   return lut_search(ctx, LUT_OBSW, dtype, B, nb, lut, M, obs, weights, k, idx, cost, workspace, workspace_bytes,
                     spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k), stream, [&](auto t, char* wsp, hipStream_t st) {
-                      return lut_wide_impl<decltype(t), true>(dtype, B, nb, lut, M, obs, weights, k, idx, cost, wsp, st);
+                      using T = decltype(t);
+                      return lut_wide_impl<T, true>(dtype, B, nb, lut, M, obs, weights, k, k, 0.0, true, wsp, st,
+                                                    lutw_topk_consumer<T, true>((const T*)lut, (const T*)obs, (const T*)weights,
+                                                                                nb, B, M, k, idx, cost));
                     });
 }
 
@@ -1842,6 +1904,61 @@ int spart_lut_topk_obs_weights_stats(spart_ctx* ctx, int dtype, int64_t B, int n
   return lut_read_stats(ctx, "spart_lut_topk_obs_weights_stats", dtype, workspace,
                         spart_lut_topk_obs_weights_workspace_bytes(dtype, B, nb, M, k) != 0,
                         [&] { return lut_wide_layout(dtype, B, nb, M, k, true).ctl; }, counts, 3, nbound);
+}
+
+// The posterior shares the per-observation-weights layout of a k = LUT_BAYES_CAPK search: same chunks, same flag list.
+static bool lut_bayes_sizes_ok(int dtype, int64_t B, int nb, int64_t M) {
+  return lut_sizes_ok(LUT_OBSW, dtype, B, nb, M, LUT_BAYES_CAPK) && B <= 2000000000LL && M <= 2000000000LL;
+}
+
+size_t spart_lut_bayes_workspace_bytes(int dtype, int64_t B, int nb, int64_t M) {
+  return lut_bayes_sizes_ok(dtype, B, nb, M) ? lut_wide_layout(dtype, B, nb, M, LUT_BAYES_CAPK, true).total : 0;
+}
+
+// (lut_search's checks and order, with the parameter table, the options and the output struct; an empty LUT is an answer here)
+int spart_lut_bayes(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int P, const double* params, int64_t M,
+                    const void* obs, const void* weights, const spart_lut_bayes_opt* opt, const spart_lut_bayes_out* out,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_lut_bayes";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (!dtype_ok(dtype)) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  if (B < 0 || M < 0 || !LUT_OBSW.nb_ok(nb) || P < 1 || P > LUT_BAYES_MAXP || B > 2000000000LL || M > 2000000000LL)
+    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d P=%d; 1 <= nb <= %d, 1 <= P <= %d, B and M <= 2e9)", who,
+                (long long)B, (long long)M, nb, P, LUT_OBSW.nb_max, LUT_BAYES_MAXP);
+  if (!opt || !out) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  if (!(opt->cut >= 0.0)) return fail(SPART_ERR_INVALID, "%s: cut = %g, expected >= 0 (or +inf)", who, opt->cut);
+  if (!(opt->temperature >= 0.0) || std::isinf(opt->temperature))
+    return fail(SPART_ERR_INVALID, "%s: temperature = %g, expected 0 (= 1.0) or finite > 0", who, opt->temperature);
+  if (opt->brute_force != 0 && opt->brute_force != 1)
+    return fail(SPART_ERR_INVALID, "%s: brute_force = %d, expected 0 or 1", who, opt->brute_force);
+  if (M == 0) return SPART_OK;                         // (the (0,) outputs of an empty batch have no address)
+  if (!out->mean && !out->std && !out->sum_w && !out->ess && !out->count && !out->best_idx && !out->best_cost)
+    return fail(SPART_ERR_INVALID, "%s: every output is NULL", who);
+  const LutBayesOut o = {out->mean, out->std, out->sum_w, out->ess, out->count, out->best_idx, out->best_cost};
+  if (B == 0)                                          // no row: every observation gets the empty outputs
+    return guarded(ctx, who, nullptr, 0, stream, [&](hipStream_t st) {
+      return by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_lut_bayes_empty<decltype(t)>), dim3((unsigned)(M < 65536 ? M : 65536)), dim3(64), 0, st, M, P, o);
+        HIP_TRY(hipGetLastError());
+        return SPART_OK;
+      });
+    });
+  if (!lut || !params || !obs || !weights) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  const size_t need = spart_lut_bayes_workspace_bytes(dtype, B, nb, M);
+  if (!workspace || workspace_bytes < need)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) {
+      return lut_bayes_impl<decltype(t)>(dtype, B, nb, lut, P, params, M, obs, weights, *opt, o, (char*)workspace, st);
+    });
+  });
+}
+
+int spart_lut_bayes_stats(spart_ctx* ctx, int dtype, int64_t B, int nb, int64_t M, const void* workspace, int64_t* n_brute_force,
+                          int64_t* n_candidates, int64_t* max_candidates, double* nbound) {
+  int64_t* const counts[] = {n_brute_force, n_candidates, max_candidates};
+  return lut_read_stats(ctx, "spart_lut_bayes_stats", dtype, workspace, spart_lut_bayes_workspace_bytes(dtype, B, nb, M) != 0,
+                        [&] { return lut_wide_layout(dtype, B, nb, M, LUT_BAYES_CAPK, true).ctl; }, counts, 3, nbound);
 }
 
 // (the argument checks of lut_search, in its order, for a call without dtype, bands and workspace)

@@ -1720,11 +1720,13 @@ __global__ __launch_bounds__(256) void k_lutow_gemm(const T* __restrict__ lut, c
   }
 }
 
-// one wave per observation of the chunk: thr = U + Delta (ce, cf with the 1 % slack), resets the candidate count
+// one wave per observation of the chunk: thr = U + cut + Delta(cut) (ce, cf with the 1 % slack), resets the candidate count.
+// cut = 0.0 is the top-k rule above, operation for operation (x + 0.0 == x for every x >= 0 and every NaN); cut > 0 is the
+// radius rule of spart_lut_bayes ("likelihood-weighted posterior" below, which derives it); cut = +inf gives thr = +inf
 template <typename T>
 __global__ __launch_bounds__(256) void k_lutow_bound(const T* __restrict__ part_cost, const T* __restrict__ part_sec,
                                                      const double* __restrict__ yn, int nb, int64_t M, int npart, int k, double ce,
-                                                     double cf, T* __restrict__ thr, int* __restrict__ cand_n) {
+                                                     double cf, double cut, T* __restrict__ thr, int* __restrict__ cand_n) {
   const int lane = threadIdx.x & 63;
   const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;                                  // (whole wave)
@@ -1734,15 +1736,15 @@ __global__ __launch_bounds__(256) void k_lutow_bound(const T* __restrict__ part_
     const double big = sizeof(T) == 4 ? 3.4028234663852886e38 : 1.7976931348623157e308;
     const double u = (double)LutNum<T>::u, f = (nb + 3.0) * u, grow = 1.01 * (1.0 + f) / (1.0 - f);
     double N = nq, C = 0.0;
-    for (int it = 0; it < 3; ++it) {                   // C(N_0), N_1, C(N_1), N_2, C(N_2)
+    for (int it = 0; it < 3; ++it) {                   // C(N_0), N_1, C(N_1), N_2, C(N_2); C carries + cut
       C = (double)U + Y + ce * (N + Y);
-      C = C > 0.0 ? C : 0.0;
+      C = (C > 0.0 ? C : 0.0) + cut;
       if (it == 2) break;
       const double s = __builtin_sqrt(Y) + __builtin_sqrt(C * grow + 4.04 * u * (N + Y));
       const double ns = 1.01 * s * s;
       N = ns < N ? ns : N;
     }
-    double t = (double)U + (2.0 * ce * (N + Y) + cf * C);
+    double t = (double)U + ((2.0 * ce * (N + Y) + cf * C) + cut);
     t = t + (4.0 * (double)LutNum<T>::u * __builtin_fabs(t) + (double)LutNum<T>::tiny);
     if (!(4.0 * (nq + Y) < big)) t = __builtin_nan("");   // (NaN Y: an observation the filter must not decide)
     T tt = (T)t;                                       // (NaN / inf stay non-finite: the select flags m)
@@ -1895,6 +1897,266 @@ __global__ __launch_bounds__(64) void k_lut_summarise(const double* __restrict__
         med = r1 == r2 ? s1 : (s1 + s2) / 2.0;
       }
       median[o] = med;
+    }
+  }
+}
+
+// ---- likelihood-weighted posterior (spart_lut_bayes): for observation m, over E = the accepted rows with a finite c_T(b, m)
+// (cost, row rule and observation rule of the per-observation-weights search above), c* = min c_T, e_b = (double)c_T(b) -
+// (double)c*, S = {b in E: e_b <= cut} in ascending row order, omega_b = exp(-(e_b / (2 tau))): count = |S|, sum_w, ess and the
+// omega-weighted mean and spread of the parameter rows, as include/spart_hip.h defines them (float64, ascending rows, no FMA).
+//
+// A radius query is the per-observation-weights pipeline with another threshold and another consumer:
+//   1-4.  k_lut_centre, k_lutw_norm (w = NULL), k_lutow_q, k_lutow_obs, k_lutow_gemm<false>: unchanged
+//   5.    k_lutow_bound with k = 1 and cut: U = the smallest partial value, thr = U + cut + Delta(cut) (below)
+//   6.    k_lutow_gemm<true>: the candidate tiles under thr, capacity lut_topk_cap(LUT_BAYES_CAPK) tiles per observation
+//   7.    k_lut_bayes<., ., false>: one wave per observation over the rows of its candidate tiles
+//   8.    k_lut_bayes<., ., true>: the same passes over EVERY row for the flagged observations
+//
+// The threshold.  a^1 is the row behind U, so a~(a^1) = U, and with (i)-(v) of the per-observation weights
+//     c* <= c_T(a^1) <= c(a^1) + F_a1 <= U + Y + E_a1 + F_a1.
+// b in S means fl64(c_T(b) - c*) <= cut.  The float64 subtraction of two values of T rounds once and rounding is monotone, so
+// c_T(b) - c* <= cut' = cut (1 + 2^-50) (what the host hands to k_lutow_bound as `cut`; 0 stays 0, +inf stays +inf).  Then
+//     a~(b) <= c(b) - Y + E_b <= c_T(b) + F_b - Y + E_b <= c* + cut' + F_b - Y + E_b <= U + cut' + (E_a1 + E_b) + (F_a1 + F_b).
+// The F terms: c(a^1) <= C(N) = max(U + Y + ce (N + Y), 0) as before, and c(b) <= c_T(b) / (1 - f) <= (c_T(a^1) + cut') / (1 - f)
+// <= (C(N) + cut') (1 + f) / (1 - f), f = (nb + 3) u; so F_a1 + F_b <= 2.01 f (C(N) + cut').  The N iteration bounds N_a1 and N_b
+// through sqrt(N_b) <= sqrt(Y) + sqrt(c'(b)) with c'(b) <= c(b) + 4 u (N + Y): the same step with C(N) + cut' in place of C(N)
+// (it bounds c(a^1) as well, cut' >= 0).  So
+//     thr = U + cut' + 2 ce (N_2 + Y) + cf (C(N_2) + cut'),
+// k_lutow_bound's expression with C + cut' for C, evaluated in float64 and rounded up to T.  cut = +inf gives thr = +inf, a
+// finite cut whose thr overflows T likewise: such observations are flagged for the brute force, as a non-finite threshold
+// always is.  If the rows of the candidate tiles hold no finite cost (the rows behind U overflowed in the direct evaluation) the
+// observation is flagged too.
+//
+// k_lut_bayes.  Single-wave workgroups; dynamic LDS = LUT_BAYES_SORT tile numbers, the observation and its weight row.
+//   sort    the collect pass appends candidate tiles in atomic order; a bitonic sort of the tile numbers (padded with INT_MAX to
+//           a power of two) makes the row order, and with it every sum, reproducible.  A tile is appended at most once.
+//   pass A  lanes over rows (64 per round, ascending with the lane): exact c_T, the wave minimum and its lowest row
+//   pass B  the same rows again; a ballot of e <= cut gives the included rows of the round, which are then taken one at a time
+//           in row order: omega and the row number come from the owning lane by a shuffle, lane p < P reads params[r P + p]
+//           (one coalesced row of P doubles) and adds omega, omega^2 and omega x to its own running sums
+//   pass C  the same for (omega d) d with d = x - mean
+//   The costs are recomputed in every pass (deterministic: one lane, one sequential loop), not cached: the candidate rows of
+//   one observation can be 34 816 values.  Traffic per pass and observation: rows x nb values of the LUT (a lane reads one row,
+//   as in k_lutw_select), and in passes B and C count x P doubles of the parameter table.
+//   Every row number is range-checked (0 <= r < B) and norm-checked before an address is formed from it.
+constexpr int LUT_BAYES_CAPK = LUT_TOPK_MAXK;         // the candidate capacity is that of a k = 256 search: 1088 tiles
+constexpr int LUT_BAYES_SORT = 2048;                  // tile numbers sorted in LDS: the power of two above the capacity
+constexpr int LUT_BAYES_MAXP = LUT_SUM_MAXP;
+static_assert(LUT_BAYES_SORT >= 4 * LUT_BAYES_CAPK + 64 && (LUT_BAYES_SORT & (LUT_BAYES_SORT - 1)) == 0,
+              "k_lut_bayes sorts a whole candidate list, padded to a power of two");
+static_assert(LUT_BAYES_MAXP <= 64, "k_lut_bayes: lane = parameter");
+
+struct LutBayesOut {                                  // spart_lut_bayes_out
+  double *mean, *sdev, *sum_w, *ess;
+  int64_t *count, *best_idx;
+  void* best_cost;
+};
+
+inline size_t lut_bayes_lds_bytes(int nb, size_t es) { return (size_t)LUT_BAYES_SORT * 4 + 2 * (size_t)nb * es; }
+
+// the outputs of an observation with an empty E, written by the whole wave
+template <typename T>
+__device__ __forceinline__ void lut_bayes_empty(const LutBayesOut& out, int64_t m, int P, int lane) {
+  const double qnan = __builtin_nan("");
+  if (lane < P) {
+    if (out.mean) out.mean[m * P + lane] = qnan;
+    if (out.sdev) out.sdev[m * P + lane] = qnan;
+  }
+  if (lane == 0) {
+    if (out.sum_w) out.sum_w[m] = 0.0;
+    if (out.ess) out.ess[m] = qnan;
+    if (out.count) out.count[m] = 0;
+    if (out.best_idx) out.best_idx[m] = -1;
+    if (out.best_cost) static_cast<T*>(out.best_cost)[m] = (T)INFINITY;
+  }
+}
+
+// B = 0: every observation is empty
+template <typename T>
+__global__ __launch_bounds__(64) void k_lut_bayes_empty(int64_t M, int P, LutBayesOut out) {
+  for (int64_t m = blockIdx.x; m < M; m += gridDim.x) lut_bayes_empty<T>(out, m, P, threadIdx.x);
+}
+
+// c_T(b, m) of the per-observation weights, operation for operation (k_lutw_select<., ., ., true>)
+template <typename T>
+__device__ __forceinline__ T lut_bayes_cost(const T* __restrict__ x, const T* ys, const T* wsm, int nb) {
+  SPART_NO_CONTRACT
+  T c = T(0);
+  for (int j = 0; j < nb; ++j) {
+    const T wj = wsm[j];
+    if (wj == T(0)) continue;                          // the mask: no operation at all
+    const T d = x[j] - ys[j];
+    c = c + (wj * d) * d;
+  }
+  return c;
+}
+
+template <typename T, int ROWS, bool BRUTE>
+__global__ __launch_bounds__(64) void k_lut_bayes(const T* __restrict__ lut, const T* __restrict__ obs, const T* __restrict__ w,
+                                                  const T* __restrict__ norm, const double* __restrict__ params, int nb, int64_t B,
+                                                  int P, int64_t m_off, int64_t Mc, double cut, double two_tau, int force,
+                                                  const T* __restrict__ thr, const int* __restrict__ cand_n,
+                                                  const int* __restrict__ cand, int cap, unsigned long long* __restrict__ ctl,
+                                                  int* __restrict__ flag_list, LutBayesOut out) {
+  SPART_NO_CONTRACT
+  extern __shared__ __attribute__((aligned(16))) char lutb_smem[];
+  int* tiles = reinterpret_cast<int*>(lutb_smem);
+  T* ys = reinterpret_cast<T*>(tiles + LUT_BAYES_SORT);
+  T* wsm = ys + nb;
+  const int lane = threadIdx.x & 63;
+  const unsigned count = BRUTE ? (unsigned)ctl[1] : 0u;
+  const int64_t nwork = BRUTE ? (int64_t)count : Mc;
+  const int64_t stride_w = BRUTE ? (int64_t)gridDim.x : nwork;
+  for (int64_t item = blockIdx.x; item < nwork; item += stride_w) {
+    const int64_t m = BRUTE ? (int64_t)flag_list[item] : m_off + item;
+    lut_wave_sync();                                   // (the previous item's reads of ys / tiles are done)
+    bool fin = true;
+    for (int j = lane; j < nb; j += 64) {
+      const T v = obs[m * nb + j], wj = w[m * nb + j];
+      ys[j] = v;
+      wsm[j] = wj;
+      fin = fin && wj >= T(0) && LutNum<T>::finite(wj) && (wj == T(0) || LutNum<T>::finite(v));
+    }
+    lut_wave_sync();
+    if (__all(fin) == 0) {                             // an invalid observation matches no row
+      lut_bayes_empty<T>(out, m, P, lane);
+      continue;
+    }
+    auto to_brute = [&] {
+      if (lane == 0) {
+        const unsigned long long pos = atomicAdd(&ctl[1], 1ull);
+        flag_list[pos] = (int)m;
+      }
+    };
+    int64_t nrows = B;
+    int ncand = 0;
+    if (!BRUTE) {
+      bool flag = force != 0;
+      if (!flag) {
+        ncand = cand_n[item];
+        flag = !LutNum<T>::finite(thr[item]) || ncand > cap;
+        if (lane == 0) {
+          atomicAdd(&ctl[2], (unsigned long long)ncand);
+          atomicMax(&ctl[3], (unsigned long long)ncand);
+        }
+      }
+      if (flag) {
+        to_brute();
+        continue;
+      }
+      // the candidate tiles in ascending order (bitonic, n2 = the power of two >= ncand, padded with INT_MAX)
+      int n2 = 2;
+      while (n2 < ncand) n2 <<= 1;
+      for (int i = lane; i < n2; i += 64) tiles[i] = i < ncand ? cand[item * cap + i] : 0x7fffffff;
+      lut_wave_sync();
+      for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+          for (int i = lane; i < n2 / 2; i += 64) {
+            const int t = ((i & ~(stride - 1)) << 1) | (i & (stride - 1));
+            const int p = t | stride;
+            const int vt = tiles[t], vp = tiles[p];
+            if ((vp < vt) == ((t & size) == 0)) {
+              tiles[t] = vp;
+              tiles[p] = vt;
+            }
+          }
+          lut_wave_sync();
+        }
+      nrows = (int64_t)ncand * ROWS;
+    }
+    // this lane's row of the round that starts at r0, or -1: range- and norm-checked, ascending with the lane
+    auto row_of = [&](int64_t r0) -> int {
+      int64_t r = -1;
+      if (BRUTE) {
+        r = r0 + lane;
+      } else {
+        const int ci = (int)(r0 / ROWS) + lane / ROWS;
+        if (ci < ncand) {
+          const int tl = tiles[ci];
+          if (tl >= 0) r = (int64_t)tl * ROWS + lane % ROWS;
+        }
+      }
+      if (r < 0 || r >= B) return -1;
+      return LutNum<T>::finite(norm[r]) ? (int)r : -1;
+    };
+    // pass A: c* and its lowest row
+    T bc = (T)INFINITY;
+    int br = -1;
+    for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+      const int r = row_of(r0);
+      if (r >= 0) {
+        const T c = lut_bayes_cost<T>(lut + (int64_t)r * nb, ys, wsm, nb);
+        if (LutNum<T>::finite(c) && c < bc) {          // (a lane's rows ascend: the first of equal costs stays)
+          bc = c;
+          br = r;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const T oc = __shfl_xor(bc, off, 64);
+      const int orow = __shfl_xor(br, off, 64);
+      if (orow >= 0 && (br < 0 || oc < bc || (oc == bc && orow < br))) {
+        bc = oc;
+        br = orow;
+      }
+    }
+    if (br < 0) {                                      // E is empty among these rows
+      if (BRUTE) lut_bayes_empty<T>(out, m, P, lane);
+      else to_brute();
+      continue;
+    }
+    const double cstar = (double)bc;
+    // passes B and C.  second = false: sum_w, s2 and the sums of omega x; second = true: the sums of (omega d) d
+    double sw = 0.0, s2 = 0.0, sx = 0.0, sv = 0.0, mu = 0.0;
+    int64_t n = 0;
+    for (int second = 0; second < 2; ++second) {
+      for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+        const int r = row_of(r0);
+        bool inc = false;
+        double om = 0.0;
+        if (r >= 0) {
+          const T c = lut_bayes_cost<T>(lut + (int64_t)r * nb, ys, wsm, nb);
+          if (LutNum<T>::finite(c)) {
+            const double e = (double)c - cstar;
+            if (e <= cut) {
+              inc = true;
+              om = Mx<double>::exp_poly(-(e / two_tau));
+            }
+          }
+        }
+        unsigned long long mask = __ballot(inc);
+        if (!second) n += __builtin_popcountll(mask);
+        while (mask) {
+          const int src = __builtin_ctzll(mask);
+          mask &= mask - 1;
+          const int rr = __shfl(r, src, 64);
+          const double o = __shfl(om, src, 64);
+          const double x = lane < P ? params[(int64_t)rr * P + lane] : 0.0;
+          if (!second) {
+            sw = sw + o;
+            s2 = s2 + o * o;
+            sx = sx + o * x;
+          } else {
+            const double d = x - mu;
+            sv = sv + (o * d) * d;
+          }
+        }
+      }
+      if (!second) mu = sx / sw;
+      if (!out.sdev) break;
+    }
+    if (lane < P) {
+      if (out.mean) out.mean[m * P + lane] = mu;
+      if (out.sdev) out.sdev[m * P + lane] = __builtin_sqrt(sv / sw);
+    }
+    if (lane == 0) {
+      if (out.sum_w) out.sum_w[m] = sw;
+      if (out.ess) out.ess[m] = (sw * sw) / s2;
+      if (out.count) out.count[m] = n;
+      if (out.best_idx) out.best_idx[m] = (int64_t)br;
+      if (out.best_cost) static_cast<T*>(out.best_cost)[m] = bc;
     }
   }
 }

@@ -46,6 +46,16 @@ class SpartPosteriorOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("x", "y", "jac", "cov", "ak", "std", "dfs", "cost", "nband", "status")]
 
 
+class SpartLutBayesOpt(ctypes.Structure):
+    _fields_ = [("cut", ctypes.c_double), ("temperature", ctypes.c_double), ("brute_force", ctypes.c_int32)]
+
+
+class SpartLutBayesOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("mean", "std", "sum_w", "ess", "count", "best_idx", "best_cost")]
+
+
+LUT_BAYES_OUTS = tuple(n for n, _ in SpartLutBayesOut._fields_)      # spart_lut_bayes_out, in its order
+LUT_BAYES_MAXP = 64
 POSTERIOR_OUTS = tuple(n for n, _ in SpartPosteriorOut._fields_)     # spart_posterior_out, in its order
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
 REFINE_MAXF, REFINE_MAX_ITER = 16, 100
@@ -96,6 +106,11 @@ SIGNATURES = {
                            ("", (ctypes.c_int, _LUT_TOPK_CALL)),
                            ("_stats", (ctypes.c_int, _LUT_TOPK_STATS)))},
     "spart_lut_summarise": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "spart_lut_bayes_workspace_bytes": (ctypes.c_size_t, _LUT_SIZES),
+    "spart_lut_bayes": (ctypes.c_int, [vp] + _LUT_SIZES[:3] + [vp, ctypes.c_int, vp, ctypes.c_int64, vp, vp,
+                                                              ctypes.POINTER(SpartLutBayesOpt), ctypes.POINTER(SpartLutBayesOut),
+                                                              vp, ctypes.c_size_t, vp]),
+    "spart_lut_bayes_stats": (ctypes.c_int, [vp] + _LUT_SIZES + [vp, c_i64p, c_i64p, c_i64p, c_dp]),
     "spart_refine_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
     "spart_refine": (ctypes.c_int, _REFINE_CALL),
     "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),

@@ -1039,6 +1039,60 @@ class Engine:
         _lib.check(self.lib, self.ctx, rc)
         return res
 
+    def lut_bayes(self, lut, params, obs, weights=None, cut=50.0, temperature=1.0, dtype="float32", stats=False, brute_force=False):
+        """The likelihood-weighted LUT estimate (include/spart_hip.h: spart_lut_bayes, which pins every sum): every accepted row b
+        of lut (B, nb) whose cost lies within ``cut`` of the best one, e_b = c(b) - c* <= cut, gets the weight
+        exp(-e_b / (2 temperature)); the cost is lut_topk's with (M, nb) weights (chi^2 when the weights are 1 / sigma^2).
+        ``params`` (B, P) float64, 1 <= P <= 64; ``weights`` None (ones), (nb,) (expanded to (M, nb) on the device: the C call
+        knows one layout) or (M, nb), a zero weight masking its band.  ``cut`` >= 0 or inf (every accepted row).
+        -> dict of device tensors: mean, std (M, P) float64 -- the weighted mean and spread of the parameter rows --, sum_w, ess
+        (M,) float64 -- the effective sample size (sum w)^2 / sum w^2 --, count, best_idx (M,) int64 and best_cost (M,) in
+        ``dtype`` (lut_topk(k=1)'s, bit for bit); an observation that matches nothing gets count 0, best_idx -1, best_cost inf,
+        sum_w 0 and NaN.  ``brute_force=True`` sends every observation through the brute-force kernel (the same result bit for
+        bit).  With ``stats=True`` -> (dict, stats): brute-forced observations, candidate tiles (sum and maximum) and "nbound"
+        (spart_lut_bayes_stats; synchronises)."""
+        torch = self.torch
+        dt = DTYPES[dtype]
+        td = self._tdtype(dt)
+        lut = torch.as_tensor(lut).to(device=self.device, dtype=td).contiguous()
+        obs = torch.as_tensor(obs).to(device=self.device, dtype=td).contiguous()
+        params = torch.as_tensor(params).to(device=self.device, dtype=torch.float64).contiguous()
+        if lut.dim() != 2 or obs.dim() != 2 or lut.shape[1] != obs.shape[1]:
+            raise ValueError("lut (B, nb) and obs (M, nb) must share nb")
+        B, nb = lut.shape
+        M = obs.shape[0]
+        if params.dim() != 2 or params.shape[0] != B:
+            raise ValueError(f"params must be (B, P) = ({B}, P), got shape {tuple(params.shape)}")
+        P = params.shape[1]
+        if weights is None:
+            w = torch.ones((M, nb), dtype=td, device=self.device)
+        else:
+            w = torch.as_tensor(weights).to(device=self.device, dtype=td)
+            if lut_weights_kind(w.shape, M, nb) == "shared":
+                w = w.expand(M, nb)
+            w = w.contiguous()
+        res = {n: torch.empty((M, P), dtype=torch.float64, device=self.device) for n in ("mean", "std")}
+        res.update({n: torch.empty((M,), dtype=torch.float64, device=self.device) for n in ("sum_w", "ess")})
+        res.update({n: torch.empty((M,), dtype=torch.int64, device=self.device) for n in ("count", "best_idx")})
+        res["best_cost"] = torch.empty((M,), dtype=td, device=self.device)
+        opt = _lib.SpartLutBayesOpt(float(cut), float(temperature), int(bool(brute_force)))
+        out = _lib.SpartLutBayesOut(*[res[n].data_ptr() for n in _lib.LUT_BAYES_OUTS])
+        nbytes = max(self.lib.spart_lut_bayes_workspace_bytes(dt, B, nb, M), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_lut_bayes"] += 1
+        rc = self.lib.spart_lut_bayes(self.ctx, dt, B, nb, lut.data_ptr(), P, params.data_ptr(), M, obs.data_ptr(), w.data_ptr(),
+                                      ctypes.byref(opt), ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        if not stats:
+            return res
+        names = ("brute_force", "candidate_tiles", "max_candidate_tiles")
+        counts, word = [ctypes.c_int64(0) for _ in names], ctypes.c_double(0.0)
+        if M > 0 and B > 0:
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self.lib, self.ctx, self.lib.spart_lut_bayes_stats(
+                self.ctx, dt, B, nb, M, ws.data_ptr(), *[ctypes.byref(c) for c in counts], ctypes.byref(word)))
+        return res, {**{n: int(c.value) for n, c in zip(names, counts)}, "nbound": float(word.value)}
+
     def _refine_columns(self, params, M):
         """the start rows of refine() / posterior() as 27 float64 device columns of M values"""
         if self.torch.is_tensor(params):

@@ -582,8 +582,60 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     return plan, opts, meta.get("sensor"), sensor_info
 
 
+BAYES_OPTS = ("cut", "temperature")
+BAYES_KEYS = {"bayes_mean": "mean", "bayes_std": "std", "bayes_ess": "ess", "bayes_sum_w": "sum_w", "bayes_count": "count"}
+
+
+def _bayes_setup(bayes, shard=False, group=None):
+    """retrieve(bayes=...): None, or a dict with some of BAYES_OPTS -> None or Engine.lut_bayes' keyword arguments, checked"""
+    if bayes is None:
+        return None
+    if not isinstance(bayes, dict):
+        raise ValueError(f"bayes = {bayes!r}, expected a dict with some of {BAYES_OPTS}")
+    stray = [n for n in bayes if n not in BAYES_OPTS]
+    if stray:
+        raise ValueError(f"bayes: unknown option(s) {stray}; expected some of {BAYES_OPTS}")
+    opts = {"cut": float(bayes.get("cut", 50.0)), "temperature": float(bayes.get("temperature", 1.0))}
+    if not opts["cut"] >= 0:
+        raise ValueError(f'bayes["cut"] = {opts["cut"]}, expected >= 0 (inf: every accepted row)')
+    if not (0 < opts["temperature"] < np.inf):
+        raise ValueError(f'bayes["temperature"] = {opts["temperature"]}, expected finite and > 0')
+    if _group_info(shard, group)[0] > 1:
+        raise ValueError("retrieve(bayes=...) does not take shard=True under a process group of more than one rank: every rank "
+                         "holds only its own rows (the sharded posterior is not built yet)")
+    return opts
+
+
+def _bayes_shapes(M, P):
+    return {"bayes_mean": ((M, P), np.float64), "bayes_std": ((M, P), np.float64), "bayes_ess": ((M,), np.float64),
+            "bayes_sum_w": ((M,), np.float64), "bayes_count": ((M,), np.int64)}
+
+
+def _bayes_maps(eng, lut_t, par_t, obs_t, weights, dtype, opts):
+    """Engine.lut_bayes -> its BAYES_KEYS tensors"""
+    r = eng.lut_bayes(lut_t, par_t, obs_t, weights=weights, dtype=dtype, **opts)
+    return {key: r[name] for key, name in BAYES_KEYS.items()}
+
+
+def _retrieve_bayes(lut_dir, obs, column, weights, device, cols, opts):
+    """the bayes_* arrays of retrieve(): the column and the chosen parameter columns go up as _upload_lut does, one
+    Engine.lut_bayes for all M observations; an empty table or M = 0 gets the empty-observation values"""
+    import torch
+    meta, params, tabs = load_lut(lut_dir)
+    table = tabs[column]
+    npdt = _np_dtype(meta["dtype"])
+    M, B = np.shape(obs)[0], table.shape[0]
+    if B == 0 or M == 0:
+        return _unmatched(_bayes_shapes(M, len(cols)))
+    eng = get_engine(None, device)
+    o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=_torch_dtype(npdt))
+    w = None if weights is None else _host_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
+    return {n: v.cpu().numpy() for n, v in _bayes_maps(eng, *_upload_lut(eng, table, params, cols, npdt), o, w, meta["dtype"], opts).items()}
+
+
 # what an observation that matches nothing gets, by output name (retrieve, retrieve_stream and the fit)
 _EMPTY = {"idx": -1, "cost": np.inf, "best_cost": np.inf, "mean": np.nan, "median": np.nan, "std": np.nan, "count": 0,
+          "bayes_mean": np.nan, "bayes_std": np.nan, "bayes_ess": np.nan, "bayes_sum_w": 0.0, "bayes_count": 0,
           "refined": np.nan, "refined_std": np.nan, "refined_cost": np.nan, "refined_cost0": np.nan, "refined_accepts": -1,
           "refined_cov": np.nan, "refined_ak": np.nan, "refined_dfs": np.nan}
 
@@ -674,7 +726,7 @@ def _refine_best(setup, dict_prior, lut_dir, obs, idx, column, weights, device):
 
 
 def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=None, device=None, summary="host",
-             params_cols=None, refine=None, refine_opts=None, sensor_info=None):
+             params_cols=None, refine=None, refine_opts=None, sensor_info=None, bayes=None):
     """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
     mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
     ``weights`` as for invert_lut: (nb,) or (M, nb), e.g. noise_weights(obs, rel_sigma=0.02).
@@ -705,13 +757,24 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     ``refined_cov`` (M, F, F), the full posterior covariance, ``refined_ak`` (M, F, F), the averaging kernel, and ``refined_dfs``
     (M,), its trace, the degrees of freedom for signal (Engine.posterior at the fitted rows; NaN without a row).  The sensor is
     meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band model other than the
-    LUT's and for ``shard=True`` under a process group of more than one rank (sharded refinement is not built yet)."""
+    LUT's and for ``shard=True`` under a process group of more than one rank (sharded refinement is not built yet).
+
+    ``bayes``: a dict with some of ``cut`` (default 50.0) and ``temperature`` (default 1.0); unknown keys are a ValueError.
+    The likelihood-weighted estimate over EVERY accepted row whose cost lies within ``cut`` of the best one
+    (Engine.lut_bayes / spart_lut_bayes; weight exp(-(c - c*) / (2 temperature))), not just the k nearest: the result gains
+    ``bayes_mean``, ``bayes_std`` (M, P over ``params_cols``), ``bayes_ess`` (the effective sample size: is the LUT dense enough
+    for this noise?), ``bayes_sum_w`` and ``bayes_count`` (M,) int64; every other key stays bit for bit.  It goes with either
+    ``summary`` and uploads the column and the parameter columns once more; a pixel that matches nothing gets NaN, sum_w 0 and
+    count 0.  ``shard=True`` under a process group of more than one rank: ValueError (the sharded posterior is not built yet)."""
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
+    bayes = _bayes_setup(bayes, shard, group)
     setup = _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info)
     dict_prior = _dict_prior(setup, np.shape(obs)[0])                    # (an array that is not (M,): refused before the search)
     out = _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, summary, params_cols, names, cols)
+    if bayes is not None:
+        out.update(_retrieve_bayes(lut_dir, obs, column, weights, device, cols, bayes))
     if setup is not None:
         out.update(_refine_best(setup, dict_prior, lut_dir, obs, out["idx"], column, weights, device))
     return out
@@ -764,9 +827,10 @@ class _DeviceStage:
     """The device side of retrieve_stream: the LUT column and the parameter columns, uploaded once; two sets of chunk
     buffers; three streams.  upload / launch / download are what _run_pipeline calls for buffer j = chunk number % 2."""
 
-    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights, fit=None, params=None):
+    def __init__(self, eng, lut_t, par_t, k, dtype, chunk, per_obs_weights, shared_weights, fit=None, params=None, bayes=None):
         import torch
         self.torch, self.eng, self.lut, self.par, self.k, self.dtype = torch, eng, lut_t, par_t, k, dtype
+        self.bayes = bayes              # retrieve_stream(bayes=...): Engine.lut_bayes' keyword arguments, or None
         dev = self.dev = eng.device
         nb = lut_t.shape[1]
         self.compute = torch.cuda.current_stream(dev)
@@ -810,6 +874,8 @@ class _DeviceStage:
         w = self.w[j][:n] if self.w is not None else self.shared
         idx, cost, res = _topk_summary(self.eng, self.lut, self.par, self.obs[j][:n], self.k, w, self.dtype)
         res["best_cost"] = cost[:, 0].contiguous()
+        if self.bayes is not None:
+            res.update(_bayes_maps(self.eng, self.lut, self.par, self.obs[j][:n], w, self.dtype, self.bayes))
         if self.fit is not None:
             start = self.table.index_select(0, idx[:, 0].clamp(min=0)).t().contiguous()      # (27, n)
             o64 = self.obs64[j][:n] if self.wide else self.obs[j][:n]
@@ -855,7 +921,7 @@ def _stream_chunks(obs, weights, chunk, out, stage, npdt, wide=False):
 
 
 def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=None, chunk=1 << 16, device=None, out=None,
-                    refine=None, refine_opts=None, sensor_info=None, _stage=None):
+                    refine=None, refine_opts=None, sensor_info=None, bayes=None, _stage=None):
     """A scene in, parameter maps out: retrieve(summary="device") for any number of observations, in chunks.
     ``obs`` (M, nb) on the HOST (array or memmap; any M, also 0); ``weights`` None, (nb,) or (M, nb) (sliced with the chunks),
     as for invert_lut; ``params_cols`` as for retrieve.  The LUT column and the chosen parameter columns are uploaded ONCE;
@@ -874,7 +940,12 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     ``refined_std`` (M, F), ``refined_cost``, ``refined_cost0`` (M,), ``refined_accepts`` (M,) int32 and ``refined_names``, each
     equal to retrieve(summary="device", refine=...)'s bit for bit whatever the chunk size; a pixel without a row gets NaN
     and -1; with refine_opts={"posterior": True} ``refined_cov``, ``refined_ak`` and ``refined_dfs`` as maps too.  A
-    per-observation prior dict goes up once too, as its (M, F) float64 mean and weight."""
+    per-observation prior dict goes up once too, as its (M, F) float64 mean and weight.
+
+    ``bayes`` as for retrieve: one more call per chunk (Engine.lut_bayes on the chunk's own buffers, the LUT and the parameter
+    columns already on the device); the result (and ``out``) gains ``bayes_mean``, ``bayes_std``, ``bayes_ess``,
+    ``bayes_sum_w`` and ``bayes_count`` as maps, each equal to retrieve(bayes=...)'s bit for bit whatever the chunk size."""
+    bayes = _bayes_setup(bayes)
     setup = _refine_setup(lut_dir, refine, refine_opts, False, None, sensor_info)
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
@@ -889,7 +960,7 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     if weights is not None and not isinstance(weights, np.memmap):
         weights = np.asarray(weights)
     kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
-    shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt)}
+    shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt), **({} if bayes is None else _bayes_shapes(M, len(cols)))}
     if setup is not None:
         shapes.update(_refined_shapes(M, len(setup[0]["names"]), bool(setup[1].get("posterior", False))))
     dict_prior = _dict_prior(setup, M)
@@ -906,7 +977,7 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
             if shared is not None:
                 shared = _host_tensor(np.ascontiguousarray(shared, dtype=npdt)).to(eng.device)
             stage = _DeviceStage(eng, *_upload_lut(eng, table, params, cols, npdt), k, meta["dtype"], max(1, min(int(chunk), M)),
-                                 kind == "per_observation", shared, fit=fit, params=params)
+                                 kind == "per_observation", shared, fit=fit, params=params, bayes=bayes)
         _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt,
                        wide=bool(getattr(stage, "wide", False)))
     res["names"] = names
