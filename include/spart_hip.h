@@ -68,7 +68,8 @@ extern "C" {
  * caller of version 14 still calls what it called; a binding that needs the symbol looks it up when it loads the library.
  * spart_refine_views, spart_views_workspace_bytes and spart_refine_views_opt were added by the same rule: new symbols
  * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise, and
- * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out. */
+ * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out.
+ * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -578,6 +579,82 @@ int spart_refine_views(spart_ctx *ctx, int64_t M, const double *const base[SPART
                        const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
                        const spart_refine_views_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
                        double *y, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Refinement with parameters shared by a TILE of pixels: one atmosphere per window, one leaf-angle parameter per field.  The
+ * first Fs = n_shared entries of free_cols are ONE unknown per tile, the other Fl = F - Fs one unknown per pixel; a tile is the
+ * contiguous pixels tile_start[t] ... tile_start[t + 1] - 1, at most 4096 of them.  One Levenberg-Marquardt decision is taken
+ * per tile on the summed cost; the damped system of a tile is block-arrowhead and is solved by eliminating every pixel's
+ * locals.  base, free_cols, lo, hi (per name), obs, weights and opt->fit are spart_refine's; opt->fit.prior_* is the prior of
+ * the LOCAL unknowns, (Fl,) or (M, Fl) with prior_per_obs = 1; the prior of the shared ones is shared_prior_*, (Fs,) or (T, Fs).
+ * Definition (tools/refine_tiles_defined.py is the same text in numpy; float64, no FMA contraction, IEEE division and sqrt; the
+ * per-entry arithmetic is spart_refine's):
+ *   order    inside a pixel the unknowns are taken in SOLVE ORDER: every local first (q = b for local name Fs + b), then the
+ *            shared (q = Fl + a).  The unknowns of a tile are every live pixel's locals, pixels ascending, then the shared.
+ *   start    shared z_a = clip(base[free[a]][tile_start[t]]), the tile's first pixel: the other pixels' entries of a shared
+ *            column are never read and may be NaN.  Local l_(m,b) = clip(base[free[Fs + b]][m]).  lambda_t = lambda0.
+ *   rows     spart_refine's F + 1 rows per pixel from the tile's trial z and the pixel's trial l; s_f by spart_refine's rule on
+ *            the trial value, so a shared name has one sign per tile
+ *   c_m      spart_refine's band loop, then the local prior loop, b ascending
+ *   dead pixel  decided at it = 0: a negative, NaN or infinite band weight or local prior weight, or c_m not < +inf.
+ *            status -1, local = the clipped start, local_std NaN, y = Y_0, pixel_cost = c_m; it takes part in no sum of its
+ *            tile for the rest of the call
+ *   C        C = 0; for live m ascending: C = C + c_m; then the shared prior loop, a ascending, weight 0 skipped
+ *   dead tile   decided at it = 0: no live pixel, a bad shared prior weight, or C not < +inf.  n_accept -1, shared = the clipped
+ *            start, cost = cost0 = C, every std of the tile NaN; its live pixels get status 1, y = Y_0, pixel_cost = c_m and
+ *            keep the clipped start.  Nothing about the tile changes afterwards
+ *   decide   per tile: accept iff C_t < C (a NaN never passes); lambda_t and n_accept move by spart_refine's rules
+ *   sums     at an accepted point, per live pixel spart_refine's packed A_m and g_m over the unknowns in solve order (so a
+ *            shared row holds (w J_shared) J_local), the local prior added to the local diagonal and to g; per tile, for shared
+ *            a >= b: S_ab = 0; for live m ascending: S_ab = S_ab + A_m[a, b]; gs_a likewise; then the shared prior is added to
+ *            S_aa and gs_a as spart_refine adds it.  A rejection restores these
+ *   propose  D = the diagonal entry if > 0 else 1 (A_m[bb] for a local, S_aa for a shared unknown); B = A + lambda_t D on the
+ *            diagonal; B delta = -g by spart_refine's Cholesky text on the tile's matrix in the tile's unknown order, entries
+ *            between locals of different pixels skipped: R_m = chol(B_m[local, local]);
+ *            W_m[a, j] = (A_m[a, j] - sum_{k < j} W_m[a, k] R_m[j, k]) / R_m[j, j];
+ *            Ls from s = B_ab; for live m ascending, k = 0 ... Fl-1: s = s - W_m[a, k] W_m[b, k]; for shared k < b:
+ *            s = s - Ls[a, k] Ls[b, k]; the forward substitution in that same order (the locals of m; then the shared with
+ *            s = -gs_a; for m ascending, k ascending: s = s - W_m[a, k] d_(m,k); then the shared k < a); the back substitution
+ *            of the shared from Fs - 1 down, then each local j from Fl - 1 down with k = j + 1 ... Fl-1 first and the shared a
+ *            ascending after.  A pivot !(s > 0) anywhere in the tile, or any non-finite delta, gives delta = 0 for the whole
+ *            tile.  t = clip(x + delta).  No early exit
+ *   std      from the undamped matrices by spart_refine's std recurrence in the same unknown order: for a shared f, k runs over
+ *            the shared unknowns >= f; for a local (m, j), over m's locals >= j and then every shared unknown.  A failed
+ *            factorisation makes every std of the tile NaN
+ * Consequences.  With every tile one pixel the call is spart_refine (band_model 1: spart_refine_srf) with free_cols = local
+ * names then shared names and the two priors concatenated per observation in that order, bit for bit, x / std permuted
+ * accordingly (of a dead pixel, which is then a dead tile, cost and cost0 are the TILE's C: no pixel's cost is in it).  A
+ * tile's outputs are the same bits whichever other tiles are in the call and whichever chunk it lands in.  A dead pixel in a
+ * live tile changes nothing but its own outputs.
+ * Pixels go in chunks of whole tiles, greedily: consecutive tiles while the pixel count stays <= 2^19 / (F + 1).  The
+ * workspace, spart_tiles_workspace_bytes(ctx, M, F, n_shared), is sized from those three alone, is bounded by one chunk and is
+ * 0 exactly for refused sizes.  tile_start is read on the host before the call returns; the call waits for `stream` once per
+ * chunk, after it has queued the copy of that chunk's tile map.
+ * Refused before anything is launched or written: spart_refine's list in its order (the required outputs -- cost; shared when
+ * Fs > 0; local when Fl > 0 -- count as spart_refine's x and cost do), then n_shared outside 0 ... F, then band_model outside
+ * 0 / 1, then T < 0 or T = 0 with M > 0, then a bad tile_start (NULL, or the first offending index named), then exactly one
+ * shared prior pointer NULL or shared_prior_per_tile outside 0 / 1; SPART_ERR_WORKSPACE, the last of spart_refine's list, comes
+ * after these, because n_shared sizes the workspace.  M = 0 launches nothing and, as in spart_refine, returns before them.  Added WITHOUT a new interface number, by spart_refine_srf's rule: two symbols and two structs. */
+typedef struct spart_refine_tiles_opt {
+  spart_refine_opt fit;    /* column, n_iter, weights_per_obs, fast_prelude, nlayers, rel_step, lambda0; prior_*: the LOCAL prior */
+  int32_t n_shared;        /* Fs: the first Fs entries of free_cols are shared by a tile, the other Fl = F - Fs are per pixel */
+  int32_t band_model;      /* 0: centre columns (spart_refine's forward call), 1: SRF columns (spart_refine_srf's) */
+  int32_t shared_prior_per_tile;                          /* 0: (Fs,), 1: (T, Fs) */
+  const double *shared_prior_mean, *shared_prior_weight;  /* device, both NULL or both given */
+} spart_refine_tiles_opt;
+typedef struct spart_tiles_out {   /* device memory; cost is required, shared when Fs > 0, local when Fl > 0; the rest may be NULL */
+  double *shared, *shared_std;     /* (T, Fs) */
+  double *local, *local_std;       /* (M, Fl) */
+  double *cost, *cost0;            /* (T,) */
+  int32_t *n_accept;               /* (T,)  -1: dead tile */
+  double *pixel_cost;              /* (M,)  c_m at the accepted point */
+  int32_t *status;                 /* (M,)  0 live, -1 dead pixel, 1 live pixel of a dead tile */
+  double *y;                       /* (M, nb) */
+} spart_tiles_out;
+size_t spart_tiles_workspace_bytes(const spart_ctx *ctx, int64_t M, int F, int n_shared);
+int spart_refine_tiles(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                       const double *lo, const double *hi /* HOST, (F,) per name */, int64_t T, const int64_t *tile_start /* HOST (T+1,) */,
+                       const double *obs, const double *weights, const spart_refine_tiles_opt *opt, const spart_tiles_out *out,
+                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
  * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging

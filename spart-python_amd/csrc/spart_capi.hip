@@ -22,6 +22,7 @@
 #include "spart_refine.h"
 #include "spart_refine_posterior.h"
 #include "spart_refine_views.h"
+#include "spart_refine_tiles.h"
 
 using namespace spart;
 
@@ -254,9 +255,12 @@ bool chunk_fits_32bit(int chunk, int pitch, size_t es) {
 // shortens the tail of the launch, 1.4 % at B = 1M against 2048 rows), so the per-chunk band sums stay <= 256 MB
 // (fp32) whatever B is.  Small batches: at least min(32, B/256) samples per workgroup so that the table loads are
 // amortised while ~2000 workgroups remain.
-int pick_chunk(int64_t B) {
+int forced_chunk() {
   static const int forced = [] { const char* e = std::getenv("SPART_CHUNK"); return e ? std::atoi(e) : 0; }();   // tuning knob
-  if (forced > 0) return forced;
+  return forced;
+}
+int pick_chunk(int64_t B) {
+  if (const int forced = forced_chunk(); forced > 0) return forced;
   int64_t c = (B + 8191) / 8192;
   int64_t small = (B + 255) / 256;
   if (small > 32) small = 32;
@@ -280,6 +284,17 @@ Workspace carve(int dtype, int64_t B) {
   w.bs_off = o;  o = align_up(o + (size_t)w.nchunk * (size_t)(NTILE * TILE) * 4 * es);
   w.total = o;
   return w;
+}
+
+// A bound of carve(SPART_F64, B).total over EVERY batch 1 <= B <= R (carve itself is not monotonic in B: the band-sum rows
+// follow pick_chunk).  The three per-sample blocks grow with row_pitch_of(B), which is monotonic, so R bounds them.  The
+// band-sum block has nchunk = ceil(B / pick_chunk(B)) rows: pick_chunk(B) >= ceil(B / 8192) >= B / 8192 gives nchunk <= 8192,
+// and nchunk <= B <= R always; a forced SPART_CHUNK = c gives ceil(B / c) <= ceil(R / c).
+size_t carve_bound_f64(int64_t R) {
+  const Workspace w = carve(SPART_F64, R);
+  const int forced = forced_chunk();
+  const int64_t nmax = forced > 0 ? (R + forced - 1) / forced : std::min<int64_t>(R, 8192);
+  return align_up(w.bs_off + (size_t)nmax * (size_t)(NTILE * TILE) * 4 * 8);
 }
 
 // the constants block of dtype T in a call's workspace, and the context's table of that dtype
@@ -1311,8 +1326,10 @@ struct RefineArgs {
 // The one argument check and refusal order of the family.  `have_opt`: the entry's own option and output structs are there;
 // `have_data`: so are the obs, x and cost it requires.  before(r) reads the options into r.o, r.s and r.srf once they are
 // known to be there and may refuse; after() may refuse once the fit is checked; run(r, st) queues the checked call.
-template <typename Before, typename After, typename Run>
-static int refine_entry(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after, Run&& run) {
+// layout(r) sizes the workspace into r.l and may refuse what the size depends on: the last check before the workspace's own.
+template <typename Before, typename After, typename Layout, typename Run>
+static int refine_entry_sized(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after,
+                              Layout&& layout, Run&& run) {
   if (!a.ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
   if (a.M < 0 || a.M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)a.M);
   if (a.F < 1 || a.F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, a.F, REFINE_MAXF);
@@ -1330,10 +1347,19 @@ static int refine_entry(const char* who, const RefineArgs& a, bool have_opt, boo
   if (r.o.weights_per_obs && !a.weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
   for (int p = 0; p < SPART_NPARAM; ++p) r.cfg.base[p] = a.base[p];
   for (int f = 0; f < a.F; ++f) r.cfg.freebase[f] = a.base[r.cfg.free_col[f]];
-  r.l = refine_layout(a.ctx->nb, a.M, r.s.V, r.s.F, r.s.n);
+  if (int rc = layout(r)) return rc;
   if (!a.workspace || a.workspace_bytes < r.l.total)
     return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, r.l.total, a.workspace_bytes);
   return guarded(a.ctx, who, a.workspace, r.l.total, a.stream, [&](hipStream_t st) { return run(r, st); });
+}
+template <typename Before, typename After, typename Run>
+static int refine_entry(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after, Run&& run) {
+  return refine_entry_sized(
+      who, a, have_opt, have_data, before, after, [&](RefineRun& r) {
+        r.l = refine_layout(a.ctx->nb, a.M, r.s.V, r.s.F, r.s.n);
+        return SPART_OK;
+      },
+      run);
 }
 static int refine_no_check() { return SPART_OK; }
 
@@ -1345,6 +1371,123 @@ static int refine_call(const char* who, bool srf, const RefineArgs& a, const spa
         return SPART_OK;
       },
       refine_no_check, [&](const RefineRun& r, hipStream_t st) { return refine_impl(r, out, st); });
+}
+
+// ---- spart_refine_tiles (csrc/spart_refine_tiles.h).  The table, the column blocks and the forward call's scratch are the
+// family's (RefineLayout, so refine_forward serves); the state per pixel and per tile is its own.  A chunk is a run of whole
+// tiles of at most mcap = min(M, tiles_chunk(F)) pixels, so its row count depends on the partition: the forward call's scratch
+// is sized by carve_bound_f64, which holds for every row count up to the cap.
+struct TilesLayout {
+  size_t lt, ct, Ap, Lp, zt, St, Lt, lam, live, na, code, flag, tstart, ptile;
+};
+static TilesLayout tiles_layout(int nb, int64_t M, int F, int Fs, RefineLayout& l) {
+  TilesLayout x;
+  l.mcap = std::min<int64_t>(M, tiles_chunk(F));
+  const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(F + 1), P = (size_t)(refine_ntri(F) + F), Ps = (size_t)(refine_ntri(Fs) + Fs);
+  const size_t Fl = (size_t)(F - Fs);
+  Carver c;
+  l.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.t = l.A = l.lam = l.na = 0;                                     // (the family's state blocks are not used)
+  l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
+  l.cfg_free = c.take(REFINE_MAXF * 4);
+  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  x.lt = c.take(mc * Fl * 8);
+  x.ct = c.take(mc * 8);
+  x.Ap = c.take(mc * P * 8);
+  x.Lp = c.take(mc * P * 8);
+  x.zt = c.take(mc * (size_t)Fs * 8);                               // (a chunk of mc pixels holds at most mc tiles)
+  x.St = c.take(mc * Ps * 8);
+  x.Lt = c.take(mc * Ps * 8);
+  x.lam = c.take(mc * 8);
+  x.live = c.take(mc * 4);
+  x.na = c.take(mc * 4);
+  x.code = c.take(mc * 4);
+  x.flag = c.take(mc * 4);
+  x.tstart = c.take((mc + 1) * 4);
+  x.ptile = c.take(mc * 4);
+  l.total = c.o;
+  return x;
+}
+
+static bool tiles_sizes_ok(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
+  return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF && n_shared >= 0 && n_shared <= F;
+}
+
+// The chunk loop over whole tiles: the tile map of a chunk is built here, copied, and the stream waited for before the host
+// copy goes away; then k_tiles_init and n_iter + 1 times the forward call and the seven kernels.
+static int tiles_impl(const RefineRun& r, const TilesLayout& x, int Fs, int64_t T, const int64_t* tile_start,
+                      const spart_refine_tiles_opt& to, const spart_tiles_out& out, hipStream_t st) {
+  const RefineLayout& l = r.l;
+  const spart_refine_opt& o = r.o;
+  const int nb = r.ctx->nb, F = r.s.F, Fl = F - Fs, P = refine_ntri(F) + F;
+  const size_t lds = tiles_lds_bytes(F);
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
+  if (r.srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  double* table = (double*)(r.wsp + l.table);
+  double* cfg = (double*)(r.wsp + l.cfg);
+  int32_t* cfg_free = (int32_t*)(r.wsp + l.cfg_free);
+  const double* ycol = cols[o.column];
+  auto at = [&](size_t off) { return r.wsp + off; };
+  const TilesState s = {(double*)at(x.lt),   (double*)at(x.ct),   (double*)at(x.Ap),    (double*)at(x.Lp),    (double*)at(x.zt),
+                        (double*)at(x.St),   (double*)at(x.Lt),   (double*)at(x.lam),   (int32_t*)at(x.live), (int32_t*)at(x.na),
+                        (int32_t*)at(x.code), (int32_t*)at(x.flag), (int32_t*)at(x.tstart), (int32_t*)at(x.ptile)};
+  std::vector<int32_t> tstart, ptile;
+  for (int64_t t0 = 0; t0 < T;) {
+    const int64_t m0 = tile_start[t0];
+    int64_t t1 = t0 + 1;                                            // (one tile always fits: TILES_MAXG <= tiles_chunk(16))
+    while (t1 < T && tile_start[t1 + 1] - m0 <= l.mcap) ++t1;
+    const int tc = (int)(t1 - t0), mc = (int)(tile_start[t1] - m0);
+    tstart.resize((size_t)tc + 1);
+    ptile.resize((size_t)mc);
+    for (int t = 0; t <= tc; ++t) tstart[t] = (int32_t)(tile_start[t0 + t] - m0);
+    for (int t = 0; t < tc; ++t)
+      for (int m = tstart[t]; m < tstart[t + 1]; ++m) ptile[m] = t;
+    HIP_TRY(hipMemcpyAsync(s.tstart, tstart.data(), ((size_t)tc + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.ptile, ptile.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const TilesOut oc = {rows_at(out.shared, t0, Fs),    rows_at(out.shared_std, t0, Fs), rows_at(out.local, m0, Fl),
+                         rows_at(out.local_std, m0, Fl), rows_at(out.cost, t0, 1),       rows_at(out.cost0, t0, 1),
+                         rows_at(out.n_accept, t0, 1),   rows_at(out.pixel_cost, m0, 1), rows_at(out.status, m0, 1),
+                         rows_at(out.y, m0, nb)};
+    const double* obs = r.obs + m0 * nb;
+    const double* wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
+    const double* pmu = rows_at(o.prior_mean, m0, Fl, o.prior_per_obs);
+    const double* ppw = rows_at(o.prior_weight, m0, Fl, o.prior_per_obs);
+    const double* smu = rows_at(to.shared_prior_mean, t0, Fs, to.shared_prior_per_tile);
+    const double* spw = rows_at(to.shared_prior_weight, t0, Fs, to.shared_prior_per_tile);
+    const int wper = o.weights_per_obs ? 1 : 0, pper = o.prior_per_obs ? 1 : 0, sper = to.shared_prior_per_tile ? 1 : 0;
+    const int64_t rows = (int64_t)mc * (F + 1);
+    const unsigned per_pixel = (unsigned)((mc + 255) / 256), groups = (unsigned)((mc + TILES_GROUP - 1) / TILES_GROUP);
+    hipLaunchKernelGGL(k_tiles_init, dim3(per_pixel), dim3(256), 0, st, r.cfg, m0, mc, F, Fs, o.lambda0, s, table, oc, cfg, cfg_free);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    for (int it = 0; it <= o.n_iter; ++it) {
+      const int last = it == o.n_iter ? 1 : 0;
+      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
+      hipLaunchKernelGGL(k_tiles_cost, dim3(per_pixel), dim3(256), 0, st, ycol, obs, wts, wper, pmu, ppw, pper, mc, Fl, nb, it, s, oc);
+      hipLaunchKernelGGL(k_tiles_decide, dim3((unsigned)tc), dim3(64), 0, st, smu, spw, sper, Fs, it, last, s, oc);
+      hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, ycol, obs, wts, wper, pmu,
+                         ppw, pper, (const double*)cfg, mc, F, Fs, nb, s, oc);
+      hipLaunchKernelGGL(k_tiles_eliminate, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, s);
+      if (Fs > 0)                                                   // (without shared unknowns there is nothing to walk or to solve)
+        hipLaunchKernelGGL(k_tiles_schur, dim3((unsigned)tc), dim3(TILES_SCHUR_THREADS), 0, st, smu, spw, sper, F, Fs, last, s, oc);
+      hipLaunchKernelGGL(k_tiles_local, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, s, oc);
+      if (!last)
+        hipLaunchKernelGGL(k_tiles_apply, dim3(per_pixel), dim3(256), 0, st, (const double*)cfg, (const int32_t*)cfg_free, table, mc, F,
+                           Fs, s, oc);
+      HIP_TRY(hipGetLastError());
+    }
+    t0 = t1;
+  }
+  return SPART_OK;
 }
 
 // ---- SRF support (include/spart_hip.h: spart_srf_support)
@@ -1589,6 +1732,57 @@ int spart_refine_views(spart_ctx* ctx, int64_t M, const double* const base[SPART
         return refine_check_band_model(who, opt->band_model);
       },
       refine_no_check, [&](const RefineRun& r, hipStream_t st) { return views_impl(r, out, st); });
+}
+
+size_t spart_tiles_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
+  if (!tiles_sizes_ok(ctx, M, F, n_shared)) return 0;
+  RefineLayout l;
+  tiles_layout(ctx->nb, M, F, n_shared, l);
+  return l.total;
+}
+
+// spart_refine's refusals in refine_entry's order; what is about the tiles comes after them and before the workspace's size,
+// which n_shared decides
+int spart_refine_tiles(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                       const double* lo, const double* hi, int64_t T, const int64_t* tile_start, const double* obs,
+                       const double* weights, const spart_refine_tiles_opt* opt, const spart_tiles_out* out, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  const char* who = "spart_refine_tiles";
+  spart_refine_tiles_opt to;
+  spart_tiles_out oo;
+  TilesLayout x;
+  const bool have_out = opt && out && out->cost && (out->shared || opt->n_shared <= 0) && (out->local || opt->n_shared >= F);
+  return refine_entry_sized(
+      who, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt && out, obs && have_out,
+      [&](RefineRun& r) {
+        to = *opt, oo = *out;
+        r.o = to.fit, r.srf = to.band_model == 1;
+        return SPART_OK;
+      },
+      refine_no_check,
+      [&](RefineRun& r) {
+        if (to.n_shared < 0 || to.n_shared > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, to.n_shared, F);
+        if (int rc = refine_check_band_model(who, to.band_model)) return rc;
+        if (T < 0 || (T == 0 && M > 0))
+          return fail(SPART_ERR_INVALID, "%s: T = %lld tiles for M = %lld pixels", who, (long long)T, (long long)M);
+        if (!tile_start) return fail(SPART_ERR_INVALID, "%s: tile_start is null", who);
+        if (tile_start[0] != 0) return fail(SPART_ERR_INVALID, "%s: tile_start[0] = %lld, expected 0", who, (long long)tile_start[0]);
+        for (int64_t t = 1; t <= T; ++t) {
+          const int64_t g = tile_start[t] - tile_start[t - 1];
+          if (g < 1 || g > TILES_MAXG || tile_start[t] > M)
+            return fail(SPART_ERR_INVALID, "%s: tile_start[%lld] = %lld after %lld: 1 ... %d pixels per tile within M = %lld expected",
+                        who, (long long)t, (long long)tile_start[t], (long long)tile_start[t - 1], TILES_MAXG, (long long)M);
+        }
+        if (tile_start[T] != M)
+          return fail(SPART_ERR_INVALID, "%s: tile_start[%lld] = %lld, expected M = %lld", who, (long long)T, (long long)tile_start[T], (long long)M);
+        if (!to.shared_prior_mean != !to.shared_prior_weight)
+          return fail(SPART_ERR_INVALID, "%s: shared_prior_mean and shared_prior_weight come together (both NULL = no prior)", who);
+        if (to.shared_prior_per_tile != 0 && to.shared_prior_per_tile != 1)
+          return fail(SPART_ERR_INVALID, "%s: shared_prior_per_tile = %d (0: one row for all, 1: one row per tile)", who, to.shared_prior_per_tile);
+        x = tiles_layout(ctx->nb, M, F, to.n_shared, r.l);
+        return SPART_OK;
+      },
+      [&](const RefineRun& r, hipStream_t st) { return tiles_impl(r, x, to.n_shared, T, tile_start, to, oo, st); });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

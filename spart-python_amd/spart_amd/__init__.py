@@ -13,6 +13,6 @@ from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401
 from .lut import (generate_lut, invert_lut, jacobian, load_lut, lut_to_parquet, noise_weights, posterior, refine, refine_views,  # noqa: F401
-                  retrieve, retrieve_stream)
+                  refine_tiles, retrieve, retrieve_stream, tiles_from_labels, window_tiles)
 
 __version__ = "0.1.0"

@@ -42,6 +42,16 @@ class SpartRefineViewsOpt(ctypes.Structure):
     _fields_ = [("fit", SpartRefineOpt), ("V", ctypes.c_int32), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32)]
 
 
+class SpartRefineTilesOpt(ctypes.Structure):
+    _fields_ = [("fit", SpartRefineOpt), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32),
+                ("shared_prior_per_tile", ctypes.c_int32), ("shared_prior_mean", vp), ("shared_prior_weight", vp)]
+
+
+class SpartTilesOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("shared", "shared_std", "local", "local_std", "cost", "cost0", "n_accept", "pixel_cost", "status",
+                                  "y")]
+
+
 class SpartPosteriorOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("x", "y", "jac", "cov", "ak", "std", "dfs", "cost", "nband", "status")]
 
@@ -60,6 +70,8 @@ POSTERIOR_OUTS = tuple(n for n, _ in SpartPosteriorOut._fields_)     # spart_pos
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
 REFINE_MAXF, REFINE_MAX_ITER = 16, 100
 REFINE_MAXV = 64                                    # spart_refine_views_opt.V
+TILES_OUTS = tuple(n for n, _ in SpartTilesOut._fields_)             # spart_tiles_out, in its order
+TILES_MAXG = 4096                                   # pixels per tile of spart_refine_tiles
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -116,6 +128,9 @@ SIGNATURES = {
     "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),
     "spart_views_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spart_refine_views": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartRefineViewsOpt)] + _REFINE_CALL[10:]),
+    "spart_tiles_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "spart_refine_tiles": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + _REFINE_CALL[7:9] +
+                           [ctypes.POINTER(SpartRefineTilesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),
     "spart_refine_posterior": (ctypes.c_int, _REFINE_CALL[:10] + [ctypes.c_int, ctypes.POINTER(SpartPosteriorOut)] + _REFINE_CALL[16:]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

@@ -376,6 +376,59 @@ def refine_views_args(params, obs, shared, local, bounds, weights, column, n_ite
     return plan, params, (M, V, Fs, n), wper, prior_mean, prior_weight, per_obs
 
 
+def tile_starts(M, tile_size, tile_start):
+    """refine_tiles' partition: exactly one of ``tile_size`` (uniform runs of G pixels, a shorter last one) and ``tile_start``
+    ((T + 1,) integers, 0 = s_0 < s_1 < ... < s_T = M) -> tile_start as int64; no tile above 4096 pixels"""
+    if (tile_size is None) == (tile_start is None):
+        raise ValueError("exactly one of tile_size and tile_start is expected")
+    if tile_size is not None:
+        if isinstance(tile_size, bool) or int(tile_size) != tile_size or not 1 <= int(tile_size) <= _lib.TILES_MAXG:
+            raise ValueError(f"tile_size = {tile_size!r}, expected an integer 1 ... {_lib.TILES_MAXG}")
+        G = int(tile_size)
+        return np.minimum(np.arange(0, M + G, G, dtype=np.int64)[:(M + G - 1) // G + 1], M)
+    ts = np.asarray(tile_start)
+    if ts.ndim != 1 or ts.size < 1 or not np.issubdtype(ts.dtype, np.integer):
+        raise ValueError(f"tile_start: expected a (T + 1,) integer array, got shape {ts.shape} of {ts.dtype}")
+    ts = np.ascontiguousarray(ts, dtype=np.int64)
+    if ts[0] != 0 or ts[-1] != M:
+        raise ValueError(f"tile_start runs from {int(ts[0])} to {int(ts[-1])}, expected 0 ... M = {M}")
+    size = np.diff(ts)
+    if ((size < 1) | (size > _lib.TILES_MAXG)).any():
+        t = int(np.flatnonzero((size < 1) | (size > _lib.TILES_MAXG))[0])
+        raise ValueError(f"tile_start: tile {t} has {int(size[t])} pixels, expected 1 ... {_lib.TILES_MAXG}")
+    return ts
+
+
+def refine_tiles_args(params, obs, shared, local, tile_size, tile_start, bounds, weights, column, n_iter, rel_step, lambda0, lidf,
+                      prior, band_model, nb=None):
+    """Every argument check of spart_amd.refine_tiles and Engine.refine_tiles that needs no device: refine_args on the names
+    shared + local (the plan, obs (M, nb), params, weights), the partition (tile_starts), and the prior dict split by name --
+    a shared name takes scalars or (T,) arrays, a local name scalars or (M,) arrays.
+    -> (plan, params, M, Fs, weights per observation 0 / 1, tile_start, local prior, shared prior), a prior being
+    (mean, weight, per row 0 / 1) with (None, None, 0) for none"""
+    shared, local = [str(s) for s in shared], [str(s) for s in local]
+    plan, params, M, kind = refine_args(params, obs, shared + local, bounds, weights, column, n_iter, rel_step, lambda0, lidf, None,
+                                        None, None, band_model, nb=nb)[:4]
+    ts = tile_starts(M, tile_size, tile_start)
+    priors = []
+    if prior is not None and not isinstance(prior, dict):
+        raise ValueError(f"prior = {prior!r}, expected a dict {{name: (mean, sigma)}}")
+    stray = [k for k in (prior or {}) if k not in plan["names"]]
+    if stray:
+        raise ValueError(f"prior: {stray} not free")
+    for names, rows, what in ((local, M, "pixels"), (shared, ts.size - 1, "tiles")):
+        part = {k: v for k, v in (prior or {}).items() if k in names}
+        if not part:
+            priors.append((None, None, 0))
+            continue
+        pp = _prior_plan(names, part)
+        if pp["rows"] not in (None, rows):
+            raise ValueError(f"prior: arrays of {pp['rows']} values for the {rows} {what} of {names}")
+        mean, weight = prior_arrays(pp, rows)
+        priors.append((mean, weight, int(mean.ndim == 2)))
+    return plan, params, M, len(shared), int(kind == "per_observation"), ts, priors[0], priors[1]
+
+
 BAND_MODELS = ("centre", "srf")
 _FIT_OUTS = ("x", "cost", "cost0", "std", "n_accept", "y")     # of spart_refine / _srf / _views, in the order of their argument lists
 
@@ -1106,11 +1159,12 @@ class Engine:
         shapes = {"x": (M, n), "cost": (M,), "cost0": (M,), "std": (M, n), "n_accept": (M,), "y": yshape}
         return {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device) for k in _FIT_OUTS}
 
-    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None):
+    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None, tiles=None):
         """What every entry point of the refinement family does once its parameter columns ``cols`` and its outputs are on the
         device: obs and weights as float64 device tensors, spart_refine_opt from the plan, the prior (mean, weight, per
         observation 0 / 1) hooked up, the workspace, the call count, the C call and its check.  ``outs``: the C arguments between
-        the options and the workspace; ``views`` = (V, Fs, srf) wraps the options in spart_refine_views_opt.
+        the options and the workspace; ``views`` = (V, Fs, srf) wraps the options in spart_refine_views_opt;
+        ``tiles`` = (Fs, srf, tile_start, shared prior) wraps them in spart_refine_tiles_opt and passes the partition.
         -> (obs, weights) as the call got them"""
         torch = self.torch
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -1123,7 +1177,16 @@ class Engine:
             pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in prior[:2])
             opt.prior_per_obs, opt.prior_mean, opt.prior_weight = prior[2], pm.data_ptr(), pw.data_ptr()
         F = len(plan["names"])
-        if views is None:
+        part = []
+        if tiles is not None:
+            Fs, srf, ts, sprior = tiles
+            nbytes = int(self.lib.spart_tiles_workspace_bytes(self.ctx, M, F, Fs))
+            opt = _lib.SpartRefineTilesOpt(fit=opt, n_shared=Fs, band_model=int(srf))
+            if sprior[0] is not None:
+                sm, sw = (torch.as_tensor(v).to(**f64).contiguous() for v in sprior[:2])
+                opt.shared_prior_per_tile, opt.shared_prior_mean, opt.shared_prior_weight = sprior[2], sm.data_ptr(), sw.data_ptr()
+            part = [ts.size - 1, ts.ctypes.data_as(_lib.c_i64p)]
+        elif views is None:
             nbytes = int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F))
         else:
             V, Fs, srf = views
@@ -1133,7 +1196,7 @@ class Engine:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.calls[entry] += 1
         rc = getattr(self.lib, entry)(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                      _dp(plan["lo"]), _dp(plan["hi"]), o.data_ptr() if o is not None else None,
+                                      _dp(plan["lo"]), _dp(plan["hi"]), *part, o.data_ptr() if o is not None else None,
                                       w.data_ptr() if w is not None else None, ctypes.byref(opt), *outs, ws.data_ptr(), nbytes,
                                       self._stream())
         _lib.check(self.lib, self.ctx, rc)
@@ -1276,6 +1339,41 @@ class Engine:
         for k, src in (("local", "x"), ("local_std", "std")):
             res[k] = res[src][:, Fs:].reshape(M, V, F - Fs)
         res["names"] = list(plan["names"])
+        return res
+
+    def refine_tiles(self, params, obs, shared, local=(), tile_size=None, tile_start=None, bounds=None, weights=None,
+                     column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None, prior=None,
+                     band_model="centre"):
+        """refine() with parameters shared by a TILE of pixels: the ``shared`` names are ONE unknown per tile -- one atmosphere
+        per window, one leaf-angle parameter per field -- and the ``local`` names one unknown per pixel; one Levenberg-Marquardt
+        decision is taken per tile on the summed cost (include/spart_hip.h: spart_refine_tiles; tools/refine_tiles_defined.py
+        is the numpy form).
+        params, obs, weights, bounds, column, n_iter, rel_step, lambda0, lidf, nlayers, band_model : as for refine(); a shared
+                 parameter starts from its tile's first pixel
+        tile_size : G: uniform runs of G pixels, the last one shorter;  or  tile_start : (T + 1,) integers, tile t being the
+                 pixels tile_start[t] ... tile_start[t + 1] - 1 (tiles_from_labels / window_tiles make them); 1 ... 4096 pixels
+        prior : {name: (mean, sigma)}: a shared name takes scalars or (T,) arrays, a local name scalars or (M,) arrays
+        -> dict of device tensors shared, shared_std (T, Fs), local, local_std (M, Fl), cost, cost0 (T,), n_accept (T,) int32
+        (-1: a dead tile), pixel_cost (M,), status (M,) int32 (0 live, -1 a dead pixel, which takes no part in its tile, 1 a live
+        pixel of a dead tile), y (M, nb); and ``names`` = shared + local, ``tile_start`` (numpy int64).
+        retrieve / retrieve_stream do not call this."""
+        plan, params, M, Fs, wper, ts, lprior, sprior = refine_tiles_args(
+            params, obs, shared, local, tile_size, tile_start, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior,
+            band_model, nb=self.nb)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        T, Fl = ts.size - 1, len(plan["names"]) - Fs
+        # ---- the device from here on
+        torch = self.torch
+        cols = self._refine_columns(params, M)
+        shapes = {"shared": (T, Fs), "shared_std": (T, Fs), "local": (M, Fl), "local_std": (M, Fl), "cost": (T,), "cost0": (T,),
+                  "n_accept": (T,), "pixel_cost": (M,), "status": (M,), "y": (M, self.nb)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("n_accept", "status") else torch.float64, device=self.device)
+               for k in _lib.TILES_OUTS}
+        out = _lib.SpartTilesOut(**{k: v.data_ptr() for k, v in res.items()})
+        self._refine_device("spart_refine_tiles", plan, M, cols, obs, weights, wper, lidf, nl, lprior, [ctypes.byref(out)],
+                            tiles=(Fs, srf, ts, sprior))
+        res["names"], res["tile_start"] = list(plan["names"]), ts
         return res
 
     def profile(self, max_calls):

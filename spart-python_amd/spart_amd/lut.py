@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, params_rows,
-                     prior_arrays, refine_args, refine_plan, refine_views_args)
+                     prior_arrays, refine_args, refine_plan, refine_tiles_args, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -524,6 +524,50 @@ def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=Non
                            lambda0=lambda0, lidf=lidf, nlayers=nlayers, prior=prior, prior_mean=prior_mean,
                            prior_weight=prior_weight, band_model=band_model)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def refine_tiles(params, obs, sensor, shared, local=(), tile_size=None, tile_start=None, bounds=None, weights=None, column="R_TOC",
+                 n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None, sensor_info=None, device=None, prior=None,
+                 band_model="centre"):
+    """The host form of Engine.refine_tiles: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays, ``obs``
+    (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``); everything else as for Engine.refine_tiles.
+    -> dict of numpy arrays shared, shared_std, local, local_std, cost, cost0, n_accept, pixel_cost, status, y, tile_start and
+    the list ``names``.  Every argument check that needs no device runs before one is asked for."""
+    params = refine_tiles_args(params, obs, shared, local, tile_size, tile_start, bounds, weights, column, n_iter, rel_step, lambda0,
+                               lidf, prior, band_model)[1]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.refine_tiles(params, np.asarray(obs, dtype=np.float64), shared, local, tile_size=tile_size, tile_start=tile_start,
+                           bounds=bounds, weights=weights, column=column, n_iter=n_iter, rel_step=rel_step, lambda0=lambda0,
+                           lidf=lidf, nlayers=nlayers, prior=prior, band_model=band_model)
+    return {k: (v if k in ("names", "tile_start") else v.cpu().numpy()) for k, v in res.items()}
+
+
+def tiles_from_labels(labels):
+    """Tiles for an object-based inversion: ``labels`` (M,), one label per pixel (a field, a segment) -> (order, tile_start):
+    ``order`` (M,) int64 sorts the pixels by label, stably, so that pixels of one label are contiguous and keep their order;
+    tile t is order[tile_start[t]:tile_start[t + 1]].  Pass params[:, order], obs[order] to refine_tiles and scatter the pixel
+    outputs back with out[order] = res[...].  A label of more than 4096 pixels is for the caller to split."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1:
+        raise ValueError(f"labels has shape {labels.shape}, expected (M,)")
+    order = np.argsort(labels, kind="stable").astype(np.int64)
+    srt = labels[order]
+    cut = np.flatnonzero(srt[1:] != srt[:-1]) + 1 if labels.size else np.zeros(0, dtype=np.int64)
+    return order, np.concatenate([[0], cut, [labels.size]]).astype(np.int64) if labels.size else np.zeros(1, dtype=np.int64)
+
+
+def window_tiles(height, width, win):
+    """Tiles for one atmosphere per window: square windows of ``win`` x ``win`` pixels over a (height, width) raster in
+    row-major pixel order, the windows at the right and bottom edges smaller -> (order, tile_start) as tiles_from_labels gives
+    them (windows in row-major order, the pixels of a window in row-major order)."""
+    for what, v in (("height", height), ("width", width), ("win", win)):
+        if isinstance(v, bool) or int(v) != v or int(v) < (1 if what == "win" else 0):
+            raise ValueError(f"{what} = {v!r}, expected an integer >= {1 if what == 'win' else 0}")
+    height, width, win = int(height), int(width), int(win)
+    if win * win > _lib.TILES_MAXG:
+        raise ValueError(f"win = {win}: a window of {win * win} pixels, at most {_lib.TILES_MAXG} fit a tile")
+    r, c = np.divmod(np.arange(height * width, dtype=np.int64), max(width, 1))
+    return tiles_from_labels((r // win) * ((width + win - 1) // win) + c // win)
 
 
 REFINE_OPTS = ("bounds", "n_iter", "rel_step", "lambda0", "lidf", "nlayers", "prior", "prior_floor", "band_model",
