@@ -69,7 +69,8 @@ extern "C" {
  * spart_refine_views, spart_views_workspace_bytes and spart_refine_views_opt were added by the same rule: new symbols
  * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise, and
  * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out.
- * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too. */
+ * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too,
+ * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -428,6 +429,57 @@ int spart_lut_bayes(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lu
  * spart_lut_topk_obs_weights_stats: brute-forced observations, candidate tiles (sum and maximum) and the largest Nbound_m. */
 int spart_lut_bayes_stats(spart_ctx *ctx, int dtype, int64_t B, int nb, int64_t M, const void *workspace, int64_t *n_brute_force,
                           int64_t *n_candidates, int64_t *max_candidates, double *nbound);
+
+/* spart_lut_bayes with weighted quantiles: a median and a credible interval of every parameter over the same posterior, which
+ * is rarely symmetric (LAI saturates, Cab and Cw pile up at 0, a sparse LUT gives two clusters).  Every argument and every
+ * output of spart_lut_bayes keeps its meaning, and the seven base outputs are spart_lut_bayes' bit for bit; quant (M, P, nq)
+ * float64 row-major, device memory, is new.  levels is a HOST array of nq levels, read before the call returns.
+ * Definition.  E, c*, e_b, S (ascending row order), omega_b and sum_w are spart_lut_bayes', word for word, and so are the row
+ * rule, the observation rule and the mask rule.  For observation m, parameter p and level q_i (0 <= q_i <= 1), with
+ * x_b = params[b, p] for b in S:
+ *   target_i   q_i * sum_w, one float64 multiplication
+ *   F_p(v)     the float64 sum of omega_b over the rows b of S with x_b <= v: sequential from 0 in ascending row order, no
+ *              FMA; a row that does not qualify adds nothing.  It is the ordered sum that gives sum_w, restricted to a subset.
+ *   quant[m, p, i]   the smallest value v among {x_b : b in S} with F_p(v) >= target_i: the inverted-CDF quantile, always a
+ *              value of the parameter table, never interpolated.  Of values that compare equal (-0.0 and 0.0) the one in the
+ *              lowest row is returned.
+ *   NaN        if any x_b over S is NaN, all nq quantiles of that (m, p) are NaN (the rule of spart_lut_summarise's median);
+ *              +inf and -inf are ordinary ordered values.  An empty E or an invalid observation: NaN beside spart_lut_bayes'
+ *              empty outputs.
+ * Two facts the definition leans on:
+ *   - F_p is non-decreasing in v: an ordered sum of non-negative terms over a larger subset is never smaller, because every
+ *     addition is rounded monotonically.  So the smallest qualifying v is well defined and a bisection finds it.
+ *   - if no x is NaN, F_p(max) is sum_w bit for bit (the same additions), and q_i * sum_w <= sum_w: q = 1 gives the maximum
+ *     over S and q = 0 the minimum.
+ * Consequences:
+ *   - cut = 0 and a unique minimum: every quantile is params[best_idx] exactly.
+ *   - all weights of an observation zero: omega = 1 and every sum an exact integer, so for dyadic q the result is
+ *     sort(x)[max(ceil(q n) - 1, 0)] exactly.  q = 0.5 is therefore the LOWER median, not spart_lut_summarise's averaged one.
+ *   - quantiles are non-decreasing in q; levels need not be sorted or distinct, and a level's result does not depend on the
+ *     others.
+ *   - the same bits with brute_force 0 or 1, in any batch and in any chunk.
+ * Refused as spart_lut_bayes refuses, in its order; behind the NULL check of opt and out, SPART_ERR_INVALID for nq outside
+ * 1 ... 8, a NULL levels, and a level that is NaN or outside [0, 1] (the message names the first such index).  "Every output
+ * is NULL" counts quant as an eighth output; quant == NULL with another output given is accepted and the call is then
+ * spart_lut_bayes.  M = 0 launches nothing; B = 0 with M > 0 writes NaN to quant beside the empty outputs.  The workspace is
+ * spart_lut_bayes_workspace_bytes', and spart_lut_bayes_stats reads it afterwards as before: the stats of a quantile call equal
+ * those of the plain call on the same inputs.
+ * How (csrc/spart_lut.h, "weighted quantiles of the posterior"): a second one-wave-per-observation kernel behind each
+ * spart_lut_bayes kernel reads the same candidate lists, lane = parameter, and bisects every level of every parameter at once
+ * on the order-preserving integer image of the doubles, one pass over S per step with the interval ends snapped to data values:
+ * about log2(count) passes, never more than 64. */
+typedef struct spart_lut_bayes_q_opt {
+  spart_lut_bayes_opt base;
+  int32_t nq;           /* 1 ... 8 */
+  const double *levels; /* HOST (nq,), each in [0, 1] */
+} spart_lut_bayes_q_opt;
+typedef struct spart_lut_bayes_q_out {
+  spart_lut_bayes_out base;
+  double *quant; /* (M, P, nq) row-major, device; may be NULL */
+} spart_lut_bayes_q_out;
+int spart_lut_bayes_quantiles(spart_ctx *ctx, int dtype, int64_t B, int nb, const void *lut, int P, const double *params, int64_t M,
+                              const void *obs, const void *weights, const spart_lut_bayes_q_opt *opt,
+                              const spart_lut_bayes_q_out *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Parameter summaries of the rows a top-k search selected (what a LUT retrieval reports: maps of LAI, Cab, ... with a spread;
  * no reference counterpart).  params (B, P) float64 row-major, the LUT's parameter table; idx (M, k) int64, the output of any

@@ -928,6 +928,45 @@ static int lut_bayes_impl(int dtype, int64_t B, int nb, const void* lut_, int P,
       });
 }
 
+// spart_lut_bayes_quantiles once its arguments are checked: lut_bayes_impl's pipeline and launches, with k_lut_posterior_quant
+// (csrc/spart_lut.h, "weighted quantiles of the posterior") queued behind every k_lut_bayes over the same chunk or flag list.
+template <typename T>
+static int lut_bayes_quant_impl(int dtype, int64_t B, int nb, const void* lut_, int P, const double* params, int64_t M,
+                                const void* obs_, const void* weights, const spart_lut_bayes_opt& opt, const LutBayesOut& out,
+                                const LutBayesLevels& lv, double* quant, char* wsp, hipStream_t st) {
+  constexpr int ROWS = LutWide<T>::ROWS;
+  const T *lut = (const T*)lut_, *obs = (const T*)obs_, *w = (const T*)weights;
+  const double two_tau = 2.0 * (opt.temperature == 0.0 ? 1.0 : opt.temperature);
+  const double cut = opt.cut;
+  const int force = opt.brute_force;
+  const size_t lds = lut_bayes_lds_bytes(nb, sizeof(T));
+  return lut_wide_impl<T, true>(
+      dtype, B, nb, lut_, M, obs_, weights, LUT_BAYES_CAPK, 1, cut * (1.0 + 0x1p-50), force == 0, wsp, st,
+      [=](bool brute, int64_t m0, int64_t mc, const LutWideLayout& L, char* ws, hipStream_t s) {
+        unsigned long long* ctl = (unsigned long long*)(ws + L.ctl);
+        int* flags = (int*)(ws + L.flags);
+        const T* norm = (const T*)(ws + L.norm);
+        if (!brute) {
+          hipLaunchKernelGGL((k_lut_bayes<T, ROWS, false>), dim3((unsigned)mc), dim3(64), lds, s, lut, obs, w, norm, params, nb, B, P,
+                             m0, mc, cut, two_tau, force, (const T*)(ws + L.thr), (const int*)(ws + L.cn),
+                             (const int*)(ws + L.cand), L.cap, ctl, flags, out);
+          HIP_TRY(hipGetLastError());
+          hipLaunchKernelGGL((k_lut_posterior_quant<T, ROWS, false>), dim3((unsigned)mc), dim3(64), lds, s, lut, obs, w, norm, params, nb,
+                             B, P, m0, mc, cut, two_tau, force, (const T*)(ws + L.thr), (const int*)(ws + L.cn),
+                             (const int*)(ws + L.cand), L.cap, (const unsigned long long*)ctl, (const int*)flags, lv, quant);
+        } else {
+          hipLaunchKernelGGL((k_lut_bayes<T, ROWS, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), lds, s, lut, obs, w, norm, params, nb,
+                             B, P, (int64_t)0, M, cut, two_tau, force, (const T*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                             L.cap, ctl, flags, out);
+          HIP_TRY(hipGetLastError());
+          hipLaunchKernelGGL((k_lut_posterior_quant<T, ROWS, true>), dim3(LUTW_SELECT_BLOCKS), dim3(64), lds, s, lut, obs, w, norm,
+                             params, nb, B, P, (int64_t)0, M, cut, two_tau, force, (const T*)nullptr, (const int*)nullptr,
+                             (const int*)nullptr, L.cap, (const unsigned long long*)ctl, (const int*)flags, lv, quant);
+        }
+        return SPART_OK;
+      });
+}
+
 // The checks every batched entry point over B samples starts with, in this order (the LUT searches have lut_search's).
 // B == 0 passes them: the caller has nothing to do.  Otherwise `ws` is the layout of the call's workspace.
 static int gate(const spart_ctx* ctx, const char* who, int dtype, int64_t B, const void* workspace, size_t workspace_bytes,
@@ -2144,6 +2183,66 @@ int spart_lut_bayes(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lu
   return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
     return by_dtype(dtype, [&](auto t) {
       return lut_bayes_impl<decltype(t)>(dtype, B, nb, lut, P, params, M, obs, weights, *opt, o, (char*)workspace, st);
+    });
+  });
+}
+
+// (spart_lut_bayes' checks in its order, with the levels behind the NULL check of opt and out and quant as an eighth output)
+int spart_lut_bayes_quantiles(spart_ctx* ctx, int dtype, int64_t B, int nb, const void* lut, int P, const double* params, int64_t M,
+                              const void* obs, const void* weights, const spart_lut_bayes_q_opt* qopt,
+                              const spart_lut_bayes_q_out* qout, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_lut_bayes_quantiles";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (!dtype_ok(dtype)) return fail(SPART_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  if (B < 0 || M < 0 || !LUT_OBSW.nb_ok(nb) || P < 1 || P > LUT_BAYES_MAXP || B > 2000000000LL || M > 2000000000LL)
+    return fail(SPART_ERR_INVALID, "%s: bad sizes (B=%lld M=%lld nb=%d P=%d; 1 <= nb <= %d, 1 <= P <= %d, B and M <= 2e9)", who,
+                (long long)B, (long long)M, nb, P, LUT_OBSW.nb_max, LUT_BAYES_MAXP);
+  if (!qopt || !qout) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  if (qopt->nq < 1 || qopt->nq > LUT_BAYES_MAXQ)
+    return fail(SPART_ERR_INVALID, "%s: nq = %d, expected 1 <= nq <= %d", who, qopt->nq, LUT_BAYES_MAXQ);
+  if (!qopt->levels) return fail(SPART_ERR_INVALID, "%s: null levels", who);
+  LutBayesLevels lv = {};
+  lv.nq = qopt->nq;
+  for (int i = 0; i < lv.nq; ++i) {
+    lv.q[i] = qopt->levels[i];
+    if (!(lv.q[i] >= 0.0 && lv.q[i] <= 1.0))
+      return fail(SPART_ERR_INVALID, "%s: levels[%d] = %g, expected a level in [0, 1]", who, i, lv.q[i]);
+  }
+  const spart_lut_bayes_opt* opt = &qopt->base;
+  const spart_lut_bayes_out* out = &qout->base;
+  if (!(opt->cut >= 0.0)) return fail(SPART_ERR_INVALID, "%s: cut = %g, expected >= 0 (or +inf)", who, opt->cut);
+  if (!(opt->temperature >= 0.0) || std::isinf(opt->temperature))
+    return fail(SPART_ERR_INVALID, "%s: temperature = %g, expected 0 (= 1.0) or finite > 0", who, opt->temperature);
+  if (opt->brute_force != 0 && opt->brute_force != 1)
+    return fail(SPART_ERR_INVALID, "%s: brute_force = %d, expected 0 or 1", who, opt->brute_force);
+  if (M == 0) return SPART_OK;                         // (the (0,) outputs of an empty batch have no address)
+  double* quant = qout->quant;
+  if (!out->mean && !out->std && !out->sum_w && !out->ess && !out->count && !out->best_idx && !out->best_cost && !quant)
+    return fail(SPART_ERR_INVALID, "%s: every output is NULL", who);
+  const LutBayesOut o = {out->mean, out->std, out->sum_w, out->ess, out->count, out->best_idx, out->best_cost};
+  if (B == 0)                                          // no row: every observation gets the empty outputs, every quantile NaN
+    return guarded(ctx, who, nullptr, 0, stream, [&](hipStream_t st) {
+      return by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((k_lut_bayes_empty<decltype(t)>), dim3((unsigned)(M < 65536 ? M : 65536)), dim3(64), 0, st, M, P, o);
+        HIP_TRY(hipGetLastError());
+        if (quant) {
+          const int64_t n = M * P * lv.nq, blocks = (n + 255) / 256;
+          hipLaunchKernelGGL(k_lut_posterior_quant_empty, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, n, quant);
+          HIP_TRY(hipGetLastError());
+        }
+        return SPART_OK;
+      });
+    });
+  if (!lut || !params || !obs || !weights) return fail(SPART_ERR_INVALID, "%s: null argument", who);
+  const size_t need = spart_lut_bayes_workspace_bytes(dtype, B, nb, M);
+  if (!workspace || workspace_bytes < need)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+  return guarded(ctx, who, workspace, need, stream, [&](hipStream_t st) {
+    return by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      if (!quant)                                      // no quantile asked for: the call is spart_lut_bayes
+        return lut_bayes_impl<T>(dtype, B, nb, lut, P, params, M, obs, weights, *opt, o, (char*)workspace, st);
+      return lut_bayes_quant_impl<T>(dtype, B, nb, lut, P, params, M, obs, weights, *opt, o, lv, quant, (char*)workspace, st);
     });
   });
 }

@@ -2161,4 +2161,281 @@ __global__ __launch_bounds__(64) void k_lut_bayes(const T* __restrict__ lut, con
   }
 }
 
+// ---- weighted quantiles of the posterior (spart_lut_bayes_quantiles): for observation m, parameter p and level q_i the
+// smallest value v among {x_b = params[b, p] : b in S} with F_p(v) >= q_i * sum_w, where F_p(v) is the ordered float64 sum of
+// omega_b over the rows of S with x_b <= v (include/spart_hip.h defines it; E, c*, S, omega and sum_w are k_lut_bayes').
+//
+// k_lut_posterior_quant is a SECOND consumer of the same candidate lists, queued right after k_lut_bayes for the same chunk (the
+// lists stay in the workspace until the next chunk's collect pass) and once more after the last chunk over the flag list.  It
+// reaches k_lut_bayes' decisions by the same reads and writes nothing but quant: a forced, overflowing or non-finite-threshold
+// observation, and one without a finite cost among its candidates, is skipped by the filter instance (k_lut_bayes flagged it)
+// and picked up by the brute instance from flag_list; ctl and flag_list are read only.
+//   sort, row_of, pass A   k_lut_bayes', line for line: the same rows in the same order, the same c*
+//   pass 0   pass B's loop (ballot of e <= cut, the included rows one at a time in row order, lane p reads params[r P + p]):
+//            sum_w by the same additions (the same bits), per lane the minimum and maximum of x, a NaN flag and the first zero
+//            of the column (the sign a zero answer takes).  While they fit, (row, omega) of the included rows go to the part of
+//            the LDS tile buffer the sorted list does not use (all of it in the brute instance): later passes then read the
+//            members back instead of evaluating every row's cost again.  A set that does not fit is never truncated: its passes
+//            recompute, as k_lut_bayes' do; omega is a pure function of the row, so the bits are the same either way.
+//   search   per lane and level an interval [lo, hi] of DATA values that holds the answer, on the order-preserving unsigned
+//            64-bit image of the doubles (-0.0 and +0.0 share one image).  A pass takes pivot = lo + (hi - lo) / 2 for every
+//            level of every lane at once and gives F(pivot), the largest x <= pivot and the smallest x > pivot; F(pivot) >=
+//            target moves hi to the former, otherwise lo to the latter.  hi - lo at least halves per pass, so 64 passes bound
+//            the loop for any data; the snap to data values ends it after about log2(count) passes on spread-out columns.
+//            F is non-decreasing in v (an ordered sum of non-negative terms over a larger subset is never smaller), so the
+//            bisection finds THE smallest qualifying value; F(max) is sum_w by the same additions, so hi = max qualifies.
+//   The loop runs while any (lane, level) is open (__any: wave-uniform); LUT_BAYES_QG levels are searched together, a call
+//   with more takes the search again for the next group.
+constexpr int LUT_BAYES_MAXQ = 8;                     // levels per call
+constexpr int LUT_BAYES_QG = 4;                       // levels searched together (registers: 7 doubles per level and lane)
+
+struct LutBayesLevels {                               // spart_lut_bayes_q_opt.levels, by value
+  double q[LUT_BAYES_MAXQ];
+  int nq;
+};
+
+// the order-preserving image of a non-NaN double (both zeros -> the image of +0.0) and its inverse
+__device__ __forceinline__ unsigned long long lut_bayes_key(double x) {
+  unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  if ((b << 1) == 0ull) b = 0ull;
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double lut_bayes_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// B = 0: every quantile is NaN
+__global__ __launch_bounds__(256) void k_lut_posterior_quant_empty(int64_t n, double* __restrict__ quant) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) quant[i] = __builtin_nan("");
+}
+
+template <typename T, int ROWS, bool BRUTE>
+__global__ __launch_bounds__(64) void k_lut_posterior_quant(const T* __restrict__ lut, const T* __restrict__ obs,
+                                                        const T* __restrict__ w, const T* __restrict__ norm,
+                                                        const double* __restrict__ params, int nb, int64_t B, int P, int64_t m_off,
+                                                        int64_t Mc, double cut, double two_tau, int force,
+                                                        const T* __restrict__ thr, const int* __restrict__ cand_n,
+                                                        const int* __restrict__ cand, int cap,
+                                                        const unsigned long long* __restrict__ ctl,
+                                                        const int* __restrict__ flag_list, LutBayesLevels lv,
+                                                        double* __restrict__ quant) {
+  SPART_NO_CONTRACT
+  extern __shared__ __attribute__((aligned(16))) char lutq_smem[];
+  int* tiles = reinterpret_cast<int*>(lutq_smem);
+  T* ys = reinterpret_cast<T*>(tiles + LUT_BAYES_SORT);
+  T* wsm = ys + nb;
+  const int lane = threadIdx.x & 63;
+  const int nq = lv.nq;
+  const double qnan = __builtin_nan("");
+  const unsigned count = BRUTE ? (unsigned)ctl[1] : 0u;
+  const int64_t nwork = BRUTE ? (int64_t)count : Mc;
+  const int64_t stride_w = BRUTE ? (int64_t)gridDim.x : nwork;
+  for (int64_t item = blockIdx.x; item < nwork; item += stride_w) {
+    const int64_t m = BRUTE ? (int64_t)flag_list[item] : m_off + item;
+    auto all_nan = [&] {
+      if (lane < P)
+        for (int i = 0; i < nq; ++i) quant[(m * P + lane) * nq + i] = qnan;
+    };
+    lut_wave_sync();                                   // (the previous item's reads of ys / tiles are done)
+    bool fin = true;
+    for (int j = lane; j < nb; j += 64) {
+      const T v = obs[m * nb + j], wj = w[m * nb + j];
+      ys[j] = v;
+      wsm[j] = wj;
+      fin = fin && wj >= T(0) && LutNum<T>::finite(wj) && (wj == T(0) || LutNum<T>::finite(v));
+    }
+    lut_wave_sync();
+    if (__all(fin) == 0) {                             // an invalid observation matches no row
+      all_nan();
+      continue;
+    }
+    int64_t nrows = B;
+    int ncand = 0;
+    if (!BRUTE) {
+      if (force != 0) continue;                        // (k_lut_bayes flagged it: the brute instance's)
+      ncand = cand_n[item];
+      if (!LutNum<T>::finite(thr[item]) || ncand > cap) continue;
+      // the candidate tiles in ascending order (bitonic, n2 = the power of two >= ncand, padded with INT_MAX)
+      int n2 = 2;
+      while (n2 < ncand) n2 <<= 1;
+      for (int i = lane; i < n2; i += 64) tiles[i] = i < ncand ? cand[item * cap + i] : 0x7fffffff;
+      lut_wave_sync();
+      for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+          for (int i = lane; i < n2 / 2; i += 64) {
+            const int t = ((i & ~(stride - 1)) << 1) | (i & (stride - 1));
+            const int p = t | stride;
+            const int vt = tiles[t], vp = tiles[p];
+            if ((vp < vt) == ((t & size) == 0)) {
+              tiles[t] = vp;
+              tiles[p] = vt;
+            }
+          }
+          lut_wave_sync();
+        }
+      nrows = (int64_t)ncand * ROWS;
+    }
+    // this lane's row of the round that starts at r0, or -1: range- and norm-checked, ascending with the lane
+    auto row_of = [&](int64_t r0) -> int {
+      int64_t r = -1;
+      if (BRUTE) {
+        r = r0 + lane;
+      } else {
+        const int ci = (int)(r0 / ROWS) + lane / ROWS;
+        if (ci < ncand) {
+          const int tl = tiles[ci];
+          if (tl >= 0) r = (int64_t)tl * ROWS + lane % ROWS;
+        }
+      }
+      if (r < 0 || r >= B) return -1;
+      return LutNum<T>::finite(norm[r]) ? (int)r : -1;
+    };
+    // pass A: c* (its row only says whether E is empty here)
+    T bc = (T)INFINITY;
+    int br = -1;
+    for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+      const int r = row_of(r0);
+      if (r >= 0) {
+        const T c = lut_bayes_cost<T>(lut + (int64_t)r * nb, ys, wsm, nb);
+        if (LutNum<T>::finite(c) && c < bc) {
+          bc = c;
+          br = r;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const T oc = __shfl_xor(bc, off, 64);
+      const int orow = __shfl_xor(br, off, 64);
+      if (orow >= 0 && (br < 0 || oc < bc || (oc == bc && orow < br))) {
+        bc = oc;
+        br = orow;
+      }
+    }
+    if (br < 0) {                                      // E is empty among these rows
+      if (BRUTE) all_nan();                            // (filter instance: flagged by k_lut_bayes, the brute instance's)
+      continue;
+    }
+    const double cstar = (double)bc;
+    // the (row, omega) cache: the 8-byte-aligned rest of the tile buffer behind the ncand sorted tile numbers
+    const int c_off = BRUTE ? 0 : (ncand + 1) & ~1;    // in ints
+    const int c_cap = (LUT_BAYES_SORT - c_off) / 3;    // 12 bytes per member
+    double* c_om = reinterpret_cast<double*>(tiles + c_off);
+    int* c_row = tiles + c_off + 2 * c_cap;
+    // one pass over S in row order without the cache: feed(row, omega) is called by the whole wave, member by member
+    auto recompute = [&](auto&& feed) {
+      for (int64_t r0 = 0; r0 < nrows; r0 += 64) {
+        const int r = row_of(r0);
+        bool inc = false;
+        double om = 0.0;
+        if (r >= 0) {
+          const T c = lut_bayes_cost<T>(lut + (int64_t)r * nb, ys, wsm, nb);
+          if (LutNum<T>::finite(c)) {
+            const double e = (double)c - cstar;
+            if (e <= cut) {
+              inc = true;
+              om = Mx<double>::exp_poly(-(e / two_tau));
+            }
+          }
+        }
+        unsigned long long mask = __ballot(inc);
+        while (mask) {
+          const int src = __builtin_ctzll(mask);
+          mask &= mask - 1;
+          feed(__shfl(r, src, 64), __shfl(om, src, 64));
+        }
+      }
+    };
+    // pass 0: sum_w, the range of every column, its NaN flag and first zero; fills the cache while the members fit
+    double sw = 0.0, zfirst = 0.0;
+    unsigned long long kmin = ~0ull, kmax = 0ull;
+    bool has_nan = false, zseen = false;
+    int n = 0;
+    recompute([&](int rr, double o) {
+      const double x = lane < P ? params[(int64_t)rr * P + lane] : 0.0;
+      if (n < c_cap && lane == 0) {
+        c_om[n] = o;
+        c_row[n] = rr;
+      }
+      ++n;
+      sw = sw + o;
+      has_nan = has_nan || x != x;
+      if (x == 0.0 && !zseen) {
+        zseen = true;
+        zfirst = x;
+      }
+      const unsigned long long kx = lut_bayes_key(x);
+      kmin = kx < kmin ? kx : kmin;
+      kmax = kx > kmax ? kx : kmax;
+    });
+    const bool cached = n <= c_cap;
+    lut_wave_sync();                                   // (lane 0's cache entries are visible to the wave)
+    for (int g0 = 0; g0 < nq; g0 += LUT_BAYES_QG) {
+      unsigned long long lo[LUT_BAYES_QG], hi[LUT_BAYES_QG];
+      double tg[LUT_BAYES_QG];
+#pragma unroll
+      for (int u = 0; u < LUT_BAYES_QG; ++u) {
+        const bool live = g0 + u < nq && lane < P && !has_nan;
+        tg[u] = lv.q[g0 + u < nq ? g0 + u : g0] * sw;
+        lo[u] = kmin;
+        hi[u] = live ? kmax : kmin;
+      }
+      for (int it = 0; it < 64; ++it) {                // (hi - lo at least halves per pass: never more than 64)
+        bool open = false;
+#pragma unroll
+        for (int u = 0; u < LUT_BAYES_QG; ++u) open = open || lo[u] < hi[u];
+        if (__any(open) == 0) break;
+        unsigned long long piv[LUT_BAYES_QG], bel[LUT_BAYES_QG], abv[LUT_BAYES_QG];
+        double F[LUT_BAYES_QG];
+#pragma unroll
+        for (int u = 0; u < LUT_BAYES_QG; ++u) {
+          piv[u] = lo[u] + ((hi[u] - lo[u]) >> 1);
+          bel[u] = lo[u];
+          abv[u] = hi[u];
+          F[u] = 0.0;
+        }
+        auto feed = [&](double x, double o) {
+          const unsigned long long kx = lut_bayes_key(x);
+#pragma unroll
+          for (int u = 0; u < LUT_BAYES_QG; ++u) {
+            const bool le = kx <= piv[u];
+            F[u] = F[u] + (le ? o : 0.0);              // (a row that does not qualify adds +0.0: no change to F >= 0)
+            bel[u] = le && kx > bel[u] ? kx : bel[u];
+            abv[u] = !le && kx < abv[u] ? kx : abv[u];
+          }
+        };
+        if (cached) {
+          for (int j0 = 0; j0 < n; j0 += 4) {          // four parameter rows in flight
+            double xs[4], os[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+              const int j = j0 + v < n ? j0 + v : j0;
+              os[v] = c_om[j];
+              xs[v] = lane < P ? params[(int64_t)c_row[j] * P + lane] : 0.0;
+            }
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+              if (j0 + v < n) feed(xs[v], os[v]);
+          }
+        } else {
+          recompute([&](int rr, double o) { feed(lane < P ? params[(int64_t)rr * P + lane] : 0.0, o); });
+        }
+#pragma unroll
+        for (int u = 0; u < LUT_BAYES_QG; ++u)
+          if (lo[u] < hi[u]) {
+            if (F[u] >= tg[u]) hi[u] = bel[u];
+            else lo[u] = abv[u];
+          }
+      }
+#pragma unroll
+      for (int u = 0; u < LUT_BAYES_QG; ++u)
+        if (g0 + u < nq && lane < P) {
+          double v = lut_bayes_unkey(hi[u]);
+          if (v == 0.0) v = zfirst;                    // (of values that compare equal, the one in the lowest row)
+          quant[(m * P + lane) * nq + g0 + u] = has_nan ? qnan : v;
+        }
+    }
+  }
+}
+
 }  // namespace spart

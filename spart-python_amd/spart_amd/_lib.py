@@ -64,8 +64,17 @@ class SpartLutBayesOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("mean", "std", "sum_w", "ess", "count", "best_idx", "best_cost")]
 
 
+class SpartLutBayesQOpt(ctypes.Structure):
+    _fields_ = [("base", SpartLutBayesOpt), ("nq", ctypes.c_int32), ("levels", c_dp)]      # levels: HOST (nq,)
+
+
+class SpartLutBayesQOut(ctypes.Structure):
+    _fields_ = [("base", SpartLutBayesOut), ("quant", vp)]
+
+
 LUT_BAYES_OUTS = tuple(n for n, _ in SpartLutBayesOut._fields_)      # spart_lut_bayes_out, in its order
 LUT_BAYES_MAXP = 64
+LUT_BAYES_MAXQ = 8                                  # spart_lut_bayes_q_opt.nq
 POSTERIOR_OUTS = tuple(n for n, _ in SpartPosteriorOut._fields_)     # spart_posterior_out, in its order
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
 REFINE_MAXF, REFINE_MAX_ITER = 16, 100
@@ -123,6 +132,9 @@ SIGNATURES = {
                                                               ctypes.POINTER(SpartLutBayesOpt), ctypes.POINTER(SpartLutBayesOut),
                                                               vp, ctypes.c_size_t, vp]),
     "spart_lut_bayes_stats": (ctypes.c_int, [vp] + _LUT_SIZES + [vp, c_i64p, c_i64p, c_i64p, c_dp]),
+    "spart_lut_bayes_quantiles": (ctypes.c_int, [vp] + _LUT_SIZES[:3] + [vp, ctypes.c_int, vp, ctypes.c_int64, vp, vp,
+                                                                        ctypes.POINTER(SpartLutBayesQOpt),
+                                                                        ctypes.POINTER(SpartLutBayesQOut), vp, ctypes.c_size_t, vp]),
     "spart_refine_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
     "spart_refine": (ctypes.c_int, _REFINE_CALL),
     "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),

@@ -607,6 +607,17 @@ def sensor_block(sensor_info):
 
 
 
+def quantile_levels(quantiles):
+    """Engine.lut_bayes(quantiles=...): a sequence of 1 ... 8 floats in [0, 1] -> a list of floats; anything else is a ValueError"""
+    try:
+        levels = [float(q) for q in quantiles]
+    except (TypeError, ValueError):
+        raise ValueError(f"quantiles = {quantiles!r}, expected a sequence of 1 ... {_lib.LUT_BAYES_MAXQ} levels in [0, 1]") from None
+    if not 1 <= len(levels) <= _lib.LUT_BAYES_MAXQ or not all(0.0 <= q <= 1.0 for q in levels):
+        raise ValueError(f"quantiles = {quantiles!r}, expected 1 ... {_lib.LUT_BAYES_MAXQ} levels, each in [0, 1]")
+    return levels
+
+
 class Engine:
     def __init__(self, sensor=None, device=0, sensor_info=None, lib_path=None, row_pitch=ROW_PITCH, optical_params=None,
                  et_params=None, need=OPTICAL_KEYS):
@@ -1092,7 +1103,8 @@ class Engine:
         _lib.check(self.lib, self.ctx, rc)
         return res
 
-    def lut_bayes(self, lut, params, obs, weights=None, cut=50.0, temperature=1.0, dtype="float32", stats=False, brute_force=False):
+    def lut_bayes(self, lut, params, obs, weights=None, cut=50.0, temperature=1.0, dtype="float32", stats=False, brute_force=False,
+                  quantiles=None):
         """The likelihood-weighted LUT estimate (include/spart_hip.h: spart_lut_bayes, which pins every sum): every accepted row b
         of lut (B, nb) whose cost lies within ``cut`` of the best one, e_b = c(b) - c* <= cut, gets the weight
         exp(-e_b / (2 temperature)); the cost is lut_topk's with (M, nb) weights (chi^2 when the weights are 1 / sigma^2).
@@ -1103,7 +1115,13 @@ class Engine:
         ``dtype`` (lut_topk(k=1)'s, bit for bit); an observation that matches nothing gets count 0, best_idx -1, best_cost inf,
         sum_w 0 and NaN.  ``brute_force=True`` sends every observation through the brute-force kernel (the same result bit for
         bit).  With ``stats=True`` -> (dict, stats): brute-forced observations, candidate tiles (sum and maximum) and "nbound"
-        (spart_lut_bayes_stats; synchronises)."""
+        (spart_lut_bayes_stats; synchronises).
+        ``quantiles``: None, or 1 ... 8 levels in [0, 1] (ValueError otherwise, before any GPU work): the call is then
+        spart_lut_bayes_quantiles and the dict gains "quantiles", (M, P, Q) float64 -- per parameter and level the smallest
+        value of the column whose omega-weighted share of the set reaches the level (the inverted-CDF quantile: a table value,
+        0.5 the lower median; NaN where the column holds a NaN over the set or nothing matched); every other entry is the same
+        bits as without."""
+        levels = None if quantiles is None else quantile_levels(quantiles)
         torch = self.torch
         dt = DTYPES[dtype]
         td = self._tdtype(dt)
@@ -1132,9 +1150,18 @@ class Engine:
         out = _lib.SpartLutBayesOut(*[res[n].data_ptr() for n in _lib.LUT_BAYES_OUTS])
         nbytes = max(self.lib.spart_lut_bayes_workspace_bytes(dt, B, nb, M), 256)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self.calls["spart_lut_bayes"] += 1
-        rc = self.lib.spart_lut_bayes(self.ctx, dt, B, nb, lut.data_ptr(), P, params.data_ptr(), M, obs.data_ptr(), w.data_ptr(),
-                                      ctypes.byref(opt), ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
+        if levels is None:
+            self.calls["spart_lut_bayes"] += 1
+            rc = self.lib.spart_lut_bayes(self.ctx, dt, B, nb, lut.data_ptr(), P, params.data_ptr(), M, obs.data_ptr(), w.data_ptr(),
+                                          ctypes.byref(opt), ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
+        else:
+            res["quantiles"] = torch.empty((M, P, len(levels)), dtype=torch.float64, device=self.device)
+            qopt = _lib.SpartLutBayesQOpt(opt, len(levels), (ctypes.c_double * len(levels))(*levels))
+            qout = _lib.SpartLutBayesQOut(out, res["quantiles"].data_ptr())
+            self.calls["spart_lut_bayes_quantiles"] += 1
+            rc = self.lib.spart_lut_bayes_quantiles(self.ctx, dt, B, nb, lut.data_ptr(), P, params.data_ptr(), M, obs.data_ptr(),
+                                                    w.data_ptr(), ctypes.byref(qopt), ctypes.byref(qout), ws.data_ptr(), nbytes,
+                                                    self._stream())
         _lib.check(self.lib, self.ctx, rc)
         if not stats:
             return res

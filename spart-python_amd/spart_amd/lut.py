@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, params_rows,
-                     prior_arrays, refine_args, refine_plan, refine_tiles_args, refine_views_args)
+                     prior_arrays, quantile_levels, refine_args, refine_plan, refine_tiles_args, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -626,7 +626,7 @@ def _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info):
     return plan, opts, meta.get("sensor"), sensor_info
 
 
-BAYES_OPTS = ("cut", "temperature")
+BAYES_OPTS = ("cut", "temperature", "quantiles")
 BAYES_KEYS = {"bayes_mean": "mean", "bayes_std": "std", "bayes_ess": "ess", "bayes_sum_w": "sum_w", "bayes_count": "count"}
 
 
@@ -644,21 +644,26 @@ def _bayes_setup(bayes, shard=False, group=None):
         raise ValueError(f'bayes["cut"] = {opts["cut"]}, expected >= 0 (inf: every accepted row)')
     if not (0 < opts["temperature"] < np.inf):
         raise ValueError(f'bayes["temperature"] = {opts["temperature"]}, expected finite and > 0')
+    if bayes.get("quantiles") is not None:                         # (the key is there only when asked for)
+        opts["quantiles"] = quantile_levels(bayes["quantiles"])
     if _group_info(shard, group)[0] > 1:
         raise ValueError("retrieve(bayes=...) does not take shard=True under a process group of more than one rank: every rank "
                          "holds only its own rows (the sharded posterior is not built yet)")
     return opts
 
 
-def _bayes_shapes(M, P):
+def _bayes_shapes(M, P, opts=None):
+    """the bayes_* outputs of M observations and P parameter columns; ``opts`` (_bayes_setup's) with levels: bayes_quantiles too"""
+    nq = len((opts or {}).get("quantiles") or ())
     return {"bayes_mean": ((M, P), np.float64), "bayes_std": ((M, P), np.float64), "bayes_ess": ((M,), np.float64),
-            "bayes_sum_w": ((M,), np.float64), "bayes_count": ((M,), np.int64)}
+            "bayes_sum_w": ((M,), np.float64), "bayes_count": ((M,), np.int64),
+            **({"bayes_quantiles": ((M, P, nq), np.float64)} if nq else {})}
 
 
 def _bayes_maps(eng, lut_t, par_t, obs_t, weights, dtype, opts):
     """Engine.lut_bayes -> its BAYES_KEYS tensors"""
     r = eng.lut_bayes(lut_t, par_t, obs_t, weights=weights, dtype=dtype, **opts)
-    return {key: r[name] for key, name in BAYES_KEYS.items()}
+    return {**{key: r[name] for key, name in BAYES_KEYS.items()}, **({"bayes_quantiles": r["quantiles"]} if "quantiles" in r else {})}
 
 
 def _retrieve_bayes(lut_dir, obs, column, weights, device, cols, opts):
@@ -670,7 +675,7 @@ def _retrieve_bayes(lut_dir, obs, column, weights, device, cols, opts):
     npdt = _np_dtype(meta["dtype"])
     M, B = np.shape(obs)[0], table.shape[0]
     if B == 0 or M == 0:
-        return _unmatched(_bayes_shapes(M, len(cols)))
+        return _unmatched(_bayes_shapes(M, len(cols), opts))
     eng = get_engine(None, device)
     o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=_torch_dtype(npdt))
     w = None if weights is None else _host_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
@@ -680,6 +685,7 @@ def _retrieve_bayes(lut_dir, obs, column, weights, device, cols, opts):
 # what an observation that matches nothing gets, by output name (retrieve, retrieve_stream and the fit)
 _EMPTY = {"idx": -1, "cost": np.inf, "best_cost": np.inf, "mean": np.nan, "median": np.nan, "std": np.nan, "count": 0,
           "bayes_mean": np.nan, "bayes_std": np.nan, "bayes_ess": np.nan, "bayes_sum_w": 0.0, "bayes_count": 0,
+          "bayes_quantiles": np.nan,
           "refined": np.nan, "refined_std": np.nan, "refined_cost": np.nan, "refined_cost0": np.nan, "refined_accepts": -1,
           "refined_cov": np.nan, "refined_ak": np.nan, "refined_dfs": np.nan}
 
@@ -803,13 +809,17 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     meta.json's ``sensor``, or ``sensor_info=`` for a LUT of a custom sensor.  ValueError for a band model other than the
     LUT's and for ``shard=True`` under a process group of more than one rank (sharded refinement is not built yet).
 
-    ``bayes``: a dict with some of ``cut`` (default 50.0) and ``temperature`` (default 1.0); unknown keys are a ValueError.
+    ``bayes``: a dict with some of ``cut`` (default 50.0), ``temperature`` (default 1.0) and ``quantiles`` (1 ... 8 levels in
+    [0, 1]); unknown keys are a ValueError.
     The likelihood-weighted estimate over EVERY accepted row whose cost lies within ``cut`` of the best one
     (Engine.lut_bayes / spart_lut_bayes; weight exp(-(c - c*) / (2 temperature))), not just the k nearest: the result gains
     ``bayes_mean``, ``bayes_std`` (M, P over ``params_cols``), ``bayes_ess`` (the effective sample size: is the LUT dense enough
     for this noise?), ``bayes_sum_w`` and ``bayes_count`` (M,) int64; every other key stays bit for bit.  It goes with either
     ``summary`` and uploads the column and the parameter columns once more; a pixel that matches nothing gets NaN, sum_w 0 and
-    count 0.  ``shard=True`` under a process group of more than one rank: ValueError (the sharded posterior is not built yet)."""
+    count 0.  ``shard=True`` under a process group of more than one rank: ValueError (the sharded posterior is not built yet).
+    With ``"quantiles": [0.05, 0.5, 0.95]`` the result also gains ``bayes_quantiles`` (M, P, Q over ``params_cols``): the
+    weighted quantiles of each parameter over the same rows (spart_lut_bayes_quantiles: inverted CDF, always a table value;
+    NaN where nothing matched), a median and a credible interval where mean and std mislead."""
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
@@ -988,7 +998,8 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
 
     ``bayes`` as for retrieve: one more call per chunk (Engine.lut_bayes on the chunk's own buffers, the LUT and the parameter
     columns already on the device); the result (and ``out``) gains ``bayes_mean``, ``bayes_std``, ``bayes_ess``,
-    ``bayes_sum_w`` and ``bayes_count`` as maps, each equal to retrieve(bayes=...)'s bit for bit whatever the chunk size."""
+    ``bayes_sum_w`` and ``bayes_count`` as maps (and ``bayes_quantiles`` (M, P, Q) with ``"quantiles"``), each equal to
+    retrieve(bayes=...)'s bit for bit whatever the chunk size."""
     bayes = _bayes_setup(bayes)
     setup = _refine_setup(lut_dir, refine, refine_opts, False, None, sensor_info)
     meta, params, tabs = load_lut(lut_dir)
@@ -1004,7 +1015,7 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     if weights is not None and not isinstance(weights, np.memmap):
         weights = np.asarray(weights)
     kind = lut_weights_kind(None if weights is None else weights.shape, M, nb)
-    shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt), **({} if bayes is None else _bayes_shapes(M, len(cols)))}
+    shapes = {**_summary_shapes(M, len(cols)), "best_cost": ((M,), npdt), **({} if bayes is None else _bayes_shapes(M, len(cols), bayes))}
     if setup is not None:
         shapes.update(_refined_shapes(M, len(setup[0]["names"]), bool(setup[1].get("posterior", False))))
     dict_prior = _dict_prior(setup, M)
