@@ -70,7 +70,7 @@ extern "C" {
  * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise, and
  * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out.
  * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too,
- * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged. */
+ * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -757,6 +757,54 @@ int spart_refine_posterior(spart_ctx *ctx, int64_t M, const double *const base[S
                            const double *lo, const double *hi /* HOST, (F,) */, const double *obs /* may be NULL */,
                            const double *weights, const spart_refine_opt *opt, int band_model /* 0 centre, 1 srf */,
                            const spart_posterior_out *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Canopy products of a parameter row: what a vegetation product publishes next to LAI (no reference counterpart).  Five
+ * numbers per sample, float64, each a deterministic function of the row's leaf, soil and canopy parameters and the sun zenith
+ * angle tts.  They do not depend on tto, psi, the atmosphere, DOY or a sensor: a context without a sensor (nb = 0) serves.
+ * A LUT carries them as further columns of its parameter table (spart_amd.lut_products), so that the k nearest rows or the
+ * posterior weights average the product itself and not the product of the averaged inputs.
+ * Definition (tools/products_defined.py is the same text in numpy on the oracle's operations).  For model band i = 0 ... 2000
+ * (400 + i nm): rho, tau the PROSPECT leaf, rs the wet BSM soil, tss = exp(-k LAI) (sailh.py:200), rho_dd, tau_dd, tau_sd,
+ * rho_sd of sailh.py:205-209, Ea the context's ET irradiance table.
+ *     d      = 1 - rs rho_dd
+ *     rsd    = rho_sd + (tss + tau_sd) rs tau_dd / d            sailh.py:232, what the library already returns
+ *     rdd    = rho_dd + tau_dd rs tau_dd / d                    sailh.py:233
+ *     a_s    = 1 - rsd - (1 - rs) (tss + tau_sd) / d            canopy absorptance, direct illumination
+ *     a_d    = 1 - rdd - (1 - rs) tau_dd / d                    canopy absorptance, diffuse illumination
+ *     fAPAR_bs  = sum_{i=0..300}  Ea_i a_s,i / sum_{i=0..300}  Ea_i       400-700 nm
+ *     fAPAR_ws  = the same with a_d
+ *     albedo_bs = sum_{i=0..2000} Ea_i rsd_i / sum_{i=0..2000} Ea_i       400-2400 nm
+ *     albedo_ws = the same with rdd
+ *     fCover    = 1 - exp(-LAI sum_{j=0..12} lidf_j cos(litab_j pi / 180))
+ * lidf is what spart_lidf_batch returns (the literal iteration), litab is sailh.py:49; the fCover exponent is the reference's
+ * volscatt at tto = 0, where chi_o = cos(theta_l).  The (1 - rs)(.) / d terms are the flux the soil absorbs, so each absorptance
+ * is an energy balance on the model's own fluxes.  The thermal evaluation takes no part.  A NaN in a parameter a product reads
+ * gives NaN (fCover reads LAI, LIDFa and LIDFb only; the other four read every leaf, soil and canopy parameter but q, and tts).
+ * One exception, as everywhere in the library: SMp and SMC enter through the test mu > 0 (bsm.py:101), which a NaN fails, so a
+ * NaN there is a dry soil.
+ * Blue-sky mixing, (1 - f_dif) bs + f_dif ws, is the caller's business.
+ * The model as it is.  sailh.py:189 has denom = 1 - rinf2 ** 2 where SAIL has 1 - rinf^2 e2, and the library reproduces the
+ * reference's line.  The isolated canopy therefore does not conserve energy: at LAI -> 0 tau_dd -> 1 / (1 + rinf^2), not 1, and
+ * fAPAR does not go to 0 with LAI (3e-4 at LAI = 1e-6); outside the PAR range a_s and a_d go slightly negative.  The products
+ * are defined on the model the reflectances come from (albedo_* are weighted means of the very rsd / rdd it materialises), and
+ * no physical limit is promised.
+ * Order of summation.  The two denominators are summed once in spart_ctx_create, float64, i ascending.  A numerator is four
+ * interleaved partial sums p_r over i = r (mod 4), each with i ascending from 0.0 and one fused multiply-add per band,
+ * p = fma(Ea_i, x_i, p), joined as (p_0 + p_1) + (p_2 + p_3); then one IEEE division.  The fCover sum runs j ascending with a
+ * multiplication and an addition per class.  A row's five values are therefore the same bits wherever the row stands in
+ * whatever batch.
+ * params: spart_run_batch's columns; params[0 ... 21] must not be NULL, params[22 ... 26] are not read and may be.  out: each
+ * member (B,) device memory, optional.  The workspace is spart_workspace_bytes(ctx, SPART_F64, B).  Refused before anything is
+ * launched or written, SPART_ERR_INVALID: a NULL out; with B > 0 all five outputs NULL, a NULL params or a NULL among
+ * params[0 ... 21] (the message names the first).  B = 0 launches nothing.  Float64 only; the prelude is the literal one.
+ * How (csrc/spart_products.h): the prelude's leaf, soil and canopy constants, then one kernel, lane = sample, the band
+ * wave-uniform; its canopy solve (canopy_flux) computes the four flux terms and nothing that depends on the view direction.
+ * Added WITHOUT a new interface number, by spart_refine_srf's rule: one more symbol and one new struct. */
+typedef struct spart_products_out {
+  double *fapar_bs, *fapar_ws, *albedo_bs, *albedo_ws, *fcover; /* each (B,) device, optional */
+} spart_products_out;
+int spart_products(spart_ctx *ctx, int64_t B, const double *const params[SPART_NPARAM], const spart_products_out *out,
+                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

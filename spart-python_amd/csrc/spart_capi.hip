@@ -23,6 +23,7 @@
 #include "spart_refine_posterior.h"
 #include "spart_refine_views.h"
 #include "spart_refine_tiles.h"
+#include "spart_products.h"
 
 using namespace spart;
 
@@ -46,6 +47,7 @@ struct spart_ctx {
   float* tabF = nullptr;    // (NTAB, NWL)
   double* tabD = nullptr;   // (NTAB, NWL)
   double* Ea = nullptr;     // (NWL)
+  double ea_par = 0.0, ea_all = 0.0;   // sum of Ea over bands 0 ... 300 / 0 ... 2000, float64, ascending (spart_products)
   int nb = 0;
   int pf = NWLS, po = NWL;  // row pitch (elements) of the 2162- / 2001-wide spectrum arrays (spart_ctx_set_row_pitch)
   int* band0 = nullptr;      // (nb) evaluation index of the np.interp support point at / below the band centre (k_columns)
@@ -1663,6 +1665,10 @@ int spart_ctx_create(spart_ctx** out, int device, const spart_tables* t) {
   int rc;
   std::vector<double> ea(t->Ea, t->Ea + NWL);
   if ((rc = upload(&ctx->tabD, tab)) || (rc = upload(&ctx->tabF, tabf)) || (rc = upload(&ctx->Ea, ea))) return rc;
+  for (int i = 0; i < NWL; ++i) {                   // the two denominators of spart_products
+    ctx->ea_all = ctx->ea_all + ea[i];
+    if (i == PRODUCTS_PAR_LAST) ctx->ea_par = ctx->ea_all;
+  }
 
   // --- sensor block
   ctx->nb = t->nb;
@@ -1990,6 +1996,27 @@ int spart_sailh_batch(spart_ctx* ctx, int dtype, int64_t B, const void* rho, con
     using T = decltype(t);
     hipLaunchKernelGGL((k_sailh<T, nt>), dim3((unsigned)(ws.nchunk * NTILE_FULL)), dim3(TILE), 0, st, cst, ws.Bp, B, ws.chunk,
                        ctx->pf, (const T*)rho, (const T*)tau, (const T*)rs, (T*)out4[0], (T*)out4[1], (T*)out4[2], (T*)out4[3]);
+  });
+}
+
+int spart_products(spart_ctx* ctx, int64_t B, const double* const params[SPART_NPARAM], const spart_products_out* out,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_products";
+  constexpr int NREAD = 22;                         // params[22 ... 26] (atmosphere, DOY) are not read
+  Workspace ws;
+  if (int rc = gate(ctx, who, SPART_F64, B, workspace, workspace_bytes, ws); rc) return rc;
+  if (!out) return fail(SPART_ERR_INVALID, "%s: null out", who);
+  if (B == 0) return SPART_OK;
+  if (!out->fapar_bs && !out->fapar_ws && !out->albedo_bs && !out->albedo_ws && !out->fcover)
+    return fail(SPART_ERR_INVALID, "%s: every output is null", who);
+  if (!params) return fail(SPART_ERR_INVALID, "%s: null params", who);
+  if (int i = first_null(params, NREAD); i < NREAD) return fail(SPART_ERR_INVALID, "%s: params[%d] is null", who, i);
+  const ProductsOut po{out->fapar_bs, out->fapar_ws, out->albedo_bs, out->albedo_ws, out->fcover};
+  return stage_call(ctx, who, SPART_F64, B, param_slice(0, params, NREAD), PRE_LEAF | PRE_SOIL | PRE_CANOPY, ctx->po, workspace,
+                    ws, stream, [&](auto t, auto, hipStream_t st, auto tab, auto cst) {
+    if constexpr (std::is_same_v<decltype(t), double>)
+      hipLaunchKernelGGL(k_products, dim3((unsigned)((B + 63) / 64)), dim3(64 * COL_WAVES), 0, st, tab, cst, ws.Bp,
+                         (const double*)ctx->Ea, ctx->ea_par, ctx->ea_all, params[16], params[17], B, po);
   });
 }
 

@@ -8,11 +8,11 @@ from .api import (BSM, PROSPECT_5D, SAILH, SMAC, SPART, Angles, AtmosphericOptic
                   calculate_leafangles, calculate_spectral_convolution, calculate_tav, soilwat, load_ET_parameters,
                   load_optical_parameters, load_sensor_info, set_leaf_refl_trans_assumptions,
                   set_soil_refl_trans_assumptions)
-from .engine import Engine, get_engine, knn_prior  # noqa: F401
+from .engine import PRODUCT_NAMES, Engine, get_engine, knn_prior  # noqa: F401
 from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401
-from .lut import (generate_lut, invert_lut, jacobian, load_lut, lut_to_parquet, noise_weights, posterior, refine, refine_views,  # noqa: F401
-                  refine_tiles, retrieve, retrieve_stream, tiles_from_labels, window_tiles)
+from .lut import (generate_lut, invert_lut, jacobian, load_lut, lut_products, lut_to_parquet, noise_weights, posterior, products,  # noqa: F401
+                  refine, refine_views, refine_tiles, retrieve, retrieve_stream, tiles_from_labels, window_tiles)
 
 __version__ = "0.1.0"

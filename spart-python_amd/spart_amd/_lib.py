@@ -72,6 +72,12 @@ class SpartLutBayesQOut(ctypes.Structure):
     _fields_ = [("base", SpartLutBayesOut), ("quant", vp)]
 
 
+class SpartProductsOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("fapar_bs", "fapar_ws", "albedo_bs", "albedo_ws", "fcover")]
+
+
+PRODUCT_NAMES = ("fAPAR_bs", "fAPAR_ws", "albedo_bs", "albedo_ws", "fCover")      # spart_products_out, in its order
+PRODUCTS_NREAD = 22                                 # spart_products reads params[0 ... 21]
 LUT_BAYES_OUTS = tuple(n for n, _ in SpartLutBayesOut._fields_)      # spart_lut_bayes_out, in its order
 LUT_BAYES_MAXP = 64
 LUT_BAYES_MAXQ = 8                                  # spart_lut_bayes_q_opt.nq
@@ -144,6 +150,7 @@ SIGNATURES = {
     "spart_refine_tiles": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + _REFINE_CALL[7:9] +
                            [ctypes.POINTER(SpartRefineTilesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),
     "spart_refine_posterior": (ctypes.c_int, _REFINE_CALL[:10] + [ctypes.c_int, ctypes.POINTER(SpartPosteriorOut)] + _REFINE_CALL[16:]),
+    "spart_products": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.POINTER(SpartProductsOut), vp, ctypes.c_size_t, vp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

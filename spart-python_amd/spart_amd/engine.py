@@ -433,6 +433,43 @@ BAND_MODELS = ("centre", "srf")
 _FIT_OUTS = ("x", "cost", "cost0", "std", "n_accept", "y")     # of spart_refine / _srf / _views, in the order of their argument lists
 
 
+PRODUCT_NAMES = _lib.PRODUCT_NAMES
+
+
+def product_names(names=None):
+    """``names`` of Engine.products (None = all five, in PRODUCT_NAMES order) -> the tuple asked for, in the caller's order;
+    an unknown, repeated or missing name is a ValueError"""
+    if names is None:
+        return tuple(PRODUCT_NAMES)
+    if isinstance(names, str):
+        raise ValueError(f"names must be a list of names from {list(PRODUCT_NAMES)}, got the string {names!r}")
+    names = tuple(names)
+    unknown = [n for n in names if n not in PRODUCT_NAMES]
+    if unknown or not names or len(set(names)) != len(names):
+        raise ValueError(f"names = {list(names)}: expected distinct names from {list(PRODUCT_NAMES)}"
+                         + (f"; unknown {unknown}" if unknown else ""))
+    return names
+
+
+def products_columns(params):
+    """The parameter columns spart_products reads, checked without a device: a (27, B) block passes through; a list of 27
+    gives its first 22 entries (Cab ... psi; none may be None), the atmosphere and DOY entries are not read and may be None"""
+    if isinstance(params, (list, tuple)):
+        if len(params) != _lib.NPARAM:
+            raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+        read = list(params[:_lib.PRODUCTS_NREAD])
+        missing = [i for i, c in enumerate(read) if c is None]
+        if missing:
+            raise ValueError(f"params[{missing[0]}] is None: products read params[0 ... {_lib.PRODUCTS_NREAD - 1}] "
+                             f"(only the atmosphere and DOY entries may be None)")
+        batch_size(read)
+        return read
+    shape = tuple(np.shape(params))
+    if len(shape) != 2 or shape[0] != _lib.NPARAM:
+        raise ValueError(f"params must be (27, B) or a list of 27 columns, got shape {shape}")
+    return params
+
+
 def params_rows(params):
     """the number of rows a params argument of refine() / posterior() stands for when no obs says it: the second axis of a
     (27, M) block, else the largest entry of the list"""
@@ -947,6 +984,41 @@ class Engine:
                 _lib.check(lib, ctx, rc)
             return keep[6]
         return call
+
+    def products(self, params, names=None, out=None):
+        """fAPAR and albedo, black- and white-sky, and fCover of every column of ``params`` (include/spart_hip.h: spart_products,
+        which defines them; float64; no sensor needed).  ``params`` as for run(): a (27, B) float64 block or a list of 27
+        scalars / arrays, of which the atmosphere and DOY entries (22 ... 26) are not read and may be None.  ``names``: which of
+        PRODUCT_NAMES to compute, in the order wanted (None = all five); only those are asked of the kernel.  ``out``: optional
+        dict of preallocated (B,) float64 tensors on the engine's device for some of the names.
+        -> dict {name: (B,) float64 device tensor} in the order of ``names``."""
+        torch = self.torch
+        names = product_names(names)
+        params = products_columns(params)
+        if out is not None and set(out) - set(names):
+            raise ValueError(f"out has entries {sorted(set(out) - set(names))} that names = {list(names)} does not ask for")
+        if isinstance(params, list):
+            cols, B = self.columns(params)
+            col_ptrs = self._ptrs(cols + [None] * (_lib.NPARAM - len(cols)))
+        else:
+            P = cols = torch.as_tensor(params).to(device=self.device, dtype=torch.float64).contiguous()
+            B = P.shape[1]
+            col_ptrs = (_lib.vp * _lib.NPARAM)(*[P.data_ptr() + 8 * B * i for i in range(_lib.NPARAM)])
+        res = {}
+        for n in names:
+            if out is not None and n in out:
+                self._check_out(n, out[n], (B,), torch.float64, 1)
+                res[n] = out[n]
+            else:
+                res[n] = torch.empty((B,), dtype=torch.float64, device=self.device)
+        po = _lib.SpartProductsOut()
+        for n, (field, _) in zip(PRODUCT_NAMES, _lib.SpartProductsOut._fields_):
+            setattr(po, field, res[n].data_ptr() if n in res and B > 0 else None)
+        ws, wsn = self._workspace(_lib.SPART_F64, B)
+        self.calls["spart_products"] += 1
+        rc = self.lib.spart_products(self.ctx, B, col_ptrs, ctypes.byref(po), ws, wsn, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        return res
 
     def prepare(self, params, dtype="float32", out=None, **kw):
         """run() with its argument marshalling done ONCE: returns ``call()`` which issues the same spart_run_batch on the current

@@ -7,6 +7,7 @@ On-disk layout (a directory):
     meta.json                  sensor, band ids, band centres, dtype, parameter names, number of rows, band model
     params.npy   (B, 27) f64   the parameter table (workloads.PARAM_NAMES order)
     R_TOC.npy / R_TOA.npy / L_TOA.npy   (B, nb) in the chosen dtype
+    products.npy (B, 5) f64    optional, written by lut_products: fAPAR_bs, fAPAR_ws, albedo_bs, albedo_ws, fCover of every row
 All .npy files are plain numpy arrays (np.load(..., mmap_mode="r") works for tables larger than RAM).
 """
 import ctypes
@@ -17,8 +18,9 @@ import warnings
 import numpy as np
 
 from . import _lib, workloads
-from .engine import (BAND_MODELS, DTYPES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind, params_rows,
-                     prior_arrays, quantile_levels, refine_args, refine_plan, refine_tiles_args, refine_views_args)
+from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind,
+                     params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
+                     refine_tiles_args, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -455,14 +457,99 @@ STREAM_MAPS = ("mean", "median", "std")            # the (M, P) float64 arrays o
 
 
 def _param_columns(params_cols):
-    """params_cols (None = every parameter, or a list of names from workloads.PARAM_NAMES) -> (names, column numbers)"""
+    """params_cols (None = every parameter, or a list of names from workloads.PARAM_NAMES and PRODUCT_NAMES) -> (names, column
+    numbers): the parameter names in the order given, then the product names in the order given; a product's column number
+    is NPARAM + its place in PRODUCT_NAMES, its column of the stacked table (_summary_table)"""
     if params_cols is None:
         return list(workloads.PARAM_NAMES), list(range(workloads.NPARAM))
-    names = list(params_cols)
-    unknown = [n for n in names if n not in workloads.PARAM_NAMES]
-    if unknown or not names:
-        raise ValueError(f"params_cols: unknown parameter name(s) {unknown}; expected names from {list(workloads.PARAM_NAMES)}")
-    return names, [workloads.PARAM_NAMES.index(n) for n in names]
+    given = list(params_cols)
+    unknown = [n for n in given if n not in workloads.PARAM_NAMES and n not in PRODUCT_NAMES]
+    if unknown or not given:
+        raise ValueError(f"params_cols: unknown parameter name(s) {unknown}; expected names from {list(workloads.PARAM_NAMES)} "
+                         f"or, for a LUT with products.npy (lut_products), {list(PRODUCT_NAMES)}")
+    names = [n for n in given if n in workloads.PARAM_NAMES] + [n for n in given if n in PRODUCT_NAMES]
+    return names, [workloads.PARAM_NAMES.index(n) if n in workloads.PARAM_NAMES else workloads.NPARAM + PRODUCT_NAMES.index(n)
+                   for n in names]
+
+
+class _Stacked:
+    """params.npy (B, 27) and products.npy (B, 5) read as ONE (B, 32) table, the parameter columns first: rows are gathered
+    from both files (memmaps read only the rows asked for), np.asarray gives the whole table"""
+
+    def __init__(self, params, products):
+        if products.shape != (params.shape[0], len(PRODUCT_NAMES)):
+            raise ValueError(f"products.npy is {products.shape}, params.npy {params.shape}: run lut_products again")
+        self.params, self.products = params, products
+        self.shape = (params.shape[0], params.shape[1] + products.shape[1])
+
+    def __getitem__(self, rows):
+        return np.concatenate([np.asarray(self.params[rows], dtype=np.float64), np.asarray(self.products[rows], dtype=np.float64)], axis=1)
+
+    def __array__(self, dtype=None, copy=None):
+        return self[slice(None)]
+
+
+def _needs_products(lut_dir, cols):
+    """ValueError when ``cols`` names a product column and the LUT directory has no products.npy; before any search"""
+    if max(cols, default=0) >= workloads.NPARAM and not os.path.exists(os.path.join(lut_dir, "products.npy")):
+        raise ValueError(f"params_cols names a product ({list(PRODUCT_NAMES)}) but {lut_dir} has no products.npy: "
+                         "run spart_amd.lut_products(lut_dir) first")
+
+
+def _summary_table(lut_dir, params, cols):
+    """the table ``cols`` index: params.npy itself while only parameters are chosen, else params.npy | products.npy"""
+    if max(cols, default=0) < workloads.NPARAM:
+        return params
+    _needs_products(lut_dir, cols)
+    return _Stacked(params, np.load(os.path.join(lut_dir, "products.npy"), mmap_mode="r"))
+
+
+def products(params_host, names=None, device=None):
+    """The host form of Engine.products: numpy in and out.  ``params_host``: a (27, B) array or a list of 27 scalars / arrays
+    (workloads.PARAM_NAMES order; the atmosphere and DOY entries are not read and may be None); ``names``: some of
+    PRODUCT_NAMES in the order wanted (None = all five).  -> dict {name: (B,) float64 array}.  No sensor is involved.
+    Every argument check that needs no device runs before one is asked for."""
+    names = product_names(names)
+    cols = products_columns(params_host if isinstance(params_host, (list, tuple)) else np.asarray(params_host, dtype=np.float64))
+    eng = get_engine(None, device)
+    padded = cols + [None] * (workloads.NPARAM - len(cols)) if isinstance(cols, list) else cols
+    return {n: v.cpu().numpy() for n, v in eng.products(padded, names).items()}
+
+
+def lut_products(lut_dir, chunk=1 << 18, device=None, shard=False, group=None):
+    """Give an existing generate_lut directory its product columns: params.npy is read in chunks of ``chunk`` rows, every row
+    goes through Engine.products (spart_products), and the directory gains products.npy (rows, 5) float64 in PRODUCT_NAMES
+    order; meta.json gains ``"product_names"`` and keeps every other key.  retrieve / retrieve_stream then take product names
+    in ``params_cols``: the k nearest rows, or the posterior weights, average the product itself.  The values do not depend
+    on ``chunk`` (a row's products are the same bits in any batch).  No sensor engine is needed.  ``shard=True`` under a
+    process group of more than one rank is a ValueError (sharded products are not built).  -> the (rows, 5) array."""
+    if _group_info(shard, group)[0] > 1:
+        raise ValueError("lut_products does not take shard=True under a process group of more than one rank: "
+                         "run it on one rank after generate_lut")
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk = {chunk}, expected >= 1")
+    with open(os.path.join(lut_dir, "meta.json")) as f:
+        meta = json.load(f)
+    params = np.load(os.path.join(lut_dir, "params.npy"), mmap_mode="r")
+    B = params.shape[0]
+    out = np.empty((B, len(PRODUCT_NAMES)), dtype=np.float64)
+    if B > 0:
+        import torch
+        eng = get_engine(None, device)
+        for lo in range(0, B, chunk):
+            block = torch.as_tensor(np.ascontiguousarray(np.array(params[lo:lo + chunk], dtype=np.float64).T))    # (a copy: the memmap is read-only)
+            res = eng.products(block)
+            for j, n in enumerate(PRODUCT_NAMES):
+                out[lo:lo + chunk, j] = res[n].cpu().numpy()
+    tmp = os.path.join(lut_dir, f"products.npy.tmp.{os.getpid()}")
+    with open(tmp, "wb") as f:
+        np.save(f, out)
+    os.replace(tmp, os.path.join(lut_dir, "products.npy"))
+    meta["product_names"] = list(PRODUCT_NAMES)
+    with open(os.path.join(lut_dir, "meta.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    return out
 
 
 def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2,
@@ -679,7 +766,8 @@ def _retrieve_bayes(lut_dir, obs, column, weights, device, cols, opts):
     eng = get_engine(None, device)
     o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=_torch_dtype(npdt))
     w = None if weights is None else _host_tensor(np.ascontiguousarray(weights, dtype=npdt)).to(eng.device)
-    return {n: v.cpu().numpy() for n, v in _bayes_maps(eng, *_upload_lut(eng, table, params, cols, npdt), o, w, meta["dtype"], opts).items()}
+    up = _upload_lut(eng, table, _summary_table(lut_dir, params, cols), cols, npdt)
+    return {n: v.cpu().numpy() for n, v in _bayes_maps(eng, *up, o, w, meta["dtype"], opts).items()}
 
 
 # what an observation that matches nothing gets, by output name (retrieve, retrieve_stream and the fit)
@@ -780,7 +868,11 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     """LUT retrieval: the k nearest rows of a generate_lut directory per observed spectrum (invert_lut(k=k)) and the
     mean, median and standard deviation of their parameters (params.npy, workloads.PARAM_NAMES order; padded rows excluded).
     ``weights`` as for invert_lut: (nb,) or (M, nb), e.g. noise_weights(obs, rel_sigma=0.02).
-    ``params_cols``: a list of names from workloads.PARAM_NAMES, to summarise only those columns (``names`` follows it).
+    ``params_cols``: a list of names from workloads.PARAM_NAMES, to summarise only those columns (``names`` follows it).  Once
+    lut_products has written products.npy it may also name products (PRODUCT_NAMES): the summarised table is then the chosen
+    parameter columns followed by the chosen product columns, ``names`` in that order, and mean / median / std, the bayes_*
+    outputs and their quantiles cover the products like any other column (the k nearest rows or the posterior weights average
+    the product itself).  A product name without products.npy is a ValueError that says to run lut_products.
     ``summary="host"`` (default): summarise_rows on the host, in numpy.  ``summary="device"``: params.npy (or the chosen columns)
     is uploaded once, the indices stay on the device between the search and Engine.lut_summarise (spart_lut_summarise), and
     the result gains ``count`` (M,) int32, the rows found per observation.  The search is the same, so idx and cost are equal
@@ -823,6 +915,7 @@ def retrieve(lut_dir, obs, k, column="R_TOC", weights=None, shard=False, group=N
     if summary not in SUMMARIES:
         raise ValueError(f"summary = {summary!r}, expected one of {SUMMARIES}")
     names, cols = _param_columns(params_cols)
+    _needs_products(lut_dir, cols)
     bayes = _bayes_setup(bayes, shard, group)
     setup = _refine_setup(lut_dir, refine, refine_opts, shard, group, sensor_info)
     dict_prior = _dict_prior(setup, np.shape(obs)[0])                    # (an array that is not (M,): refused before the search)
@@ -839,7 +932,7 @@ def _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, su
     if summary == "host":
         idx, cost = invert_lut(lut_dir, obs, column=column, weights=weights, shard=shard, group=group, device=device, k=k)
         _, params, _ = load_lut(lut_dir)
-        mean, median, std = summarise_rows(params, idx)
+        mean, median, std = summarise_rows(_summary_table(lut_dir, params, cols), idx)
         if params_cols is not None:
             mean, median, std = (np.ascontiguousarray(a[:, cols]) for a in (mean, median, std))
         return {"idx": idx, "cost": cost, "mean": mean, "median": median, "std": std, "names": names}
@@ -855,7 +948,8 @@ def _retrieve_summary(lut_dir, obs, k, column, weights, shard, group, device, su
     o = torch.as_tensor(np.asarray(obs)).to(device=eng.device, dtype=_torch_dtype(npdt))
     M, B = o.shape[0], table.shape[0]
     if B > 0 and M > 0:
-        idx, cost, res = _topk_summary(eng, *_upload_lut(eng, table, params, cols, npdt), o, k, weights, meta["dtype"])
+        idx, cost, res = _topk_summary(eng, *_upload_lut(eng, table, _summary_table(lut_dir, params, cols), cols, npdt), o, k, weights,
+                                       meta["dtype"])
         out = {n: v.cpu().numpy() for n, v in {"idx": idx, "cost": cost, **res}.items()}
     else:
         out = _unmatched({"idx": ((M, k), np.int64), "cost": ((M, k), npdt), **_summary_shapes(M, len(cols))})
@@ -1005,6 +1099,7 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
     meta, params, tabs = load_lut(lut_dir)
     table = tabs[column]
     names, cols = _param_columns(params_cols)
+    _needs_products(lut_dir, cols)
     k = _check_k(int(k))
     B, nb = table.shape
     npdt = _np_dtype(meta["dtype"])
@@ -1031,7 +1126,8 @@ def retrieve_stream(lut_dir, obs, k, column="R_TOC", weights=None, params_cols=N
             fit = None if setup is None else _Fit(setup, params, column, shared, dict_prior, device)
             if shared is not None:
                 shared = _host_tensor(np.ascontiguousarray(shared, dtype=npdt)).to(eng.device)
-            stage = _DeviceStage(eng, *_upload_lut(eng, table, params, cols, npdt), k, meta["dtype"], max(1, min(int(chunk), M)),
+            up = _upload_lut(eng, table, _summary_table(lut_dir, params, cols), cols, npdt)
+            stage = _DeviceStage(eng, *up, k, meta["dtype"], max(1, min(int(chunk), M)),
                                  kind == "per_observation", shared, fit=fit, params=params, bayes=bayes)
         _stream_chunks(obs, weights if kind == "per_observation" else None, chunk, res, stage, npdt,
                        wide=bool(getattr(stage, "wide", False)))
