@@ -70,7 +70,9 @@ extern "C" {
  * and a new struct that embeds spart_refine_opt unchanged.  spart_refine_posterior and spart_posterior_out likewise, and
  * spart_lut_bayes, spart_lut_bayes_workspace_bytes and spart_lut_bayes_stats with spart_lut_bayes_opt / _out.
  * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too,
- * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise. */
+ * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise.
+ * spart_refine_series and spart_series_workspace_bytes with spart_refine_series_opt, which embeds spart_refine_tiles_opt
+ * unchanged, likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -707,6 +709,67 @@ int spart_refine_tiles(spart_ctx *ctx, int64_t M, const double *const base[SPART
                        const double *lo, const double *hi /* HOST, (F,) per name */, int64_t T, const int64_t *tile_start /* HOST (T+1,) */,
                        const double *obs, const double *weights, const spart_refine_tiles_opt *opt, const spart_tiles_out *out,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* Refinement of TIME SERIES of a pixel with a smoothness prior: a season of overpasses in which LAI or Cab move slowly from
+ * date to date, leaf angle or soil brightness stay fixed and some dates are cloudy.  A ROW is one date of one pixel and carries
+ * its own 27 base parameters (geometry, atmosphere, DOY), obs row and weights, exactly as a pixel of spart_refine_tiles; series
+ * s is the contiguous rows series_start[s] ... series_start[s + 1] - 1, at most 256 of them (the std recurrence is quadratic
+ * in the length).  The first Fs = n_shared names are one unknown per series and start from the series' first row, the other
+ * Fl = F - Fs >= 1 are one unknown per row.  The temporal regulariser (EO-LDAS, the Whittaker smoother) is a first-difference
+ * penalty between consecutive rows of a series: the damped system is block-tridiagonal with a border, O(rows) to factorise;
+ * the gap under a cloud is filled by its neighbours.  spart_tiles_out is reused with "tile" read as series.
+ * Definition (tools/refine_series_defined.py is the same text in numpy): spart_refine_tiles' text with these additions; float64,
+ * no FMA contraction, IEEE division and sqrt, every sum in one pinned order.
+ *   kappa    for row m with a successor in its series and local b: kappa_(m,b) = smooth[b] * link[m], one multiplication
+ *            (link NULL: link[m] = 1).  kappa == 0: that tie is absent.  The link entry of a series' last row is never read
+ *   dead     decided at it = 0.  A row is bad by tiles' rule (a bad band weight, a bad local prior weight, c_m not < +inf) or
+ *            if a link entry that is read is negative, NaN or infinite.  A series with any bad row, a bad shared prior weight
+ *            or C not < +inf is dead AS A WHOLE (a chain cannot lose a link): n_accept -1, shared and local at the clipped
+ *            start, cost = cost0 = C, every std NaN, y = Y_0, pixel_cost = c_m; its bad rows get status -1, the others 1.
+ *            A row whose weights are all zero is live with c_m = 0: the masked date; obs may be NaN there
+ *   C        C = 0; for m ascending: C = C + c_m; then for m ascending over rows with a successor, b ascending, kappa != 0:
+ *            e = t_(m+1,b) - t_(m,b) on the trial values, C = C + (kappa e) e; then the shared prior loop as in tiles
+ *   sums     at an accepted point each row has tiles' packed A_m, g_m (local prior included), then for local b of row m: if m
+ *            has a predecessor with kappa_(m-1,b) != 0: A_m[bb] = A_m[bb] + kappa_(m-1,b), g_(m,b) = g_(m,b) + kappa_(m-1,b)
+ *            e_(m-1,b); if m has a successor with kappa_(m,b) != 0: A_m[bb] = A_m[bb] + kappa_(m,b), g_(m,b) = g_(m,b) -
+ *            kappa_(m,b) e_(m,b).  The entry between (m+1, b) and (m, b) is -kappa_(m,b).  S, gs are tiles'.  A rejection
+ *            restores all of it
+ *   propose  D and lambda are tiles', on the augmented diagonal.  B delta = -g by spart_refine's Cholesky text in the unknown
+ *            order row 0's locals, row 1's locals, ..., then the shared, over the structurally present entries only: a row's
+ *            own local block, the full Fl x Fl block between rows m + 1 and m (present iff some kappa_(m,.) != 0; it starts
+ *            from -kappa on its diagonal and 0.0 elsewhere), every shared x local entry, the shared block.  A sum runs over
+ *            the k present in both of its rows, ascending in that order; everything else is skipped, never multiplied in as a
+ *            zero: X_m[i, j] = (B[(m+1,i),(m,j)] - sum_{k<j} X_m[i,k] R_m[j,k]) / R_m[j,j]; R_(m+1) subtracts X_m's rows
+ *            (k = 0 ... Fl-1), then its own k < j; W_(m+1)[a, j] subtracts W_m[a,k] X_m[j,k] (k = 0 ... Fl-1), then its own
+ *            k < j; the Schur sums over m then k are tiles'.  Forward and back substitution in the same order (back, local
+ *            (m, j): the row's k = j+1 ... Fl-1, the next row's i = 0 ... Fl-1 through X_m[i, j], the shared a ascending).  A
+ *            pivot !(s > 0) or a non-finite delta anywhere gives delta = 0 for the series.  t = clip(x + delta).  No early exit
+ *   std      from the undamped factors by spart_refine's std recurrence in the same order: for a local (m, j), k runs over m's
+ *            locals >= j, then every later row's locals, then the shared (their right-hand sides summed over m then i); for a
+ *            shared unknown as in tiles.  A failed factorisation gives NaN for the whole series.  With shared_std and
+ *            local_std both NULL none of this is computed
+ * Consequences.  With every smooth[b] = 0 (or link all zero) and no bad row the call is spart_refine_tiles on tiles equal to the
+ * series, bit for bit in every output; with one-row series it is spart_refine / spart_refine_srf in tiles' permuted form.  A
+ * series' bits depend on neither the other series nor the chunk.  cost <= cost0, and n_iter = k is a prefix of k + 1.  With
+ * smooth[b] = 0 a masked date's local b stays at its clipped start exactly and, without a prior, the series' std is NaN; with
+ * smooth[b] > 0 and link > 0 on at least one side it moves and std is finite.
+ * Rows go in tiles' greedy chunks of whole series (one series always fits); spart_series_workspace_bytes(ctx, M, F, n_shared)
+ * is 0 exactly for refused sizes (Fl = 0 included).  series_start and smooth are read on the host before the call returns.
+ * Refused before anything is launched or written: spart_refine_tiles' list in its order (series_start under the 256-row rule),
+ * then Fl = 0 ("nothing to link: use spart_refine_tiles"), then a NULL smooth or an entry of it that is negative, NaN or
+ * infinite (the first index named), then SPART_ERR_WORKSPACE.  M = 0 launches nothing.  Second differences, the joint
+ * covariance of a series and series of more than 256 rows are out of scope.  Added WITHOUT a new interface number, by
+ * spart_refine_srf's rule: two symbols and one struct that embeds spart_refine_tiles_opt unchanged. */
+typedef struct spart_refine_series_opt {
+  spart_refine_tiles_opt tiles;  /* unchanged: fit (local prior), n_shared, band_model, shared prior (per series) */
+  const double *smooth;          /* HOST (Fl,): gamma_b >= 0, finite; one per LOCAL name, in free_cols order */
+  const double *link;            /* DEVICE (M,) float64 or NULL (= 1): link[m] scales the tie between rows m and m + 1 */
+} spart_refine_series_opt;
+size_t spart_series_workspace_bytes(const spart_ctx *ctx, int64_t M, int F, int n_shared);
+int spart_refine_series(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                        const double *lo, const double *hi /* HOST, (F,) per name */, int64_t S, const int64_t *series_start /* HOST (S+1,) */,
+                        const double *obs, const double *weights, const spart_refine_series_opt *opt, const spart_tiles_out *out,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
  * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging

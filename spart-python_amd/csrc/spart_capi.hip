@@ -23,6 +23,7 @@
 #include "spart_refine_posterior.h"
 #include "spart_refine_views.h"
 #include "spart_refine_tiles.h"
+#include "spart_refine_series.h"
 #include "spart_products.h"
 
 using namespace spart;
@@ -1786,6 +1787,31 @@ size_t spart_tiles_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n
   return l.total;
 }
 
+// What spart_refine_tiles and spart_refine_series check about the partition and the shared prior, in one order, after the
+// family's list and before the workspace's size
+static int tiles_check(const char* who, const spart_refine_tiles_opt& to, int64_t M, int F, int64_t T, const int64_t* tile_start,
+                       const char* count, const char* name, const char* units, const char* per, int maxg) {
+  if (to.n_shared < 0 || to.n_shared > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, to.n_shared, F);
+  if (int rc = refine_check_band_model(who, to.band_model)) return rc;
+  if (T < 0 || (T == 0 && M > 0))
+    return fail(SPART_ERR_INVALID, "%s: %s = %lld %s for M = %lld pixels", who, count, (long long)T, units, (long long)M);
+  if (!tile_start) return fail(SPART_ERR_INVALID, "%s: %s is null", who, name);
+  if (tile_start[0] != 0) return fail(SPART_ERR_INVALID, "%s: %s[0] = %lld, expected 0", who, name, (long long)tile_start[0]);
+  for (int64_t t = 1; t <= T; ++t) {
+    const int64_t g = tile_start[t] - tile_start[t - 1];
+    if (g < 1 || g > maxg || tile_start[t] > M)
+      return fail(SPART_ERR_INVALID, "%s: %s[%lld] = %lld after %lld: 1 ... %d %s within M = %lld expected", who, name, (long long)t,
+                  (long long)tile_start[t], (long long)tile_start[t - 1], maxg, per, (long long)M);
+  }
+  if (tile_start[T] != M)
+    return fail(SPART_ERR_INVALID, "%s: %s[%lld] = %lld, expected M = %lld", who, name, (long long)T, (long long)tile_start[T], (long long)M);
+  if (!to.shared_prior_mean != !to.shared_prior_weight)
+    return fail(SPART_ERR_INVALID, "%s: shared_prior_mean and shared_prior_weight come together (both NULL = no prior)", who);
+  if (to.shared_prior_per_tile != 0 && to.shared_prior_per_tile != 1)
+    return fail(SPART_ERR_INVALID, "%s: shared_prior_per_tile = %d (0: one row for all, 1: one row per tile)", who, to.shared_prior_per_tile);
+  return SPART_OK;
+}
+
 // spart_refine's refusals in refine_entry's order; what is about the tiles comes after them and before the workspace's size,
 // which n_shared decides
 int spart_refine_tiles(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
@@ -1806,28 +1832,166 @@ int spart_refine_tiles(spart_ctx* ctx, int64_t M, const double* const base[SPART
       },
       refine_no_check,
       [&](RefineRun& r) {
-        if (to.n_shared < 0 || to.n_shared > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, to.n_shared, F);
-        if (int rc = refine_check_band_model(who, to.band_model)) return rc;
-        if (T < 0 || (T == 0 && M > 0))
-          return fail(SPART_ERR_INVALID, "%s: T = %lld tiles for M = %lld pixels", who, (long long)T, (long long)M);
-        if (!tile_start) return fail(SPART_ERR_INVALID, "%s: tile_start is null", who);
-        if (tile_start[0] != 0) return fail(SPART_ERR_INVALID, "%s: tile_start[0] = %lld, expected 0", who, (long long)tile_start[0]);
-        for (int64_t t = 1; t <= T; ++t) {
-          const int64_t g = tile_start[t] - tile_start[t - 1];
-          if (g < 1 || g > TILES_MAXG || tile_start[t] > M)
-            return fail(SPART_ERR_INVALID, "%s: tile_start[%lld] = %lld after %lld: 1 ... %d pixels per tile within M = %lld expected",
-                        who, (long long)t, (long long)tile_start[t], (long long)tile_start[t - 1], TILES_MAXG, (long long)M);
-        }
-        if (tile_start[T] != M)
-          return fail(SPART_ERR_INVALID, "%s: tile_start[%lld] = %lld, expected M = %lld", who, (long long)T, (long long)tile_start[T], (long long)M);
-        if (!to.shared_prior_mean != !to.shared_prior_weight)
-          return fail(SPART_ERR_INVALID, "%s: shared_prior_mean and shared_prior_weight come together (both NULL = no prior)", who);
-        if (to.shared_prior_per_tile != 0 && to.shared_prior_per_tile != 1)
-          return fail(SPART_ERR_INVALID, "%s: shared_prior_per_tile = %d (0: one row for all, 1: one row per tile)", who, to.shared_prior_per_tile);
+        if (int rc = tiles_check(who, to, M, F, T, tile_start, "T", "tile_start", "tiles", "pixels per tile", TILES_MAXG)) return rc;
         x = tiles_layout(ctx->nb, M, F, to.n_shared, r.l);
         return SPART_OK;
       },
       [&](const RefineRun& r, hipStream_t st) { return tiles_impl(r, x, to.n_shared, T, tile_start, to, oo, st); });
+}
+
+// ---- spart_refine_series (csrc/spart_refine_series.h).  The layout is tiles' with the factors of the link blocks, Xp
+// (mcap, Fl Fl), and gamma (REFINE_MAXF) behind it; the chunk loop is tiles' over whole series.
+struct SeriesLayout {
+  TilesLayout x;
+  size_t Xp, gamma;
+};
+static SeriesLayout series_layout(int nb, int64_t M, int F, int Fs, RefineLayout& l) {
+  SeriesLayout y;
+  y.x = tiles_layout(nb, M, F, Fs, l);
+  const size_t Fl = (size_t)(F - Fs);
+  Carver c;
+  c.take(l.total);
+  y.Xp = c.take((size_t)l.mcap * Fl * Fl * 8);
+  y.gamma = c.take(REFINE_MAXF * 8);
+  l.total = c.o;
+  return y;
+}
+
+static int series_impl(const RefineRun& r, const SeriesLayout& y, int Fs, int64_t T, const int64_t* series_start,
+                       const spart_refine_series_opt& so, const spart_tiles_out& out, hipStream_t st) {
+  const RefineLayout& l = r.l;
+  const TilesLayout& x = y.x;
+  const spart_refine_opt& o = r.o;
+  const spart_refine_tiles_opt& to = so.tiles;
+  const int nb = r.ctx->nb, F = r.s.F, Fl = F - Fs, P = refine_ntri(F) + F, Ps = refine_ntri(Fs) + Fs, W = series_group(F);
+  const size_t lds_f = series_factor_lds(F, Fs, W), lds_b = series_back_lds(F, Fs, W), lds_s = series_std_lds(F, Fs);
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
+  if (r.srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  double* table = (double*)(r.wsp + l.table);
+  double* cfg = (double*)(r.wsp + l.cfg);
+  int32_t* cfg_free = (int32_t*)(r.wsp + l.cfg_free);
+  const double* ycol = cols[o.column];
+  auto at = [&](size_t off) { return r.wsp + off; };
+  const TilesState s = {(double*)at(x.lt),   (double*)at(x.ct),   (double*)at(x.Ap),    (double*)at(x.Lp),    (double*)at(x.zt),
+                        (double*)at(x.St),   (double*)at(x.Lt),   (double*)at(x.lam),   (int32_t*)at(x.live), (int32_t*)at(x.na),
+                        (int32_t*)at(x.code), (int32_t*)at(x.flag), (int32_t*)at(x.tstart), (int32_t*)at(x.ptile)};
+  double* Xp = (double*)at(y.Xp);
+  double* gamma = (double*)at(y.gamma);
+  const bool want_std = out.shared_std || out.local_std;
+  std::vector<int32_t> tstart, ptile;
+  for (int64_t t0 = 0; t0 < T;) {
+    const int64_t m0 = series_start[t0];
+    int64_t t1 = t0 + 1;                                            // (one series always fits: SERIES_MAXT <= tiles_chunk(16))
+    while (t1 < T && series_start[t1 + 1] - m0 <= l.mcap) ++t1;
+    const int tc = (int)(t1 - t0), mc = (int)(series_start[t1] - m0);
+    tstart.resize((size_t)tc + 1);
+    ptile.resize((size_t)mc);
+    for (int t = 0; t <= tc; ++t) tstart[t] = (int32_t)(series_start[t0 + t] - m0);
+    for (int t = 0; t < tc; ++t)
+      for (int m = tstart[t]; m < tstart[t + 1]; ++m) ptile[m] = t;
+    HIP_TRY(hipMemcpyAsync(s.tstart, tstart.data(), ((size_t)tc + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.ptile, ptile.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(gamma, so.smooth, (size_t)Fl * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const TilesOut oc = {rows_at(out.shared, t0, Fs),    rows_at(out.shared_std, t0, Fs), rows_at(out.local, m0, Fl),
+                         rows_at(out.local_std, m0, Fl), rows_at(out.cost, t0, 1),       rows_at(out.cost0, t0, 1),
+                         rows_at(out.n_accept, t0, 1),   rows_at(out.pixel_cost, m0, 1), rows_at(out.status, m0, 1),
+                         rows_at(out.y, m0, nb)};
+    const double* obs = r.obs + m0 * nb;
+    const double* wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
+    const double* pmu = rows_at(o.prior_mean, m0, Fl, o.prior_per_obs);
+    const double* ppw = rows_at(o.prior_weight, m0, Fl, o.prior_per_obs);
+    const double* smu = rows_at(to.shared_prior_mean, t0, Fs, to.shared_prior_per_tile);
+    const double* spw = rows_at(to.shared_prior_weight, t0, Fs, to.shared_prior_per_tile);
+    const double* link = rows_at(so.link, m0, 1);
+    const int wper = o.weights_per_obs ? 1 : 0, pper = o.prior_per_obs ? 1 : 0, sper = to.shared_prior_per_tile ? 1 : 0;
+    const int64_t rows = (int64_t)mc * (F + 1);
+    const unsigned per_pixel = (unsigned)((mc + 255) / 256), groups = (unsigned)((tc + W - 1) / W);
+    hipLaunchKernelGGL(k_tiles_init, dim3(per_pixel), dim3(256), 0, st, r.cfg, m0, mc, F, Fs, o.lambda0, s, table, oc, cfg, cfg_free);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    for (int it = 0; it <= o.n_iter; ++it) {
+      const int last = it == o.n_iter ? 1 : 0;
+      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
+      hipLaunchKernelGGL(k_tiles_cost, dim3(per_pixel), dim3(256), 0, st, ycol, obs, wts, wper, pmu, ppw, pper, mc, Fl, nb, it, s, oc);
+      hipLaunchKernelGGL(k_series_decide, dim3((unsigned)((tc + 255) / 256)), dim3(256), 0, st, smu, spw, sper, tc, Fs, Fl, it, last,
+                         (const double*)gamma, link, s, oc);
+      hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, ycol, obs, wts, wper, pmu,
+                         ppw, pper, (const double*)cfg, mc, F, Fs, nb, s, oc);
+      if (!last || want_std) {                                      // (the sums of the last point are only for the std)
+        hipLaunchKernelGGL(k_series_augment, dim3((unsigned)(((int64_t)mc * Fl + 255) / 256)), dim3(256), 0, st, mc, F, Fs,
+                           (const double*)gamma, link, s);
+        if (Fs > 0)
+          hipLaunchKernelGGL(k_series_sums, dim3((unsigned)(((int64_t)tc * Ps + 255) / 256)), dim3(256), 0, st, smu, spw, sper, tc, F,
+                             Fs, s, oc);
+        hipLaunchKernelGGL(W == 8 ? k_series_factor<8> : k_series_factor<4>, dim3(groups), dim3(64), lds_f, st, tc, F, Fs, last,
+                           (const double*)gamma, link, s, Xp);
+        if (Fs > 0)
+          hipLaunchKernelGGL(k_series_shared, dim3((unsigned)((tc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)),
+                             dim3(SERIES_STD_THREADS), (size_t)Fs * SERIES_STD_THREADS * 8, st, tc, Fs, last, s, oc.shared_std);
+      }
+      if (!last) {
+        hipLaunchKernelGGL(W == 8 ? k_series_back<8> : k_series_back<4>, dim3(groups), dim3(64), lds_b, st, tc, F, Fs,
+                           (const double*)gamma, link, s, (const double*)Xp);
+        hipLaunchKernelGGL(k_tiles_apply, dim3(per_pixel), dim3(256), 0, st, (const double*)cfg, (const int32_t*)cfg_free, table, mc, F,
+                           Fs, s, oc);
+      } else if (out.local_std) {
+        hipLaunchKernelGGL(k_series_std, dim3((unsigned)((mc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)),
+                           dim3(SERIES_STD_THREADS), lds_s, st, mc, F, Fs, (const double*)gamma, link, s, (const double*)Xp, oc.local_std);
+      }
+      HIP_TRY(hipGetLastError());
+    }
+    t0 = t1;
+  }
+  return SPART_OK;
+}
+
+size_t spart_series_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
+  if (!tiles_sizes_ok(ctx, M, F, n_shared) || n_shared >= F) return 0;
+  RefineLayout l;
+  series_layout(ctx->nb, M, F, n_shared, l);
+  return l.total;
+}
+
+// spart_refine_tiles' refusals in its order (series_start under the 256-row rule), then Fl = 0, then smooth; the workspace last
+int spart_refine_series(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                        const double* lo, const double* hi, int64_t S, const int64_t* series_start, const double* obs,
+                        const double* weights, const spart_refine_series_opt* opt, const spart_tiles_out* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  const char* who = "spart_refine_series";
+  spart_refine_series_opt so;
+  spart_tiles_out oo;
+  SeriesLayout y;
+  const bool have_out =
+      opt && out && out->cost && (out->shared || opt->tiles.n_shared <= 0) && (out->local || opt->tiles.n_shared >= F);
+  return refine_entry_sized(
+      who, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt && out, obs && have_out,
+      [&](RefineRun& r) {
+        so = *opt, oo = *out;
+        r.o = so.tiles.fit, r.srf = so.tiles.band_model == 1;
+        return SPART_OK;
+      },
+      refine_no_check,
+      [&](RefineRun& r) {
+        if (int rc = tiles_check(who, so.tiles, M, F, S, series_start, "S", "series_start", "series", "rows per series", SERIES_MAXT))
+          return rc;
+        const int Fl = F - so.tiles.n_shared;
+        if (Fl == 0) return fail(SPART_ERR_INVALID, "%s: n_shared = F = %d, nothing to link: use spart_refine_tiles", who, F);
+        if (!so.smooth) return fail(SPART_ERR_INVALID, "%s: smooth is null", who);
+        for (int b = 0; b < Fl; ++b)
+          if (!(so.smooth[b] >= 0.0) || std::isinf(so.smooth[b]))
+            return fail(SPART_ERR_INVALID, "%s: smooth[%d] = %g, expected a finite value >= 0", who, b, so.smooth[b]);
+        y = series_layout(ctx->nb, M, F, so.tiles.n_shared, r.l);
+        return SPART_OK;
+      },
+      [&](const RefineRun& r, hipStream_t st) { return series_impl(r, y, so.tiles.n_shared, S, series_start, so, oo, st); });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

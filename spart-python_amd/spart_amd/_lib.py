@@ -47,6 +47,10 @@ class SpartRefineTilesOpt(ctypes.Structure):
                 ("shared_prior_per_tile", ctypes.c_int32), ("shared_prior_mean", vp), ("shared_prior_weight", vp)]
 
 
+class SpartRefineSeriesOpt(ctypes.Structure):
+    _fields_ = [("tiles", SpartRefineTilesOpt), ("smooth", c_dp), ("link", vp)]        # smooth: HOST (Fl,); link: device (M,) or NULL
+
+
 class SpartTilesOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("shared", "shared_std", "local", "local_std", "cost", "cost0", "n_accept", "pixel_cost", "status",
                                   "y")]
@@ -87,6 +91,7 @@ REFINE_MAXF, REFINE_MAX_ITER = 16, 100
 REFINE_MAXV = 64                                    # spart_refine_views_opt.V
 TILES_OUTS = tuple(n for n, _ in SpartTilesOut._fields_)             # spart_tiles_out, in its order
 TILES_MAXG = 4096                                   # pixels per tile of spart_refine_tiles
+SERIES_MAXT = 256                                   # rows per series of spart_refine_series
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -149,6 +154,9 @@ SIGNATURES = {
     "spart_tiles_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "spart_refine_tiles": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + _REFINE_CALL[7:9] +
                            [ctypes.POINTER(SpartRefineTilesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),
+    "spart_series_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "spart_refine_series": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + _REFINE_CALL[7:9] +
+                            [ctypes.POINTER(SpartRefineSeriesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),
     "spart_refine_posterior": (ctypes.c_int, _REFINE_CALL[:10] + [ctypes.c_int, ctypes.POINTER(SpartPosteriorOut)] + _REFINE_CALL[16:]),
     "spart_products": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.POINTER(SpartProductsOut), vp, ctypes.c_size_t, vp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),

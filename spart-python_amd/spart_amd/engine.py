@@ -400,23 +400,24 @@ def tile_starts(M, tile_size, tile_start):
 
 
 def refine_tiles_args(params, obs, shared, local, tile_size, tile_start, bounds, weights, column, n_iter, rel_step, lambda0, lidf,
-                      prior, band_model, nb=None):
+                      prior, band_model, nb=None, partition=None, units=("pixels", "tiles")):
     """Every argument check of spart_amd.refine_tiles and Engine.refine_tiles that needs no device: refine_args on the names
     shared + local (the plan, obs (M, nb), params, weights), the partition (tile_starts), and the prior dict split by name --
     a shared name takes scalars or (T,) arrays, a local name scalars or (M,) arrays.
     -> (plan, params, M, Fs, weights per observation 0 / 1, tile_start, local prior, shared prior), a prior being
-    (mean, weight, per row 0 / 1) with (None, None, 0) for none"""
+    (mean, weight, per row 0 / 1) with (None, None, 0) for none.  ``partition`` (M -> tile_start) and ``units`` are
+    refine_series_args' way in: its rows and series in place of pixels and tiles"""
     shared, local = [str(s) for s in shared], [str(s) for s in local]
     plan, params, M, kind = refine_args(params, obs, shared + local, bounds, weights, column, n_iter, rel_step, lambda0, lidf, None,
                                         None, None, band_model, nb=nb)[:4]
-    ts = tile_starts(M, tile_size, tile_start)
+    ts = tile_starts(M, tile_size, tile_start) if partition is None else partition(M)
     priors = []
     if prior is not None and not isinstance(prior, dict):
         raise ValueError(f"prior = {prior!r}, expected a dict {{name: (mean, sigma)}}")
     stray = [k for k in (prior or {}) if k not in plan["names"]]
     if stray:
         raise ValueError(f"prior: {stray} not free")
-    for names, rows, what in ((local, M, "pixels"), (shared, ts.size - 1, "tiles")):
+    for names, rows, what in ((local, M, units[0]), (shared, ts.size - 1, units[1])):
         part = {k: v for k, v in (prior or {}).items() if k in names}
         if not part:
             priors.append((None, None, 0))
@@ -427,6 +428,66 @@ def refine_tiles_args(params, obs, shared, local, tile_size, tile_start, bounds,
         mean, weight = prior_arrays(pp, rows)
         priors.append((mean, weight, int(mean.ndim == 2)))
     return plan, params, M, len(shared), int(kind == "per_observation"), ts, priors[0], priors[1]
+
+
+def series_starts(M, n_dates, series_start):
+    """refine_series' partition: exactly one of ``n_dates`` (uniform series of T rows; M must be a multiple) and
+    ``series_start`` ((S + 1,) integers, 0 = s_0 < s_1 < ... < s_S = M) -> series_start as int64; no series above 256 rows"""
+    if (n_dates is None) == (series_start is None):
+        raise ValueError("exactly one of n_dates and series_start is expected")
+    if n_dates is not None:
+        if isinstance(n_dates, bool) or int(n_dates) != n_dates or not 1 <= int(n_dates) <= _lib.SERIES_MAXT:
+            raise ValueError(f"n_dates = {n_dates!r}, expected an integer 1 ... {_lib.SERIES_MAXT}")
+        T = int(n_dates)
+        if M % T:
+            raise ValueError(f"n_dates = {T} does not divide the {M} rows of obs")
+        return np.arange(0, M + 1, T, dtype=np.int64)
+    ts = np.asarray(series_start)
+    if ts.ndim != 1 or ts.size < 1 or not np.issubdtype(ts.dtype, np.integer):
+        raise ValueError(f"series_start: expected a (S + 1,) integer array, got shape {ts.shape} of {ts.dtype}")
+    ts = np.ascontiguousarray(ts, dtype=np.int64)
+    if ts[0] != 0 or ts[-1] != M:
+        raise ValueError(f"series_start runs from {int(ts[0])} to {int(ts[-1])}, expected 0 ... M = {M}")
+    size = np.diff(ts)
+    if ((size < 1) | (size > _lib.SERIES_MAXT)).any():
+        t = int(np.flatnonzero((size < 1) | (size > _lib.SERIES_MAXT))[0])
+        raise ValueError(f"series_start: series {t} has {int(size[t])} rows, expected 1 ... {_lib.SERIES_MAXT}")
+    return ts
+
+
+def refine_series_args(params, obs, shared, local, n_dates, series_start, smooth, link, bounds, weights, column, n_iter, rel_step,
+                       lambda0, lidf, prior, band_model, nb=None):
+    """Every argument check of spart_amd.refine_series and Engine.refine_series that needs no device: refine_tiles_args with
+    the series partition, at least one local name, ``smooth`` = {local name: sigma > 0} (gamma = 1 / sigma^2; a local that
+    is not named gets gamma = 0) and ``link`` (None, or (M,) values; a tensor is left for the device to judge).
+    -> refine_tiles_args' tuple, then gamma (Fl,) float64"""
+    local = [str(s) for s in local]
+    if not local:
+        raise ValueError("local: at least one local name is expected (nothing to link: use refine_tiles)")
+    out = refine_tiles_args(params, obs, shared, local, None, None, bounds, weights, column, n_iter, rel_step, lambda0, lidf, prior,
+                            band_model, nb=nb, partition=lambda M: series_starts(M, n_dates, series_start), units=("rows", "series"))
+    if smooth is not None and not isinstance(smooth, dict):
+        raise ValueError(f"smooth = {smooth!r}, expected a dict {{local name: sigma}}")
+    stray = [k for k in (smooth or {}) if k not in local]
+    if stray:
+        raise ValueError(f"smooth: {stray} not local")
+    gamma = np.zeros(len(local))
+    for k, sigma in (smooth or {}).items():
+        try:
+            sg = float(sigma)
+        except (TypeError, ValueError):
+            raise ValueError(f"smooth[{k!r}] = {sigma!r}, expected one sigma > 0") from None
+        if not (sg > 0.0 and np.isfinite(sg) and sg * sg > 0.0 and np.isfinite(1.0 / (sg * sg))):
+            raise ValueError(f"smooth[{k!r}]: sigma = {sigma!r}, expected a finite number > 0 with a finite 1 / sigma^2")
+        gamma[local.index(k)] = 1.0 / (sg * sg)
+    M = out[2]
+    if link is not None and not hasattr(link, "data_ptr"):
+        ln = np.asarray(link, dtype=np.float64)
+        if ln.shape != (M,):
+            raise ValueError(f"link has shape {ln.shape}, expected ({M},)")
+    elif link is not None and tuple(link.shape) != (M,):
+        raise ValueError(f"link has shape {tuple(link.shape)}, expected ({M},)")
+    return out + (gamma,)
 
 
 BAND_MODELS = ("centre", "srf")
@@ -1258,12 +1319,13 @@ class Engine:
         shapes = {"x": (M, n), "cost": (M,), "cost0": (M,), "std": (M, n), "n_accept": (M,), "y": yshape}
         return {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device) for k in _FIT_OUTS}
 
-    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None, tiles=None):
+    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None, tiles=None, series=None):
         """What every entry point of the refinement family does once its parameter columns ``cols`` and its outputs are on the
         device: obs and weights as float64 device tensors, spart_refine_opt from the plan, the prior (mean, weight, per
         observation 0 / 1) hooked up, the workspace, the call count, the C call and its check.  ``outs``: the C arguments between
         the options and the workspace; ``views`` = (V, Fs, srf) wraps the options in spart_refine_views_opt;
-        ``tiles`` = (Fs, srf, tile_start, shared prior) wraps them in spart_refine_tiles_opt and passes the partition.
+        ``tiles`` = (Fs, srf, tile_start, shared prior) wraps them in spart_refine_tiles_opt and passes the partition;
+        ``series`` = (gamma, link) with ``tiles`` wraps those in spart_refine_series_opt.
         -> (obs, weights) as the call got them"""
         torch = self.torch
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -1285,6 +1347,11 @@ class Engine:
                 sm, sw = (torch.as_tensor(v).to(**f64).contiguous() for v in sprior[:2])
                 opt.shared_prior_per_tile, opt.shared_prior_mean, opt.shared_prior_weight = sprior[2], sm.data_ptr(), sw.data_ptr()
             part = [ts.size - 1, ts.ctypes.data_as(_lib.c_i64p)]
+            if series is not None:
+                gamma, link = series
+                ln = None if link is None else torch.as_tensor(link).to(**f64).contiguous()
+                nbytes = int(self.lib.spart_series_workspace_bytes(self.ctx, M, F, Fs))
+                opt = _lib.SpartRefineSeriesOpt(tiles=opt, smooth=_dp(gamma), link=None if ln is None else ln.data_ptr())
         elif views is None:
             nbytes = int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F))
         else:
@@ -1473,6 +1540,42 @@ class Engine:
         self._refine_device("spart_refine_tiles", plan, M, cols, obs, weights, wper, lidf, nl, lprior, [ctypes.byref(out)],
                             tiles=(Fs, srf, ts, sprior))
         res["names"], res["tile_start"] = list(plan["names"]), ts
+        return res
+
+    def refine_series(self, params, obs, shared=(), local=(), n_dates=None, series_start=None, smooth=None, link=None, bounds=None,
+                      weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None, prior=None,
+                      band_model="centre"):
+        """refine_tiles() with the tile read as a TIME SERIES of one pixel and a smoothness prior between consecutive dates: a
+        row is one date with its own geometry, atmosphere, observation and weights; the ``shared`` names are ONE unknown per
+        series (leaf angle, soil brightness), the ``local`` names (at least one) one unknown per date, tied to the next date by
+        a first-difference penalty (include/spart_hip.h: spart_refine_series; tools/refine_series_defined.py is the numpy form).
+        A date whose weights are all zero is a masked (cloudy) date: its locals are filled by its neighbours.
+        n_dates : T: uniform series of T rows (M a multiple of T);  or  series_start : (S + 1,) integers; 1 ... 256 rows each
+        smooth : {local name: sigma}: the tie of that parameter between consecutive dates has weight 1 / sigma^2 (times link);
+                 a local that is not named is not tied
+        link   : None, or (M,) values >= 0: link[m] scales the tie between rows m and m + 1 (date_links makes 1 / dt); the
+                 entry of a series' last row is not read
+        everything else as for refine_tiles(); prior: a shared name takes scalars or (S,) arrays, a local name scalars or (M,)
+        -> refine_tiles()'s dict with ``series_start`` in place of ``tile_start``: cost, cost0, n_accept per series (-1: a dead
+        series -- a bad row kills its whole series: status -1 on the bad rows, 1 on the others).
+        retrieve / retrieve_stream do not call this."""
+        plan, params, M, Fs, wper, ts, lprior, sprior, gamma = refine_series_args(
+            params, obs, shared, local, n_dates, series_start, smooth, link, bounds, weights, column, n_iter, rel_step, lambda0, lidf,
+            prior, band_model, nb=self.nb)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        T, Fl = ts.size - 1, len(plan["names"]) - Fs
+        # ---- the device from here on
+        torch = self.torch
+        cols = self._refine_columns(params, M)
+        shapes = {"shared": (T, Fs), "shared_std": (T, Fs), "local": (M, Fl), "local_std": (M, Fl), "cost": (T,), "cost0": (T,),
+                  "n_accept": (T,), "pixel_cost": (M,), "status": (M,), "y": (M, self.nb)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("n_accept", "status") else torch.float64, device=self.device)
+               for k in _lib.TILES_OUTS}
+        out = _lib.SpartTilesOut(**{k: v.data_ptr() for k, v in res.items()})
+        self._refine_device("spart_refine_series", plan, M, cols, obs, weights, wper, lidf, nl, lprior, [ctypes.byref(out)],
+                            tiles=(Fs, srf, ts, sprior), series=(gamma, link))
+        res["names"], res["series_start"] = list(plan["names"]), ts
         return res
 
     def profile(self, max_calls):

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
-                     refine_tiles_args, refine_views_args)
+                     refine_series_args, refine_tiles_args, refine_views_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -627,6 +627,42 @@ def refine_tiles(params, obs, sensor, shared, local=(), tile_size=None, tile_sta
                            bounds=bounds, weights=weights, column=column, n_iter=n_iter, rel_step=rel_step, lambda0=lambda0,
                            lidf=lidf, nlayers=nlayers, prior=prior, band_model=band_model)
     return {k: (v if k in ("names", "tile_start") else v.cpu().numpy()) for k, v in res.items()}
+
+
+def refine_series(params, obs, sensor, shared=(), local=(), n_dates=None, series_start=None, smooth=None, link=None, bounds=None,
+                  weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None, sensor_info=None,
+                  device=None, prior=None, band_model="centre"):
+    """The host form of Engine.refine_series: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays, one column
+    per date, ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``); everything else as for
+    Engine.refine_series.  -> dict of numpy arrays (refine_tiles' keys, ``series_start`` in place of ``tile_start``) and the list
+    ``names``.  Every argument check that needs no device runs before one is asked for."""
+    params = refine_series_args(params, obs, shared, local, n_dates, series_start, smooth, link, bounds, weights, column, n_iter,
+                                rel_step, lambda0, lidf, prior, band_model)[1]
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.refine_series(params, np.asarray(obs, dtype=np.float64), shared, local, n_dates=n_dates, series_start=series_start,
+                            smooth=smooth, link=link, bounds=bounds, weights=weights, column=column, n_iter=n_iter, rel_step=rel_step,
+                            lambda0=lambda0, lidf=lidf, nlayers=nlayers, prior=prior, band_model=band_model)
+    return {k: (v if k in ("names", "series_start") else v.cpu().numpy()) for k, v in res.items()}
+
+
+def date_links(days, series_start, power=1):
+    """The ``link`` of refine_series from acquisition days: ``days`` (M,) increasing within every series, ``series_start``
+    (S + 1,) -> (M,) float64 with 1 / dt^power at row m for dt = days[m + 1] - days[m], and 0 at each series' last row.
+    Days that do not increase within a series are a ValueError."""
+    days = np.asarray(days, dtype=np.float64)
+    ts = np.asarray(series_start, dtype=np.int64)
+    if days.ndim != 1 or ts.ndim != 1 or ts.size < 1 or ts[0] != 0 or ts[-1] != days.size or (np.diff(ts) < 1).any():
+        raise ValueError(f"days {days.shape} and series_start {ts.tolist() if ts.ndim == 1 else ts.shape}: (M,) and 0 = s_0 < ... < s_S = M expected")
+    link = np.zeros(days.size)
+    if days.size:
+        inner = np.ones(days.size, dtype=bool)
+        inner[ts[1:] - 1] = False
+        dt = np.diff(days, append=days[-1])
+        if not (dt[inner] > 0.0).all():
+            m = int(np.flatnonzero(inner & ~(dt > 0.0))[0])
+            raise ValueError(f"days must increase within a series: days[{m + 1}] = {days[m + 1]} after {days[m]}")
+        link[inner] = 1.0 / dt[inner] ** power
+    return link
 
 
 def tiles_from_labels(labels):
