@@ -72,7 +72,7 @@ extern "C" {
  * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too,
  * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise.
  * spart_refine_series and spart_series_workspace_bytes with spart_refine_series_opt, which embeds spart_refine_tiles_opt
- * unchanged, likewise. */
+ * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -770,6 +770,67 @@ int spart_refine_series(spart_ctx *ctx, int64_t M, const double *const base[SPAR
                         const double *lo, const double *hi /* HOST, (F,) per name */, int64_t S, const int64_t *series_start /* HOST (S+1,) */,
                         const double *obs, const double *weights, const spart_refine_series_opt *opt, const spart_tiles_out *out,
                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* GLOBAL, variance-based sensitivity of a sensor column to the free parameters over their ranges: Sobol' first-order and total
+ * indices of every band, with delete-one-block jackknife standard errors -- what says WHICH parameters a retrieval can free.
+ * M is the number of SITES: base[p] is (M,) device float64, one fixed row per site (its geometry, atmosphere and everything not
+ * freed).  The designs uA, uB (N, F) row-major on the device, in the unit cube, are shared by all sites and used as given: the
+ * library holds no random numbers and checks no range; a NaN or out-of-range u gives the x it gives.
+ * Definition (tools/sobol_defined.py is the same text in numpy), per site m, float64, every written operation one rounded
+ * operation, no FMA contraction, IEEE division and sqrt:
+ *   points    xA[n,f] = lo_f + uA[n,f] * (hi_f - lo_f), the difference formed first; xB likewise from uB
+ *   rows      A_n is base_m with column free[f] = xA[n,f] for every f; B_n the same with xB; C^f_n = A_n with the one column
+ *             free[f] = xB[n,f]: N (F + 2) rows.  yA, yB, yC^f (N, nb) are the chosen column of those rows, bit for bit what
+ *             spart_run_batch(SPART_F64, prune_unused_bands = 1) returns for them (thermal inputs at their defaults, no rdry_in /
+ *             lidf_in, fast_prelude and nlayers honoured); with band_model 1 the *_srf column instead
+ *   shift     c_j = yA[0,j];  a = yA - c,  b = yB - c,  d^f = (yC^f - c) - a.  The estimators are shift-invariant in exact
+ *             arithmetic; the shift only keeps E[y^2] - E[y]^2 from cancelling
+ *   blocks    block g is samples 64 g ... 64 g + 63.  For each of the Q = 4 + 3 F quantities the 64 per-sample terms t_0 .. t_63
+ *             are joined by one fixed tree: for s = 32, 16, 8, 4, 2, 1: t_r = t_r + t_{r+s} for r < s; the result is t_0.
+ *             The quantities: sa = a, sb = b, saa = a*a, sbb = b*b, and per f: u_f = b*d^f, t_f = d^f*d^f, e_f = d^f
+ *   totals    each quantity summed over the blocks g ascending from 0.0: SA, SB, SAA, SBB, U_f, T_f, D_f
+ *   finish    with n = (double)N:  mu = (SA + SB) / (2 n);  m2 = (SAA + SBB) / (2 n);  var = m2 - mu*mu;  mean = c + mu;
+ *             S1_f = (U_f / n - mu * (D_f / n)) / var;  ST_f = (T_f / (2 n)) / var  -- Saltelli et al. 2010, Table 2 (b) and (f),
+ *             on mean-centred outputs (Sobol' & Levitan 1999).  A zero or non-finite var, or a NaN row, propagates as IEEE
+ *             gives: nothing is clamped and nothing is replaced by 0
+ *   jackknife with G = N / 64: for each g the finish formulas on X - x_g for every total X (one subtraction each) with
+ *             n' = n - 64 give theta_g for each of the 2 F indices;  thetabar = (sum_g theta_g, g ascending from 0.0) / G;
+ *             v = 0; for g ascending: e = theta_g - thetabar, v = v + e*e;  se = sqrt((v * (G - 1)) / G)
+ * Consequences (a row's column is a pure function of its own 27 parameters).  A site's outputs are the same bits alone or among
+ * other sites, in whichever chunk it falls.  Permuting free_cols / lo / hi together with the columns of uA / uB permutes S1, ST
+ * and the two se and leaves mean and var unchanged.  With uB == uA every d^f is exactly 0, so S1, ST and both se are 0.  DOY
+ * (column 26) as a free parameter with column 0 or 1 gives S1 == ST == 0 for it (only L_TOA reads it) and leaves the other
+ * parameters' indices bit-equal to the call without it.
+ * Forward rows go in chunks of whole blocks of 64 (F + 2) rows, at most 2^19 rows per chunk, site-major: many small sites
+ * share a forward call, a large site runs over several.  spart_sobol_workspace_bytes is 0 exactly for refused sizes; with
+ * G = N / 64, bcap = min(M G, 2^19 / (64 (F + 2))) blocks, R = 64 (F + 2) bcap rows and nslot = min(M, bcap / G + 2) it is
+ * (each term rounded up to 256 bytes)
+ *   8 * 27 R  +  3 * 8 R nb  +  forward scratch of R rows  +  8 nslot nb  +  8 nslot G nb Q:
+ * one chunk of forward rows plus the block sums of the sites in flight, constant in M once M G >= 2^19 / (64 (F + 2)).
+ * Everything is queued on `stream`; nothing synchronises.  Refused before anything is launched or written: SPART_ERR_INVALID
+ * for a NULL context; F outside 1 ... 16; NULL free_cols / lo / hi; column, nlayers; a free column out of range or named
+ * twice, bounds not finite lo < hi (spart_refine's checks in its order); then band_model outside 0 / 1; then N not a multiple of
+ * 64 or outside 128 ... 2^20; then M < 0 or M > 2e9; then, with M > 0, a NULL opt, out, base or base column (the first named),
+ * a NULL uA or uB, or all six outputs NULL.  Then SPART_ERR_NOSENSOR, then (M = 0 launches nothing) SPART_ERR_WORKSPACE.
+ * Second-order indices, bootstrap intervals, grouped parameters and designs made on the device are out of scope.  Added WITHOUT
+ * a new interface number, by spart_refine_srf's rule: two symbols, two structs. */
+typedef struct spart_sobol_opt {
+  int32_t column;        /* 0 R_TOC, 1 R_TOA, 2 L_TOA */
+  int32_t band_model;    /* 0 centre columns, 1 SRF columns (spart_refine_srf's forward call) */
+  int32_t fast_prelude;  /* as spart_materialize */
+  int32_t nlayers;       /* as spart_materialize, 0 = 60 */
+} spart_sobol_opt;
+typedef struct spart_sobol_out {      /* device, float64, each may be NULL, not all */
+  double *mean, *var;                 /* (M, nb)    over the 2N rows of A and B, ddof 0 */
+  double *S1, *ST;                    /* (M, nb, F) first-order and total index */
+  double *S1_se, *ST_se;              /* (M, nb, F) delete-one-block jackknife standard errors */
+} spart_sobol_out;
+size_t spart_sobol_workspace_bytes(const spart_ctx *ctx, int64_t M, int64_t N, int F);
+int spart_sobol(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F,
+                const int32_t *free_cols /* HOST */, const double *lo, const double *hi /* HOST (F,) */,
+                int64_t N, const double *uA, const double *uB /* DEVICE (N, F) row-major, unit cube */,
+                const spart_sobol_opt *opt, const spart_sobol_out *out,
+                void *workspace, size_t workspace_bytes, void *stream);
 
 /* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
  * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging

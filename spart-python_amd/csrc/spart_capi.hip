@@ -24,6 +24,7 @@
 #include "spart_refine_views.h"
 #include "spart_refine_tiles.h"
 #include "spart_refine_series.h"
+#include "spart_sobol.h"
 #include "spart_products.h"
 
 using namespace spart;
@@ -1992,6 +1993,130 @@ int spart_refine_series(spart_ctx* ctx, int64_t M, const double* const base[SPAR
         return SPART_OK;
       },
       [&](const RefineRun& r, hipStream_t st) { return series_impl(r, y, so.tiles.n_shared, S, series_start, so, oo, st); });
+}
+
+// ---- spart_sobol (csrc/spart_sobol.h).  Workspace: ONE chunk of forward rows -- the (27, R) table, the three (R, nb)
+// column blocks and the forward call's scratch, R = 64 (F + 2) bcap -- then c_j and the block sums of the nslot sites a chunk
+// can touch ((N / 64) nb Q doubles each).  bcap = min(M G, sobol_chunk_blocks(F)) blocks, G = N / 64: it depends on M only
+// while the whole call is smaller than one chunk.
+struct SobolLayout {
+  int64_t bcap;                 // blocks per chunk
+  int nslot;                    // sites whose block sums are kept at once
+  size_t table, cols[3], fwd, cbuf, bs, total;
+};
+static SobolLayout sobol_layout(int nb, int64_t M, int64_t N, int F) {
+  SobolLayout l;
+  const int64_t G = N / SOBOL_BLOCK;
+  l.bcap = std::min<int64_t>(M * G, sobol_chunk_blocks(F));
+  l.nslot = (int)std::min<int64_t>(M, l.bcap / G + 2);            // (bc consecutive blocks touch at most bc / G + 2 sites)
+  const size_t rows = (size_t)l.bcap * SOBOL_BLOCK * (size_t)(F + 2);
+  Carver c;
+  l.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  l.cbuf = c.take((size_t)l.nslot * nb * 8);
+  l.bs = c.take((size_t)l.nslot * (size_t)G * (size_t)sobol_nq(F) * nb * 8);
+  l.total = c.o;
+  return l;
+}
+
+static bool sobol_n_ok(int64_t N) { return N >= SOBOL_MIN_N && N <= SOBOL_MAX_N && N % SOBOL_BLOCK == 0; }
+
+size_t spart_sobol_workspace_bytes(const spart_ctx* ctx, int64_t M, int64_t N, int F) {
+  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF || !sobol_n_ok(N)) return 0;
+  return sobol_layout(ctx->nb, M, N, F).total;
+}
+
+// the chunk loop: the table, the forward call, the block sums, then the sites whose last block lies in the chunk
+static int sobol_impl(spart_ctx* ctx, const SobolCfg& cfg, int64_t M, int F, int64_t N, const double* uA, const double* uB,
+                      const spart_sobol_opt& o, const SobolOut& out, char* wsp, const SobolLayout& l, hipStream_t st) {
+  const int nb = ctx->nb, G = (int)(N / SOBOL_BLOCK), per = SOBOL_BLOCK * (F + 2);
+  const bool srf = o.band_model == 1;
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
+  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  double* table = (double*)(wsp + l.table);
+  double* cbuf = (double*)(wsp + l.cbuf);
+  double* bs = (double*)(wsp + l.bs);
+  const int64_t B = M * G;
+  for (int64_t b0 = 0; b0 < B; b0 += l.bcap) {
+    const int bc = (int)std::min<int64_t>(l.bcap, B - b0);
+    const int64_t rows = (int64_t)bc * per;
+    hipLaunchKernelGGL(k_sobol_rows, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, F, b0, bc, G, uA, uB, table);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, wsp + l.fwd,
+                                                  ws, st, !srf))
+      return rc;
+    hipLaunchKernelGGL(k_sobol_blocks, dim3((unsigned)(((int64_t)bc * nb + 3) / 4)), dim3(256), 0, st, (const double*)cols[o.column],
+                       nb, F, b0, bc, G, l.nslot, cbuf, bs);
+    const int64_t m0 = b0 / G, m1 = (b0 + bc) / G;                 // sites m0 <= m < m1 end in this chunk
+    if (m1 > m0)
+      hipLaunchKernelGGL(k_sobol_finish, dim3((unsigned)((nb * F + 63) / 64), (unsigned)(m1 - m0)), dim3(64), 0, st,
+                         (const double*)bs, (const double*)cbuf, nb, F, G, l.nslot, m0, (double)N, out);
+    HIP_TRY(hipGetLastError());
+  }
+  return SPART_OK;
+}
+
+// spart_refine's checks of F, the four host arrays, the options and the free columns in its order; then band_model, N, M;
+// then, with M > 0, what is NULL; the workspace last
+int spart_sobol(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols, const double* lo,
+                const double* hi, int64_t N, const double* uA, const double* uB, const spart_sobol_opt* opt,
+                const spart_sobol_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_sobol";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  spart_sobol_opt o;
+  std::memset(&o, 0, sizeof(o));
+  if (opt) o = *opt;
+  if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
+  if (o.nlayers < 0 || o.nlayers > SPART_MAX_NLAYERS)
+    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
+  SobolCfg cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  for (int f = 0; f < F; ++f) {
+    const int c = free_cols[f];
+    if (c < 0 || c >= SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, SPART_NPARAM - 1);
+    if (cfg.is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
+    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
+      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
+    cfg.is_free[c] = 1;
+    cfg.free_col[f] = c;
+    cfg.lo[f] = lo[f];
+    cfg.hi[f] = hi[f];
+  }
+  if (int rc = refine_check_band_model(who, o.band_model)) return rc;
+  if (!sobol_n_ok(N))
+    return fail(SPART_ERR_INVALID, "%s: N = %lld, expected a multiple of %d in %lld ... %lld", who, (long long)N, SOBOL_BLOCK,
+                (long long)SOBOL_MIN_N, (long long)SOBOL_MAX_N);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (M > 0) {
+    if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
+    if (!out) return fail(SPART_ERR_INVALID, "%s: out is null", who);
+    if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
+    if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+    if (!uA) return fail(SPART_ERR_INVALID, "%s: uA is null", who);
+    if (!uB) return fail(SPART_ERR_INVALID, "%s: uB is null", who);
+    if (!out->mean && !out->var && !out->S1 && !out->ST && !out->S1_se && !out->ST_se)
+      return fail(SPART_ERR_INVALID, "%s: every output is null", who);
+  }
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  const SobolLayout l = sobol_layout(ctx->nb, M, N, F);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
+  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
+  const SobolOut so = {out->mean, out->var, out->S1, out->ST, out->S1_se, out->ST_se};
+  return guarded(ctx, who, workspace, l.total, stream,
+                 [&](hipStream_t st) { return sobol_impl(ctx, cfg, M, F, N, uA, uB, o, so, (char*)workspace, l, st); });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

@@ -80,6 +80,14 @@ class SpartProductsOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("fapar_bs", "fapar_ws", "albedo_bs", "albedo_ws", "fcover")]
 
 
+class SpartSobolOpt(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("column", "band_model", "fast_prelude", "nlayers")]
+
+
+class SpartSobolOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("mean", "var", "S1", "ST", "S1_se", "ST_se")]
+
+
 PRODUCT_NAMES = ("fAPAR_bs", "fAPAR_ws", "albedo_bs", "albedo_ws", "fCover")      # spart_products_out, in its order
 PRODUCTS_NREAD = 22                                 # spart_products reads params[0 ... 21]
 LUT_BAYES_OUTS = tuple(n for n, _ in SpartLutBayesOut._fields_)      # spart_lut_bayes_out, in its order
@@ -92,6 +100,8 @@ REFINE_MAXV = 64                                    # spart_refine_views_opt.V
 TILES_OUTS = tuple(n for n, _ in SpartTilesOut._fields_)             # spart_tiles_out, in its order
 TILES_MAXG = 4096                                   # pixels per tile of spart_refine_tiles
 SERIES_MAXT = 256                                   # rows per series of spart_refine_series
+SOBOL_OUTS = tuple(n for n, _ in SpartSobolOut._fields_)             # spart_sobol_out, in its order
+SOBOL_BLOCK, SOBOL_MIN_N, SOBOL_MAX_N = 64, 128, 1 << 20             # spart_sobol: N a multiple of 64 in 128 ... 2^20
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -159,6 +169,9 @@ SIGNATURES = {
                             [ctypes.POINTER(SpartRefineSeriesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),
     "spart_refine_posterior": (ctypes.c_int, _REFINE_CALL[:10] + [ctypes.c_int, ctypes.POINTER(SpartPosteriorOut)] + _REFINE_CALL[16:]),
     "spart_products": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.POINTER(SpartProductsOut), vp, ctypes.c_size_t, vp]),
+    "spart_sobol_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "spart_sobol": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, vp, vp, ctypes.POINTER(SpartSobolOpt),
+                                                     ctypes.POINTER(SpartSobolOut)] + _REFINE_CALL[16:]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

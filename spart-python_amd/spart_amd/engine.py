@@ -490,6 +490,52 @@ def refine_series_args(params, obs, shared, local, n_dates, series_start, smooth
     return out + (gamma,)
 
 
+def sobol_design(N, F, seed=0):
+    """The two designs of sobol(): -> (uA, uB), float64 (N, F) in [0, 1): the first and the last F columns of ONE scrambled
+    torch.quasirandom.SobolEngine(2 F, scramble=True, seed=seed) draw of N points in float64 (Saltelli's scheme wants A and B
+    as the two halves of one 2 F-dimensional sequence).  Needs no device."""
+    import torch
+    if isinstance(N, bool) or int(N) != N or int(N) < 1:
+        raise ValueError(f"N = {N!r}, expected an integer >= 1")
+    if isinstance(F, bool) or int(F) != F or not 1 <= int(F) <= _lib.REFINE_MAXF:
+        raise ValueError(f"F = {F!r}, expected an integer 1 ... {_lib.REFINE_MAXF}")
+    N, F = int(N), int(F)
+    u = torch.quasirandom.SobolEngine(2 * F, scramble=True, seed=int(seed)).draw(N, dtype=torch.float64).numpy()
+    return np.ascontiguousarray(u[:, :F]), np.ascontiguousarray(u[:, F:])
+
+
+def sobol_args(params, free, N, bounds, design, seed, column, band_model, lidf):
+    """Every argument check of spart_amd.sobol and Engine.sobol that needs no device: refine_plan on ``free`` / ``bounds`` /
+    ``column``, the band model's name, lidf, params (a (27, M) block or 27 entries of 1 or M values; M sites), and the design:
+    ``design`` = (uA, uB), two (N, F) arrays or tensors used as given (their N counts), or None for sobol_design(N, F, seed).
+    N: a multiple of 64 in 128 ... 2^20.  -> (plan, params, M, N, uA, uB); params as refine_args returns it"""
+    import torch
+    plan = refine_plan(free, bounds, 0, column, 1e-3, 1e-2)
+    _band_model(band_model)
+    if lidf not in ("literal", "newton"):
+        raise ValueError("lidf must be 'literal' or 'newton'")
+    F = len(plan["names"])
+    if design is not None:
+        if not isinstance(design, (tuple, list)) or len(design) != 2:
+            raise ValueError("design: expected (uA, uB), two (N, F) arrays")
+        uA, uB = (d if torch.is_tensor(d) else np.ascontiguousarray(d, dtype=np.float64) for d in design)
+        for name, u in (("uA", uA), ("uB", uB)):
+            if len(u.shape) != 2 or int(u.shape[1]) != F:
+                raise ValueError(f"design: {name} has shape {tuple(u.shape)}, expected (N, {F})")
+        if tuple(uA.shape) != tuple(uB.shape):
+            raise ValueError(f"design: uA {tuple(uA.shape)} and uB {tuple(uB.shape)} differ in shape")
+        N = int(uA.shape[0])
+    if isinstance(N, bool) or int(N) != N or int(N) % _lib.SOBOL_BLOCK or not _lib.SOBOL_MIN_N <= int(N) <= _lib.SOBOL_MAX_N:
+        raise ValueError(f"N = {N!r}, expected a multiple of {_lib.SOBOL_BLOCK} in {_lib.SOBOL_MIN_N} ... {_lib.SOBOL_MAX_N}")
+    N = int(N)
+    M = params_rows(params)
+    params = refine_args(params, np.broadcast_to(np.float64(0.0), (M, 1)), free, bounds, None, column, 0, 1e-3, 1e-2, lidf, None,
+                         None, None, band_model, _plan=plan)[1]
+    if design is None:
+        uA, uB = sobol_design(N, F, seed)
+    return plan, params, M, N, uA, uB
+
+
 BAND_MODELS = ("centre", "srf")
 _FIT_OUTS = ("x", "cost", "cost0", "std", "n_accept", "y")     # of spart_refine / _srf / _views, in the order of their argument lists
 
@@ -1576,6 +1622,41 @@ class Engine:
         self._refine_device("spart_refine_series", plan, M, cols, obs, weights, wper, lidf, nl, lprior, [ctypes.byref(out)],
                             tiles=(Fs, srf, ts, sprior), series=(gamma, link))
         res["names"], res["series_start"] = list(plan["names"]), ts
+        return res
+
+    def sobol(self, params, free, N=4096, bounds=None, design=None, seed=0, column="R_TOC", band_model="centre", lidf="literal",
+              nlayers=None):
+        """GLOBAL sensitivity of a sensor column to the ``free`` parameters over their ranges, on the device in one call
+        (include/spart_hip.h: spart_sobol, which defines every sum; tools/sobol_defined.py is the numpy form): Sobol' first-order
+        and total indices of every band with jackknife standard errors -- what tells which parameters a retrieval can free.
+        params : the SITES: a (27, M) block or 27 entries of 1 or M values; a site fixes geometry, atmosphere and every
+                 parameter that is not free
+        free, bounds : as for refine(): names, and {name: (lo, hi)} with workloads.RANGES as the default
+        N : base samples, a multiple of 64 in 128 ... 2^20: N (F + 2) forward rows per site
+        design : None (sobol_design(N, F, seed)) or (uA, uB), two (N, F) arrays in the unit cube, used as given
+        column, band_model, lidf, nlayers : as for refine()
+        -> dict of device tensors mean, var (M, nb) (over the 2 N rows of A and B), S1, ST, S1_se, ST_se (M, nb, F); and ``names``.
+        A band that does not vary has var 0 and NaN indices; nothing is clamped."""
+        plan, params, M, N, uA, uB = sobol_args(params, free, N, bounds, design, seed, column, band_model, lidf)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        F, nb = len(plan["names"]), self.nb
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        cols = self._refine_columns(params, M)
+        uA, uB = (torch.as_tensor(u).to(**f64).contiguous() for u in (uA, uB))
+        res = {k: torch.empty((M, nb) if k in ("mean", "var") else (M, nb, F), **f64) for k in _lib.SOBOL_OUTS}
+        out = _lib.SpartSobolOut(**{k: v.data_ptr() for k, v in res.items()})
+        opt = _lib.SpartSobolOpt(column=plan["column"], band_model=int(srf), fast_prelude=1 if lidf == "newton" else 0, nlayers=nl)
+        nbytes = max(int(self.lib.spart_sobol_workspace_bytes(self.ctx, M, N, F)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_sobol"] += 1
+        rc = self.lib.spart_sobol(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                  _dp(plan["lo"]), _dp(plan["hi"]), N, uA.data_ptr(), uB.data_ptr(), ctypes.byref(opt),
+                                  ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        res["names"] = list(plan["names"])
         return res
 
     def profile(self, max_calls):

@@ -18,9 +18,9 @@ import warnings
 import numpy as np
 
 from . import _lib, workloads
-from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, _band_model, get_engine, knn_prior, lut_weights_kind,
+from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, get_engine, knn_prior, lut_weights_kind,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
-                     refine_series_args, refine_tiles_args, refine_views_args)
+                     refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -582,6 +582,19 @@ def posterior(params, obs, sensor, free, bounds=None, weights=None, column="R_TO
     eng = get_engine(sensor, device, sensor_info=sensor_info)
     res = eng.posterior(params, None if obs is None else np.asarray(obs, dtype=np.float64), free, weights=weights, lidf=lidf,
                         nlayers=nlayers, prior_mean=prior_mean, prior_weight=prior_weight, band_model=band_model, _plan=plan)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def sobol(params, sensor, free, N=4096, bounds=None, design=None, seed=0, column="R_TOC", band_model="centre", lidf="literal",
+          nlayers=None, sensor_info=None, device=None):
+    """The host form of Engine.sobol: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays, one column per
+    site, ``sensor`` / ``sensor_info`` as for refine(); everything else as for Engine.sobol.  -> dict of numpy arrays mean, var
+    (M, nb), S1, ST, S1_se, ST_se (M, nb, F) and the list ``names``.  Every argument check that needs no device runs before
+    one is asked for."""
+    params, _, N, uA, uB = sobol_args(params, free, N, bounds, design, seed, column, band_model, lidf)[1:]
+    Engine._nlayers(nlayers)
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.sobol(params, free, N=N, bounds=bounds, design=(uA, uB), column=column, band_model=band_model, lidf=lidf, nlayers=nlayers)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
