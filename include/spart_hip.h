@@ -72,7 +72,8 @@ extern "C" {
  * spart_refine_tiles and spart_tiles_workspace_bytes with spart_refine_tiles_opt / spart_tiles_out came by that rule too,
  * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise.
  * spart_refine_series and spart_series_workspace_bytes with spart_refine_series_opt, which embeds spart_refine_tiles_opt
- * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise. */
+ * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise, and
+ * spart_sample and spart_sample_workspace_bytes with spart_sample_opt / spart_sample_out. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -831,6 +832,98 @@ int spart_sobol(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM
                 int64_t N, const double *uA, const double *uB /* DEVICE (N, F) row-major, unit cube */,
                 const spart_sobol_opt *opt, const spart_sobol_out *out,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* The SHAPE of the posterior around a fit, sampled with the forward model itself: the affine-invariant ensemble sampler
+ * (Goodman & Weare 2010) in the two-half-ensemble stretch-move form of emcee (Foreman-Mackey et al. 2013), W walkers per
+ * observation inside the box lo ... hi, for M observations at once.  It has no proposal scale to tune.  base, free_cols, lo, hi,
+ * obs, weights and the prior (opt->prior_*) are spart_refine's, with its mask rule and its weights_per_obs / prior_per_obs
+ * forms; the density sampled is exp(-cost / (2 temperature)) on the box, cost being spart_refine's (prior included).
+ * The random numbers are made on the device by a counter-based generator and are a pure function of (seed, global observation
+ * number, step, walker, draw): the call is one defined result, the same bits in any batch, chunk or launch shape.
+ * Definition (tools/sample_defined.py is the same text in numpy), per observation m, float64, every written operation one
+ * rounded operation, no FMA contraction:
+ *   numbers   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85); key = (low, high 32
+ *             bits of seed); counter = (low 32 bits of g, high 32 bits of g, s mod 2^32, (k << 8) | d) with g = obs_offset + m,
+ *             s the absolute step, k the walker, d the draw; output words w0 .. w3.
+ *             u53(a, b) = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53: exact, in [0, 1)
+ *   start     (s = step0)  x0 = clip(base[free]) by spart_refine's clip; r_f = init_radius[m, f] if given, else
+ *             rel_init * (hi_f - lo_f).  Without init: walker k, coordinate f takes the block (s = step0, k, d = f),
+ *             u = u53(w0, w1), a_f = max(lo_f, x0_f - r_f), b_f = min(hi_f, x0_f + r_f), x_kf = a_f + u * (b_f - a_f), the
+ *             difference formed first; nothing is clipped.  With init: x_k as given.  The costs c_k: the rows are base_m with
+ *             the free columns set to x_k; spart_refine's cost, then the prior's term; half 0, then half 1, by a step's path
+ *   dead      status -1: a negative, NaN or infinite band or prior weight; a radius not finite and > 0; a given init
+ *             coordinate outside [lo, hi] or NaN; a non-finite start cost of any walker.  Every floating output of a dead
+ *             observation is NaN and its n_accept is -1; nothing else depends on it
+ *   step      for s = step0 + 1 ... step0 + n_steps, and within s for h = 0, 1, the walkers k of half h (h W/2 <= k < (h+1) W/2)
+ *             move together against the other half as it stands.  Block d = 0: u1 = u53(w0, w1), partner
+ *             j = (1 - h) W/2 + (w2 mod W/2); block d = 1: u2 = u53(w0, w1).  t = (a - 1) * u1 + 1;  z = (t * t) / a;
+ *             y_f = x_jf + z * (x_kf - x_jf).  Inside iff lo_f <= y_f <= hi_f for every f (a NaN is outside).  The forward row is
+ *             base_m with the free columns at y (for an outside proposal at x_k; the result is then ignored).  c' = cost(y),
+ *             prior included;  zp = 1 multiplied by z F - 1 times;  q = zp * exp(-((c' - c_k) / (2 * temperature))).
+ *             Accept iff inside and u2 < q (a NaN never accepts): x_k = y, c_k = c', n_accept += 1
+ *   best      after the start and after every half-step, for k ascending in that half: c_k < best_cost, strictly, takes the
+ *             walker into best_x, best_cost (the first-seen minimum)
+ *   kept      step s is kept iff s - step0 > burn and (s - step0 - burn) % thin == 0, as keep number t = 0 ... n_keep - 1,
+ *             n_keep = (n_steps - burn) / thin: chain[m, t] and chain_cost[m, t] take the ensemble, and with k ascending
+ *             e_f = x_kf - x0_f,  S_f += e_f,  Q_ab += e_a * e_b for a >= b
+ *   finish    n = (double)(n_keep W);  mean_f = x0_f + S_f / n;  cov_ab = Q_ab / n - (S_a / n) * (S_b / n), mirrored;
+ *             std_f = sqrt(cov_ff);  nothing is clamped.  last, last_cost are the final ensemble
+ * exp is the one operation not pinned to the bit (the library's exp_poly, within 3e-16 relative of a correctly rounded exp):
+ * a decision whose |u2 - q| / q is below 1e-12 may differ between implementations; the chance is 2e-12 per decision.
+ * Consequences.  An observation's outputs are the same bits alone or among others, in whichever chunk it falls: rows [a, b)
+ * sampled with obs_offset = a give the rows of the whole call.  A run of n1 + n2 steps, and a run of n1 steps followed by a run
+ * of n2 steps with init = last and step0 = n1, give the same last, last_cost and kept states.  With F = 1, zp = 1.
+ * Observations go in chunks of Mc = min(M, 2^19 / (W/2)); a chunk runs all its steps before the next starts, 2 (n_steps + 1)
+ * forward calls of Mc W/2 rows each, everything queued on `stream`, nothing synchronises.  spart_sample_workspace_bytes is 0
+ * exactly for refused sizes; with R = Mc W/2 it is (each term rounded up to 256 bytes)
+ *   8 * 27 R  +  3 * 8 R nb  +  forward scratch of R rows  +  the state: 8 Mc (W F + W + 3 F + F (F + 1) / 2 + 2) + 4 Mc
+ *   +  8 * 2 R + 4 R + 64 + 88 (the hand-over between the kernels), constant in M once M >= 2^19 / (W/2).
+ * Refused before anything is launched or written, SPART_ERR_INVALID: a NULL context; F outside 1 ... 16; NULL free_cols / lo /
+ * hi; then spart_refine's checks of the fit in its order (column, nlayers, prior_per_obs, prior_mean without prior_weight or the
+ * reverse, a free column out of range or named twice, bounds not finite lo < hi); then band_model outside 0 / 1; W not one of 8,
+ * 16, 32, 64 or < 2 F; n_steps outside 1 ... 2^20, burn outside 0 ... n_steps - 1, thin < 1 or n_keep < 1; a not 0 and not
+ * finite > 1; temperature not 0 and not finite > 0; rel_init not 0 and not finite > 0; step0 or obs_offset < 0; M < 0 or
+ * M > 2e9; then, with M > 0, a NULL opt, out, base or base column (the first named), a NULL obs, weights_per_obs without
+ * weights, or all eleven outputs NULL.  Then SPART_ERR_NOSENSOR, then (M = 0 launches nothing) SPART_ERR_WORKSPACE.
+ * Other moves, parallel tempering and posterior-predictive spectra are out of scope.  Added WITHOUT a new interface number, by
+ * spart_refine_srf's rule: two symbols, two structs. */
+typedef struct spart_sample_opt {
+  int32_t column;          /* 0 R_TOC, 1 R_TOA, 2 L_TOA */
+  int32_t band_model;      /* 0 centre columns, 1 SRF columns (spart_sobol's meaning) */
+  int32_t fast_prelude;    /* as spart_materialize */
+  int32_t nlayers;         /* as spart_materialize, 0 = 60 */
+  int32_t weights_per_obs; /* as spart_refine_opt */
+  int32_t prior_per_obs;   /* as spart_refine_opt */
+  const double *prior_mean, *prior_weight;  /* as spart_refine_opt: both NULL, or (F,) / (M, F) on the device */
+  int32_t W;               /* walkers: 8, 16, 32 or 64, and W >= 2 F */
+  int32_t reserved;        /* 0 */
+  int64_t n_steps;         /* 1 ... 2^20 */
+  int64_t burn;            /* 0 ... n_steps - 1 */
+  int64_t thin;            /* >= 1; n_keep = (n_steps - burn) / thin >= 1 */
+  double a;                /* stretch scale, 0 = 2.0, else finite and > 1 */
+  double temperature;      /* 0 = 1.0, else finite and > 0 (spart_lut_bayes's tau) */
+  double rel_init;         /* 0 = 0.01 */
+  const double *init_radius; /* NULL, or device (M, F) */
+  const double *init;      /* NULL, or device (M, W, F): a given ensemble, for resuming */
+  int64_t step0;           /* >= 0: steps already taken */
+  int64_t obs_offset;      /* >= 0: global number of observation 0 */
+  uint64_t seed;
+} spart_sample_opt;
+typedef struct spart_sample_out {     /* device, each may be NULL, not all */
+  double *mean;                       /* (M, F) */
+  double *cov;                        /* (M, F, F) */
+  double *std;                        /* (M, F) */
+  double *best_x, *best_cost;         /* (M, F), (M,) */
+  int64_t *n_accept;                  /* (M,) accepted proposals of all walkers, -1: dead */
+  int32_t *status;                    /* (M,) 0, or -1: dead */
+  double *chain, *chain_cost;         /* (M, n_keep, W, F), (M, n_keep, W) */
+  double *last, *last_cost;           /* (M, W, F), (M, W) */
+} spart_sample_out;
+size_t spart_sample_workspace_bytes(const spart_ctx *ctx, int64_t M, int F, int W);
+int spart_sample(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F,
+                 const int32_t *free_cols /* HOST */, const double *lo, const double *hi /* HOST (F,) */,
+                 const double *obs, const double *weights, const spart_sample_opt *opt, const spart_sample_out *out,
+                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
  * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging

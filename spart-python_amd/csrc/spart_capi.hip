@@ -25,6 +25,7 @@
 #include "spart_refine_tiles.h"
 #include "spart_refine_series.h"
 #include "spart_sobol.h"
+#include "spart_sample.h"
 #include "spart_products.h"
 
 using namespace spart;
@@ -2117,6 +2118,172 @@ int spart_sobol(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM
   const SobolOut so = {out->mean, out->var, out->S1, out->ST, out->S1_se, out->ST_se};
   return guarded(ctx, who, workspace, l.total, stream,
                  [&](hipStream_t st) { return sobol_impl(ctx, cfg, M, F, N, uA, uB, o, so, (char*)workspace, l, st); });
+}
+
+// ---- spart_sample (csrc/spart_sample.h).  Workspace: ONE chunk of Mc = min(M, sample_chunk(W)) observations -- the (27, R)
+// table, the three (R, nb) column blocks and the forward call's scratch, R = Mc W / 2 rows of a half-step -- then the chunk's
+// state and the per-row hand-over between k_sample_table and k_sample_step.
+struct SampleLayout {
+  int64_t mcap;                 // observations per chunk
+  size_t table, cols[3], fwd, x, c, x0, S, Q, bx, bc, na, dead, zp, u2, inside, free_col, out, total;
+};
+static SampleLayout sample_layout(int nb, int64_t M, int F, int W) {
+  SampleLayout l;
+  l.mcap = std::min<int64_t>(M, sample_chunk(W));
+  const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(W / 2);
+  Carver c;
+  l.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  l.x = c.take(mc * (size_t)W * F * 8);
+  l.c = c.take(mc * (size_t)W * 8);
+  l.x0 = c.take(mc * F * 8);
+  l.S = c.take(mc * F * 8);
+  l.Q = c.take(mc * (size_t)refine_ntri(F) * 8);
+  l.bx = c.take(mc * F * 8);
+  l.bc = c.take(mc * 8);
+  l.na = c.take(mc * 8);
+  l.dead = c.take(mc * 4);
+  l.zp = c.take(rows * 8);
+  l.u2 = c.take(rows * 8);
+  l.inside = c.take(rows * 4);
+  l.free_col = c.take(REFINE_MAXF * 4);
+  l.out = c.take(sizeof(SampleOut));
+  l.total = c.o;
+  return l;
+}
+
+size_t spart_sample_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int W) {
+  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF || !sample_walkers_ok(W, F)) return 0;
+  return sample_layout(ctx->nb, M, F, W).total;
+}
+
+// the chunk loop: per chunk k_sample_init, then for the start and every step, per half: the table, the forward call, the step
+static int sample_impl(spart_ctx* ctx, const SampleCfg& cfg, int64_t M, int F, const double* obs, const double* weights,
+                       const spart_sample_opt& o, const SampleOut& out, char* wsp, const SampleLayout& l, hipStream_t st) {
+  const int nb = ctx->nb, W = o.W, H = W / 2;
+  const bool srf = o.band_model == 1;
+  spart_materialize mat;
+  std::memset(&mat, 0, sizeof(mat));
+  mat.prune_unused_bands = 1;
+  mat.fast_prelude = o.fast_prelude;
+  mat.nlayers = o.nlayers;
+  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
+  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
+  double* table = (double*)(wsp + l.table);
+  const SampleState state = {(double*)(wsp + l.x),  (double*)(wsp + l.c),      (double*)(wsp + l.x0),    (double*)(wsp + l.S),
+                             (double*)(wsp + l.Q),  (double*)(wsp + l.bx),     (double*)(wsp + l.bc),    (int64_t*)(wsp + l.na),
+                             (int32_t*)(wsp + l.dead), (double*)(wsp + l.zp),  (double*)(wsp + l.u2),    (int32_t*)(wsp + l.inside),
+                             (int32_t*)(wsp + l.free_col), (SampleOut*)(wsp + l.out)};
+  const int64_t n_keep = (o.n_steps - o.burn) / o.thin;
+  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
+    const int64_t rows = (int64_t)mc * H;
+    const uint64_t g0 = (uint64_t)o.obs_offset + (uint64_t)m0;
+    const SampleOut oc = {rows_at(out.mean, m0, F),     rows_at(out.cov, m0, F * F),            rows_at(out.std, m0, F),
+                          rows_at(out.best_x, m0, F),   rows_at(out.best_cost, m0, 1),          rows_at(out.n_accept, m0, 1),
+                          rows_at(out.status, m0, 1),   rows_at(out.chain, m0, n_keep * W * F), rows_at(out.chain_cost, m0, n_keep * W),
+                          rows_at(out.last, m0, W * F), rows_at(out.last_cost, m0, W)};
+    hipLaunchKernelGGL(k_sample_init, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, W, o.seed, g0,
+                       (uint64_t)o.step0, o.rel_init, o.init_radius, o.init, table, state, oc);
+    HIP_TRY(hipGetLastError());
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    const Workspace ws = carve(SPART_F64, rows);
+    SampleStep a;
+    a.cols = cols[o.column];
+    a.obs = obs + m0 * nb;
+    a.wts = rows_at(weights, m0, nb, o.weights_per_obs);
+    a.pmu = rows_at(o.prior_mean, m0, F, o.prior_per_obs);
+    a.ppw = rows_at(o.prior_weight, m0, F, o.prior_per_obs);
+    a.table = table;
+    a.Mc = mc, a.F = F, a.nb = nb, a.W = W, a.wper = o.weights_per_obs ? 1 : 0, a.pper = o.prior_per_obs ? 1 : 0;
+    a.n_keep = n_keep;
+    a.two_tau = 2.0 * o.temperature;
+    a.n = (double)(n_keep * W);
+    a.st = state;
+    for (int64_t rel = 0; rel <= o.n_steps; ++rel) {
+      a.start = rel == 0 ? 1 : 0;
+      a.last = rel == o.n_steps ? 1 : 0;
+      a.keep = rel == 0 ? -1 : sample_keep(rel, o.burn, o.thin);
+      for (int h = 0; h < 2; ++h) {
+        a.h = h;
+        hipLaunchKernelGGL(k_sample_table, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, mc, F, W, h, a.start, o.seed,
+                           g0, (uint64_t)(o.step0 + rel), o.a, table, state);
+        HIP_TRY(hipGetLastError());
+        if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
+                                                      wsp + l.fwd, ws, st, !srf))
+          return rc;
+        hipLaunchKernelGGL(k_sample_step, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, a);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+  }
+  return SPART_OK;
+}
+
+// spart_sobol's checks of F and the host arrays, spart_refine's check of the fit (refine_check_fit), then the sampler's own
+// options in the header's order, M, what is NULL with M > 0, the sensor, the workspace
+int spart_sample(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols, const double* lo,
+                 const double* hi, const double* obs, const double* weights, const spart_sample_opt* opt, const spart_sample_out* out,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "spart_sample";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  spart_sample_opt o;
+  std::memset(&o, 0, sizeof(o));
+  if (opt) o = *opt;
+  spart_refine_opt ro;
+  std::memset(&ro, 0, sizeof(ro));
+  ro.column = o.column, ro.nlayers = o.nlayers, ro.prior_per_obs = o.prior_per_obs;
+  ro.prior_mean = o.prior_mean, ro.prior_weight = o.prior_weight;
+  RefineCfg rc;
+  if (int r = refine_check_fit(who, ro, F, free_cols, lo, hi, rc)) return r;
+  if (int r = refine_check_band_model(who, o.band_model)) return r;
+  if (!sample_walkers_ok(o.W, F))
+    return fail(SPART_ERR_INVALID, "%s: W = %d, expected 8, 16, 32 or 64 and W >= 2 F = %d", who, o.W, 2 * F);
+  if (o.n_steps < 1 || o.n_steps > SAMPLE_MAX_STEPS || o.burn < 0 || o.burn > o.n_steps - 1 || o.thin < 1 ||
+      (o.n_steps - o.burn) / o.thin < 1)
+    return fail(SPART_ERR_INVALID, "%s: n_steps = %lld, burn = %lld, thin = %lld: expected 1 <= n_steps <= %d, 0 <= burn < n_steps, "
+                "thin >= 1 and (n_steps - burn) / thin >= 1", who, (long long)o.n_steps, (long long)o.burn, (long long)o.thin,
+                SAMPLE_MAX_STEPS);
+  if (o.a == 0.0) o.a = 2.0;
+  if (!std::isfinite(o.a) || !(o.a > 1.0)) return fail(SPART_ERR_INVALID, "%s: a must be finite and > 1 (0 = the default 2.0)", who);
+  if (o.temperature == 0.0) o.temperature = 1.0;
+  if (!std::isfinite(o.temperature) || !(o.temperature > 0.0))
+    return fail(SPART_ERR_INVALID, "%s: temperature must be finite and > 0 (0 = the default 1.0)", who);
+  if (o.rel_init == 0.0) o.rel_init = 0.01;
+  if (!std::isfinite(o.rel_init) || !(o.rel_init > 0.0))
+    return fail(SPART_ERR_INVALID, "%s: rel_init must be finite and > 0 (0 = the default 0.01)", who);
+  if (o.step0 < 0 || o.obs_offset < 0)
+    return fail(SPART_ERR_INVALID, "%s: step0 = %lld and obs_offset = %lld must be >= 0", who, (long long)o.step0, (long long)o.obs_offset);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (M > 0) {
+    if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
+    if (!out) return fail(SPART_ERR_INVALID, "%s: out is null", who);
+    if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
+    if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+    if (!obs) return fail(SPART_ERR_INVALID, "%s: obs is null", who);
+    if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+    if (!out->mean && !out->cov && !out->std && !out->best_x && !out->best_cost && !out->n_accept && !out->status && !out->chain &&
+        !out->chain_cost && !out->last && !out->last_cost)
+      return fail(SPART_ERR_INVALID, "%s: every output is null", who);
+  }
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  const SampleLayout l = sample_layout(ctx->nb, M, F, o.W);
+  if (!workspace || workspace_bytes < l.total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
+  SampleCfg cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p], cfg.is_free[p] = rc.is_free[p];
+  for (int f = 0; f < F; ++f)
+    cfg.free_col[f] = rc.free_col[f], cfg.freebase[f] = base[rc.free_col[f]], cfg.lo[f] = rc.lo[f], cfg.hi[f] = rc.hi[f];
+  const SampleOut so = {out->mean,   out->cov,   out->std,        out->best_x, out->best_cost, out->n_accept,
+                        out->status, out->chain, out->chain_cost, out->last,   out->last_cost};
+  return guarded(ctx, who, workspace, l.total, stream,
+                 [&](hipStream_t st) { return sample_impl(ctx, cfg, M, F, obs, weights, o, so, (char*)workspace, l, st); });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {

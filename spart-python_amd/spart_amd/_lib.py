@@ -88,6 +88,19 @@ class SpartSobolOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("mean", "var", "S1", "ST", "S1_se", "ST_se")]
 
 
+class SpartSampleOpt(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("column", "band_model", "fast_prelude", "nlayers", "weights_per_obs", "prior_per_obs")] + [
+        ("prior_mean", vp), ("prior_weight", vp), ("W", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_steps", ctypes.c_int64),
+        ("burn", ctypes.c_int64), ("thin", ctypes.c_int64), ("a", ctypes.c_double), ("temperature", ctypes.c_double),
+        ("rel_init", ctypes.c_double), ("init_radius", vp), ("init", vp), ("step0", ctypes.c_int64), ("obs_offset", ctypes.c_int64),
+        ("seed", ctypes.c_uint64)]
+
+
+class SpartSampleOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("mean", "cov", "std", "best_x", "best_cost", "n_accept", "status", "chain", "chain_cost", "last",
+                                  "last_cost")]
+
+
 PRODUCT_NAMES = ("fAPAR_bs", "fAPAR_ws", "albedo_bs", "albedo_ws", "fCover")      # spart_products_out, in its order
 PRODUCTS_NREAD = 22                                 # spart_products reads params[0 ... 21]
 LUT_BAYES_OUTS = tuple(n for n, _ in SpartLutBayesOut._fields_)      # spart_lut_bayes_out, in its order
@@ -102,6 +115,8 @@ TILES_MAXG = 4096                                   # pixels per tile of spart_r
 SERIES_MAXT = 256                                   # rows per series of spart_refine_series
 SOBOL_OUTS = tuple(n for n, _ in SpartSobolOut._fields_)             # spart_sobol_out, in its order
 SOBOL_BLOCK, SOBOL_MIN_N, SOBOL_MAX_N = 64, 128, 1 << 20             # spart_sobol: N a multiple of 64 in 128 ... 2^20
+SAMPLE_OUTS = tuple(n for n, _ in SpartSampleOut._fields_)           # spart_sample_out, in its order
+SAMPLE_WALKERS, SAMPLE_MAX_STEPS = (8, 16, 32, 64), 1 << 20          # spart_sample_opt.W (and W >= 2 F), n_steps
 
 # the LUT searches: (dtype, B, nb, M) of every call; the three top-k searches share one argument list per function
 c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -172,6 +187,8 @@ SIGNATURES = {
     "spart_sobol_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "spart_sobol": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, vp, vp, ctypes.POINTER(SpartSobolOpt),
                                                      ctypes.POINTER(SpartSobolOut)] + _REFINE_CALL[16:]),
+    "spart_sample_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "spart_sample": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartSampleOpt), ctypes.POINTER(SpartSampleOut)] + _REFINE_CALL[16:]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

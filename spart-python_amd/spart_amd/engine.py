@@ -536,6 +536,89 @@ def sobol_args(params, free, N, bounds, design, seed, column, band_model, lidf):
     return plan, params, M, N, uA, uB
 
 
+def sample_args(params, obs, free, bounds, weights, prior, prior_mean, prior_weight, walkers, n_steps, burn, thin, a, temperature,
+                rel_init, init, init_radius, step0, obs_offset, seed, column, band_model, lidf, nb=None):
+    """Every argument check of spart_amd.sample and Engine.sample that needs no device: refine_args (refine_plan on ``free`` /
+    ``bounds`` / ``column``, the prior, the shapes of obs, params and weights), then the sampler's own options: ``walkers`` one
+    of 8, 16, 32, 64 with W >= 2 F (None: the smallest such), n_steps 1 ... 2^20, burn 0 ... n_steps - 1 (None: n_steps // 2),
+    thin >= 1 with (n_steps - burn) // thin >= 1, a > 1, temperature > 0, rel_init > 0, step0, obs_offset >= 0, seed in
+    0 ... 2^64 - 1, init (M, W, F) and init_radius (M, F) or None.
+    -> (plan, params, M, weights kind, prior_mean, prior_weight, prior per observation, opt): ``opt`` a dict W, n_steps, burn,
+    thin, n_keep, a, temperature, rel_init, step0, obs_offset, seed"""
+    head = refine_args(params, obs, free, bounds, weights, column, 0, 1e-3, 1e-2, lidf, prior, prior_mean, prior_weight, band_model, nb=nb)
+    plan, M = head[0], head[2]
+    F = len(plan["names"])
+
+    def whole(name, v, lo, hi=None):
+        if isinstance(v, bool) or int(v) != v or int(v) < lo or (hi is not None and int(v) > hi):
+            raise ValueError(f"{name} = {v!r}, expected an integer >= {lo}" + ("" if hi is None else f" and <= {hi}"))
+        return int(v)
+    if walkers is None:
+        walkers = min(w for w in _lib.SAMPLE_WALKERS if w >= 2 * F)
+    if isinstance(walkers, bool) or walkers not in _lib.SAMPLE_WALKERS or walkers < 2 * F:
+        raise ValueError(f"walkers = {walkers!r}, expected one of {_lib.SAMPLE_WALKERS} and >= 2 F = {2 * F}")
+    W = int(walkers)
+    n_steps = whole("n_steps", n_steps, 1, _lib.SAMPLE_MAX_STEPS)
+    burn = n_steps // 2 if burn is None else whole("burn", burn, 0, n_steps - 1)
+    thin = whole("thin", thin, 1)
+    if (n_steps - burn) // thin < 1:
+        raise ValueError(f"thin = {thin} keeps no step of the {n_steps - burn} after the burn-in")
+    for name, v, lo in (("a", a, 1.0), ("temperature", temperature, 0.0), ("rel_init", rel_init, 0.0)):
+        if not (np.isfinite(v) and v > lo):
+            raise ValueError(f"{name} = {v!r}, expected a finite value > {lo:g}")
+    for name, v, shape in (("init", init, (M, W, F)), ("init_radius", init_radius, (M, F))):
+        if v is not None and tuple(int(n) for n in v.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {shape}")
+    opt = {"W": W, "n_steps": n_steps, "burn": burn, "thin": thin, "n_keep": (n_steps - burn) // thin, "a": float(a),
+           "temperature": float(temperature), "rel_init": float(rel_init), "step0": whole("step0", step0, 0),
+           "obs_offset": whole("obs_offset", obs_offset, 0), "seed": whole("seed", seed, 0, 2 ** 64 - 1)}
+    return head + (opt,)
+
+
+def chain_summary(chain, q=(0.05, 0.5, 0.95)):
+    """What a chain of sample(chain=True) says about itself, per observation and parameter, on the host.  chain: (M, n_keep, W, F)
+    or (n_keep, W, F), a numpy array or a tensor.  -> dict of numpy arrays
+      quantiles (M, len(q), F)  over kept steps x walkers
+      rhat (M, F)               split-R^: the first and the second half of the kept steps as the two groups (Gelman et al. 2013)
+      tau (M, F)                integrated autocorrelation time, in kept steps, of the ensemble-mean series: 1 + 2 sum of the
+                                autocorrelations from lag 1 up to (not including) the first negative one
+      ess (M, F)                n_keep W / tau
+    (the leading axis is dropped for a 3-D chain).  A parameter that does not move has NaN rhat, tau and ess."""
+    x = chain.detach().cpu().numpy() if hasattr(chain, "detach") else np.asarray(chain)
+    x = np.asarray(x, dtype=np.float64)
+    single = x.ndim == 3
+    if single:
+        x = x[None]
+    if x.ndim != 4 or x.shape[1] < 4:
+        raise ValueError(f"chain has shape {tuple(np.shape(chain))}, expected (M, n_keep, W, F) or (n_keep, W, F) with n_keep >= 4")
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or not ((q >= 0.0) & (q <= 1.0)).all():
+        raise ValueError("q: levels in 0 ... 1")
+    M, T, W, F = x.shape
+    quant = np.quantile(x.reshape(M, T * W, F), q, axis=1).transpose(1, 0, 2)
+    half = T // 2
+    with np.errstate(all="ignore"):
+        groups = np.stack([x[:, :half].reshape(M, half * W, F), x[:, T - half:].reshape(M, half * W, F)])      # (2, M, n, F)
+        n = half * W
+        within = groups.var(axis=2, ddof=1).mean(axis=0)
+        between = n * groups.mean(axis=2).var(axis=0, ddof=1)
+        rhat = np.sqrt(((n - 1) / n * within + between / n) / within)
+        series = x.mean(axis=2)                                               # (M, T, F)
+        d = series - series.mean(axis=1, keepdims=True)
+        size = 1 << int(2 * T - 1).bit_length()
+        f = np.fft.rfft(d, n=size, axis=1)
+        acov = np.fft.irfft(f * np.conj(f), n=size, axis=1)[:, :T]
+        rho = acov / acov[:, :1]
+        neg = rho < 0.0
+        first = np.where(neg.any(axis=1), neg.argmax(axis=1), T)              # (M, F): the first negative lag
+        lag = np.arange(T)[None, :, None]
+        tau = 1.0 + 2.0 * np.where((lag >= 1) & (lag < first[:, None, :]), rho, 0.0).sum(axis=1)
+        tau = np.where(np.isfinite(rho[:, 0]), tau, np.nan)
+        ess = T * W / tau
+    res = {"quantiles": quant, "rhat": rhat, "tau": tau, "ess": ess}
+    return {k: v[0] for k, v in res.items()} if single else res
+
+
 BAND_MODELS = ("centre", "srf")
 _FIT_OUTS = ("x", "cost", "cost0", "std", "n_accept", "y")     # of spart_refine / _srf / _views, in the order of their argument lists
 
@@ -1656,6 +1739,67 @@ class Engine:
                                   _dp(plan["lo"]), _dp(plan["hi"]), N, uA.data_ptr(), uB.data_ptr(), ctypes.byref(opt),
                                   ctypes.byref(out), ws.data_ptr(), nbytes, self._stream())
         _lib.check(self.lib, self.ctx, rc)
+        res["names"] = list(plan["names"])
+        return res
+
+    def sample(self, params, obs, free, bounds=None, weights=None, prior=None, walkers=None, n_steps=1000, burn=None, thin=1, seed=0,
+               init=None, init_radius=None, step0=0, obs_offset=0, column="R_TOC", band_model="centre", chain=False, a=2.0,
+               temperature=1.0, rel_init=0.01, prior_mean=None, prior_weight=None, lidf="literal", nlayers=None):
+        """The SHAPE of the posterior around a fit, sampled with the forward model itself, on the device in one call
+        (include/spart_hip.h: spart_sample, which defines every operation; tools/sample_defined.py is the numpy form): the
+        affine-invariant ensemble sampler (Goodman & Weare; emcee's stretch move) with ``walkers`` walkers per observation inside
+        the bounds.  The density is exp(-cost / (2 temperature)), cost being refine()'s: with weights = 1 / sigma^2 and
+        temperature 1 it is the posterior of the retrieval.
+        params, obs, free, bounds, weights, prior / prior_mean / prior_weight, column, band_model, lidf, nlayers : as for
+                 refine(); the walkers start in a box of +- rel_init (hi - lo) (or +- init_radius (M, F)) around ``params``
+                 clipped to the bounds, so ``params`` is best the fitted point
+        walkers : 8, 16, 32 or 64 and >= 2 F; None: the smallest such
+        n_steps, burn, thin : steps, of which the first ``burn`` (None: n_steps // 2) are dropped and then every thin-th kept
+        seed, obs_offset, step0 : the random numbers are a pure function of (seed, obs_offset + row, step0 + step, walker): rows
+                 [a, b) sampled with obs_offset = a give the rows of the whole call
+        init : (M, W, F), a given ensemble (with step0 = the steps already taken, the ``last`` of an earlier call resumes it)
+        chain : True adds chain (M, n_keep, W, F) and chain_cost (M, n_keep, W); chain_summary() reads them
+        -> dict of device tensors mean, std (M, F), cov (M, F, F) over the kept states, best (M, F), best_cost (M,) the lowest cost
+        seen, accept_fraction (M,), status (M,) int32 (0; -1: a dead observation, everything of it is NaN), last (M, W, F),
+        last_cost (M, W); and ``names``."""
+        plan, params, M, kind, prior_mean, prior_weight, per_obs, so = sample_args(
+            params, obs, free, bounds, weights, prior, prior_mean, prior_weight, walkers, n_steps, burn, thin, a, temperature,
+            rel_init, init, init_radius, step0, obs_offset, seed, column, band_model, lidf, nb=self.nb)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        F, W, nk = len(plan["names"]), so["W"], so["n_keep"]
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        cols = self._refine_columns(params, M)
+        dev = lambda v: None if v is None else torch.as_tensor(v).to(**f64).contiguous()     # noqa: E731
+        o, w, pm, pw, x_init, radius = (dev(v) for v in (obs, weights, prior_mean, prior_weight, init, init_radius))
+        shapes = {"mean": (M, F), "cov": (M, F, F), "std": (M, F), "best_x": (M, F), "best_cost": (M,), "n_accept": (M,),
+                  "status": (M,), "chain": (M, nk, W, F), "chain_cost": (M, nk, W), "last": (M, W, F), "last_cost": (M, W)}
+        kinds = {"n_accept": torch.int64, "status": torch.int32}
+        raw = {k: torch.empty(shapes[k], dtype=kinds.get(k, torch.float64), device=self.device) for k in _lib.SAMPLE_OUTS
+               if chain or k not in ("chain", "chain_cost")}
+        out = _lib.SpartSampleOut(**{k: v.data_ptr() for k, v in raw.items()})
+        ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+        opt = _lib.SpartSampleOpt(column=plan["column"], band_model=int(srf), fast_prelude=1 if lidf == "newton" else 0, nlayers=nl,
+                                  weights_per_obs=1 if kind == "per_observation" else 0, prior_per_obs=per_obs, prior_mean=ptr(pm),
+                                  prior_weight=ptr(pw), W=W, n_steps=so["n_steps"], burn=so["burn"], thin=so["thin"], a=so["a"],
+                                  temperature=so["temperature"], rel_init=so["rel_init"], init_radius=ptr(radius), init=ptr(x_init),
+                                  step0=so["step0"], obs_offset=so["obs_offset"], seed=so["seed"])
+        nbytes = max(int(self.lib.spart_sample_workspace_bytes(self.ctx, M, F, W)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_sample"] += 1
+        rc = self.lib.spart_sample(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   _dp(plan["lo"]), _dp(plan["hi"]), ptr(o), ptr(w), ctypes.byref(opt), ctypes.byref(out),
+                                   ws.data_ptr(), nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        res = {k: raw[k] for k in ("mean", "std", "cov", "best_cost", "status", "last", "last_cost")}
+        res["best"] = raw["best_x"]
+        na = raw["n_accept"]
+        res["accept_fraction"] = torch.where(na < 0, torch.full_like(res["best_cost"], float("nan")),
+                                             na.to(torch.float64) / float(W * so["n_steps"]))
+        if chain:
+            res["chain"], res["chain_cost"] = raw["chain"], raw["chain_cost"]
         res["names"] = list(plan["names"])
         return res
 

@@ -18,7 +18,8 @@ import warnings
 import numpy as np
 
 from . import _lib, workloads
-from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, get_engine, knn_prior, lut_weights_kind,
+from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, chain_summary, get_engine, knn_prior,  # noqa: F401
+                     lut_weights_kind, sample_args,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
                      refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design)
 
@@ -595,6 +596,26 @@ def sobol(params, sensor, free, N=4096, bounds=None, design=None, seed=0, column
     Engine._nlayers(nlayers)
     eng = get_engine(sensor, device, sensor_info=sensor_info)
     res = eng.sobol(params, free, N=N, bounds=bounds, design=(uA, uB), column=column, band_model=band_model, lidf=lidf, nlayers=nlayers)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def sample(params, obs, sensor, free, bounds=None, weights=None, prior=None, walkers=None, n_steps=1000, burn=None, thin=1, seed=0,
+           init=None, init_radius=None, step0=0, obs_offset=0, column="R_TOC", band_model="centre", chain=False, a=2.0,
+           temperature=1.0, rel_init=0.01, prior_mean=None, prior_weight=None, lidf="literal", nlayers=None, sensor_info=None,
+           device=None):
+    """The host form of Engine.sample: numpy in and out.  ``params`` (27, M) or a list of 27 scalars / arrays, ``obs`` (M, nb),
+    ``sensor`` / ``sensor_info`` as for refine(); everything else as for Engine.sample.  -> dict of numpy arrays mean, std, cov,
+    best, best_cost, accept_fraction, status, last, last_cost (chain, chain_cost with chain=True) and the list ``names``.  Every
+    argument check that needs no device runs before one is asked for."""
+    init, init_radius = (None if v is None else np.asarray(v, dtype=np.float64) for v in (init, init_radius))
+    sample_args(params, obs, free, bounds, weights, prior, prior_mean, prior_weight, walkers, n_steps, burn, thin, a, temperature,
+                rel_init, init, init_radius, step0, obs_offset, seed, column, band_model, lidf)
+    Engine._nlayers(nlayers)
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.sample(params, obs, free, bounds=bounds, weights=weights, prior=prior, walkers=walkers, n_steps=n_steps, burn=burn,
+                     thin=thin, seed=seed, init=init, init_radius=init_radius, step0=step0, obs_offset=obs_offset, column=column,
+                     band_model=band_model, chain=chain, a=a, temperature=temperature, rel_init=rel_init, prior_mean=prior_mean,
+                     prior_weight=prior_weight, lidf=lidf, nlayers=nlayers)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
