@@ -73,7 +73,8 @@ extern "C" {
  * and spart_lut_bayes_quantiles with spart_lut_bayes_q_opt / _q_out, which embed spart_lut_bayes_opt / _out unchanged.  spart_products with spart_products_out likewise.
  * spart_refine_series and spart_series_workspace_bytes with spart_refine_series_opt, which embeds spart_refine_tiles_opt
  * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise, and
- * spart_sample and spart_sample_workspace_bytes with spart_sample_opt / spart_sample_out. */
+ * spart_sample and spart_sample_workspace_bytes with spart_sample_opt / spart_sample_out.  spart_refine_mix and
+ * spart_mix_workspace_bytes with spart_refine_mix_opt, which embeds spart_refine_opt unchanged, and spart_refine_mix_out likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -634,6 +635,68 @@ int spart_refine_views(spart_ctx *ctx, int64_t M, const double *const base[SPART
                        const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
                        const spart_refine_views_opt *opt, double *x, double *cost, double *cost0, double *std, int32_t *n_accept,
                        double *y, void *workspace, size_t workspace_bytes, void *stream);
+
+/* spart_refine with a LINEAR MIXTURE of V canopies per pixel (crop plus bare soil with the cover fraction as an unknown; a MODIS
+ * or OLCI pixel over several land covers): the observed column is y_j = sum_v a_v Y_v[j] over V components, each with its own
+ * 27-parameter row.  The first Fs = opt->n_shared entries of free_cols are SHARED by all components (soil brightness, atmosphere),
+ * the other Fl = F - Fs are LOCAL to a component, and only where opt->local_active says so (LAI and Cab of the crop, not of the
+ * bare-soil component); the fractions a_v are given (a land-cover map) or fitted on the simplex.  The chosen column itself is
+ * mixed: for R_TOA / L_TOA that neglects the coupling of neighbouring surfaces through the atmosphere.
+ *   base[27]  each (V, M) component-major float64 device memory: element [v M + m] is component v of pixel m.  The entries of a
+ *             shared column in components 1 ... V-1 are never read (they may be NaN)
+ *   free_cols, lo, hi  HOST (F,): one bound pair per NAME
+ *   obs       (M, nb);  weights NULL, (nb,) or (M, nb) (opt->fit.weights_per_obs = 1)
+ *   frac      (M, V) device: the given fractions, or the start of the fitted ones (its last column is then never read)
+ *   opt->fit  spart_refine's options; prior_mean / prior_weight are (n,) or (M, n) (prior_per_obs = 1), per unknown
+ *   out       x, std (M, n); cost, cost0, n_accept (M,); y (M, nb) the mixed column at x; frac (M, V) all V fractions at x;
+ *             y_comp (M, V, nb) the components' own columns at x.  x and cost are required, every other may be NULL
+ * Definition (tools/refine_mix_defined.py is the same text in numpy; float64, no FMA contraction, every sum in one order).
+ *   unknowns  in this order: the Fs shared names; the ACTIVE locals, v ascending and within a component l ascending
+ *             (local_active is (V, Fl), NULL = all active; an inactive local of a component stays at that component's base value
+ *             and is no unknown); with fit_fractions q_0 ... q_{V-2}.  nm counts the model unknowns, n = nm + (V - 1 if
+ *             fit_fractions else 0), 1 <= n <= 16, 1 <= V <= 8.  Bounds and step of a model unknown are those of its name; a
+ *             fraction unknown has the box [frac_lo, frac_hi] and no step
+ *   start     shared: component 0's base; local: its own component's base; q_v: frac[m, v]; everything clipped
+ *   rows      a trial evaluates V (F + 1) rows per pixel exactly as spart_refine_views does: block f + 1 of component v moves
+ *             column free[f] by s_a h_a of the unknown it belongs to; where that local is inactive in v the block is the unmoved
+ *             trial row, evaluated and never read
+ *   fractions fitted: s = 0; for v < V - 1 ascending a_v = t[nm + v], s = s + a_v; a_{V-1} = 1 - s.  The trial is FEASIBLE iff
+ *             a_{V-1} >= 0 (a NaN is not).  Given: a_v = frac[m, v] as it is, no sum rule; a negative, NaN or infinite entry
+ *             makes the pixel dead (the rule of a bad weight)
+ *   y         y_j = a_0 Y_(0,0)j; then for v = 1 ... V - 1: y_j = y_j + a_v Y_(v,0)j
+ *   cost      spart_refine's band loop on y, then the prior over the n unknowns; after that an infeasible trial's cost is +inf:
+ *             an infeasible proposal is rejected and raises lambda, an infeasible start is a dead pixel with cost = cost0 = +inf
+ *   J         dense over the nb bands.  Local unknown a of component v, name f: J_ja = a_v ((Y_(v,f+1)j - Y_(v,0)j) / (s_a h_a));
+ *             shared unknown: that product for v = 0, then + a_v (...) for v = 1 ... V - 1 ascending; fraction q_v:
+ *             J_ja = Y_(v,0)j - Y_(V-1,0)j
+ *   everything else is spart_refine's text with F read as n: decision, dead pixels, lambda and its clamps, the sums of A and g,
+ *   the prior's additions, D, Cholesky and its failure rule, clip, std, no early exit, the prefix property, cost <= cost0.
+ * Consequences: V = 1 is spart_refine (band_model 0) / spart_refine_srf (band_model 1) bit for bit, with or without
+ * fit_fractions (1 z and 1 - 0 are exact); the fitted fractions sum to 1 to within one rounding and the last is >= 0 on every
+ * live pixel.  Pixels go in chunks of max(1, (1 << 19) / ((F + 1) V)); the workspace is spart_refine_views' layout with this n.
+ * Refused before anything is launched or written: spart_refine's list in its order, with -- after the NULL check of base,
+ * free_cols, lo, hi, opt, out -- V outside 1 ... 8, n_shared outside 0 ... F, band_model or fit_fractions outside 0 / 1, a
+ * local_active entry outside 0 / 1, a local name that is active in no component, n outside 1 ... 16, a bad fraction box, a NULL
+ * frac.  M = 0 launches nothing.  spart_mix_workspace_bytes is 0 exactly for refused sizes. */
+typedef struct spart_refine_mix_opt {
+  spart_refine_opt fit;          /* column, n_iter, weights_per_obs, fast_prelude, nlayers, rel_step, lambda0, the prior */
+  int32_t V;                     /* components per pixel, 1 ... 8 */
+  int32_t n_shared;              /* Fs: the first Fs entries of free_cols are shared, the other F - Fs local */
+  int32_t band_model;            /* 0: centre columns (spart_refine's forward call), 1: SRF columns (spart_refine_srf's) */
+  int32_t fit_fractions;         /* 0: frac is given, 1: q_0 ... q_{V-2} are unknowns */
+  const int32_t *local_active;   /* HOST (V, Fl) row-major 0 / 1, or NULL = all active */
+  double frac_lo, frac_hi;       /* the box of a fitted fraction: both 0 = [0, 1]; else 0 <= lo < hi <= 1 */
+} spart_refine_mix_opt;
+typedef struct spart_refine_mix_out {
+  double *x, *cost, *cost0, *std;
+  int32_t *n_accept;
+  double *y, *frac, *y_comp;
+} spart_refine_mix_out;
+size_t spart_mix_workspace_bytes(const spart_ctx *ctx, int64_t M, int V, int F, int n);
+int spart_refine_mix(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F, const int32_t *free_cols /* HOST */,
+                     const double *lo, const double *hi /* HOST, (F,) */, const double *obs, const double *weights,
+                     const double *frac, const spart_refine_mix_opt *opt, const spart_refine_mix_out *out, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* Refinement with parameters shared by a TILE of pixels: one atmosphere per window, one leaf-angle parameter per field.  The
  * first Fs = n_shared entries of free_cols are ONE unknown per tile, the other Fl = F - Fs one unknown per pixel; a tile is the

@@ -22,6 +22,7 @@
 #include "spart_refine.h"
 #include "spart_refine_posterior.h"
 #include "spart_refine_views.h"
+#include "spart_refine_mix.h"
 #include "spart_refine_tiles.h"
 #include "spart_refine_series.h"
 #include "spart_sobol.h"
@@ -1128,10 +1129,10 @@ static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t 
   return SPART_OK;
 }
 
-// ---- The refinement family (csrc/spart_refine.h, spart_refine_views.h, spart_refine_posterior.h): spart_refine,
-// spart_refine_srf, spart_refine_posterior and spart_refine_views share one workspace layout, one chunk loop and one entry
-// check.  A call fits n unknowns per observation from V views of it, F free columns each, the first Fs of them shared by the
-// views; the single-view entries are {1, F, F, F}.
+// ---- The refinement family (csrc/spart_refine.h, spart_refine_views.h, spart_refine_mix.h, spart_refine_posterior.h):
+// spart_refine, spart_refine_srf, spart_refine_posterior, spart_refine_views and spart_refine_mix share one workspace layout, one
+// chunk loop and one entry check.  A call fits n unknowns per observation from V views (or mixture components) of it, F free
+// columns each, the first Fs of them shared by the views; the single-view entries are {1, F, F, F}.
 struct RefineShape {
   int V, F, Fs, n;
 };
@@ -1313,6 +1314,46 @@ static int views_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) 
         a.ppw = rows_at(o.prior_weight, m0, n, o.prior_per_obs);
         hipLaunchKernelGGL(W == 8 ? k_refine_views_step<8> : k_refine_views_step<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds,
                            st, a);
+      });
+}
+
+// spart_refine_mix: views' table in views' row order from k_refine_mix_init, then n_iter + 1 times the forward call and the
+// mixture's step kernel; o.prior_* are per unknown, the fractions included
+static int mix_impl(const RefineRun& r, const MixMap& map, int fit, double frac_lo, double frac_hi, const double* frac,
+                    const MixOut& out, hipStream_t st) {
+  const spart_refine_opt& o = r.o;
+  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, W = mix_group(n);
+  const size_t lds = mix_lds_bytes(n, W);
+  return refine_loop(
+      r, o.n_iter + 1, st,
+      [&](const RefineWs& w, int64_t m0, int mc) {
+        MixInit a;
+        a.cfg = r.cfg, a.map = map;
+        a.M = r.M, a.m0 = m0, a.Mc = mc, a.V = V, a.F = F, a.Fs = Fs, a.fit = fit;
+        a.lambda0 = o.lambda0, a.frac_lo = frac_lo, a.frac_hi = frac_hi;
+        a.frac = frac;
+        a.table = w.table, a.x = out.x + m0 * n, a.t = w.t, a.lam = w.lam, a.na = w.na, a.dcfg = w.cfg, a.dcfg_free = w.cfg_free;
+        hipLaunchKernelGGL(k_refine_mix_init, dim3((unsigned)(((int64_t)mc * V + 255) / 256)), dim3(256), 0, st, a);
+      },
+      [&](const RefineWs& w, int64_t m0, int mc, int it) {
+        MixStep a;
+        a.cols = w.cols;
+        a.obs = r.obs + m0 * nb;
+        a.wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
+        a.cfg = w.cfg;
+        a.frac = frac + m0 * V;
+        a.cfg_free = w.cfg_free;
+        a.table = w.table;
+        a.Mc = mc, a.V = V, a.F = F, a.Fs = Fs, a.nb = nb, a.it = it, a.last = it == o.n_iter ? 1 : 0;
+        a.wper = o.weights_per_obs ? 1 : 0, a.pper = o.prior_per_obs ? 1 : 0, a.fit = fit;
+        a.st = w.t, a.sA = w.A, a.slam = w.lam, a.sna = w.na;
+        a.out = {rows_at(out.x, m0, n),        rows_at(out.cost, m0, 1), rows_at(out.cost0, m0, 1), rows_at(out.sdev, m0, n),
+                 rows_at(out.n_accept, m0, 1), rows_at(out.y, m0, nb),   rows_at(out.frac, m0, V),  rows_at(out.y_comp, m0, (int64_t)V * nb)};
+        a.pmu = rows_at(o.prior_mean, m0, n, o.prior_per_obs);
+        a.ppw = rows_at(o.prior_weight, m0, n, o.prior_per_obs);
+        a.map = map;
+        hipLaunchKernelGGL(W == 8 ? k_refine_mix_step<8> : k_refine_mix_step<4>, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st,
+                           a);
       });
 }
 
@@ -1780,6 +1821,56 @@ int spart_refine_views(spart_ctx* ctx, int64_t M, const double* const base[SPART
         return refine_check_band_model(who, opt->band_model);
       },
       refine_no_check, [&](const RefineRun& r, hipStream_t st) { return views_impl(r, out, st); });
+}
+
+size_t spart_mix_workspace_bytes(const spart_ctx* ctx, int64_t M, int V, int F, int n) {
+  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF) return 0;
+  if (V < 1 || V > MIX_MAXV || n < 1 || n > REFINE_MAXF) return 0;
+  return refine_layout(ctx->nb, M, V, F, n).total;
+}
+
+// the mixture's own refusals come once the options they are read from are known to be there, before the fit, as for the views
+int spart_refine_mix(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols,
+                     const double* lo, const double* hi, const double* obs, const double* weights, const double* frac,
+                     const spart_refine_mix_opt* opt, const spart_refine_mix_out* out, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  const char* who = "spart_refine_mix";
+  MixMap map;
+  MixOut oo;
+  int fit = 0;
+  double flo = 0.0, fhi = 1.0;
+  return refine_entry(
+      who, {ctx, M, base, F, free_cols, lo, hi, obs, weights, workspace, workspace_bytes, stream}, opt && out,
+      obs && out && out->x && out->cost,
+      [&](RefineRun& r) {
+        const int V = opt->V, Fs = opt->n_shared;
+        if (V < 1 || V > MIX_MAXV) return fail(SPART_ERR_INVALID, "%s: V = %d, expected 1 <= V <= %d", who, V, MIX_MAXV);
+        if (Fs < 0 || Fs > F) return fail(SPART_ERR_INVALID, "%s: n_shared = %d, expected 0 ... F = %d", who, Fs, F);
+        if (int rc = refine_check_band_model(who, opt->band_model)) return rc;
+        if (opt->fit_fractions != 0 && opt->fit_fractions != 1)
+          return fail(SPART_ERR_INVALID, "%s: fit_fractions = %d (0: given, 1: fitted on the simplex)", who, opt->fit_fractions);
+        const int Fl = F - Fs;
+        if (opt->local_active)
+          for (int i = 0; i < V * Fl; ++i)
+            if (opt->local_active[i] != 0 && opt->local_active[i] != 1)
+              return fail(SPART_ERR_INVALID, "%s: local_active[%d] = %d, expected 0 / 1", who, i, opt->local_active[i]);
+        fit = opt->fit_fractions;
+        const int n = mix_build_map(V, Fs, Fl, opt->local_active, fit, &map);
+        if (n == -1) return fail(SPART_ERR_INVALID, "%s: a local name is active in no component", who);
+        if (n < 1 || n > REFINE_MAXF)
+          return fail(SPART_ERR_INVALID, "%s: the unknowns per pixel (shared + active locals + fitted fractions): expected 1 ... %d", who,
+                      REFINE_MAXF);
+        if (opt->frac_lo != 0.0 || opt->frac_hi != 0.0) {
+          flo = opt->frac_lo, fhi = opt->frac_hi;
+          if (!(flo >= 0.0 && flo < fhi && fhi <= 1.0))
+            return fail(SPART_ERR_INVALID, "%s: fraction box (%g, %g): both 0 = [0, 1], else 0 <= lo < hi <= 1", who, flo, fhi);
+        }
+        if (!frac) return fail(SPART_ERR_INVALID, "%s: frac is null", who);
+        r.o = opt->fit, r.srf = opt->band_model == 1, r.s = {V, F, Fs, n};
+        oo = {out->x, out->cost, out->cost0, out->std, out->n_accept, out->y, out->frac, out->y_comp};
+        return SPART_OK;
+      },
+      refine_no_check, [&](const RefineRun& r, hipStream_t st) { return mix_impl(r, map, fit, flo, fhi, frac, oo, st); });
 }
 
 size_t spart_tiles_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n_shared) {

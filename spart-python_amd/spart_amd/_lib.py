@@ -42,6 +42,16 @@ class SpartRefineViewsOpt(ctypes.Structure):
     _fields_ = [("fit", SpartRefineOpt), ("V", ctypes.c_int32), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32)]
 
 
+class SpartRefineMixOpt(ctypes.Structure):
+    _fields_ = [("fit", SpartRefineOpt), ("V", ctypes.c_int32), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32),
+                ("fit_fractions", ctypes.c_int32), ("local_active", ctypes.POINTER(ctypes.c_int32)),      # local_active: HOST (V, Fl)
+                ("frac_lo", ctypes.c_double), ("frac_hi", ctypes.c_double)]
+
+
+class SpartRefineMixOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("x", "cost", "cost0", "std", "n_accept", "y", "frac", "y_comp")]
+
+
 class SpartRefineTilesOpt(ctypes.Structure):
     _fields_ = [("fit", SpartRefineOpt), ("n_shared", ctypes.c_int32), ("band_model", ctypes.c_int32),
                 ("shared_prior_per_tile", ctypes.c_int32), ("shared_prior_mean", vp), ("shared_prior_weight", vp)]
@@ -110,6 +120,8 @@ POSTERIOR_OUTS = tuple(n for n, _ in SpartPosteriorOut._fields_)     # spart_pos
 REFINE_COLUMNS = ("R_TOC", "R_TOA", "L_TOA")       # spart_refine_opt.column
 REFINE_MAXF, REFINE_MAX_ITER = 16, 100
 REFINE_MAXV = 64                                    # spart_refine_views_opt.V
+MIX_MAXV = 8                                        # spart_refine_mix_opt.V
+MIX_OUTS = tuple(n for n, _ in SpartRefineMixOut._fields_)           # spart_refine_mix_out, in its order
 TILES_OUTS = tuple(n for n, _ in SpartTilesOut._fields_)             # spart_tiles_out, in its order
 TILES_MAXG = 4096                                   # pixels per tile of spart_refine_tiles
 SERIES_MAXT = 256                                   # rows per series of spart_refine_series
@@ -176,6 +188,9 @@ SIGNATURES = {
     "spart_refine_srf": (ctypes.c_int, _REFINE_CALL),
     "spart_views_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spart_refine_views": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartRefineViewsOpt)] + _REFINE_CALL[10:]),
+    "spart_mix_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spart_refine_mix": (ctypes.c_int, _REFINE_CALL[:9] + [vp, ctypes.POINTER(SpartRefineMixOpt), ctypes.POINTER(SpartRefineMixOut)] +
+                         _REFINE_CALL[16:]),
     "spart_tiles_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "spart_refine_tiles": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + _REFINE_CALL[7:9] +
                            [ctypes.POINTER(SpartRefineTilesOpt), ctypes.POINTER(SpartTilesOut)] + _REFINE_CALL[16:]),

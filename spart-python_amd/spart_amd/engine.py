@@ -376,6 +376,163 @@ def refine_views_args(params, obs, shared, local, bounds, weights, column, n_ite
     return plan, params, (M, V, Fs, n), wper, prior_mean, prior_weight, per_obs
 
 
+def mix_maps(V, Fs, Fl, active, fit_fractions):
+    """The unknowns of refine_mix in their order -- the Fs shared names, the ACTIVE locals (component v ascending, l ascending
+    within it), with fitted fractions q_0 ... q_{V-2} -> (unknown (V, Fl) int: the unknown of local l in component v or -1, nm
+    the number of model unknowns, n)"""
+    unknown = np.full((V, Fl), -1, dtype=np.int64)
+    nm = Fs
+    for v in range(V):
+        for l in range(Fl):
+            if active[v, l]:
+                unknown[v, l] = nm
+                nm += 1
+    return unknown, nm, nm + (V - 1 if fit_fractions else 0)
+
+
+def _mix_prior(names, Fs, V, unknown, nm, n, prior):
+    """refine_mix's prior: {name: (mean, sigma)} -> (mean, weight) per UNKNOWN, (n,) or -- when any value has a pixel axis --
+    (M, n).  A shared name takes a scalar or (M,); a local name a scalar, (V,) or (M, V) (the entries of components where it is
+    inactive are not read); the key "fractions" a scalar, (V - 1,) or (M, V - 1), one entry per fitted fraction."""
+    if not isinstance(prior, dict):
+        raise ValueError(f"prior = {prior!r}, expected a dict {{name: (mean, sigma)}}")
+    stray = [k for k in prior if k not in names and k != "fractions"]
+    if stray:
+        raise ValueError(f"prior: {stray} not free")
+    if "fractions" in prior and n == nm:
+        raise ValueError("prior: 'fractions' without a fitted fraction")
+    rows, parts = None, {}
+    for name, entry in prior.items():
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"prior[{name!r}]: expected (mean, sigma)")
+        mu, sigma = (np.asarray(v, dtype=np.float64) for v in entry)
+        if not (np.all(sigma > 0) and not np.isnan(sigma).any()):
+            raise ValueError(f"prior[{name!r}]: sigma must be > 0 (finite, or inf for no prior), got {entry[1]!r}")
+        width = None if name != "fractions" and names.index(name) < Fs else (n - nm if name == "fractions" else V)
+        for what, v in (("mean", mu), ("sigma", sigma)):
+            ok = v.ndim == 0 or (v.ndim == 1 and (width is None or v.shape[0] == width)) or (width is not None and v.ndim == 2 and
+                                                                                             v.shape[1] == width)
+            m = v.shape[0] if (v.ndim == 2 or (v.ndim == 1 and width is None)) else None
+            if not ok or (m is not None and rows not in (None, m)):
+                raise ValueError(f"prior[{name!r}]: {what} has shape {v.shape}, expected a scalar, " +
+                                 ("or (M,)" if width is None else f"({width},) or (M, {width})"))
+            rows = m if m is not None else rows
+        with np.errstate(over="ignore"):
+            parts[name] = (mu, 1.0 / (sigma * sigma))
+    R = 1 if rows is None else rows
+    mean, weight = np.zeros((R, n)), np.zeros((R, n))
+    for name, (mu, w) in parts.items():
+        for out, v in ((mean, mu), (weight, w)):
+            if name == "fractions":
+                out[:, nm:] = np.broadcast_to(v, (R, n - nm))
+            elif names.index(name) < Fs:
+                out[:, names.index(name)] = v
+            else:
+                l, full = names.index(name) - Fs, np.broadcast_to(v, (R, V))
+                for c in range(V):
+                    if unknown[c, l] >= 0:
+                        out[:, unknown[c, l]] = full[:, c]
+    return (mean[0], weight[0]) if rows is None else (mean, weight)
+
+
+def refine_mix_args(params, obs, shared, local, active, fractions, fit_fractions, fraction_bounds, bounds, weights, column, n_iter,
+                    rel_step, lambda0, lidf, prior, band_model, nb=None):
+    """Every argument check of spart_amd.refine_mix and Engine.refine_mix that needs no device: refine_plan on the names
+    shared + local, then the shapes -- obs (M, nb), params a (27, V, M) block or 27 entries each broadcastable to (V, M) (V is then
+    read from ``fractions``, from an ``active`` array or from the entries), 1 <= V <= 8, ``active`` a dict {local name:
+    components} or a (V, Fl) array of 0 / 1 with every local active somewhere, ``fractions`` None / (V,) / (M, V), the fraction
+    box, n in 1 ... 16, weights None / (nb,) / (M, nb), the prior per unknown.
+    -> (plan, params, (M, V, Fs, nm, n), active (V, Fl) int32, fractions (M, V) float64, (frac_lo, frac_hi), weights per
+    observation 0 / 1, prior_mean, prior_weight, prior per observation 0 / 1)"""
+    import torch
+
+    def make_plan():
+        nonlocal shared, local
+        shared, local = [str(s) for s in shared], [str(s) for s in local]
+        return refine_plan(shared + local, bounds, n_iter, column, rel_step, lambda0)
+    plan = _refine_head(make_plan, lidf, prior, None, None, band_model)
+    oshape = tuple(int(k) for k in np.shape(obs))
+    if len(oshape) != 2 or (nb is not None and oshape[1] != nb):
+        raise ValueError(f"obs has shape {oshape}, expected (M, nb)" + ("" if nb is None else f" = (M, {nb})"))
+    M, Fs, Fl = oshape[0], len(shared), len(local)
+    if isinstance(fit_fractions, (bool, np.bool_)):
+        fit_fractions = bool(fit_fractions)
+    else:
+        raise ValueError(f"fit_fractions = {fit_fractions!r}, expected True or False")
+    fr = None if fractions is None else np.asarray(fractions, dtype=np.float64)
+    if fr is not None and fr.ndim not in (1, 2):
+        raise ValueError(f"fractions has shape {fr.shape}, expected (V,) or (M, V)")
+    act = None if active is None or isinstance(active, dict) else np.asarray(active)
+    if act is not None and act.ndim != 2:
+        raise ValueError(f"active has shape {act.shape}, expected (V, Fl) = (V, {Fl}), or a dict {{local name: components}}")
+    if not isinstance(params, (list, tuple)):
+        if not torch.is_tensor(params):
+            params = np.asarray(params, dtype=np.float64)
+        if len(params.shape) != 3 or params.shape[0] != _lib.NPARAM or params.shape[2] != M:
+            raise ValueError(f"params must be (27, V, M) = (27, V, {M}) or a list of 27 entries, got shape {tuple(params.shape)}")
+        V = int(params.shape[1])
+    else:
+        if len(params) != _lib.NPARAM:
+            raise ValueError(f"params must have {_lib.NPARAM} entries, got {len(params)}")
+        params = fill_nulls(params)
+        V = fr.shape[-1] if fr is not None else act.shape[0] if act is not None else max(
+            [1] + [int(np.shape(c)[0]) for c in params if len(np.shape(c)) == 2])
+    if not 1 <= V <= _lib.MIX_MAXV:
+        raise ValueError(f"V = {V} components, expected 1 ... {_lib.MIX_MAXV}")
+    if isinstance(params, list):
+        for i, c in enumerate(params):
+            try:
+                bad = len(np.shape(c)) > 2
+                np.broadcast_shapes(tuple(np.shape(c)), (V, M))
+            except ValueError:
+                bad = True
+            if bad:
+                raise ValueError(f"params[{i}] of shape {tuple(np.shape(c))} does not broadcast to (V, M) = ({V}, {M})")
+    if isinstance(active, dict):
+        stray = [k for k in active if k not in local]
+        if stray:
+            raise ValueError(f"active: {stray} not local")
+        act = np.ones((V, Fl), dtype=np.int32)
+        for name, comps in active.items():
+            comps = [comps] if np.ndim(comps) == 0 else list(comps)
+            if any(isinstance(c, bool) or int(c) != c or not 0 <= int(c) < V for c in comps):
+                raise ValueError(f"active[{name!r}] = {comps!r}, expected components 0 ... {V - 1}")
+            act[:, local.index(name)] = 0
+            act[[int(c) for c in comps], local.index(name)] = 1
+    elif act is None:
+        act = np.ones((V, Fl), dtype=np.int32)
+    else:
+        if act.shape != (V, Fl) or not np.isin(act, (0, 1)).all():
+            raise ValueError(f"active has shape {act.shape}, expected (V, Fl) = ({V}, {Fl}) of 0 / 1")
+        act = act.astype(np.int32)
+    nowhere = [local[l] for l in range(Fl) if not act[:, l].any()]
+    if nowhere:
+        raise ValueError(f"active: {nowhere} active in no component")
+    act = np.ascontiguousarray(act, dtype=np.int32)
+    if fr is None:
+        fr = np.full((M, V), 1.0 / V)
+    elif fr.shape not in ((V,), (M, V)):
+        raise ValueError(f"fractions has shape {fr.shape}, expected (V,) = ({V},) or (M, V) = ({M}, {V})")
+    fr = np.array(np.broadcast_to(fr, (M, V)), order="C")
+    try:
+        flo, fhi = (float(v) for v in fraction_bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f"fraction_bounds = {fraction_bounds!r}, expected (lo, hi)") from None
+    if not 0.0 <= flo < fhi <= 1.0:
+        raise ValueError(f"fraction_bounds = ({flo}, {fhi}), expected 0 <= lo < hi <= 1")
+    unknown, nm, n = mix_maps(V, Fs, Fl, act, fit_fractions)
+    if not 1 <= n <= _lib.REFINE_MAXF:
+        raise ValueError(f"{Fs} shared + {nm - Fs} active local + {n - nm} fractions = {n} unknowns per pixel, expected 1 ... "
+                         f"{_lib.REFINE_MAXF}")
+    kind = lut_weights_kind(None if weights is None else np.shape(weights), M, oshape[1])
+    prior_mean, prior_weight, per_obs = _refine_prior(None, None, M, n, None if prior is None else _mix_prior(
+        plan["names"], Fs, V, unknown, nm, n, prior))
+    if prior is not None and per_obs and prior_mean.shape[0] != M:
+        raise ValueError(f"prior: arrays of {prior_mean.shape[0]} pixels for the {M} of obs")
+    return (plan, params, (M, V, Fs, nm, n), act, fr, (flo, fhi), 1 if kind == "per_observation" else 0, prior_mean, prior_weight,
+            per_obs)
+
+
 def tile_starts(M, tile_size, tile_start):
     """refine_tiles' partition: exactly one of ``tile_size`` (uniform runs of G pixels, a shorter last one) and ``tile_start``
     ((T + 1,) integers, 0 = s_0 < s_1 < ... < s_T = M) -> tile_start as int64; no tile above 4096 pixels"""
@@ -1448,13 +1605,15 @@ class Engine:
         shapes = {"x": (M, n), "cost": (M,), "cost0": (M,), "std": (M, n), "n_accept": (M,), "y": yshape}
         return {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device) for k in _FIT_OUTS}
 
-    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None, tiles=None, series=None):
+    def _refine_device(self, entry, plan, M, cols, obs, weights, wper, lidf, nl, prior, outs, views=None, tiles=None, series=None,
+                       mix=None):
         """What every entry point of the refinement family does once its parameter columns ``cols`` and its outputs are on the
         device: obs and weights as float64 device tensors, spart_refine_opt from the plan, the prior (mean, weight, per
         observation 0 / 1) hooked up, the workspace, the call count, the C call and its check.  ``outs``: the C arguments between
         the options and the workspace; ``views`` = (V, Fs, srf) wraps the options in spart_refine_views_opt;
         ``tiles`` = (Fs, srf, tile_start, shared prior) wraps them in spart_refine_tiles_opt and passes the partition;
-        ``series`` = (gamma, link) with ``tiles`` wraps those in spart_refine_series_opt.
+        ``series`` = (gamma, link) with ``tiles`` wraps those in spart_refine_series_opt; ``mix`` = (V, Fs, srf, fit_fractions,
+        active, frac_lo, frac_hi, n, fractions) wraps them in spart_refine_mix_opt and passes the fractions after the weights.
         -> (obs, weights) as the call got them"""
         torch = self.torch
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -1467,7 +1626,7 @@ class Engine:
             pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in prior[:2])
             opt.prior_per_obs, opt.prior_mean, opt.prior_weight = prior[2], pm.data_ptr(), pw.data_ptr()
         F = len(plan["names"])
-        part = []
+        part, after = [], []
         if tiles is not None:
             Fs, srf, ts, sprior = tiles
             nbytes = int(self.lib.spart_tiles_workspace_bytes(self.ctx, M, F, Fs))
@@ -1481,6 +1640,12 @@ class Engine:
                 ln = None if link is None else torch.as_tensor(link).to(**f64).contiguous()
                 nbytes = int(self.lib.spart_series_workspace_bytes(self.ctx, M, F, Fs))
                 opt = _lib.SpartRefineSeriesOpt(tiles=opt, smooth=_dp(gamma), link=None if ln is None else ln.data_ptr())
+        elif mix is not None:
+            V, Fs, srf, fit, act, flo, fhi, n, frd = mix
+            nbytes = int(self.lib.spart_mix_workspace_bytes(self.ctx, M, V, F, n))
+            opt = _lib.SpartRefineMixOpt(fit=opt, V=V, n_shared=Fs, band_model=int(srf), fit_fractions=int(fit),
+                                         local_active=act.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), frac_lo=flo, frac_hi=fhi)
+            after = [frd.data_ptr()]
         elif views is None:
             nbytes = int(self.lib.spart_refine_workspace_bytes(self.ctx, M, F))
         else:
@@ -1492,7 +1657,7 @@ class Engine:
         self.calls[entry] += 1
         rc = getattr(self.lib, entry)(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                       _dp(plan["lo"]), _dp(plan["hi"]), *part, o.data_ptr() if o is not None else None,
-                                      w.data_ptr() if w is not None else None, ctypes.byref(opt), *outs, ws.data_ptr(), nbytes,
+                                      w.data_ptr() if w is not None else None, *after, ctypes.byref(opt), *outs, ws.data_ptr(), nbytes,
                                       self._stream())
         _lib.check(self.lib, self.ctx, rc)
         return o, w
@@ -1633,6 +1798,72 @@ class Engine:
             res[k] = res[src][:, :Fs]
         for k, src in (("local", "x"), ("local_std", "std")):
             res[k] = res[src][:, Fs:].reshape(M, V, F - Fs)
+        res["names"] = list(plan["names"])
+        return res
+
+    def refine_mix(self, params, obs, shared=(), local=(), active=None, fractions=None, fit_fractions=True, fraction_bounds=(0, 1),
+                   bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None,
+                   prior=None, band_model="centre"):
+        """refine() with a LINEAR MIXTURE of V canopies per pixel: the observed column is sum_v a_v Y_v over V components, each
+        with its own 27 parameters -- crop plus bare soil with the cover fraction as an unknown, a coarse pixel over several land
+        covers (include/spart_hip.h: spart_refine_mix; tools/refine_mix_defined.py is the numpy form).  The chosen column itself is
+        mixed: for R_TOA / L_TOA that neglects the coupling of neighbouring surfaces through the atmosphere.
+        params : a (27, V, M) float64 device tensor, or 27 entries each broadcastable to (V, M).  A shared parameter starts from
+                 component 0's value
+        obs : (M, nb);  weights : None, (nb,) or (M, nb) (exactly 0 skips the band)
+        shared, local : names from workloads.PARAM_NAMES: a shared name has one value for all components, a local name one per
+                 component where it is active
+        active : None (every local in every component), a dict {local name: components} or a (V, Fl) array of 0 / 1; an inactive
+                 local of a component stays at that component's start value and is no unknown
+        fractions : None (1 / V each), (V,) or (M, V): the given fractions (fit_fractions=False; no sum rule, a negative or
+                 non-finite entry makes the pixel dead) or the start of the fitted ones (the last column is then not read)
+        fit_fractions : the first V - 1 fractions are unknowns in ``fraction_bounds``, the last is 1 minus their sum; a trial whose
+                 last fraction is negative is rejected
+        bounds : {name: (lo, hi)}, one pair per name; the default is workloads.RANGES[name]
+        prior : {name: (mean, sigma)}: a shared name takes scalars or (M,) arrays, a local name scalars, (V,) or (M, V); the key
+                 "fractions" a scalar, (V - 1,) or (M, V - 1) per fitted fraction
+        column, n_iter, rel_step, lambda0, lidf, nlayers, band_model : as for refine()
+        -> dict of device tensors x, std (M, n) -- the shared names, the active locals (component by component), the fitted
+        fractions --, cost, cost0 (M,), n_accept (M,) int32 (-1: a dead pixel), y (M, nb) the mixed column at x, y_comp (M, V, nb)
+        the components' own columns, fractions (M, V) and fractions_std (M, V - 1; NaN when the fractions are given), shared /
+        shared_std (M, Fs), local / local_std (M, V, Fl) where an inactive entry is the start value with std NaN; and ``names``
+        = shared + local."""
+        plan, params, (M, V, Fs, nm, n), act, fr, (flo, fhi), wper, prior_mean, prior_weight, per_obs = refine_mix_args(
+            params, obs, shared, local, active, fractions, fit_fractions, fraction_bounds, bounds, weights, column, n_iter, rel_step,
+            lambda0, lidf, prior, band_model, nb=self.nb)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        nb, F = self.nb, len(plan["names"])
+        Fl = F - Fs
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if torch.is_tensor(params):
+            P = params.to(**f64).contiguous()
+        else:
+            host = np.stack([np.broadcast_to(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float64), (V, M)) for c in params])
+            P = torch.as_tensor(host).to(self.device)
+        cols = list(P)
+        shapes = {"x": (M, n), "cost": (M,), "cost0": (M,), "std": (M, n), "n_accept": (M,), "y": (M, nb), "frac": (M, V),
+                  "y_comp": (M, V, nb)}
+        res = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device)
+               for k in _lib.MIX_OUTS}
+        out = _lib.SpartRefineMixOut(**{k: v.data_ptr() for k, v in res.items()})
+        frd = torch.as_tensor(fr).to(**f64).contiguous()
+        self._refine_device("spart_refine_mix", plan, M, cols, obs, weights, wper, lidf, nl, (prior_mean, prior_weight, per_obs),
+                            [ctypes.byref(out)], mix=(V, Fs, srf, bool(fit_fractions), act, flo, fhi, n, frd))
+        res["fractions"] = res.pop("frac")
+        res["fractions_std"] = res["std"][:, nm:] if n > nm else torch.full((M, V - 1), float("nan"), **f64)
+        res["shared"], res["shared_std"] = res["x"][:, :Fs], res["std"][:, :Fs]
+        unknown = mix_maps(V, Fs, Fl, act, False)[0]
+        loc = P[plan["cols"][Fs:].tolist()].permute(2, 1, 0).clone() if Fl else torch.empty((M, V, 0), **f64)
+        loc_std = torch.full((M, V, Fl), float("nan"), **f64)
+        for v in range(V):
+            for l in range(Fl):
+                if unknown[v, l] >= 0:
+                    loc[:, v, l] = res["x"][:, unknown[v, l]]
+                    loc_std[:, v, l] = res["std"][:, unknown[v, l]]
+        res["local"], res["local_std"] = loc, loc_std
         res["names"] = list(plan["names"])
         return res
 

@@ -21,7 +21,7 @@ from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, chain_summary, get_engine, knn_prior,  # noqa: F401
                      lut_weights_kind, sample_args,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
-                     refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design)
+                     refine_mix_args, refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -644,6 +644,24 @@ def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=Non
                            shared, local, bounds=bounds, weights=weights, column=column, n_iter=n_iter, rel_step=rel_step,
                            lambda0=lambda0, lidf=lidf, nlayers=nlayers, prior=prior, prior_mean=prior_mean,
                            prior_weight=prior_weight, band_model=band_model)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def refine_mix(params, obs, sensor, shared=(), local=(), active=None, fractions=None, fit_fractions=True, fraction_bounds=(0, 1),
+               bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3, lambda0=1e-2, lidf="literal", nlayers=None,
+               prior=None, band_model="centre", sensor_info=None, device=None):
+    """The host form of Engine.refine_mix: numpy in and out.  ``params`` (27, V, M) or 27 entries each broadcastable to (V, M),
+    ``obs`` (M, nb), ``sensor`` a packaged sensor name (or None with ``sensor_info``); everything else as for Engine.refine_mix.
+    -> dict of numpy arrays x, std, cost, cost0, n_accept, y, y_comp, fractions, fractions_std, shared, shared_std, local,
+    local_std and the list ``names``.  Every argument check that needs no device runs before one is asked for."""
+    params = refine_mix_args(params, obs, shared, local, active, fractions, fit_fractions, fraction_bounds, bounds, weights, column,
+                             n_iter, rel_step, lambda0, lidf, prior, band_model)[1]
+    Engine._nlayers(nlayers)
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.refine_mix(params if isinstance(params, list) else eng.torch.as_tensor(params), np.asarray(obs, dtype=np.float64),
+                         shared, local, active=active, fractions=fractions, fit_fractions=fit_fractions,
+                         fraction_bounds=fraction_bounds, bounds=bounds, weights=weights, column=column, n_iter=n_iter,
+                         rel_step=rel_step, lambda0=lambda0, lidf=lidf, nlayers=nlayers, prior=prior, band_model=band_model)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
