@@ -990,7 +990,7 @@ int spart_sample(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARA
 
 /* What spart_refine's optimal-estimation fit knows about a point, kept instead of reduced to std: the Jacobian of the chosen
  * sensor column with respect to the free parameters, the full posterior covariance A^-1 = (J^T W J + S_a^-1)^-1, the averaging
- * kernel A^-1 J^T W J and its trace, the degrees of freedom for signal.  ONE evaluation of the point: k_refine_init's table,
+ * kernel A^-1 J^T W J and its trace, the degrees of freedom for signal.  ONE evaluation of the point: the init kernel's table,
  * one forward call of (F + 1) rows per observation, one kernel.  base, free_cols, lo, hi, weights and opt are spart_refine's;
  * obs may be NULL (no measurement: sensitivities and the covariance a measurement WOULD give).  opt->n_iter and opt->lambda0
  * are checked but not used.  band_model 0 evaluates spart_refine's centre columns, 1 spart_refine_srf's SRF columns.

@@ -1242,16 +1242,16 @@ static int refine_loop(const RefineRun& r, int n_fwd, hipStream_t st, Init&& ini
   return SPART_OK;
 }
 
-// spart_refine / spart_refine_srf: k_refine_init, then n_iter + 1 times the forward call and k_refine_step
+// spart_refine / spart_refine_srf: k_refine_views_init at V = 1, then n_iter + 1 times the forward call and k_refine_step
 static int refine_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) {
   const spart_refine_opt& o = r.o;
-  const int nb = r.ctx->nb, F = r.s.F, W = refine_group(F);
-  const size_t lds = refine_lds_bytes(F, W);
+  const int nb = r.ctx->nb, F = r.s.F, rows = refine_lds_rows(F + 1, F, 0), W = refine_group(rows);
+  const size_t lds = refine_lds_bytes(rows, W);
   return refine_loop(
       r, o.n_iter + 1, st,
       [&](const RefineWs& w, int64_t m0, int mc) {
-        hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, m0, mc, F, o.lambda0, w.table,
-                           out.x + m0 * F, w.t, w.lam, w.na, w.cfg, w.cfg_free);
+        hipLaunchKernelGGL(k_refine_views_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, r.M, m0, mc, 1, F, F,
+                           o.lambda0, w.table, out.x + m0 * F, w.t, w.lam, w.na, w.cfg, w.cfg_free);
       },
       [&](const RefineWs& w, int64_t m0, int mc, int it) {
         hipLaunchKernelGGL(k_refine_step, dim3((unsigned)((mc + W - 1) / W)), dim3(64), lds, st, (const double*)w.cols,
@@ -1262,8 +1262,8 @@ static int refine_impl(const RefineRun& r, const RefineOut& out, hipStream_t st)
       });
 }
 
-// spart_refine_posterior: k_refine_init, ONE forward call per chunk and k_refine_posterior.  The optimiser's state of the
-// layout is not used, so its A block takes k_refine_init's x when the caller does not ask for it.
+// spart_refine_posterior: k_refine_views_init at V = 1, ONE forward call per chunk and k_refine_posterior.  The optimiser's
+// state of the layout is not used, so its A block takes the init kernel's x when the caller does not ask for it.
 static int posterior_impl(const RefineRun& r, const spart_posterior_out& out, hipStream_t st) {
   const spart_refine_opt& o = r.o;
   const int nb = r.ctx->nb, F = r.s.F, W = refine_posterior_group(F);
@@ -1271,8 +1271,8 @@ static int posterior_impl(const RefineRun& r, const spart_posterior_out& out, hi
   return refine_loop(
       r, 1, st,
       [&](const RefineWs& w, int64_t m0, int mc) {
-        hipLaunchKernelGGL(k_refine_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, m0, mc, F, o.lambda0, w.table,
-                           out.x ? out.x + m0 * F : w.A, w.t, w.lam, w.na, w.cfg, w.cfg_free);
+        hipLaunchKernelGGL(k_refine_views_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, r.cfg, r.M, m0, mc, 1, F, F,
+                           o.lambda0, w.table, out.x ? out.x + m0 * F : w.A, w.t, w.lam, w.na, w.cfg, w.cfg_free);
       },
       [&](const RefineWs& w, int64_t m0, int mc, int) {
         const PosteriorOut oc = {rows_at(out.y, m0, nb),    rows_at(out.jac, m0, (int64_t)nb * F), rows_at(out.cov, m0, F * F),
@@ -1289,9 +1289,9 @@ static int posterior_impl(const RefineRun& r, const spart_posterior_out& out, hi
 // kernel; o.prior_* are per unknown
 static int views_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) {
   const spart_refine_opt& o = r.o;
-  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, W = views_group(F, n);
+  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, rows = refine_lds_rows(F + 1, n, 0), W = refine_group(rows);
   const int64_t U = (int64_t)V * nb;
-  const size_t lds = views_lds_bytes(F, n, W);
+  const size_t lds = refine_lds_bytes(rows, W);
   return refine_loop(
       r, o.n_iter + 1, st,
       [&](const RefineWs& w, int64_t m0, int mc) {
@@ -1322,8 +1322,8 @@ static int views_impl(const RefineRun& r, const RefineOut& out, hipStream_t st) 
 static int mix_impl(const RefineRun& r, const MixMap& map, int fit, double frac_lo, double frac_hi, const double* frac,
                     const MixOut& out, hipStream_t st) {
   const spart_refine_opt& o = r.o;
-  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, W = mix_group(n);
-  const size_t lds = mix_lds_bytes(n, W);
+  const int nb = r.ctx->nb, V = r.s.V, F = r.s.F, Fs = r.s.Fs, n = r.s.n, rows = refine_lds_rows(n, n, MIX_MAXV), W = refine_group(rows);
+  const size_t lds = refine_lds_bytes(rows, W);
   return refine_loop(
       r, o.n_iter + 1, st,
       [&](const RefineWs& w, int64_t m0, int mc) {

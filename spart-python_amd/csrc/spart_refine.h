@@ -2,8 +2,8 @@
 // is tools/refine_defined.py and every function here reproduces it bit for bit).
 //
 // Part 1: the per-observation arithmetic -- cost, normal equations, damped solve, bounds, uncertainty -- as plain
-// functions of small arrays, under SPART_NO_CONTRACT.  hipcc compiles them into the two kernels of part 2 and g++ compiles
-// them for tests/hostmath/refine_host.cpp.  Every array argument comes with a stride S (element k at p[k * S]): the kernels
+// functions of small arrays, under SPART_NO_CONTRACT.  hipcc compiles them into the kernels of part 2 and of the family and
+// g++ compiles them for tests/hostmath/refine_host.cpp. Every array argument comes with a stride S (element k at p[k * S]): the kernels
 // keep one column per lane in LDS, the host build passes 1.
 //
 // Index conventions.  Only the LOWER triangle of A is formed: entry (a, b), a >= b, at refine_tri(a, b) = a (a + 1) / 2 + b,
@@ -84,6 +84,102 @@ SPART_HD double refine_lambda(double lam, bool accept) {
   }
   const double l = lam * 10.0;
   return l < REFINE_LAMBDA_MAX ? l : REFINE_LAMBDA_MAX;
+}
+
+// ---- the per-observation phases.  Every kernel of the family (spart_refine_views.h, _mix.h, _posterior.h, _tiles.h, _series.h,
+// spart_sample.h) and every host test runs THESE loops; what differs between callers arrives as a stride, a range or a count.
+
+// packed entry e < ntri(n) -> the pair a >= b
+SPART_HD void refine_pair(int e, int* a, int* b) {
+  int r = 0;
+  while ((r + 1) * (r + 2) / 2 <= e) ++r;
+  *a = r;
+  *b = e - r * (r + 1) / 2;
+}
+
+// entry e of a packed vector (nt = ntri(n) sums of A, then g): A_ab, or g_a with b = -1
+SPART_HD void refine_packed_pair(int e, int nt, int* a, int* b) {
+  if (e < nt) {
+    refine_pair(e, a, b);
+  } else {
+    *a = e - nt;
+    *b = -1;
+  }
+}
+
+// the trial cost over jn bands, ascending: a bad weight raises *bad, a band of weight 0 is skipped.  -> c
+SPART_HD double refine_tile_cost(double c, bool* bad, int jn, const double* w, int SW, const double* y, int SY, const double* obs,
+                                 int SO) {
+  SPART_NO_CONTRACT
+  for (int jj = 0; jj < jn; ++jj) {
+    const double wj = w[jj * SW];
+    if (refine_bad_weight(wj)) *bad = true;
+    if (wj == 0.0) continue;
+    c = refine_cost_band(c, wj, y[jj * SY], obs[jj * SO]);
+  }
+  return c;
+}
+
+// the prior's cost terms, unknowns ascending; t(f): the trial value of unknown f.  -> c
+template <typename T>
+SPART_HD double refine_prior_total_of(int n, double c, bool* bad, T&& t, const double* mu, const double* pw) {
+  SPART_NO_CONTRACT
+  for (int f = 0; f < n; ++f) {
+    const double p = pw[f];
+    if (refine_bad_weight(p)) *bad = true;
+    if (p == 0.0) continue;
+    c = refine_prior_cost(c, p, t(f), mu[f]);
+  }
+  return c;
+}
+SPART_HD double refine_prior_total(int n, double c, bool* bad, const double* t, const double* mu, const double* pw) {
+  return refine_prior_total_of(n, c, bad, [t](int f) { return t[f]; }, mu, pw);
+}
+
+// The decision of one call on one observation.  it == 0: alive (1) or dead from the start (2, na = -1).  Later: a dead one
+// (na < 0) stays as it is, code 0; otherwise accepted (1: ct < cost, one more in na) or rejected (3), and lambda moves.
+struct RefineDecision {
+  int code, na;
+  double lam;
+};
+SPART_HD RefineDecision refine_decide(int it, double ct, bool bad, double cost, double lam, int na) {
+  RefineDecision d = {0, na, lam};
+  if (it == 0) {
+    d.code = (ct < __builtin_inf() && !bad) ? 1 : 2;
+    if (d.code == 2) d.na = -1;
+  } else if (na >= 0) {
+    d.code = ct < cost ? 1 : 3;
+    d.lam = refine_lambda(lam, d.code == 1);
+    if (d.code == 1) ++d.na;
+  }
+  return d;
+}
+
+// one packed sum over the bands jb .. je - 1 of a tile, ascending, bands of weight 0 skipped.  -> acc
+SPART_HD double refine_tile_sum(double acc, int jb, int je, const double* w, int SW, const double* ja, int SA, const double* jc,
+                                int SC) {
+  SPART_NO_CONTRACT
+  for (int jj = jb; jj < je; ++jj) {
+    const double wj = w[jj * SW];
+    if (wj == 0.0) continue;
+    acc = refine_mac(acc, wj, ja[jj * SA], jc[jj * SC]);
+  }
+  return acc;
+}
+
+// the prior's part of the sums of an accepted point x: A_aa + p_a and, where the packed vector has its g (mu != NULL: the
+// posterior's has none), g_a + p_a e_a
+SPART_HD void refine_prior_augment(int n, double* A, int SA, const double* x, int SX, const double* mu, const double* pw) {
+  SPART_NO_CONTRACT
+  for (int a = 0; a < n; ++a) {
+    const double p = pw[a];
+    if (p == 0.0) continue;
+    double* Aaa = A + refine_tri(a, a) * SA;
+    *Aaa = *Aaa + p;
+    if (!mu) continue;
+    double* ga = A + (refine_ntri(n) + a) * SA;
+    *ga = refine_prior_gain(*ga, p, refine_residual(x[a * SX], mu[a]));
+  }
 }
 
 // In-place Cholesky of a packed lower triangle, textbook row order, sums over k ascending; false at a pivot !(s > 0)
@@ -171,7 +267,8 @@ SPART_HD void refine_std(int F, const double* A, int SA, double* L, int SL, doub
 //   cols   ((F + 1) Mc, nb) float64: the forward call's chosen sensor column, same row order;
 //   state  t (Mc, F) the trial that `table` holds, A (Mc, P) the packed normal equations of the last accepted point,
 //          lam (Mc), na (Mc) accepted steps (-1: dead);  x and cost, the caller's outputs, ARE the accepted point and its cost.
-// k_refine_init writes all of `table` once; k_refine_step only ever rewrites its F free rows.
+// k_refine_views_init (spart_refine_views.h, at V = 1 and Fs = F) writes all of `table` once; k_refine_step only ever rewrites
+// its F free rows.
 //
 // k_refine_step.  Single-wave workgroups of W consecutive observations (W = 8, or 4 where 8 do not fit REFINE_LDS_BUDGET:
 // refine_group).  The rows of one block f of `cols` that belong to W consecutive observations are ONE contiguous run of
@@ -194,13 +291,17 @@ constexpr int REFINE_LDS_BUDGET = 40960;     // dynamic LDS of one workgroup at 
 // the number of waves a CU holds, which the LDS of a group limits.  At F = 16 a group of 4 beats 8.
 constexpr int REFINE_MIN_GROUP = 4, REFINE_MAX_GROUP = 8;
 
-// doubles of LDS per observation column (+ one int flag)
-inline int refine_lds_rows(int F) { return (F + 1) * REFINE_JT + 2 * REFINE_JT + (refine_ntri(F) + F) + refine_ntri(F) + 3 * F + 1; }
-inline size_t refine_lds_bytes(int F, int W) { return (size_t)refine_lds_rows(F) * (size_t)(W + 1) * 8; }
+// The LDS of a step kernel of the family, one formula.  Doubles per observation column (+ one int flag): tile_rows tiles of
+// JT bands, weights and obs / r, the packed sums and the Cholesky factor of n unknowns, x / step / trial, `extra` rows of the
+// kernel's own.  k_refine_step: (F + 1, F, 0); k_refine_views_step: (F + 1, n, 0); k_refine_mix_step: (n, n, MIX_MAXV).
+inline int refine_lds_rows(int tile_rows, int n, int extra) {
+  return tile_rows * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1 + extra;
+}
+inline size_t refine_lds_bytes(int rows, int W) { return (size_t)rows * (size_t)(W + 1) * 8; }
 // observations per workgroup
-inline int refine_group(int F) {
+inline int refine_group(int rows) {
   int W = REFINE_MAX_GROUP;
-  while (W > REFINE_MIN_GROUP && refine_lds_bytes(F, W) > (size_t)REFINE_LDS_BUDGET) W >>= 1;
+  while (W > REFINE_MIN_GROUP && refine_lds_bytes(rows, W) > (size_t)REFINE_LDS_BUDGET) W >>= 1;
   return W;
 }
 
@@ -212,48 +313,80 @@ struct RefineCfg {
   double lo[REFINE_MAXF], hi[REFINE_MAXF], h[REFINE_MAXF];
 };
 
-// device copy of the per-call constants, written by k_refine_init: lo, hi, h (REFINE_MAXF doubles each)
+// device copy of the per-call constants, written by the init kernel: lo, hi, h (REFINE_MAXF doubles each)
 constexpr int REFINE_CFG_DOUBLES = 3 * REFINE_MAXF;
 
-// Once per chunk (observations m0 .. m0 + Mc - 1 of the call): the whole table, the clipped start as x and as the first
-// trial, lambda0.  x / t are the chunk's own rows.
-__global__ __launch_bounds__(256) void k_refine_init(RefineCfg a, int64_t m0, int Mc, int F, double lambda0,
-                                                     double* __restrict__ table, double* __restrict__ x, double* __restrict__ t,
-                                                     double* __restrict__ lam, int32_t* __restrict__ na, double* __restrict__ cfg,
-                                                     int32_t* __restrict__ cfg_free) {
-  SPART_NO_CONTRACT
-  const int m = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x == 0) {
-#pragma unroll
-    for (int f = 0; f < REFINE_MAXF; ++f)
-      if ((int)threadIdx.x == f) {
-        cfg[f] = a.lo[f];
-        cfg[REFINE_MAXF + f] = a.hi[f];
-        cfg[2 * REFINE_MAXF + f] = a.h[f];
-        cfg_free[f] = a.free_col[f];
-      }
-  }
-  if (m >= Mc) return;
-  const int64_t R = (int64_t)(F + 1) * Mc;
+// ---- what the kernels of the family share beside part 1 (the init kernel of spart_refine itself is k_refine_views_init at
+// V = 1, Fs = F: spart_refine_views.h)
+
+// One value of a parameter column in all F + 1 blocks of a table (blk doubles from block to block): block `hot` gets `moved`,
+// every other one v; hot < 0: none, a fixed parameter
+__device__ __forceinline__ void refine_fill_row(double* row, int F, int64_t blk, int hot, double v, double moved) {
+  for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * blk] = fp == hot ? moved : v;
+}
+
+// the fixed parameters of table row i (R doubles per parameter) from the caller's columns at src
+__device__ __forceinline__ void refine_fill_fixed(const RefineCfg& a, int64_t src, double* table_i, int64_t R, int F, int64_t blk) {
 #pragma unroll
   for (int p = 0; p < NPARAM; ++p) {
     if (a.is_free[p]) continue;
-    const double v = a.base[p][m0 + m];
-    double* row = table + p * R + m;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = v;
+    refine_fill_row(table_i + p * R, F, blk, -1, a.base[p][src], 0.0);
   }
+}
+
+// thread u < REFINE_MAXF of an init kernel: the device copy of lo / hi / h of name fn (none: fn < 0) as unknown u's, and
+// free_col[u]
+__device__ __forceinline__ void refine_cfg_copy(const RefineCfg& a, int u, int fn, double* cfg, int32_t* cfg_free) {
 #pragma unroll
   for (int f = 0; f < REFINE_MAXF; ++f) {
-    if (f >= F) continue;
-    const double tf = refine_clip(a.freebase[f][m0 + m], a.lo[f], a.hi[f]);
-    const double moved = tf + refine_fd_step(tf, a.h[f], a.hi[f]);
-    x[(int64_t)m * F + f] = tf;
-    t[(int64_t)m * F + f] = tf;
-    double* row = table + a.free_col[f] * R + m;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = fp == f + 1 ? moved : tf;
+    if (f == fn) {
+      cfg[u] = a.lo[f];
+      cfg[REFINE_MAXF + u] = a.hi[f];
+      cfg[2 * REFINE_MAXF + u] = a.h[f];
+    }
+    if (f == u) cfg_free[u] = a.free_col[f];
   }
-  lam[m] = lambda0;
-  na[m] = 0;
+}
+
+// The weight and observation tile of bands j0 .. j0 + JT - 1 of a group's W observations, nobs of them there: lanes run along
+// the bands (out of range: weight 0).  obs_g / wts_g: the group's rows of nj bands, `stride` doubles apart (wts_g NULL: weight
+// 1; wper == 0: one shared row, band j at wts_g[widx(j)]).  -> wl / rl [jj][o], row stride WP
+template <typename WIdx>
+__device__ __forceinline__ void refine_stage_obs(int lane, int W, int WP, int nobs, int j0, int nj, int stride, const double* obs_g,
+                                                 const double* wts_g, int wper, WIdx&& widx, double* wl, double* rl) {
+  constexpr int JT = REFINE_JT;
+  for (int i = lane; i < W * JT; i += 64) {
+    const int jj = i % JT, o = i / JT, j = j0 + jj;
+    double w = 0.0, ob = 0.0;
+    if (o < nobs && j < nj) {
+      w = wts_g ? wts_g[wper ? o * stride + j : widx(j)] : 1.0;
+      ob = obs_g[o * stride + j];
+    }
+    wl[jj * WP + o] = w;
+    rl[jj * WP + o] = ob;
+  }
+}
+
+// accepted (flag 1): the new packed sums become the state; rejected (3): the state's sums come back.  sA_g: the group's rows
+__device__ __forceinline__ void refine_exchange(int lane, int W, int WP, int P, int nobs, const int* flag, double* Al, double* sA_g) {
+  for (int i = lane; i < P * W; i += 64) {
+    const int e = i % P, o = i / P;
+    if (o >= nobs) continue;
+    const int fl = flag[o];
+    if (fl == 1) sA_g[i] = Al[e * WP + o];
+    else if (fl == 3) Al[e * WP + o] = sA_g[i];
+  }
+}
+
+// the last call's outputs of an observation that is alive: n_accept and std (each NULL: not asked for) at the observation's
+// own entry / row; A, L, d, t: its LDS columns
+__device__ __forceinline__ void refine_last_out(int n, int na, int32_t* n_accept, double* sdev, const double* A, double* L, double* d,
+                                                double* t, int WP) {
+  if (n_accept) *n_accept = na;
+  if (sdev) {
+    refine_std(n, A, WP, L, WP, d, WP, t, WP);
+    for (int f = 0; f < n; ++f) sdev[f] = t[f * WP];
+  }
 }
 
 // outputs of the call, already moved to the chunk's first observation; cost0 / sdev / n_accept / y may be NULL
@@ -299,19 +432,8 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
   const bool prior = ppw != nullptr;                     // (kernel-uniform)
   const int64_t pm = pper && mine ? (int64_t)m * F : 0;  // (lanes < W) where this lane's prior starts
 
-  // the weight and observation tile of bands j0 .. j0 + JT - 1: lanes run along the bands (out of range: weight 0)
   auto stage_obs = [&](int j0) {
-    for (int i = lane; i < W * JT; i += 64) {
-      const int jj = i % JT, o = i / JT, j = j0 + jj;
-      const bool in = g0 + o < Mc && j < nb;
-      double w = 0.0, ob = 0.0;
-      if (in) {
-        w = wts_g ? wts_g[wper ? o * nb + j : j] : 1.0;
-        ob = obs_g[o * nb + j];
-      }
-      wl[jj * WP + o] = w;
-      rl[jj * WP + o] = ob;
-    }
+    refine_stage_obs(lane, W, WP, Mc - g0, j0, nb, nb, obs_g, wts_g, wper, [](int j) { return j; }, wl, rl);
   };
 
   // ---- pass 1: the trial cost from block 0
@@ -326,41 +448,21 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
       Yl[jj * WP + o] = (g0 + o < Mc && j < nb) ? y0[o * nb + j] : 0.0;
     }
     __syncthreads();
-    if (mine)
-      for (int jj = 0; jj < JT; ++jj) {
-        const double w = wl[jj * WP + lane];
-        if (refine_bad_weight(w)) bad = true;
-        if (w == 0.0) continue;
-        ct = refine_cost_band(ct, w, Yl[jj * WP + lane], rl[jj * WP + lane]);
-      }
+    if (mine) ct = refine_tile_cost(ct, &bad, JT, wl + lane, WP, Yl + lane, WP, rl + lane, WP);
   }
-  if (prior && mine)
-    for (int f = 0; f < F; ++f) {
-      const double p = ppw[pm + f];
-      if (refine_bad_weight(p)) bad = true;
-      if (p == 0.0) continue;
-      ct = refine_prior_cost(ct, p, st[(int64_t)m * F + f], pmu[pm + f]);
-    }
+  if (prior && mine) ct = refine_prior_total(F, ct, &bad, st + (int64_t)m * F, pmu + pm, ppw + pm);
   // ---- the decision
   int code = 0, na = 0;
   double lam = 0.0;
   if (mine) {
-    na = sna[m];
-    lam = slam[m];
-    if (it == 0) {
-      code = (ct < __builtin_inf() && !bad) ? 1 : 2;
-      if (out.cost0) out.cost0[m] = ct;
-      if (code == 2) {
-        na = -1;
-        out.cost[m] = ct;
-        if (out.n_accept) out.n_accept[m] = -1;
-        if (out.sdev)
-          for (int f = 0; f < F; ++f) out.sdev[(int64_t)m * F + f] = __builtin_nan("");
-      }
-    } else if (na >= 0) {
-      code = ct < out.cost[m] ? 1 : 3;
-      lam = refine_lambda(lam, code == 1);
-      if (code == 1) ++na;
+    const RefineDecision d = refine_decide(it, ct, bad, it == 0 ? 0.0 : out.cost[m], slam[m], sna[m]);
+    code = d.code, na = d.na, lam = d.lam;
+    if (it == 0 && out.cost0) out.cost0[m] = ct;
+    if (code == 2) {
+      out.cost[m] = ct;
+      if (out.n_accept) out.n_accept[m] = -1;
+      if (out.sdev)
+        for (int f = 0; f < F; ++f) out.sdev[(int64_t)m * F + f] = __builtin_nan("");
     }
     if (code == 1) out.cost[m] = ct;
     if (code != 0) {
@@ -414,51 +516,22 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
         if (flag[o] == 1) {
           const int jn = nb - j0 < JT ? nb - j0 : JT;
           for (int e = q; e < P; e += G) {
-            int a = 0, b = -1;                             // e < nt: A_ab; else g_a against r
-            if (e < nt) {
-              while ((a + 1) * (a + 2) / 2 <= e) ++a;
-              b = e - a * (a + 1) / 2;
-            } else {
-              a = e - nt;
-            }
+            int a, b;                                      // A_ab, or (b < 0) g_a against r
+            refine_packed_pair(e, nt, &a, &b);
             const double* ja = Yl + ((a + 1) * JT) * WP + o;
             const double* jb = b >= 0 ? Yl + ((b + 1) * JT) * WP + o : rl + o;
-            double acc = Al[e * WP + o];
-            for (int jj = 0; jj < jn; ++jj) {
-              const double w = wl[jj * WP + o];
-              if (w == 0.0) continue;
-              acc = refine_mac(acc, w, ja[jj * WP], jb[jj * WP]);
-            }
-            Al[e * WP + o] = acc;
+            Al[e * WP + o] = refine_tile_sum(Al[e * WP + o], 0, jn, wl + o, WP, ja, WP, jb, WP);
           }
         }
       }
     }
     __syncthreads();
     if (prior) {
-      if (mine && code == 1)
-        for (int a = 0; a < F; ++a) {
-          const double p = ppw[pm + a];
-          if (p == 0.0) continue;
-          double* Aaa = Al + refine_tri(a, a) * WP + lane;
-          double* ga = Al + (nt + a) * WP + lane;
-          *Aaa = *Aaa + p;
-          *ga = refine_prior_gain(*ga, p, refine_residual(xl[a * WP + lane], pmu[pm + a]));
-        }
+      if (mine && code == 1) refine_prior_augment(F, Al + lane, WP, xl + lane, WP, pmu + pm, ppw + pm);
       __syncthreads();
     }
   }
-  // accepted: the new sums become the state; rejected: the state's sums come back
-  {
-    double* sA_g = sA + (int64_t)g0 * P;
-    for (int i = lane; i < P * W; i += 64) {
-      const int e = i % P, o = i / P;
-      if (g0 + o >= Mc) continue;
-      const int fl = flag[o];
-      if (fl == 1) sA_g[i] = Al[e * WP + o];
-      else if (fl == 3) Al[e * WP + o] = sA_g[i];
-    }
-  }
+  refine_exchange(lane, W, WP, P, Mc - g0, flag, Al, sA + (int64_t)g0 * P);
   __syncthreads();
 
   // ---- finish: the next trial and its table rows, or the outputs of the last call
@@ -467,17 +540,12 @@ __global__ __launch_bounds__(64) void k_refine_step(const double* __restrict__ c
       refine_propose(F, Al + lane, WP, lam, xl + lane, WP, lo, hi, Ll + lane, WP, dl + lane, WP, tl + lane, WP);
       for (int f = 0; f < F; ++f) {
         const double tf = tl[f * WP + lane];
-        const double moved = tf + refine_fd_step(tf, hh[f], hi[f]);
         st[(int64_t)m * F + f] = tf;
-        double* row = table + cfg_free[f] * R + m;
-        for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = fp == f + 1 ? moved : tf;
+        refine_fill_row(table + cfg_free[f] * R + m, F, Mc, f + 1, tf, tf + refine_fd_step(tf, hh[f], hi[f]));
       }
     } else {
-      if (out.n_accept) out.n_accept[m] = na;
-      if (out.sdev) {
-        refine_std(F, Al + lane, WP, Ll + lane, WP, dl + lane, WP, tl + lane, WP);
-        for (int f = 0; f < F; ++f) out.sdev[(int64_t)m * F + f] = tl[f * WP + lane];
-      }
+      refine_last_out(F, na, out.n_accept ? out.n_accept + m : nullptr, out.sdev ? out.sdev + (int64_t)m * F : nullptr, Al + lane,
+                      Ll + lane, dl + lane, tl + lane, WP);
     }
   }
 }

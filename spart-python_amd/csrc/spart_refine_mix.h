@@ -116,18 +116,8 @@ SPART_HD double mix_jac_fraction(double yv, double ylast) {
 // are k_refine_step's; an infeasible trial's cost becomes +inf between the cost and the decision; a new trial writes V (F + 1)
 // table entries per shared unknown, F + 1 per active local and none for a fraction; frac and y_comp are outputs.
 
-// doubles of LDS per pixel column (+ one int flag): the n Jacobian tiles (the first is the y tile of pass 1), weights, obs / r,
-// the packed sums, the Cholesky factor, x / step / trial, the V fractions
-inline int mix_lds_rows(int n) {
-  return n * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1 + MIX_MAXV;
-}
-inline size_t mix_lds_bytes(int n, int W) { return (size_t)mix_lds_rows(n) * (size_t)(W + 1) * 8; }
-// pixels per workgroup
-inline int mix_group(int n) {
-  int W = REFINE_MAX_GROUP;
-  while (W > REFINE_MIN_GROUP && mix_lds_bytes(n, W) > (size_t)REFINE_LDS_BUDGET) W >>= 1;
-  return W;
-}
+// LDS is refine_lds_rows(n, n, MIX_MAXV): the n Jacobian tiles (the first is the y tile of pass 1) and, of the kernel's own,
+// the MIX_MAXV fractions; W follows refine_group.
 
 // The arguments of k_refine_mix_init, ONE struct: the maps are indexed by run-time values, which the kernel does through the
 // kernarg segment (LATE below) so that no copy of the struct is indexed in registers.  cfg: spart_refine's RefineCfg with every
@@ -240,7 +230,10 @@ struct MixStep {
   MixMap map;
 };
 
-// Once per iteration.  W (4 or 8: mix_group) is a template parameter: the strides and the lane maps are constants.
+// Once per iteration.  W (4 or 8: refine_group) is a template parameter: the strides and the lane maps are constants.
+// The phases are written out here and in k_refine_mix_init, not called from spart_refine.h as the rest of the family calls
+// them: over those functions the two kernels had fewer instructions, and the whole call at V = 4, n = 16 measured 1.5 % slower,
+// outside the run-to-run spread (profiles/refine_phases_ab.txt).  A change to a phase there is made here as well.
 template <int W>
 __global__ __launch_bounds__(64) void k_refine_mix_step(MixStep a) {
   SPART_NO_CONTRACT

@@ -55,8 +55,8 @@ SPART_HD double refine_trace(int F, const double* d, int S) {
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------------------------------
-// Part 2: k_refine_posterior.  It runs behind k_refine_init (whose table holds the point and its F neighbours) and one forward
-// call, on refine_impl's chunk layout: cols ((F + 1) Mc, nb), row = f Mc + m; t (Mc, F) the clipped point.
+// Part 2: k_refine_posterior.  It runs behind k_refine_views_init at V = 1 (whose table holds the point and its F neighbours)
+// and one forward call, on refine_impl's chunk layout: cols ((F + 1) Mc, nb), row = f Mc + m; t (Mc, F) the clipped point.
 //
 // The shape is k_refine_step's: single-wave workgroups of W consecutive observations, tiles of REFINE_JT bands staged through
 // LDS with band-contiguous lanes, everything indexed by the run-time F in LDS at [k][o] with the odd row stride W + 1, sums and
@@ -82,7 +82,7 @@ inline int refine_posterior_group(int F) {
   return W;
 }
 
-// outputs of the call (spart_posterior_out without x, which k_refine_init writes), moved to the chunk's first observation;
+// outputs of the call (spart_posterior_out without x, which the init kernel writes), moved to the chunk's first observation;
 // each may be NULL
 struct PosteriorOut {
   double *y, *jac, *cov, *ak, *sdev, *dfs, *cost;
@@ -148,22 +148,13 @@ __global__ __launch_bounds__(64) void k_refine_posterior(const double* __restric
       rl[jj * WP + o] = in && obs ? obs[at] : 0.0;
     }
     __syncthreads();
-    if (mine)
-      for (int jj = 0; jj < JT; ++jj) {
-        const double w = wl[jj * WP + lane];
-        if (refine_bad_weight(w)) bad = true;
-        if (w == 0.0) continue;
-        ++nw;
-        if (obs) ct = refine_cost_band(ct, w, Yl[jj * WP + lane], rl[jj * WP + lane]);
-      }
-  }
-  if (prior && mine)
-    for (int f = 0; f < F; ++f) {
-      const double p = ppw[pm + f];
-      if (refine_bad_weight(p)) bad = true;
-      if (p == 0.0) continue;
-      ct = refine_prior_cost(ct, p, st[(int64_t)m * F + f], pmu[pm + f]);
+    if (mine) {
+      for (int jj = 0; jj < JT; ++jj) nw += wl[jj * WP + lane] != 0.0 ? 1 : 0;
+      const double c = refine_tile_cost(ct, &bad, JT, wl + lane, WP, Yl + lane, WP, rl + lane, WP);
+      if (obs) ct = c;                                          // (without obs the tile only raises `bad`)
     }
+  }
+  if (prior && mine) ct = refine_prior_total(F, ct, &bad, st + (int64_t)m * F, pmu + pm, ppw + pm);
   int code = 0;
   if (mine) {
     code = (ct < __builtin_inf() && !bad) ? 1 : 2;
@@ -212,18 +203,11 @@ __global__ __launch_bounds__(64) void k_refine_posterior(const double* __restric
       const int o = lane % W, q = lane / W;
       if (flag[o] == 1)
         for (int e = q; e < nt; e += G) {
-          int a = 0;
-          while ((a + 1) * (a + 2) / 2 <= e) ++a;
-          const int b = e - a * (a + 1) / 2;
+          int a, b;
+          refine_pair(e, &a, &b);
           const double* ja = Yl + ((a + 1) * JT) * WP + o;
           const double* jb = Yl + ((b + 1) * JT) * WP + o;
-          double acc = Al[e * WP + o];
-          for (int jj = 0; jj < jn; ++jj) {
-            const double w = wl[jj * WP + o];
-            if (w == 0.0) continue;
-            acc = refine_mac(acc, w, ja[jj * WP], jb[jj * WP]);
-          }
-          Al[e * WP + o] = acc;
+          Al[e * WP + o] = refine_tile_sum(Al[e * WP + o], 0, jn, wl + o, WP, ja, WP, jb, WP);
         }
     }
   }
@@ -239,13 +223,7 @@ __global__ __launch_bounds__(64) void k_refine_posterior(const double* __restric
     }
   __syncthreads();
   if (mine && code == 1) {
-    if (prior)
-      for (int a = 0; a < F; ++a) {
-        const double p = ppw[pm + a];
-        if (p == 0.0) continue;
-        double* Aaa = Al + refine_tri(a, a) * WP + lane;
-        *Aaa = *Aaa + p;
-      }
+    if (prior) refine_prior_augment(F, Al + lane, WP, nullptr, 0, nullptr, ppw + pm);     // (K has no g)
     if (refine_cholesky(F, Al + lane, WP)) refine_inverse_lower(F, Al + lane, WP, Zl + lane, WP);
     else flag[lane] = 4;
   }
@@ -253,9 +231,9 @@ __global__ __launch_bounds__(64) void k_refine_posterior(const double* __restric
   const int fl = there ? flag[o] : 0;
   if (fl == 1)
     for (int e = q; e < nt; e += G) {
-      int a = 0;
-      while ((a + 1) * (a + 2) / 2 <= e) ++a;
-      Cl[e * WP + o] = refine_cov(F, Zl + o, WP, a, e - a * (a + 1) / 2);
+      int a, b;
+      refine_pair(e, &a, &b);
+      Cl[e * WP + o] = refine_cov(F, Zl + o, WP, a, b);
     }
   __syncthreads();
   if (fl != 0) {

@@ -285,12 +285,7 @@ __global__ __launch_bounds__(256) void k_series_decide(const double* __restrict_
   }
   if (spw) {
     const int64_t pt = sper ? (int64_t)t * Fs : 0;
-    for (int a = 0; a < Fs; ++a) {
-      const double p = spw[pt + a];
-      if (refine_bad_weight(p)) bad = true;
-      if (p == 0.0) continue;
-      C = refine_prior_cost(C, p, s.zt[(int64_t)t * Fs + a], smu[pt + a]);
-    }
+    C = refine_prior_total(Fs, C, &bad, s.zt + (int64_t)t * Fs, smu + pt, spw + pt);
   }
   int code;
   double lam = s.lam[t];
@@ -365,7 +360,7 @@ __global__ __launch_bounds__(256) void k_series_sums(const double* __restrict__ 
   const int t = (int)(idx / Ps), e = (int)(idx % Ps);
   if (s.code[t] != 1) return;
   int a = e - nts, b = -1;
-  if (e < nts) tiles_pair(e, &a, &b);
+  if (e < nts) refine_pair(e, &a, &b);
   const int at = b >= 0 ? refine_tri(Fl + a, Fl + b) : nt + Fl + a;
   const int b0 = s.tstart[t], b1 = s.tstart[t + 1];
   double acc = 0.0;
@@ -427,7 +422,7 @@ __global__ __launch_bounds__(64) void k_series_factor(int Tc, int F, int Fs, int
     double v = s.St[(int64_t)(t0 + o) * Ps + e];
     if (e < nts) {
       int a, b;
-      tiles_pair(e, &a, &b);
+      refine_pair(e, &a, &b);
       if (a == b && !last) v = v + lml[o] * (v > 0.0 ? v : 1.0);
     } else {
       v = -v;
@@ -444,7 +439,7 @@ __global__ __launch_bounds__(64) void k_series_factor(int Tc, int F, int Fs, int
       double v = s.Ap[(int64_t)(sb0[o] + r) * P + e];
       if (!last && e < nt) {
         int a, b;
-        tiles_pair(e, &a, &b);
+        refine_pair(e, &a, &b);
         if (a == b && a < Fl) v = v + lml[o] * (v > 0.0 ? v : 1.0);
       }
       cur[e * WP + o] = v;

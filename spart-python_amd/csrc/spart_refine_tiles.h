@@ -1,7 +1,7 @@
 // Refinement with parameters shared by a tile of pixels (spart_refine_tiles, include/spart_hip.h; the definition is
 // tools/refine_tiles_defined.py and every function here reproduces it bit for bit): spart_refine's fit with Fs unknowns per
 // TILE of contiguous pixels and Fl = F - Fs unknowns per pixel, one Levenberg-Marquardt decision per tile.  The per-entry
-// arithmetic is csrc/spart_refine.h's part 1; k_refine_init / k_refine_step are not touched.
+// arithmetic is csrc/spart_refine.h's part 1; k_refine_step is not touched.
 //
 // Part 1: the index maps, the per-pixel elimination pieces and the small per-tile solves, SPART_HD so that g++ compiles them
 // for tests/hostmath/refine_tiles_host.cpp.  Strides as in spart_refine.h (element k at p[k * S]).
@@ -22,13 +22,8 @@ constexpr int TILES_MAXG = 4096;             // pixels per tile
 // name f -> solve index, and back
 SPART_HD int tiles_sol(int f, int Fs, int Fl) { return f < Fs ? Fl + f : f - Fs; }
 SPART_HD int tiles_name(int q, int Fs, int Fl) { return q < Fl ? Fs + q : q - Fl; }
-// packed entry e of ntri(n): the pair a >= b
-SPART_HD void tiles_pair(int e, int* a, int* b) {
-  int r = 0;
-  while ((r + 1) * (r + 2) / 2 <= e) ++r;
-  *a = r;
-  *b = e - r * (r + 1) / 2;
-}
+// refine_pair under the name this header gave it before the family shared one (host code written against that name compiles)
+SPART_HD void tiles_pair(int e, int* a, int* b) { refine_pair(e, a, b); }
 // pixels of one chunk at most
 SPART_HD int64_t tiles_chunk(int F) { return REFINE_ROWS / (int64_t)(F + 1); }
 
@@ -102,7 +97,7 @@ SPART_HD double tiles_local_std(int Fs, int Fl, int j, const double* L, int SL, 
 SPART_HD void tiles_schur_offsets(int e, int F, int Fs, int Fl, int* oa, int* ob) {
   const int nts = refine_ntri(Fs);
   int a = e - nts, b = -1;
-  if (e < nts) tiles_pair(e, &a, &b);
+  if (e < nts) refine_pair(e, &a, &b);
   *oa = refine_tri(Fl + a, 0);
   *ob = b >= 0 ? refine_tri(Fl + b, 0) : refine_ntri(F);
 }
@@ -205,26 +200,11 @@ __global__ __launch_bounds__(256) void k_tiles_init(RefineCfg a, int64_t m0, int
                                                     int32_t* __restrict__ cfg_free) {
   SPART_NO_CONTRACT
   const int m = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x == 0) {
-#pragma unroll
-    for (int f = 0; f < REFINE_MAXF; ++f)
-      if ((int)threadIdx.x == f) {
-        cfg[f] = a.lo[f];
-        cfg[REFINE_MAXF + f] = a.hi[f];
-        cfg[2 * REFINE_MAXF + f] = a.h[f];
-        cfg_free[f] = a.free_col[f];
-      }
-  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < REFINE_MAXF) refine_cfg_copy(a, threadIdx.x, threadIdx.x, cfg, cfg_free);
   if (m >= Mc) return;
   const int Fl = F - Fs, t = s.ptile[m], first = s.tstart[t];
   const int64_t R = (int64_t)(F + 1) * Mc;
-#pragma unroll
-  for (int p = 0; p < NPARAM; ++p) {
-    if (a.is_free[p]) continue;
-    const double v = a.base[p][m0 + m];
-    double* row = table + p * R + m;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = v;
-  }
+  refine_fill_fixed(a, m0 + m, table + m, R, F, Mc);
 #pragma unroll
   for (int f = 0; f < REFINE_MAXF; ++f) {
     if (f >= F) continue;
@@ -237,8 +217,7 @@ __global__ __launch_bounds__(256) void k_tiles_init(RefineCfg a, int64_t m0, int
       out.shared[(int64_t)t * Fs + f] = tf;
       s.zt[(int64_t)t * Fs + f] = tf;
     }
-    double* row = table + a.free_col[f] * R + m;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = fp == f + 1 ? moved : tf;
+    refine_fill_row(table + a.free_col[f] * R + m, F, Mc, f + 1, tf, moved);
   }
   if (m == first) {
     s.lam[t] = lambda0;
@@ -262,7 +241,7 @@ __global__ __launch_bounds__(256) void k_tiles_cost(const double* __restrict__ c
   const double* wr = wts ? (wper ? wts + (int64_t)m * nb : wts) : nullptr;
   double c = 0.0;
   bool bad = false;
-  for (int j = 0; j < nb; ++j) {
+  for (int j = 0; j < nb; ++j) {                                    // (refine_tile_cost with weights that may be absent)
     const double w = wr ? wr[j] : 1.0;
     if (refine_bad_weight(w)) bad = true;
     if (w == 0.0) continue;
@@ -270,12 +249,7 @@ __global__ __launch_bounds__(256) void k_tiles_cost(const double* __restrict__ c
   }
   if (ppw) {
     const int64_t pm = pper ? (int64_t)m * Fl : 0;
-    for (int b = 0; b < Fl; ++b) {
-      const double p = ppw[pm + b];
-      if (refine_bad_weight(p)) bad = true;
-      if (p == 0.0) continue;
-      c = refine_prior_cost(c, p, s.lt[(int64_t)m * Fl + b], pmu[pm + b]);
-    }
+    c = refine_prior_total(Fl, c, &bad, s.lt + (int64_t)m * Fl, pmu + pm, ppw + pm);
   }
   s.ct[m] = c;
   if (it == 0) {
@@ -332,12 +306,7 @@ __global__ __launch_bounds__(64) void k_tiles_decide(const double* __restrict__ 
     bool bad = false;
     if (spw) {
       const int64_t pt = sper ? (int64_t)t * Fs : 0;
-      for (int a = 0; a < Fs; ++a) {
-        const double p = spw[pt + a];
-        if (refine_bad_weight(p)) bad = true;
-        if (p == 0.0) continue;
-        C = refine_prior_cost(C, p, s.zt[(int64_t)t * Fs + a], smu[pt + a]);
-      }
+      C = refine_prior_total(Fs, C, &bad, s.zt + (int64_t)t * Fs, smu + pt, spw + pt);
     }
     int code;
     double lam = s.lam[t];
@@ -398,7 +367,7 @@ __global__ __launch_bounds__(256) void k_tiles_normal(const double* __restrict__
   }
   for (int b = e; b < Fl; b += P) out.local[(int64_t)m * Fl + b] = s.lt[(int64_t)m * Fl + b];
   int qa, qb = -1;                                                 // e < nt: A_ab; else g_a against r
-  if (e < nt) tiles_pair(e, &qa, &qb);
+  if (e < nt) refine_pair(e, &qa, &qb);
   else qa = e - nt;
   const int fa = tiles_name(qa, Fs, Fl), fb = qb >= 0 ? tiles_name(qb, Fs, Fl) : 0;
   const double* hi = cfg + REFINE_MAXF;
@@ -480,7 +449,7 @@ __global__ __launch_bounds__(TILES_SCHUR_THREADS) void k_tiles_schur(const doubl
   const int Fl = F - Fs, nt = refine_ntri(F), P = nt + F, nts = refine_ntri(Fs), Ps = nts + Fs;
   const int b0 = s.tstart[t], b1 = s.tstart[t + 1];
   int a = e - nts, b = -1;
-  if (e < nts) tiles_pair(e, &a, &b);
+  if (e < nts) refine_pair(e, &a, &b);
   // step(acc, the staged packed vector of a live pixel) for every live pixel of the tile in order (every lane takes part)
   auto walk = [&](const double* __restrict__ src, double acc, auto&& step) {
     for (int p0 = b0; p0 < b1; p0 += TILES_WALK) {
@@ -602,9 +571,7 @@ __global__ __launch_bounds__(256) void k_tiles_apply(const double* __restrict__ 
       s.lt[(int64_t)m * Fl + (f - Fs)] = tf;
     }
     if (!alive) continue;
-    const double moved = tf + refine_fd_step(tf, hh[f], hi[f]);
-    double* row = table + cfg_free[f] * R + m;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * Mc] = fp == f + 1 ? moved : tf;
+    refine_fill_row(table + cfg_free[f] * R + m, F, Mc, f + 1, tf, tf + refine_fd_step(tf, hh[f], hi[f]));
   }
 }
 #endif  // __HIPCC__

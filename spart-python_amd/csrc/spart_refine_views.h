@@ -1,8 +1,8 @@
 // Joint refinement over V views of a pixel (spart_refine_views, include/spart_hip.h; the definition is
 // tools/refine_views_defined.py and every function here reproduces it bit for bit): spart_refine's fit with ONE unknown vector
 // per pixel -- Fs shared parameters and Fl local ones per view, n = Fs + V Fl unknowns -- against V observations.  The
-// per-entry arithmetic is csrc/spart_refine.h's part 1, called with n where it says F; k_refine_init / k_refine_step are not
-// touched.
+// per-entry arithmetic and the per-observation phases are csrc/spart_refine.h's, called with n where it says F; k_refine_step
+// is not touched.
 //
 // Part 1: the index maps, SPART_HD so that g++ compiles them for tests/hostmath/refine_views_host.cpp.
 // Index conventions.  free_cols lists the F = Fs + Fl free columns by NAME, the shared ones first; bounds and steps belong to
@@ -52,24 +52,14 @@ SPART_HD int64_t views_chunk(int V, int F) {
 // differs: F + 1 blocks of Y but n unknowns (block f at virtual band u holds J of the unknown views_unknown(u / nb, f - 1));
 // a packed sum runs over the part of the tile where both its unknowns are active (views_clip_range); (nb,) weights are
 // indexed u % nb; and a new trial rewrites V (F + 1) table entries per shared column, F + 1 per local unknown.
-// LDS is sized as refine_lds_rows sizes it with ntri(n), n and F + 1, and W follows the same budget rule: n <= 16 and F <= 16
-// bound it by what k_refine_step takes at F = 16.
-
-inline int views_lds_rows(int F, int n) {
-  return (F + 1) * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1;
-}
-inline size_t views_lds_bytes(int F, int n, int W) { return (size_t)views_lds_rows(F, n) * (size_t)(W + 1) * 8; }
-// pixels per workgroup
-inline int views_group(int F, int n) {
-  int W = REFINE_MAX_GROUP;
-  while (W > REFINE_MIN_GROUP && views_lds_bytes(F, n, W) > (size_t)REFINE_LDS_BUDGET) W >>= 1;
-  return W;
-}
+// LDS is refine_lds_rows(F + 1, n, 0), and W follows the same budget rule (refine_group): n <= 16 and F <= 16 bound it by what
+// k_refine_step takes at F = 16.
 
 // Once per chunk (pixels m0 .. m0 + Mc - 1 of the call's M), one thread per table row of a block: i = m V + v.  `a` is
 // spart_refine's RefineCfg with every base column (V, M) view-major and lo / hi / h per name; the device copy `cfg` gets them
 // per UNKNOWN (lo, hi, h: REFINE_MAXF doubles each).  A shared unknown starts from view 0's entry: the other views' entries of
-// a shared column are never read.  x / t are the chunk's own rows.
+// a shared column are never read.  x / t are the chunk's own rows.  At V = 1, Fs = F this is the init kernel of spart_refine
+// and spart_refine_posterior: table row f Mc + m, unknown f = free column f.
 __global__ __launch_bounds__(256) void k_refine_views_init(RefineCfg a, int64_t M, int64_t m0, int Mc, int V, int F, int Fs,
                                                            double lambda0, double* __restrict__ table, double* __restrict__ x,
                                                            double* __restrict__ t, double* __restrict__ lam,
@@ -79,28 +69,14 @@ __global__ __launch_bounds__(256) void k_refine_views_init(RefineCfg a, int64_t 
   const int Fl = F - Fs, n = Fs + V * Fl;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.x == 0 && (int)threadIdx.x < REFINE_MAXF) {
-    const int u = threadIdx.x, fn = u < n ? views_name(u, Fs, Fl) : -1;
-#pragma unroll
-    for (int f = 0; f < REFINE_MAXF; ++f) {
-      if (f == fn) {
-        cfg[u] = a.lo[f];
-        cfg[REFINE_MAXF + u] = a.hi[f];
-        cfg[2 * REFINE_MAXF + u] = a.h[f];
-      }
-      if (f == u) cfg_free[u] = a.free_col[f];
-    }
+    const int u = threadIdx.x;
+    refine_cfg_copy(a, u, u < n ? views_name(u, Fs, Fl) : -1, cfg, cfg_free);
   }
   if (i >= Mc * V) return;
   const int m = i / V, v = i % V;
   const int64_t blk = (int64_t)Mc * V, R = (int64_t)(F + 1) * blk;
   const int64_t src = (int64_t)v * M + m0 + m;
-#pragma unroll
-  for (int p = 0; p < NPARAM; ++p) {
-    if (a.is_free[p]) continue;
-    const double val = a.base[p][src];
-    double* row = table + p * R + i;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * blk] = val;
-  }
+  refine_fill_fixed(a, src, table + i, R, F, blk);
 #pragma unroll
   for (int f = 0; f < REFINE_MAXF; ++f) {
     if (f >= F) continue;
@@ -111,8 +87,7 @@ __global__ __launch_bounds__(256) void k_refine_views_init(RefineCfg a, int64_t 
       x[(int64_t)m * n + u] = tf;
       t[(int64_t)m * n + u] = tf;
     }
-    double* row = table + a.free_col[f] * R + i;
-    for (int fp = 0; fp <= F; ++fp) row[(int64_t)fp * blk] = fp == f + 1 ? moved : tf;
+    refine_fill_row(table + a.free_col[f] * R + i, F, blk, f + 1, tf, moved);
   }
   if (v == 0) {
     lam[m] = lambda0;
@@ -137,7 +112,10 @@ struct ViewsStep {
   const double *pmu, *ppw;
 };
 
-// Once per iteration.  W (4 or 8: views_group) is a template parameter: the strides and the lane maps are constants.
+// Once per iteration.  W (4 or 8: refine_group) is a template parameter: the strides and the lane maps are constants.
+// The phases are written out here, not called from spart_refine.h's part 1 and 2 as every other kernel of the family calls
+// them: over those functions this kernel had fewer instructions and the same registers, and the whole call measured 0.9 %
+// slower, outside the run-to-run spread (profiles/refine_phases_ab.txt).  A change to a phase there is made here as well.
 template <int W>
 __global__ __launch_bounds__(64) void k_refine_views_step(ViewsStep a) {
   SPART_NO_CONTRACT

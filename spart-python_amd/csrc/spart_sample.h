@@ -145,18 +145,14 @@ SPART_HD double sample_cov(double Q, double Sa, double Sb, double n) {
   return Q / n - p;
 }
 
-// packed entry e < F (F + 1) / 2 -> (a, b), a >= b
-SPART_HD void sample_pair(int e, int* a, int* b) {
-  int r = 0;
-  while ((r + 1) * (r + 2) / 2 <= e) ++r;
-  *a = r;
-  *b = e - r * (r + 1) / 2;
-}
+// refine_pair under the name this header gave it before the family shared one (host code written against that name compiles)
+SPART_HD void sample_pair(int e, int* a, int* b) { refine_pair(e, a, b); }
 
 #if defined(__HIPCC__)
 
 constexpr int SAMPLE_JT = 16;                 // bands per LDS tile (128 B of a row)
-constexpr int SAMPLE_MAXOPW = 16;             // observations per wave at most: 64 / (W / 2) with W = 8
+static_assert(SAMPLE_JT == REFINE_JT, "refine_stage_obs stages tiles of REFINE_JT bands");
+constexpr int SAMPLE_MAXOPW = 16;            // observations per wave at most: 64 / (W / 2) with W = 8
 
 struct SampleCfg {
   const double* base[NPARAM];            // the caller's start columns (each (M,))
@@ -336,38 +332,20 @@ __global__ __launch_bounds__(64) void k_sample_step(SampleStep p) {
   bool bad = false;
   for (int j0 = 0; j0 < nb; j0 += JT) {
     __syncthreads();
-    for (int i = lane; i < OPW * JT; i += 64) {
-      const int jj = i % JT, oo = i / JT, j = j0 + jj;
-      double w = 0.0, ob = 0.0;
-      if (mf + oo < p.Mc && j < nb) {
-        w = wts_g ? wts_g[p.wper ? oo * nb + j : j] : 1.0;
-        ob = obs_g[oo * nb + j];
-      }
-      wl[jj * OP + oo] = w;
-      ol[jj * OP + oo] = ob;
-    }
+    refine_stage_obs(lane, OPW, OP, p.Mc - mf, j0, nb, nb, obs_g, wts_g, p.wper, [](int j) { return j; }, wl, ol);
     for (int i = lane; i < 64 * JT; i += 64) {
       const int jj = i % JT, rr = i / JT, j = j0 + jj;
       Yl[jj * YP + rr] = (row0 + rr < R && j < nb) ? cols_g[(int64_t)rr * nb + j] : 0.0;
     }
     __syncthreads();
-    if (valid)
-      for (int jj = 0; jj < JT; ++jj) {
-        const double w = wl[jj * OP + o];
-        if (refine_bad_weight(w)) bad = true;
-        if (w == 0.0) continue;
-        ct = refine_cost_band(ct, w, Yl[jj * YP + lane], ol[jj * OP + o]);
-      }
+    if (valid) ct = refine_tile_cost(ct, &bad, JT, wl + o, OP, Yl + lane, YP, ol + o, OP);
   }
   const int64_t xat = ((int64_t)m * W + k) * F;          // this lane's walker in the state
   if (p.ppw && valid) {
     const int64_t pm = p.pper ? (int64_t)m * F : 0;
-    for (int f = 0; f < F; ++f) {
-      const double pw = p.ppw[pm + f];
-      if (refine_bad_weight(pw)) bad = true;
-      if (pw == 0.0) continue;
-      ct = refine_prior_cost(ct, pw, p.table[st.free_col[f] * R + row], p.pmu[pm + f]);
-    }
+    const double* table = p.table;
+    const int32_t* free_col = st.free_col;
+    ct = refine_prior_total_of(F, ct, &bad, [=](int f) { return table[free_col[f] * R + row]; }, p.pmu + pm, p.ppw + pm);
   }
 
   // ---- decision
@@ -436,7 +414,7 @@ __global__ __launch_bounds__(64) void k_sample_step(SampleStep p) {
   if (valid && p.keep >= 0)
     for (int e = kk; e < nt + F; e += H) {
       int a, b = -1;
-      if (e < nt) sample_pair(e, &a, &b);
+      if (e < nt) refine_pair(e, &a, &b);
       else a = e - nt;
       double* acc_at = e < nt ? st.Q + (int64_t)m * nt + e : st.S + (int64_t)m * F + a;
       *acc_at = sample_sum(*acc_at, st.x + (int64_t)m * W * F, F, 1, W, a, b, st.x0[(int64_t)m * F + a],
@@ -450,7 +428,7 @@ __global__ __launch_bounds__(64) void k_sample_step(SampleStep p) {
   for (int e = kk; e < nt + F; e += H) {
     if (e < nt) {
       int a, b;
-      sample_pair(e, &a, &b);
+      refine_pair(e, &a, &b);
       const double v = dead ? nan : sample_cov(st.Q[(int64_t)m * nt + e], st.S[(int64_t)m * F + a], st.S[(int64_t)m * F + b], p.n);
       if (out->cov) {
         out->cov[((int64_t)m * F + a) * F + b] = v;

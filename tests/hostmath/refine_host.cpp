@@ -24,14 +24,18 @@ void rh_lambda(int64_t n, const double* lam, const int32_t* accept, double* out)
 
 // step 3 of one observation: the trial cost; *bad = a weight that kills the observation
 double rh_cost(int nb, const double* y0, const double* obs, const double* w, int32_t* bad) {
-  double c = 0.0;
-  *bad = 0;
-  for (int j = 0; j < nb; ++j) {
-    if (refine_bad_weight(w[j])) *bad = 1;
-    if (w[j] == 0.0) continue;
-    c = refine_cost_band(c, w[j], y0[j], obs[j]);
-  }
+  bool b = false;
+  const double c = refine_tile_cost(0.0, &b, nb, w, 1, y0, 1, obs, 1);
+  *bad = b ? 1 : 0;
   return c;
+}
+
+// the decision of one call: out = {code, na} and *lam_out
+void rh_decide(int it, double ct, int bad, double cost, double lam, int na, int32_t* out, double* lam_out) {
+  const RefineDecision d = refine_decide(it, ct, bad != 0, cost, lam, na);
+  out[0] = d.code;
+  out[1] = d.na;
+  *lam_out = d.lam;
 }
 
 // J_jf and r_j of one observation from its F + 1 evaluations Y ((F + 1, nb) row-major) and the steps sh (F,)
@@ -46,13 +50,10 @@ void rh_jacobian(int F, int nb, const double* Y, const double* obs, const double
 // the packed sums of one observation: J (nb, F) row-major, r, w (nb,) -> packed (F (F + 1) / 2 + F)
 void rh_normal(int F, int nb, const double* J, const double* r, const double* w, double* packed) {
   const int nt = refine_ntri(F);
-  for (int e = 0; e < nt + F; ++e) packed[e] = 0.0;
-  for (int a = 0; a < F; ++a) {
-    for (int b = 0; b <= a; ++b)
-      for (int j = 0; j < nb; ++j)
-        if (w[j] != 0.0) packed[refine_tri(a, b)] = refine_mac(packed[refine_tri(a, b)], w[j], J[j * F + a], J[j * F + b]);
-    for (int j = 0; j < nb; ++j)
-      if (w[j] != 0.0) packed[nt + a] = refine_mac(packed[nt + a], w[j], J[j * F + a], r[j]);
+  for (int e = 0; e < nt + F; ++e) {
+    int a, b;
+    refine_packed_pair(e, nt, &a, &b);
+    packed[e] = b >= 0 ? refine_tile_sum(0.0, 0, nb, w, 1, J + a, F, J + b, F) : refine_tile_sum(0.0, 0, nb, w, 1, J + a, F, r, 1);
   }
 }
 

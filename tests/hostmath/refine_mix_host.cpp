@@ -98,34 +98,21 @@ void rmh_pixel(int V, int Fs, int Fl, const int32_t* active, int fit, double flo
     }
     if (!feasible) ++*infeasible;
     // pass 1: the mixed column and the trial cost
-    double ct = 0.0;
     std::vector<double> ym(nb);
     for (int j = 0; j < nb; ++j) {
       double yj = 0.0;
       for (int v = 0; v < V; ++v) yj = mix_add(yj, a[v], Y[((size_t)v * (F + 1)) * nb + j], v == 0);
       ym[j] = yj;
-      const double wj = w ? w[j] : 1.0;
-      if (refine_bad_weight(wj)) bad = true;
-      if (wj == 0.0) continue;
-      ct = refine_cost_band(ct, wj, yj, obs[j]);
     }
-    if (pw)
-      for (int u = 0; u < n; ++u) {
-        if (refine_bad_weight(pw[u])) bad = true;
-        if (pw[u] == 0.0) continue;
-        ct = refine_prior_cost(ct, pw[u], t[u], mu[u]);
-      }
+    const double one = 1.0;                // (no weights: every band reads this one, stride 0)
+    double ct = refine_tile_cost(0.0, &bad, nb, w ? w : &one, w ? 1 : 0, ym.data(), 1, obs, 1);
+    if (pw) ct = refine_prior_total(n, ct, &bad, t, mu, pw);
     if (!feasible) ct = __builtin_inf();
-    int code;
-    if (it == 0) {
-      code = (ct < __builtin_inf() && !bad) ? 1 : 2;
-      *cost0 = ct;
-      if (code == 2) na = -1, c = ct;
-    } else {
-      code = ct < c ? 1 : 3;
-      lam = refine_lambda(lam, code == 1);
-      if (code == 1) ++na;
-    }
+    const RefineDecision dec = refine_decide(it, ct, bad, c, lam, na);
+    const int code = dec.code;
+    na = dec.na, lam = dec.lam;
+    if (it == 0) *cost0 = ct;
+    if (code == 2) c = ct;
     if (code == 1 || code == 2) {
       if (code == 1) {
         c = ct;
@@ -161,25 +148,14 @@ void rmh_pixel(int V, int Fs, int Fl, const int32_t* active, int fit, double flo
           }
         }
         for (int e = 0; e < P; ++e) {
-          int ua = 0, ub = -1;
-          if (e < nt) {
-            while ((ua + 1) * (ua + 2) / 2 <= e) ++ua;
-            ub = e - ua * (ua + 1) / 2;
-          } else {
-            ua = e - nt;
-          }
+          int ua, ub;
+          refine_packed_pair(e, nt, &ua, &ub);
           const double* ja = Jt.data() + (size_t)ua * JT;
           const double* jc = ub >= 0 ? Jt.data() + (size_t)ub * JT : rl;
-          for (int jj = 0; jj < jn; ++jj)
-            if (wl[jj] != 0.0) acc[e] = refine_mac(acc[e], wl[jj], ja[jj], jc[jj]);
+          acc[e] = refine_tile_sum(acc[e], 0, jn, wl, 1, ja, 1, jc, 1);
         }
       }
-      if (pw)
-        for (int u = 0; u < n; ++u) {
-          if (pw[u] == 0.0) continue;
-          acc[refine_tri(u, u)] = acc[refine_tri(u, u)] + pw[u];
-          acc[nt + u] = refine_prior_gain(acc[nt + u], pw[u], refine_residual(x[u], mu[u]));
-        }
+      if (pw) refine_prior_augment(n, acc, 1, x, 1, mu, pw);
       for (int e = 0; e < P; ++e) packed[e] = acc[e];
     }
     if (it < n_iter) {

@@ -16,20 +16,14 @@ int rq_posterior(int F, int nb, const double* J, const double* w, const double* 
                  double* sdev, double* dfs) {
   const int nt = refine_ntri(F);
   std::vector<double> A((size_t)nt * S), Z((size_t)nt * S), C((size_t)nt * S), Kf((size_t)F * F * S), g((size_t)F * S);
-  for (int a = 0; a < F; ++a)
-    for (int b = 0; b <= a; ++b) {
-      double acc = 0.0;
-      for (int j = 0; j < nb; ++j)
-        if (w[j] != 0.0) acc = refine_mac(acc, w[j], J[j * F + a], J[j * F + b]);
-      A[(size_t)refine_tri(a, b) * S] = acc;
-    }
+  for (int e = 0; e < nt; ++e) {
+    int a, b;
+    refine_pair(e, &a, &b);
+    A[(size_t)e * S] = refine_tile_sum(0.0, 0, nb, w, 1, J + a, F, J + b, F);
+  }
   for (int a = 0; a < F; ++a)
     for (int b = 0; b < F; ++b) K[a * F + b] = Kf[(size_t)(a * F + b) * S] = refine_sym(A.data(), S, a, b);
-  if (p)
-    for (int a = 0; a < F; ++a) {
-      if (p[a] == 0.0) continue;
-      A[(size_t)refine_tri(a, a) * S] = A[(size_t)refine_tri(a, a) * S] + p[a];
-    }
+  if (p) refine_prior_augment(F, A.data(), S, nullptr, 0, nullptr, p);      // (K has no g)
   const double nan = __builtin_nan("");
   if (!refine_cholesky(F, A.data(), S)) {
     for (int e = 0; e < F * F; ++e) cov[e] = ak[e] = nan;

@@ -9,23 +9,15 @@ extern "C" {
 
 // the prior's terms of the trial cost of one observation, after the bands: f ascending, weight 0 skipped; *bad as rh_cost's
 double rp_prior_cost(int F, double c, const double* t, const double* mu, const double* p, int32_t* bad) {
-  *bad = 0;
-  for (int f = 0; f < F; ++f) {
-    if (refine_bad_weight(p[f])) *bad = 1;
-    if (p[f] == 0.0) continue;
-    c = refine_prior_cost(c, p[f], t[f], mu[f]);
-  }
+  bool b = false;
+  c = refine_prior_total(F, c, &b, t, mu, p);
+  *bad = b ? 1 : 0;
   return c;
 }
 
 // the prior's terms of the packed sums of one observation, after the band sums, in place: a ascending, weight 0 skipped
 void rp_prior_normal(int F, const double* t, const double* mu, const double* p, double* packed) {
-  const int nt = refine_ntri(F);
-  for (int a = 0; a < F; ++a) {
-    if (p[a] == 0.0) continue;
-    packed[refine_tri(a, a)] = packed[refine_tri(a, a)] + p[a];
-    packed[nt + a] = refine_prior_gain(packed[nt + a], p[a], refine_residual(t[a], mu[a]));
-  }
+  refine_prior_augment(F, packed, 1, t, 1, mu, p);
 }
 
 }  // extern "C"

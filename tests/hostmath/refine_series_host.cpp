@@ -32,12 +32,9 @@ double rsh_series_cost(int G, const double* c, int Fl, const double* gamma, cons
       if (k != 0.0) C = series_chain_cost(C, k, lt[(m + 1) * Fl + b], lt[m * Fl + b]);
     }
   }
-  if (spw)
-    for (int a = 0; a < Fs; ++a) {
-      if (refine_bad_weight(spw[a])) *bad = 1;
-      if (spw[a] == 0.0) continue;
-      C = refine_prior_cost(C, spw[a], zt[a], smu[a]);
-    }
+  bool b = false;
+  if (spw) C = refine_prior_total(Fs, C, &b, zt, smu, spw);
+  if (b) *bad = 1;
   return C;
 }
 
@@ -71,7 +68,7 @@ static bool series_factor(int G, const double* Ap, const double* St, int F, int 
     double v = St[e];
     if (e < nts) {
       int a, b;
-      tiles_pair(e, &a, &b);
+      refine_pair(e, &a, &b);
       if (a == b && damp) v = v + lam * (v > 0.0 ? v : 1.0);
     } else {
       v = -v;

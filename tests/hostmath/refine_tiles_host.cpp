@@ -23,7 +23,7 @@ void rth_maps(int Fs, int Fl, int32_t* sol, int32_t* name, int32_t* pa, int32_t*
   }
   for (int e = 0; e < refine_ntri(F); ++e) {
     int a, b;
-    tiles_pair(e, &a, &b);
+    refine_pair(e, &a, &b);
     pa[e] = a, pb[e] = b;
   }
 }
@@ -35,20 +35,11 @@ double rth_lambda(double lam, int accept) { return refine_lambda(lam, accept != 
 // c_m: the band loop on Y0 (nb,), then the local prior loop (pmu / ppw NULL or (Fl,))
 double rth_pixel_cost(int nb, int Fl, const double* Y0, const double* obs, const double* w, const double* lt, const double* pmu,
                       const double* ppw, int32_t* bad) {
-  double c = 0.0;
-  *bad = 0;
-  for (int j = 0; j < nb; ++j) {
-    const double wj = w ? w[j] : 1.0;
-    if (refine_bad_weight(wj)) *bad = 1;
-    if (wj == 0.0) continue;
-    c = refine_cost_band(c, wj, Y0[j], obs[j]);
-  }
-  if (ppw)
-    for (int b = 0; b < Fl; ++b) {
-      if (refine_bad_weight(ppw[b])) *bad = 1;
-      if (ppw[b] == 0.0) continue;
-      c = refine_prior_cost(c, ppw[b], lt[b], pmu[b]);
-    }
+  const double one = 1.0;                  // (no weights: every band reads this one, stride 0)
+  bool b = false;
+  double c = refine_tile_cost(0.0, &b, nb, w ? w : &one, w ? 1 : 0, Y0, 1, obs, 1);
+  if (ppw) c = refine_prior_total(Fl, c, &b, lt, pmu, ppw);
+  *bad = b ? 1 : 0;
   return c;
 }
 
@@ -59,7 +50,7 @@ void rth_pixel_sums(int F, int Fs, int nb, const double* Y, const double* obs, c
   const int Fl = F - Fs, nt = refine_ntri(F), P = nt + F;
   for (int e = 0; e < P; ++e) {
     int qa, qb = -1;
-    if (e < nt) tiles_pair(e, &qa, &qb);
+    if (e < nt) refine_pair(e, &qa, &qb);
     else qa = e - nt;
     const int fa = tiles_name(qa, Fs, Fl), fb = qb >= 0 ? tiles_name(qb, Fs, Fl) : 0;
     double acc = 0.0;
@@ -89,12 +80,9 @@ double rth_tile_cost(int G, const int32_t* live, const double* c, int Fs, const 
       C = C + c[m];
       *any = 1;
     }
-  if (spw)
-    for (int a = 0; a < Fs; ++a) {
-      if (refine_bad_weight(spw[a])) *bad = 1;
-      if (spw[a] == 0.0) continue;
-      C = refine_prior_cost(C, spw[a], zt[a], smu[a]);
-    }
+  bool b = false;
+  if (spw) C = refine_prior_total(Fs, C, &b, zt, smu, spw);
+  *bad = b ? 1 : 0;
   return C;
 }
 
@@ -104,7 +92,7 @@ void rth_tile_sums(int G, const int32_t* live, const double* Ap, int F, int Fs, 
   const int Fl = F - Fs, nt = refine_ntri(F), P = nt + F, nts = refine_ntri(Fs);
   for (int e = 0; e < nts + Fs; ++e) {
     int a, b = -1;
-    if (e < nts) tiles_pair(e, &a, &b);
+    if (e < nts) refine_pair(e, &a, &b);
     else a = e - nts;
     const int at = b >= 0 ? refine_tri(Fl + a, Fl + b) : nt + Fl + a;
     double acc = 0.0;
@@ -136,7 +124,7 @@ static bool tile_factor(int G, const int32_t* live, const double* Ap, const doub
   }
   for (int e = 0; e < Ps; ++e) {
     int a, b = -1;
-    if (e < nts) tiles_pair(e, &a, &b);
+    if (e < nts) refine_pair(e, &a, &b);
     else a = e - nts;
     double acc = St[e];
     if (b == a && damp) acc = acc + lam * (acc > 0.0 ? acc : 1.0);

@@ -54,14 +54,12 @@ void rvh_rows(int V, int Fs, int Fl, const double* base, const int32_t* free_col
 
 // the trial cost over the virtual bands: Y (V, F + 1, nb), obs (V nb,), w NULL, (nb,) (wper = 0) or (V nb,) (wper = 1)
 double rvh_cost(int V, int F, int nb, const double* Y, const double* obs, const double* w, int wper, int32_t* bad) {
+  const double one = 1.0;                  // (no weights: every band reads this one, stride 0)
   double c = 0.0;
-  *bad = 0;
-  for (int u = 0; u < V * nb; ++u) {
-    const double wu = w ? w[wper ? u : u % nb] : 1.0;
-    if (refine_bad_weight(wu)) *bad = 1;
-    if (wu == 0.0) continue;
-    c = refine_cost_band(c, wu, Y[((u / nb) * (F + 1)) * nb + u % nb], obs[u]);
-  }
+  bool b = false;
+  for (int v = 0; v < V; ++v)              // view v's bands are the virtual bands v nb ... (v + 1) nb - 1
+    c = refine_tile_cost(c, &b, nb, w ? (wper ? w + v * nb : w) : &one, w ? 1 : 0, Y + (v * (F + 1)) * nb, 1, obs + v * nb, 1);
+  *bad = b ? 1 : 0;
   return c;
 }
 
@@ -83,41 +81,28 @@ void rvh_sums(int V, int Fs, int Fl, int nb, const double* Y, const double* obs,
         Jt[f * JT + jj] = refine_jacobian(Y[(v * (F + 1) + f) * nb + j], y0, sh[views_unknown(v, f - 1, Fs, Fl)]);
     }
     for (int e = 0; e < P; ++e) {
-      int a = 0, b = -1;
-      if (e < nt) {
-        while ((a + 1) * (a + 2) / 2 <= e) ++a;
-        b = e - a * (a + 1) / 2;
-      } else {
-        a = e - nt;
-      }
+      int a, b;
+      refine_packed_pair(e, nt, &a, &b);
       int jb = 0, je = jn;
       views_clip_range(views_view(a, Fs, Fl), nb, j0, &jb, &je);
       if (b >= 0) views_clip_range(views_view(b, Fs, Fl), nb, j0, &jb, &je);
       const double* ja = Jt + (views_name(a, Fs, Fl) + 1) * JT;
       const double* jc = b >= 0 ? Jt + (views_name(b, Fs, Fl) + 1) * JT : rl;
-      for (int jj = jb; jj < je; ++jj)
-        if (wl[jj] != 0.0) packed[e] = refine_mac(packed[e], wl[jj], ja[jj], jc[jj]);
+      packed[e] = refine_tile_sum(packed[e], jb, je, wl, 1, ja, 1, jc, 1);
     }
   }
 }
 
 // the prior's terms: cost, then the additions to the accepted sums
 double rvh_prior_cost(int n, double c, const double* t, const double* mu, const double* pw, int32_t* bad) {
-  for (int a = 0; a < n; ++a) {
-    if (refine_bad_weight(pw[a])) *bad = 1;
-    if (pw[a] == 0.0) continue;
-    c = refine_prior_cost(c, pw[a], t[a], mu[a]);
-  }
+  bool b = false;
+  c = refine_prior_total(n, c, &b, t, mu, pw);
+  if (b) *bad = 1;
   return c;
 }
 
 void rvh_prior_normal(int n, double* packed, const double* x, const double* mu, const double* pw) {
-  const int nt = refine_ntri(n);
-  for (int a = 0; a < n; ++a) {
-    if (pw[a] == 0.0) continue;
-    packed[refine_tri(a, a)] = packed[refine_tri(a, a)] + pw[a];
-    packed[nt + a] = refine_prior_gain(packed[nt + a], pw[a], refine_residual(x[a], mu[a]));
-  }
+  refine_prior_augment(n, packed, 1, x, 1, mu, pw);
 }
 
 double rvh_lambda(double lam, int accept) { return refine_lambda(lam, accept != 0); }

@@ -120,20 +120,13 @@ void sph_step(int M, int F, int nb, int W, int h, int start, int last, int64_t k
     for (int kk = 0; kk < H; ++kk) {
       const int64_t row = (int64_t)m * H + kk;
       const int k = h * H + kk;
-      double ct = 0.0;
-      for (int j = 0; j < nb; ++j) {
-        const double w = wts ? wts[wper ? (int64_t)m * nb + j : j] : 1.0;
-        if (refine_bad_weight(w)) anybad = true;
-        if (w == 0.0) continue;
-        ct = refine_cost_band(ct, w, Y[row * nb + j], obs[(int64_t)m * nb + j]);
+      const double one = 1.0;                                  // (no weights: every band reads this one, stride 0)
+      const double* w = wts ? wts + (wper ? (int64_t)m * nb : 0) : &one;
+      double ct = refine_tile_cost(0.0, &anybad, nb, w, wts ? 1 : 0, Y + row * nb, 1, obs + (int64_t)m * nb, 1);
+      if (ppw) {
+        const int64_t pm = pper ? (int64_t)m * F : 0;
+        ct = refine_prior_total(F, ct, &anybad, rows + row * F, pmu + pm, ppw + pm);
       }
-      if (ppw)
-        for (int f = 0; f < F; ++f) {
-          const double pw = ppw[(pper ? (int64_t)m * F : 0) + f];
-          if (refine_bad_weight(pw)) anybad = true;
-          if (pw == 0.0) continue;
-          ct = refine_prior_cost(ct, pw, rows[row * F + f], pmu[(pper ? (int64_t)m * F : 0) + f]);
-        }
       double* c_at = st->c + ((int64_t)m * W + k) * S;
       if (start) {
         *c_at = ct;
@@ -186,7 +179,7 @@ void sph_step(int M, int F, int nb, int W, int h, int start, int last, int64_t k
     if (keep >= 0)
       for (int e = 0; e < nt + F; ++e) {
         int a, b = -1;
-        if (e < nt) sample_pair(e, &a, &b);
+        if (e < nt) refine_pair(e, &a, &b);
         else a = e - nt;
         double* acc_at = e < nt ? st->Q + ((int64_t)m * nt + e) * S : st->sum + ((int64_t)m * F + a) * S;
         *acc_at = sample_sum(*acc_at, st->x + (int64_t)m * W * F * S, F * S, S, W, a, b, st->x0[(int64_t)m * F + a],
@@ -196,7 +189,7 @@ void sph_step(int M, int F, int nb, int W, int h, int start, int last, int64_t k
     for (int e = 0; e < nt + F; ++e) {
       if (e < nt) {
         int a, b;
-        sample_pair(e, &a, &b);
+        refine_pair(e, &a, &b);
         const double v = dead ? nan : sample_cov(st->Q[((int64_t)m * nt + e) * S], st->sum[((int64_t)m * F + a) * S],
                                                  st->sum[((int64_t)m * F + b) * S], n);
         if (out->cov) out->cov[((int64_t)m * F + a) * F + b] = v, out->cov[((int64_t)m * F + b) * F + a] = v;

@@ -186,6 +186,64 @@ def test_cost_jacobian_and_scalars_bit_for_bit(lib, nb):
         assert o.min() >= 1e-12 and o.max() <= 1e12
 
 
+def decide_defined(it, ct, bad, c, lam, na):
+    """one observation through the decision lines of refine_defined's loop -> (code, na, lam); code as the kernels flag it:
+    0 dead already, 1 accepted, 2 dead from the start, 3 rejected"""
+    dead = na < 0
+    with np.errstate(all="ignore"):
+        accept = bool(ct < c) and not dead and not bad
+    if it == 0:
+        dead = not accept
+        if dead:
+            na = -1
+    else:
+        if not dead:
+            lam = float(rd.lambda_defined(np.float64(lam), accept))
+        na = na + int(accept)
+    return (1 if accept else 2 if it == 0 else 0 if dead else 3), na, lam
+
+
+DECIDE_CASES = [
+    # it, ct, bad, cost, lam, na -> code
+    (0, 0.25, 0, np.inf, 1e-2, 0, 1),                        # it = 0: a finite cost
+    (0, 0.0, 0, np.inf, 1e-2, 0, 1),
+    (0, np.inf, 0, np.inf, 1e-2, 0, 2),                      # +inf
+    (0, np.nan, 0, np.inf, 1e-2, 0, 2),                      # NaN
+    (0, 0.25, 1, np.inf, 1e-2, 0, 2),                        # finite under a bad weight
+    (3, 0.5, 0, 1.0, 1e-2, 2, 1),                            # it > 0: lower
+    (3, 1.0, 0, 1.0, 1e-2, 2, 3),                            # equal
+    (3, 2.0, 0, 1.0, 1e-2, 2, 3),                            # higher
+    (3, np.nan, 0, 1.0, 1e-2, 2, 3),                         # NaN
+    (3, np.inf, 0, 1.0, 1e-2, 0, 3),
+    (3, 0.5, 0, 1.0, 1e-2, -1, 0),                           # dead already: nothing moves
+    (3, np.nan, 0, np.nan, 0.3, -1, 0),
+    (1, 0.5, 0, 1.0, rd.LAMBDA_MIN, 0, 1),                   # lambda at its floor, accepted
+    (1, 0.5, 0, 1.0, 5e-12, 0, 1),                           # ... and one step above it
+    (1, 2.0, 0, 1.0, rd.LAMBDA_MAX, 7, 3),                   # lambda at its cap, rejected
+    (1, 2.0, 0, 1.0, 5e11, 7, 3),
+]
+
+
+def test_decision_against_the_definition(lib):
+    """refine_decide, the decision every step kernel of the family takes, case by case against the definition's lines"""
+    lib.rh_decide.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
+    for it, ct, bad, cost, lam, na, code in DECIDE_CASES:
+        out, lo = np.zeros(2, dtype=np.int32), np.zeros(1)
+        lib.rh_decide(it, ct, bad, 0.0 if it == 0 else cost, lam, na, ip(out), dp(lo))     # (at it = 0 no cost exists yet)
+        want = decide_defined(it, ct, bool(bad), cost, lam, na)
+        case = (it, ct, bad, cost, lam, na)
+        assert want[0] == code and (int(out[0]), int(out[1])) == want[:2] and same(lo[0], np.float64(want[2])), (case, out, lo, want)
+        if code == 0:
+            assert out[1] == -1 and same(lo[0], np.float64(lam)), case
+        if code == 2:
+            assert out[1] == -1 and same(lo[0], np.float64(lam)), case
+        if it == 0 and code == 1:
+            assert out[1] == 0 and same(lo[0], np.float64(lam)), case              # the first call moves neither
+    clamp = {c[4]: decide_defined(*c[:6])[2] for c in DECIDE_CASES if c[0] == 1}
+    assert clamp[rd.LAMBDA_MIN] == rd.LAMBDA_MIN == clamp[5e-12] and clamp[rd.LAMBDA_MAX] == rd.LAMBDA_MAX == clamp[5e11]
+
+
 def test_whole_loop_on_a_toy_model_matches_a_scalar_transcription(lib):
     """refine_defined's loop against a per-observation loop built from the g++ functions, on a cheap nonlinear forward"""
     rng = np.random.default_rng(11)

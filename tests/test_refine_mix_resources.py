@@ -1,5 +1,5 @@
 """The compiled resources of the spart_refine_mix kernels (no GPU needed): no scratch and no spills in the init kernel and in
-both instantiations of the step kernel, and the LDS formula of csrc/spart_refine_mix.h, recomputed here, within the family's
+both instantiations of the step kernel, and the LDS formula the launcher uses (refine_lds_rows(n, n, MIX_MAXV)), recomputed here, within the family's
 budget for every (V, F, n) the call accepts."""
 import os
 
@@ -7,6 +7,8 @@ from conftest import ROOT
 from helpers.compiled_meta import kernel_meta_fixture  # noqa: F401  (the `kernel_meta` fixture)
 
 HEADER = os.path.join(ROOT, "spart-python_amd", "csrc", "spart_refine_mix.h")
+REFINE = os.path.join(ROOT, "spart-python_amd", "csrc", "spart_refine.h")
+CAPI = os.path.join(ROOT, "spart-python_amd", "csrc", "spart_capi.hip")
 JT, BUDGET, MAXV = 16, 40960, 8
 
 
@@ -32,10 +34,11 @@ def group(n):
 
 
 def test_mix_lds_stays_within_the_budget():
-    """mix_lds_rows depends on n alone (the blocks are folded from global memory, not staged), so every admissible (V, F, n)
+    """refine_lds_rows(n, n, MIX_MAXV) depends on n alone (the blocks are folded from global memory, not staged), so every admissible (V, F, n)
     is covered by n = 1 ... 16: the group rule picks a W whose LDS fits the budget, 8 pixels for small n and 4 at n = 16"""
     src = open(HEADER).read()
-    assert "n * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1 + MIX_MAXV" in src
+    assert "refine_lds_rows(n, n, MIX_MAXV)" in src and "rows = refine_lds_rows(n, n, MIX_MAXV), W = refine_group(rows)" in open(CAPI).read()
+    assert "tile_rows * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1 + extra" in open(REFINE).read()
     assert "constexpr int MIX_MAXV = 8;" in src
     seen = set()
     for V in range(1, MAXV + 1):

@@ -1,4 +1,4 @@
-"""Resource guard of the refinement kernels (no GPU: hipcc cross-compiles): k_refine_init and k_refine_step keep their working
+"""Resource guard of the refinement kernels (no GPU: hipcc cross-compiles): k_refine_views_init and k_refine_step keep their working
 set in registers and LDS -- no scratch, no spills -- and the dynamic LDS the launcher asks for (refine_group / refine_lds_bytes
 of csrc/spart_refine.h, re-computed here from its constants) stays within REFINE_LDS_BUDGET for every F, so that at least two
 workgroups share a CU's 160 KiB."""
@@ -18,7 +18,7 @@ def constants():
 
 
 def lds_bytes(c, F, W):
-    """refine_lds_bytes: (F + 1) JT + 2 JT + P + ntri + 3 F + 1 rows of W + 1 doubles"""
+    """refine_lds_bytes of refine_lds_rows(F + 1, F, 0): (F + 1) JT + 2 JT + P + ntri + 3 F + 1 rows of W + 1 doubles"""
     nt = F * (F + 1) // 2
     return ((F + 1) * c["REFINE_JT"] + 2 * c["REFINE_JT"] + (nt + F) + nt + 3 * F + 1) * (W + 1) * 8
 
@@ -32,7 +32,7 @@ def group(c, F):
 
 def test_refine_kernels_use_no_scratch_and_share_a_cu(kernel_meta):
     hits = {k: v for k, v in kernel_meta.items() if "k_refine_" in k}
-    assert any("k_refine_init" in k for k in hits) and any("k_refine_step" in k for k in hits), sorted(hits)
+    assert any("k_refine_views_init" in k for k in hits) and any("k_refine_step" in k for k in hits), sorted(hits)
     c = constants()
     assert c["REFINE_MAXF"] == 16 and c["REFINE_JT"] == 16 and c["REFINE_MIN_GROUP"] == 4 and c["REFINE_MAX_GROUP"] == 8
     most = max(lds_bytes(c, F, group(c, F)) for F in range(1, c["REFINE_MAXF"] + 1))

@@ -302,13 +302,14 @@ def test_views_kernels_use_no_scratch(kernel_meta):
 
 
 def test_views_lds_stays_within_the_budget_of_k_refine_step():
-    """views_lds_rows with ntri(n), n and F + 1 is at most refine_lds_rows(16) for every (V, Fs, Fl) the call accepts, so the
+    """refine_lds_rows(F + 1, n, 0) is at most refine_lds_rows(17, 16, 0) for every (V, Fs, Fl) the call accepts, so the
     budget rule picks a W whose LDS k_refine_step already takes at F = 16"""
     def rows(F, n):
         nt = n * (n + 1) // 2
         return (F + 1) * 16 + 2 * 16 + (nt + n) + nt + 3 * n + 1
-    src = open(os.path.join(ROOT, "spart-python_amd", "csrc", "spart_refine_views.h")).read()
-    assert "(F + 1) * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1" in src
+    csrc = os.path.join(ROOT, "spart-python_amd", "csrc")
+    assert "tile_rows * REFINE_JT + 2 * REFINE_JT + (refine_ntri(n) + n) + refine_ntri(n) + 3 * n + 1 + extra" in open(os.path.join(csrc, "spart_refine.h")).read()
+    assert "rows = refine_lds_rows(F + 1, n, 0), W = refine_group(rows)" in open(os.path.join(csrc, "spart_capi.hip")).read()
     worst = 0
     for V in range(1, 65):
         for F in range(1, 17):

@@ -19,8 +19,9 @@ def kernel_code(asm):
     """{mangled kernel name: its instructions and labels}"""
     out = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\s+s_endpgm", asm, flags=re.M | re.S):
-        lines = (l.split(";")[0].strip() for l in m.group(2).split("\n"))
-        out[m.group(1)] = [l for l in lines if l and (not l.startswith(".") or re.match(r"\.LBB\d+_\d+:", l))]
+        # (a label carries its function's number in the unit, which moves when a kernel before it comes or goes)
+        lines = (re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].strip()) for l in m.group(2).split("\n"))
+        out[m.group(1)] = [l for l in lines if l and (not l.startswith(".") or re.match(r"\.LBB_\d+:", l))]
     return out
 
 
@@ -28,9 +29,14 @@ def main(dir_a, dir_b):
     for f in sorted(os.listdir(dir_a)):
         a, b = open(os.path.join(dir_a, f)).read(), open(os.path.join(dir_b, f)).read()
         ca, cb, ma, mb = kernel_code(a), kernel_code(b), read_kernels(a), read_kernels(b)
-        assert set(ca) == set(cb) == set(ma) == set(mb), f
-        diff = [n for n in ca if ca[n] != cb[n]]
-        print(f"{f}: {len(ca)} kernels, {len(ca) - len(diff)} identical, {len(diff)} differ")
+        assert set(ca) == set(ma) and set(cb) == set(mb), f
+        both = [n for n in ca if n in cb]
+        diff = [n for n in both if ca[n] != cb[n]]
+        print(f"{f}: {len(both)} kernels in both, {len(both) - len(diff)} identical, {len(diff)} differ")
+        for tag, only in (("A", set(ca) - set(cb)), ("B", set(cb) - set(ca))):
+            for d in subprocess.run(["c++filt"], input="\n".join(sorted(only)), capture_output=True, text=True).stdout.split("\n"):
+                if d:
+                    print(f"  only in {tag}: {re.sub(r'[(].*', '', d).replace('void spart::', '')}")
         names = subprocess.run(["c++filt"], input="\n".join(diff), capture_output=True, text=True).stdout.split("\n")
         for n, d in zip(diff, names):
             na, nb = (sum(1 for l in c[n] if not l.endswith(":")) for c in (ca, cb))

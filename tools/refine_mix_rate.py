@@ -37,7 +37,7 @@ KERNELS = ("k_refine_mix_step", "k_refine_mix_init", "k_refine_views_step", "k_r
 
 
 def group(n):
-    """mix_group / mix_lds_bytes of csrc/spart_refine_mix.h from the constants of csrc/spart_refine.h -> (W, LDS bytes)"""
+    """refine_group / refine_lds_bytes of refine_lds_rows(n, n, MIX_MAXV), from the constants of csrc/spart_refine.h -> (W, LDS bytes)"""
     src = open(os.path.join(ROOT, "spart-python_amd", "csrc", "spart_refine.h")).read()
     c = {k: int(v) for k, v in re.findall(r"(REFINE_[A-Z_]+) = (\d+)", src)}
     nt = n * (n + 1) // 2

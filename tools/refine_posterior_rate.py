@@ -5,7 +5,7 @@ kernel of spart_refine on the same shape.
 
 Workload: tools/refine_rate.py's -- Sentinel-2A (nb = 13), M LHS rows, the free parameters moved 10 % of their range, float64,
 weights 1 / (0.02 max(obs, 0.01))^2, a shared prior of sigma = 10 % of the range.
-  a  the whole call with all ten outputs (k_refine_init, one forward call of (F + 1) M rows in chunks, k_refine_posterior);
+  a  the whole call with all ten outputs (k_refine_views_init, one forward call of (F + 1) M rows in chunks, k_refine_posterior);
   b  the same call without jac (the nb F doubles per observation are the bulk of what the kernel writes);
   c  one eng.run(..., "float64", prune=True) of the same (F + 1) M rows: the yardstick;
   d  k_refine_posterior's row of `rocprofv3 --kernel-trace --stats` beside k_refine_step's, from a separate run in a child
@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "spart-python_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from refine_rate import NAMES, SENSOR, event_ms, prior_of, stats, workload  # noqa: E402
 
-KERNELS = ("k_refine_posterior", "k_refine_step", "k_refine_init", "k_columns", "k_prelude")
+KERNELS = ("k_refine_posterior", "k_refine_step", "k_refine_views_init", "k_columns", "k_prelude")
 
 
 def setup(torch, eng, M, F):

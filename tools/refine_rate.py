@@ -4,7 +4,7 @@
                                 [--band-model centre|srf] [--out profiles/refine_rate.txt]
 
 Workload: Sentinel-2A (nb = 13), M LHS rows as the truth, the free parameters started 10 % of their range away, float64.
-  a  the whole spart_refine call (Engine.refine: k_refine_init, n_iter + 1 forward calls, n_iter + 1 step kernels);
+  a  the whole spart_refine call (Engine.refine: k_refine_views_init, n_iter + 1 forward calls, n_iter + 1 step kernels);
   b  the same n_iter + 1 forward calls alone, eng.run(..., "float64", prune=True) on (F + 1) M rows -- the yardstick: the
      parent commit's kernels on the same number of rows;
   c  the step kernel's own time per iteration, two ways: (a - b) / (n_iter + 1) by device events (it also holds the init
@@ -115,7 +115,7 @@ def kernel_lines(a):
     rows = {}
     for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            for k in ("k_refine_step", "k_refine_init", "k_columns_srf", "k_columns", "k_prelude"):
+            for k in ("k_refine_step", "k_refine_views_init", "k_columns_srf", "k_columns", "k_prelude"):
                 if k in row["Name"] and not (k == "k_columns" and "k_columns_srf" in row["Name"]):
                     rows[k] = (int(row["Calls"]), float(row["AverageNs"]) / 1e6, float(row["MinNs"]) / 1e6, float(row["MaxNs"]) / 1e6)
     return rows, "" if "k_refine_step" in rows else "(no k_refine_step row in the kernel stats)"

@@ -29,7 +29,7 @@ SHARED, LOCAL = ["aot550"], ["LAI", "Cab"]
 TILES = (64, 4096)
 PER_PIXEL = ("k_tiles_init", "k_tiles_cost", "k_tiles_normal", "k_tiles_eliminate", "k_tiles_local", "k_tiles_apply")
 PER_TILE = ("k_tiles_decide", "k_tiles_schur")
-KERNELS = PER_PIXEL + PER_TILE + ("k_refine_step", "k_refine_init", "k_columns", "k_prelude", "k_bands")
+KERNELS = PER_PIXEL + PER_TILE + ("k_refine_step", "k_columns", "k_prelude", "k_bands")
 
 
 def workload(torch, eng, M, G):

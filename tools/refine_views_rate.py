@@ -9,7 +9,7 @@ parameters (LAI, Cab, Cw, Cdm) and Fl = 1 local one (aot550), started 10 % of th
   c  (a - b) / (n_iter + 1): init, step kernel and chunking per iteration, by device events;
 and the yardstick beside it: a, b, c of spart_refine with F = 5 (the same names, all free per observation) on V M
 observations -- the same number of forward rows.  Then the kernels' own rows of `rocprofv3 --kernel-trace --stats` from a
-separate run of both calls in a child process, the ratio of the two step kernels, and the W and LDS bytes views_group picks.
+separate run of both calls in a child process, the ratio of the two step kernels, and the W and LDS bytes refine_group picks.
 Device events, medians after two warm-up calls; every figure in the report is measured in this run.
 """
 import argparse
@@ -35,7 +35,7 @@ GEOMETRY = [dict(tts=30.0, tto=0.0, psi=0.0), dict(tts=45.0, tto=25.0, psi=20.0)
 
 
 def group(F, n):
-    """views_group / views_lds_bytes of csrc/spart_refine_views.h from the constants of csrc/spart_refine.h -> (W, LDS bytes)"""
+    """refine_group / refine_lds_bytes of refine_lds_rows(F + 1, n, 0), from the constants of csrc/spart_refine.h -> (W, LDS bytes)"""
     src = open(os.path.join(ROOT, "spart-python_amd", "csrc", "spart_refine.h")).read()
     c = {k: int(v) for k, v in re.findall(r"(REFINE_[A-Z_]+) = (\d+)", src)}
     nt = n * (n + 1) // 2
@@ -76,7 +76,7 @@ def child(a):
     torch.cuda.synchronize()
 
 
-KERNELS = ("k_refine_views_step", "k_refine_views_init", "k_refine_step", "k_refine_init", "k_columns", "k_prelude")
+KERNELS = ("k_refine_views_step", "k_refine_views_init", "k_refine_step", "k_columns", "k_prelude")
 
 
 def kernel_lines(a):
