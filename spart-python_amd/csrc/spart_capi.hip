@@ -1132,48 +1132,96 @@ static int launch_lut_summarise(int64_t B, int P, const double* params, int64_t 
 // ---- The refinement family (csrc/spart_refine.h, spart_refine_views.h, spart_refine_mix.h, spart_refine_posterior.h):
 // spart_refine, spart_refine_srf, spart_refine_posterior, spart_refine_views and spart_refine_mix share one workspace layout, one
 // chunk loop and one entry check.  A call fits n unknowns per observation from V views (or mixture components) of it, F free
-// columns each, the first Fs of them shared by the views; the single-view entries are {1, F, F, F}.
+// columns each, the first Fs of them shared by the views; the single-view entries are {1, F, F, F}.  The forward block
+// (ForwardBlock), the forward call (Forward), the size guard (fit_sizes_ok), the check of the free columns (refine_check_fit)
+// and the tail of an entry (fit_tail) also serve the tiles, the series, Sobol' and the sampler further down.
 struct RefineShape {
   int V, F, Fs, n;
 };
 
+// What every *_workspace_bytes of the family (tiles, series, Sobol' and the sampler included) asks of ctx, M and F before its own
+static bool fit_sizes_ok(const spart_ctx* ctx, int64_t M, int F) {
+  return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF;
+}
+
+// The forward block, the part of a workspace every entry that calls the forward model on a table has: the (27, rows)
+// parameter table, the three (rows, nb) column blocks and the forward call's own workspace.  The caller sizes the latter:
+// exact carve() totals where the row counts of its chunks are known, carve_bound_f64(rows) where they follow a partition.
+struct ForwardBlock {
+  size_t table, cols[3], fwd;
+};
+static ForwardBlock forward_block(Carver& c, int nb, size_t rows, size_t scratch) {
+  ForwardBlock b;
+  b.table = c.take((size_t)NPARAM * rows * 8);
+  for (size_t& o : b.cols) o = c.take(rows * (size_t)nb * 8);
+  b.fwd = c.take(scratch);
+  return b;
+}
+
+// The forward call of the block's table, built once per entry call.  The band model decides what it writes into the column
+// block the fit reads (`y`): k_columns' three centre columns, or the ONE *_srf output of k_columns_srf the fit is about
+// (k_columns is then not launched at all).
+struct Forward {
+  spart_ctx* ctx;
+  bool srf;
+  spart_materialize mat;
+  double *table, *cols[3];
+  const double* y;
+  char* scratch;
+  Forward(spart_ctx* ctx_, char* wsp, const ForwardBlock& b, int column, bool srf_, int fast_prelude, int nlayers)
+      : ctx(ctx_), srf(srf_), table((double*)(wsp + b.table)), scratch(wsp + b.fwd) {
+    std::memset(&mat, 0, sizeof(mat));
+    mat.prune_unused_bands = 1;
+    mat.fast_prelude = fast_prelude;
+    mat.nlayers = nlayers;
+    for (int k = 0; k < 3; ++k) cols[k] = (double*)(wsp + b.cols[k]);
+    y = cols[column];
+    if (srf) (column == 0 ? mat.R_TOC_srf : column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[column];
+  }
+  // a table of `rows` rows, parameter p at table + p rows (no template: the float64 forward kernels are instantiated here,
+  // ahead of the family's own)
+  int run(int64_t rows, hipStream_t st) const {
+    const double* params[SPART_NPARAM];
+    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
+    return run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, scratch,
+                                            carve(SPART_F64, rows), st, !srf);
+  }
+};
+
 // The workspace is sized by ONE chunk -- min(M, views_chunk(V, F)) observations of V (F + 1) table rows each -- whatever M
-// is: the parameter table, the three column blocks of the forward call, the optimiser's state per unknown and the forward
-// call's own workspace.
+// is: the forward block, the optimiser's state per unknown and the device copy of the call's constants.
 struct RefineLayout {
   int64_t mcap;                 // observations per chunk
-  size_t table, cols[3], t, A, lam, na, cfg, cfg_free, fwd, total;
+  ForwardBlock b;
+  size_t t, A, lam, na, cfg, cfg_free, total;
 };
 static RefineLayout refine_layout(int nb, int64_t M, int V, int F, int n) {
   RefineLayout l;
   l.mcap = std::min<int64_t>(M, views_chunk(V, F));
   const size_t mc = (size_t)l.mcap, per = (size_t)(F + 1) * V, rows = mc * per;
+  // the forward call of a full chunk and of the last, shorter one (the band-sum rows of carve() follow pick_chunk, which is
+  // not monotonic in the batch)
+  size_t fwd = carve(SPART_F64, (int64_t)rows).total;
+  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (int64_t)per).total);
   Carver c;
-  l.table = c.take((size_t)NPARAM * rows * 8);
-  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
+  l.b = forward_block(c, nb, rows, fwd);
   l.t = c.take(mc * n * 8);
   l.A = c.take(mc * (size_t)(refine_ntri(n) + n) * 8);
   l.lam = c.take(mc * 8);
   l.na = c.take(mc * 4);
   l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
   l.cfg_free = c.take(REFINE_MAXF * 4);
-  // the forward call of a full chunk and of the last, shorter one (the band-sum rows of carve() follow pick_chunk, which is
-  // not monotonic in the batch)
-  size_t fwd = carve(SPART_F64, (int64_t)rows).total;
-  if (const int64_t rest = M % l.mcap) fwd = std::max(fwd, carve(SPART_F64, rest * (int64_t)per).total);
-  l.fwd = c.take(fwd);
   l.total = c.o;
   return l;
 }
 
 static bool refine_sizes_ok(const spart_ctx* ctx, int64_t M, int V, int F, int n_shared) {
-  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF) return false;
-  if (V < 1 || V > VIEWS_MAXV || n_shared < 0 || n_shared > F) return false;
+  if (!fit_sizes_ok(ctx, M, F) || V < 1 || V > VIEWS_MAXV || n_shared < 0 || n_shared > F) return false;
   const int n = n_shared + V * (F - n_shared);
   return n >= 1 && n <= REFINE_MAXF;
 }
 
-// A checked call, as the chunk loop and the three kernel sequences see it
+// A checked call, as the chunk loops and the kernel sequences see it
 struct RefineRun {
   spart_ctx* ctx;
   bool srf;                     // the forward call writes the ONE *_srf column of the fit, not k_columns' three
@@ -1183,11 +1231,14 @@ struct RefineRun {
   spart_refine_opt o;           // (the defaults that 0 stands for filled in)
   const double *obs, *weights;
   char* wsp;
-  RefineLayout l;
+  RefineLayout l;               // refine_loop's (the tiles and the series bring their own)
+  Forward forward(const ForwardBlock& b) const { return Forward(ctx, wsp, b, o.column, srf, o.fast_prelude, o.nlayers); }
 };
 // the blocks of the workspace; `cols` is the column block the kernel after a forward call reads
 struct RefineWs {
-  double *table, *cols, *t, *A, *lam, *cfg;
+  double* table;
+  const double* cols;
+  double *t, *A, *lam, *cfg;
   int32_t *na, *cfg_free;
 };
 
@@ -1201,40 +1252,22 @@ static RefineOut rows_at(const RefineOut& o, int64_t m0, const RefineShape& s, i
           rows_at(o.y, m0, (int64_t)s.V * nb)};
 }
 
-// the forward call of `rows` table rows into the three column blocks (no template: the float64 forward kernels are instantiated
-// here, ahead of the family's own)
-static int refine_forward(const RefineRun& r, int64_t rows, const double* const* params, double* const* cols,
-                          const spart_materialize& mat, const Workspace& ws, hipStream_t st) {
-  return run_impl<double, double, double>(r.ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, r.wsp + r.l.fwd, ws,
-                                          st, !r.srf);
-}
-
 // The chunk loop.  Per chunk of mc observations from m0: init(w, m0, mc) launches the kernel that writes the table and the
 // start state, then n_fwd times the forward call of the table's rows and after(w, m0, mc, it), the kernel that reads its
-// columns.  The band model decides what the forward call writes into the column block that kernel reads: k_columns' three
-// centre columns, or the ONE *_srf output of k_columns_srf the fit is about (k_columns is then not launched at all).
+// columns.
 template <typename Init, typename After>
 static int refine_loop(const RefineRun& r, int n_fwd, hipStream_t st, Init&& init, After&& after) {
   const RefineLayout& l = r.l;
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = r.o.fast_prelude;
-  mat.nlayers = r.o.nlayers;
-  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
-  if (r.srf) (r.o.column == 0 ? mat.R_TOC_srf : r.o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[r.o.column];
-  const RefineWs w = {(double*)(r.wsp + l.table), cols[r.o.column], (double*)(r.wsp + l.t), (double*)(r.wsp + l.A),
+  const Forward fwd = r.forward(l.b);
+  const RefineWs w = {fwd.table, fwd.y, (double*)(r.wsp + l.t), (double*)(r.wsp + l.A),
                       (double*)(r.wsp + l.lam), (double*)(r.wsp + l.cfg), (int32_t*)(r.wsp + l.na), (int32_t*)(r.wsp + l.cfg_free)};
   for (int64_t m0 = 0; m0 < r.M; m0 += l.mcap) {
     const int mc = (int)std::min<int64_t>(l.mcap, r.M - m0);
     const int64_t rows = (int64_t)mc * (r.s.F + 1) * r.s.V;
     init(w, m0, mc);
     HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = w.table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
     for (int it = 0; it < n_fwd; ++it) {
-      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
+      if (int rc = fwd.run(rows, st)) return rc;
       after(w, m0, mc, it);
       HIP_TRY(hipGetLastError());
     }
@@ -1395,6 +1428,29 @@ static int refine_check_band_model(const char* who, int band_model) {
   return fail(SPART_ERR_INVALID, "%s: band_model = %d (0 centre columns, 1 SRF columns)", who, band_model);
 }
 
+// What spart_sobol and spart_sample check first, and what they require of the caller's arrays with M > 0 ahead of their own
+static int fit_check_head(const char* who, const spart_ctx* ctx, int F, const int32_t* free_cols, const double* lo, const double* hi) {
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
+  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  return SPART_OK;
+}
+static int fit_check_given(const char* who, const void* opt, const void* out, const double* const* base) {
+  if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
+  if (!out) return fail(SPART_ERR_INVALID, "%s: out is null", who);
+  if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
+  if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  return SPART_OK;
+}
+// the kernel argument of either (SobolCfg, SampleCfg) from the checked fit
+template <typename Cfg> static Cfg fit_cfg(const RefineCfg& rc, const double* const* base, int F) {
+  Cfg c;
+  std::memset(&c, 0, sizeof(c));
+  for (int p = 0; p < SPART_NPARAM; ++p) c.base[p] = base[p], c.is_free[p] = rc.is_free[p];
+  for (int f = 0; f < F; ++f) c.free_col[f] = rc.free_col[f], c.lo[f] = rc.lo[f], c.hi[f] = rc.hi[f];
+  return c;
+}
+
 // the arguments the four entry points share
 struct RefineArgs {
   spart_ctx* ctx;
@@ -1408,10 +1464,26 @@ struct RefineArgs {
   void* stream;
 };
 
+// The tail of every entry of the family, Sobol' and the sampler included, once its arguments are checked: the sensor, the
+// empty call, then -- size(total) sizes the workspace and may still refuse what only a call with M > 0 needs -- the
+// workspace's own check and the guarded call of run(st).
+template <typename Size, typename Run>
+static int fit_tail(const char* who, spart_ctx* ctx, int64_t M, void* workspace, size_t workspace_bytes, void* stream, Size&& size,
+                    Run&& run) {
+  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
+  if (M == 0) return SPART_OK;
+  size_t total = 0;
+  if (int rc = size(total)) return rc;
+  if (!workspace || workspace_bytes < total)
+    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, total, workspace_bytes);
+  return guarded(ctx, who, workspace, total, stream, run);
+}
+
 // The one argument check and refusal order of the family.  `have_opt`: the entry's own option and output structs are there;
 // `have_data`: so are the obs, x and cost it requires.  before(r) reads the options into r.o, r.s and r.srf once they are
 // known to be there and may refuse; after() may refuse once the fit is checked; run(r, st) queues the checked call.
-// layout(r) sizes the workspace into r.l and may refuse what the size depends on: the last check before the workspace's own.
+// layout(r, total) lays the workspace out, gives its size and may refuse what the size depends on: the last check before the
+// workspace's own.
 template <typename Before, typename After, typename Layout, typename Run>
 static int refine_entry_sized(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after,
                               Layout&& layout, Run&& run) {
@@ -1425,23 +1497,24 @@ static int refine_entry_sized(const char* who, const RefineArgs& a, bool have_op
   if (int rc = before(r)) return rc;
   if (int rc = refine_check_fit(who, r.o, a.F, a.free_cols, a.lo, a.hi, r.cfg)) return rc;
   if (int rc = after()) return rc;
-  if (a.ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (a.M == 0) return SPART_OK;
-  if (int i = first_null(a.base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
-  if (!have_data) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
-  if (r.o.weights_per_obs && !a.weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
-  for (int p = 0; p < SPART_NPARAM; ++p) r.cfg.base[p] = a.base[p];
-  for (int f = 0; f < a.F; ++f) r.cfg.freebase[f] = a.base[r.cfg.free_col[f]];
-  if (int rc = layout(r)) return rc;
-  if (!a.workspace || a.workspace_bytes < r.l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, r.l.total, a.workspace_bytes);
-  return guarded(a.ctx, who, a.workspace, r.l.total, a.stream, [&](hipStream_t st) { return run(r, st); });
+  return fit_tail(
+      who, a.ctx, a.M, a.workspace, a.workspace_bytes, a.stream,
+      [&](size_t& total) {
+        if (int i = first_null(a.base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+        if (!have_data) return fail(SPART_ERR_INVALID, "%s: null argument (obs, x and cost are required)", who);
+        if (r.o.weights_per_obs && !a.weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
+        for (int p = 0; p < SPART_NPARAM; ++p) r.cfg.base[p] = a.base[p];
+        for (int f = 0; f < a.F; ++f) r.cfg.freebase[f] = a.base[r.cfg.free_col[f]];
+        return layout(r, total);
+      },
+      [&](hipStream_t st) { return run(r, st); });
 }
 template <typename Before, typename After, typename Run>
 static int refine_entry(const char* who, const RefineArgs& a, bool have_opt, bool have_data, Before&& before, After&& after, Run&& run) {
   return refine_entry_sized(
-      who, a, have_opt, have_data, before, after, [&](RefineRun& r) {
+      who, a, have_opt, have_data, before, after, [&](RefineRun& r, size_t& total) {
         r.l = refine_layout(a.ctx->nb, a.M, r.s.V, r.s.F, r.s.n);
+        total = r.l.total;
         return SPART_OK;
       },
       run);
@@ -1458,25 +1531,24 @@ static int refine_call(const char* who, bool srf, const RefineArgs& a, const spa
       refine_no_check, [&](const RefineRun& r, hipStream_t st) { return refine_impl(r, out, st); });
 }
 
-// ---- spart_refine_tiles (csrc/spart_refine_tiles.h).  The table, the column blocks and the forward call's scratch are the
-// family's (RefineLayout, so refine_forward serves); the state per pixel and per tile is its own.  A chunk is a run of whole
-// tiles of at most mcap = min(M, tiles_chunk(F)) pixels, so its row count depends on the partition: the forward call's scratch
-// is sized by carve_bound_f64, which holds for every row count up to the cap.
+// ---- spart_refine_tiles (csrc/spart_refine_tiles.h).  The forward block and the forward call are the family's; the state
+// per pixel and per tile is its own.  A chunk is a run of whole tiles of at most mcap = min(M, tiles_chunk(F)) pixels, so its
+// row count depends on the partition: the forward call's scratch is sized by carve_bound_f64, which holds for every row
+// count up to the cap.
 struct TilesLayout {
-  size_t lt, ct, Ap, Lp, zt, St, Lt, lam, live, na, code, flag, tstart, ptile;
+  int64_t mcap;                 // pixels per chunk
+  ForwardBlock b;
+  size_t cfg, cfg_free, lt, ct, Ap, Lp, zt, St, Lt, lam, live, na, code, flag, tstart, ptile, total;
 };
-static TilesLayout tiles_layout(int nb, int64_t M, int F, int Fs, RefineLayout& l) {
+static TilesLayout tiles_layout(int nb, int64_t M, int F, int Fs) {
   TilesLayout x;
-  l.mcap = std::min<int64_t>(M, tiles_chunk(F));
-  const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(F + 1), P = (size_t)(refine_ntri(F) + F), Ps = (size_t)(refine_ntri(Fs) + Fs);
+  x.mcap = std::min<int64_t>(M, tiles_chunk(F));
+  const size_t mc = (size_t)x.mcap, rows = mc * (size_t)(F + 1), P = (size_t)(refine_ntri(F) + F), Ps = (size_t)(refine_ntri(Fs) + Fs);
   const size_t Fl = (size_t)(F - Fs);
   Carver c;
-  l.table = c.take((size_t)NPARAM * rows * 8);
-  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
-  l.t = l.A = l.lam = l.na = 0;                                     // (the family's state blocks are not used)
-  l.cfg = c.take(REFINE_CFG_DOUBLES * 8);
-  l.cfg_free = c.take(REFINE_MAXF * 4);
-  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  x.b = forward_block(c, nb, rows, carve_bound_f64((int64_t)rows));
+  x.cfg = c.take(REFINE_CFG_DOUBLES * 8);
+  x.cfg_free = c.take(REFINE_MAXF * 4);
   x.lt = c.take(mc * Fl * 8);
   x.ct = c.take(mc * 8);
   x.Ap = c.take(mc * P * 8);
@@ -1491,88 +1563,103 @@ static TilesLayout tiles_layout(int nb, int64_t M, int F, int Fs, RefineLayout& 
   x.flag = c.take(mc * 4);
   x.tstart = c.take((mc + 1) * 4);
   x.ptile = c.take(mc * 4);
-  l.total = c.o;
+  x.total = c.o;
   return x;
 }
 
 static bool tiles_sizes_ok(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
-  return ctx && ctx->nb > 0 && M > 0 && M <= 2000000000LL && F >= 1 && F <= REFINE_MAXF && n_shared >= 0 && n_shared <= F;
+  return fit_sizes_ok(ctx, M, F) && n_shared >= 0 && n_shared <= F;
 }
 
-// The chunk loop over whole tiles: the tile map of a chunk is built here, copied, and the stream waited for before the host
-// copy goes away; then k_tiles_init and n_iter + 1 times the forward call and the seven kernels.
-static int tiles_impl(const RefineRun& r, const TilesLayout& x, int Fs, int64_t T, const int64_t* tile_start,
-                      const spart_refine_tiles_opt& to, const spart_tiles_out& out, hipStream_t st) {
-  const RefineLayout& l = r.l;
+// A chunk of tc whole groups (tiles, or series) from group t0, mc pixels from pixel m0, as the kernels of an iteration see it
+struct TilesChunk {
+  int64_t t0, m0;
+  int tc, mc;
+  unsigned per_pixel;           // blocks of 256 threads, one thread per pixel
+  TilesState s;
+  TilesOut oc;
+  const double *ycol, *obs, *wts, *pmu, *ppw, *smu, *spw;
+  int wper, pper, sper;
+  double *table, *cfg;
+  int32_t* cfg_free;
+};
+
+// The chunk loop over whole groups of the partition (T, start), for the tiles and the series: the group map of a chunk is
+// built here, copied, and the stream waited for before the host copy goes away; then k_tiles_init and n_iter + 1 times the
+// forward call and steps(chunk, it, last), the kernels of the entry.
+template <typename Steps>
+static int tiles_loop(const RefineRun& r, const TilesLayout& x, int64_t T, const int64_t* start, const spart_refine_tiles_opt& to,
+                      const spart_tiles_out& out, hipStream_t st, Steps&& steps) {
   const spart_refine_opt& o = r.o;
-  const int nb = r.ctx->nb, F = r.s.F, Fl = F - Fs, P = refine_ntri(F) + F;
-  const size_t lds = tiles_lds_bytes(F);
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
-  if (r.srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  double* table = (double*)(r.wsp + l.table);
-  double* cfg = (double*)(r.wsp + l.cfg);
-  int32_t* cfg_free = (int32_t*)(r.wsp + l.cfg_free);
-  const double* ycol = cols[o.column];
+  const int nb = r.ctx->nb, F = r.s.F, Fs = to.n_shared, Fl = F - Fs;
+  const Forward fwd = r.forward(x.b);
   auto at = [&](size_t off) { return r.wsp + off; };
-  const TilesState s = {(double*)at(x.lt),   (double*)at(x.ct),   (double*)at(x.Ap),    (double*)at(x.Lp),    (double*)at(x.zt),
-                        (double*)at(x.St),   (double*)at(x.Lt),   (double*)at(x.lam),   (int32_t*)at(x.live), (int32_t*)at(x.na),
-                        (int32_t*)at(x.code), (int32_t*)at(x.flag), (int32_t*)at(x.tstart), (int32_t*)at(x.ptile)};
+  TilesChunk c;
+  c.s = {(double*)at(x.lt),   (double*)at(x.ct),   (double*)at(x.Ap),    (double*)at(x.Lp),    (double*)at(x.zt),
+         (double*)at(x.St),   (double*)at(x.Lt),   (double*)at(x.lam),   (int32_t*)at(x.live), (int32_t*)at(x.na),
+         (int32_t*)at(x.code), (int32_t*)at(x.flag), (int32_t*)at(x.tstart), (int32_t*)at(x.ptile)};
+  c.ycol = fwd.y, c.table = fwd.table, c.cfg = (double*)at(x.cfg), c.cfg_free = (int32_t*)at(x.cfg_free);
+  c.wper = o.weights_per_obs ? 1 : 0, c.pper = o.prior_per_obs ? 1 : 0, c.sper = to.shared_prior_per_tile ? 1 : 0;
   std::vector<int32_t> tstart, ptile;
   for (int64_t t0 = 0; t0 < T;) {
-    const int64_t m0 = tile_start[t0];
-    int64_t t1 = t0 + 1;                                            // (one tile always fits: TILES_MAXG <= tiles_chunk(16))
-    while (t1 < T && tile_start[t1 + 1] - m0 <= l.mcap) ++t1;
-    const int tc = (int)(t1 - t0), mc = (int)(tile_start[t1] - m0);
+    const int64_t m0 = start[t0];
+    int64_t t1 = t0 + 1;                                            // (one group always fits: TILES_MAXG, SERIES_MAXT <= tiles_chunk(16))
+    while (t1 < T && start[t1 + 1] - m0 <= x.mcap) ++t1;
+    const int tc = (int)(t1 - t0), mc = (int)(start[t1] - m0);
     tstart.resize((size_t)tc + 1);
     ptile.resize((size_t)mc);
-    for (int t = 0; t <= tc; ++t) tstart[t] = (int32_t)(tile_start[t0 + t] - m0);
+    for (int t = 0; t <= tc; ++t) tstart[t] = (int32_t)(start[t0 + t] - m0);
     for (int t = 0; t < tc; ++t)
       for (int m = tstart[t]; m < tstart[t + 1]; ++m) ptile[m] = t;
-    HIP_TRY(hipMemcpyAsync(s.tstart, tstart.data(), ((size_t)tc + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.ptile, ptile.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c.s.tstart, tstart.data(), ((size_t)tc + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c.s.ptile, ptile.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const TilesOut oc = {rows_at(out.shared, t0, Fs),    rows_at(out.shared_std, t0, Fs), rows_at(out.local, m0, Fl),
-                         rows_at(out.local_std, m0, Fl), rows_at(out.cost, t0, 1),       rows_at(out.cost0, t0, 1),
-                         rows_at(out.n_accept, t0, 1),   rows_at(out.pixel_cost, m0, 1), rows_at(out.status, m0, 1),
-                         rows_at(out.y, m0, nb)};
-    const double* obs = r.obs + m0 * nb;
-    const double* wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
-    const double* pmu = rows_at(o.prior_mean, m0, Fl, o.prior_per_obs);
-    const double* ppw = rows_at(o.prior_weight, m0, Fl, o.prior_per_obs);
-    const double* smu = rows_at(to.shared_prior_mean, t0, Fs, to.shared_prior_per_tile);
-    const double* spw = rows_at(to.shared_prior_weight, t0, Fs, to.shared_prior_per_tile);
-    const int wper = o.weights_per_obs ? 1 : 0, pper = o.prior_per_obs ? 1 : 0, sper = to.shared_prior_per_tile ? 1 : 0;
-    const int64_t rows = (int64_t)mc * (F + 1);
-    const unsigned per_pixel = (unsigned)((mc + 255) / 256), groups = (unsigned)((mc + TILES_GROUP - 1) / TILES_GROUP);
-    hipLaunchKernelGGL(k_tiles_init, dim3(per_pixel), dim3(256), 0, st, r.cfg, m0, mc, F, Fs, o.lambda0, s, table, oc, cfg, cfg_free);
+    c.t0 = t0, c.m0 = m0, c.tc = tc, c.mc = mc, c.per_pixel = (unsigned)((mc + 255) / 256);
+    c.oc = {rows_at(out.shared, t0, Fs),    rows_at(out.shared_std, t0, Fs), rows_at(out.local, m0, Fl),
+            rows_at(out.local_std, m0, Fl), rows_at(out.cost, t0, 1),       rows_at(out.cost0, t0, 1),
+            rows_at(out.n_accept, t0, 1),   rows_at(out.pixel_cost, m0, 1), rows_at(out.status, m0, 1),
+            rows_at(out.y, m0, nb)};
+    c.obs = r.obs + m0 * nb;
+    c.wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
+    c.pmu = rows_at(o.prior_mean, m0, Fl, o.prior_per_obs);
+    c.ppw = rows_at(o.prior_weight, m0, Fl, o.prior_per_obs);
+    c.smu = rows_at(to.shared_prior_mean, t0, Fs, to.shared_prior_per_tile);
+    c.spw = rows_at(to.shared_prior_weight, t0, Fs, to.shared_prior_per_tile);
+    hipLaunchKernelGGL(k_tiles_init, dim3(c.per_pixel), dim3(256), 0, st, r.cfg, m0, mc, F, Fs, o.lambda0, c.s, c.table, c.oc, c.cfg,
+                       c.cfg_free);
     HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
+    const int64_t rows = (int64_t)mc * (F + 1);
     for (int it = 0; it <= o.n_iter; ++it) {
-      const int last = it == o.n_iter ? 1 : 0;
-      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
-      hipLaunchKernelGGL(k_tiles_cost, dim3(per_pixel), dim3(256), 0, st, ycol, obs, wts, wper, pmu, ppw, pper, mc, Fl, nb, it, s, oc);
-      hipLaunchKernelGGL(k_tiles_decide, dim3((unsigned)tc), dim3(64), 0, st, smu, spw, sper, Fs, it, last, s, oc);
-      hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, ycol, obs, wts, wper, pmu,
-                         ppw, pper, (const double*)cfg, mc, F, Fs, nb, s, oc);
-      hipLaunchKernelGGL(k_tiles_eliminate, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, s);
-      if (Fs > 0)                                                   // (without shared unknowns there is nothing to walk or to solve)
-        hipLaunchKernelGGL(k_tiles_schur, dim3((unsigned)tc), dim3(TILES_SCHUR_THREADS), 0, st, smu, spw, sper, F, Fs, last, s, oc);
-      hipLaunchKernelGGL(k_tiles_local, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, s, oc);
-      if (!last)
-        hipLaunchKernelGGL(k_tiles_apply, dim3(per_pixel), dim3(256), 0, st, (const double*)cfg, (const int32_t*)cfg_free, table, mc, F,
-                           Fs, s, oc);
+      if (int rc = fwd.run(rows, st)) return rc;
+      steps(c, it, it == o.n_iter ? 1 : 0);
       HIP_TRY(hipGetLastError());
     }
     t0 = t1;
   }
   return SPART_OK;
+}
+
+// spart_refine_tiles: per iteration the six kernels, or seven with shared unknowns
+static int tiles_impl(const RefineRun& r, const TilesLayout& x, int64_t T, const int64_t* tile_start, const spart_refine_tiles_opt& to,
+                      const spart_tiles_out& out, hipStream_t st) {
+  const int nb = r.ctx->nb, F = r.s.F, Fs = to.n_shared, Fl = F - Fs, P = refine_ntri(F) + F;
+  const size_t lds = tiles_lds_bytes(F);
+  return tiles_loop(r, x, T, tile_start, to, out, st, [&](const TilesChunk& c, int it, int last) {
+    const int mc = c.mc, tc = c.tc;
+    const unsigned groups = (unsigned)((mc + TILES_GROUP - 1) / TILES_GROUP);
+    hipLaunchKernelGGL(k_tiles_cost, dim3(c.per_pixel), dim3(256), 0, st, c.ycol, c.obs, c.wts, c.wper, c.pmu, c.ppw, c.pper, mc, Fl, nb,
+                       it, c.s, c.oc);
+    hipLaunchKernelGGL(k_tiles_decide, dim3((unsigned)tc), dim3(64), 0, st, c.smu, c.spw, c.sper, Fs, it, last, c.s, c.oc);
+    hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, c.ycol, c.obs, c.wts, c.wper,
+                       c.pmu, c.ppw, c.pper, (const double*)c.cfg, mc, F, Fs, nb, c.s, c.oc);
+    hipLaunchKernelGGL(k_tiles_eliminate, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, c.s);
+    if (Fs > 0)                                                     // (without shared unknowns there is nothing to walk or to solve)
+      hipLaunchKernelGGL(k_tiles_schur, dim3((unsigned)tc), dim3(TILES_SCHUR_THREADS), 0, st, c.smu, c.spw, c.sper, F, Fs, last, c.s, c.oc);
+    hipLaunchKernelGGL(k_tiles_local, dim3(groups), dim3(64), lds, st, mc, F, Fs, last, c.s, c.oc);
+    if (!last)
+      hipLaunchKernelGGL(k_tiles_apply, dim3(c.per_pixel), dim3(256), 0, st, (const double*)c.cfg, (const int32_t*)c.cfg_free, c.table, mc,
+                         F, Fs, c.s, c.oc);
+  });
 }
 
 // ---- SRF support (include/spart_hip.h: spart_srf_support)
@@ -1824,8 +1911,7 @@ int spart_refine_views(spart_ctx* ctx, int64_t M, const double* const base[SPART
 }
 
 size_t spart_mix_workspace_bytes(const spart_ctx* ctx, int64_t M, int V, int F, int n) {
-  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF) return 0;
-  if (V < 1 || V > MIX_MAXV || n < 1 || n > REFINE_MAXF) return 0;
+  if (!fit_sizes_ok(ctx, M, F) || V < 1 || V > MIX_MAXV || n < 1 || n > REFINE_MAXF) return 0;
   return refine_layout(ctx->nb, M, V, F, n).total;
 }
 
@@ -1874,10 +1960,7 @@ int spart_refine_mix(spart_ctx* ctx, int64_t M, const double* const base[SPART_N
 }
 
 size_t spart_tiles_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
-  if (!tiles_sizes_ok(ctx, M, F, n_shared)) return 0;
-  RefineLayout l;
-  tiles_layout(ctx->nb, M, F, n_shared, l);
-  return l.total;
+  return tiles_sizes_ok(ctx, M, F, n_shared) ? tiles_layout(ctx->nb, M, F, n_shared).total : 0;
 }
 
 // What spart_refine_tiles and spart_refine_series check about the partition and the shared prior, in one order, after the
@@ -1924,133 +2007,80 @@ int spart_refine_tiles(spart_ctx* ctx, int64_t M, const double* const base[SPART
         return SPART_OK;
       },
       refine_no_check,
-      [&](RefineRun& r) {
+      [&](RefineRun&, size_t& total) {
         if (int rc = tiles_check(who, to, M, F, T, tile_start, "T", "tile_start", "tiles", "pixels per tile", TILES_MAXG)) return rc;
-        x = tiles_layout(ctx->nb, M, F, to.n_shared, r.l);
+        x = tiles_layout(ctx->nb, M, F, to.n_shared);
+        total = x.total;
         return SPART_OK;
       },
-      [&](const RefineRun& r, hipStream_t st) { return tiles_impl(r, x, to.n_shared, T, tile_start, to, oo, st); });
+      [&](const RefineRun& r, hipStream_t st) { return tiles_impl(r, x, T, tile_start, to, oo, st); });
 }
 
 // ---- spart_refine_series (csrc/spart_refine_series.h).  The layout is tiles' with the factors of the link blocks, Xp
-// (mcap, Fl Fl), and gamma (REFINE_MAXF) behind it; the chunk loop is tiles' over whole series.
+// (mcap, Fl Fl), and gamma (REFINE_MAXF) behind it; the chunk loop is tiles_loop over whole series.
 struct SeriesLayout {
   TilesLayout x;
-  size_t Xp, gamma;
+  size_t Xp, gamma, total;
 };
-static SeriesLayout series_layout(int nb, int64_t M, int F, int Fs, RefineLayout& l) {
+static SeriesLayout series_layout(int nb, int64_t M, int F, int Fs) {
   SeriesLayout y;
-  y.x = tiles_layout(nb, M, F, Fs, l);
+  y.x = tiles_layout(nb, M, F, Fs);
   const size_t Fl = (size_t)(F - Fs);
   Carver c;
-  c.take(l.total);
-  y.Xp = c.take((size_t)l.mcap * Fl * Fl * 8);
+  c.take(y.x.total);
+  y.Xp = c.take((size_t)y.x.mcap * Fl * Fl * 8);
   y.gamma = c.take(REFINE_MAXF * 8);
-  l.total = c.o;
+  y.total = c.o;
   return y;
 }
 
-static int series_impl(const RefineRun& r, const SeriesLayout& y, int Fs, int64_t T, const int64_t* series_start,
+// gamma goes up once, ahead of the loop: so.smooth is the caller's host memory, and the first chunk's wait for the stream
+// comes before this returns.  Per iteration tiles' cost and normal kernels around the series' own.
+static int series_impl(const RefineRun& r, const SeriesLayout& y, int64_t T, const int64_t* series_start,
                        const spart_refine_series_opt& so, const spart_tiles_out& out, hipStream_t st) {
-  const RefineLayout& l = r.l;
-  const TilesLayout& x = y.x;
-  const spart_refine_opt& o = r.o;
-  const spart_refine_tiles_opt& to = so.tiles;
-  const int nb = r.ctx->nb, F = r.s.F, Fl = F - Fs, P = refine_ntri(F) + F, Ps = refine_ntri(Fs) + Fs, W = series_group(F);
+  const int nb = r.ctx->nb, F = r.s.F, Fs = so.tiles.n_shared, Fl = F - Fs, P = refine_ntri(F) + F, Ps = refine_ntri(Fs) + Fs;
+  const int W = series_group(F);
   const size_t lds_f = series_factor_lds(F, Fs, W), lds_b = series_back_lds(F, Fs, W), lds_s = series_std_lds(F, Fs);
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* cols[3] = {(double*)(r.wsp + l.cols[0]), (double*)(r.wsp + l.cols[1]), (double*)(r.wsp + l.cols[2])};
-  if (r.srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  double* table = (double*)(r.wsp + l.table);
-  double* cfg = (double*)(r.wsp + l.cfg);
-  int32_t* cfg_free = (int32_t*)(r.wsp + l.cfg_free);
-  const double* ycol = cols[o.column];
-  auto at = [&](size_t off) { return r.wsp + off; };
-  const TilesState s = {(double*)at(x.lt),   (double*)at(x.ct),   (double*)at(x.Ap),    (double*)at(x.Lp),    (double*)at(x.zt),
-                        (double*)at(x.St),   (double*)at(x.Lt),   (double*)at(x.lam),   (int32_t*)at(x.live), (int32_t*)at(x.na),
-                        (int32_t*)at(x.code), (int32_t*)at(x.flag), (int32_t*)at(x.tstart), (int32_t*)at(x.ptile)};
-  double* Xp = (double*)at(y.Xp);
-  double* gamma = (double*)at(y.gamma);
+  double* Xp = (double*)(r.wsp + y.Xp);
+  double* gamma = (double*)(r.wsp + y.gamma);
   const bool want_std = out.shared_std || out.local_std;
-  std::vector<int32_t> tstart, ptile;
-  for (int64_t t0 = 0; t0 < T;) {
-    const int64_t m0 = series_start[t0];
-    int64_t t1 = t0 + 1;                                            // (one series always fits: SERIES_MAXT <= tiles_chunk(16))
-    while (t1 < T && series_start[t1 + 1] - m0 <= l.mcap) ++t1;
-    const int tc = (int)(t1 - t0), mc = (int)(series_start[t1] - m0);
-    tstart.resize((size_t)tc + 1);
-    ptile.resize((size_t)mc);
-    for (int t = 0; t <= tc; ++t) tstart[t] = (int32_t)(series_start[t0 + t] - m0);
-    for (int t = 0; t < tc; ++t)
-      for (int m = tstart[t]; m < tstart[t + 1]; ++m) ptile[m] = t;
-    HIP_TRY(hipMemcpyAsync(s.tstart, tstart.data(), ((size_t)tc + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.ptile, ptile.data(), (size_t)mc * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(gamma, so.smooth, (size_t)Fl * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const TilesOut oc = {rows_at(out.shared, t0, Fs),    rows_at(out.shared_std, t0, Fs), rows_at(out.local, m0, Fl),
-                         rows_at(out.local_std, m0, Fl), rows_at(out.cost, t0, 1),       rows_at(out.cost0, t0, 1),
-                         rows_at(out.n_accept, t0, 1),   rows_at(out.pixel_cost, m0, 1), rows_at(out.status, m0, 1),
-                         rows_at(out.y, m0, nb)};
-    const double* obs = r.obs + m0 * nb;
-    const double* wts = rows_at(r.weights, m0, nb, o.weights_per_obs);
-    const double* pmu = rows_at(o.prior_mean, m0, Fl, o.prior_per_obs);
-    const double* ppw = rows_at(o.prior_weight, m0, Fl, o.prior_per_obs);
-    const double* smu = rows_at(to.shared_prior_mean, t0, Fs, to.shared_prior_per_tile);
-    const double* spw = rows_at(to.shared_prior_weight, t0, Fs, to.shared_prior_per_tile);
-    const double* link = rows_at(so.link, m0, 1);
-    const int wper = o.weights_per_obs ? 1 : 0, pper = o.prior_per_obs ? 1 : 0, sper = to.shared_prior_per_tile ? 1 : 0;
-    const int64_t rows = (int64_t)mc * (F + 1);
-    const unsigned per_pixel = (unsigned)((mc + 255) / 256), groups = (unsigned)((tc + W - 1) / W);
-    hipLaunchKernelGGL(k_tiles_init, dim3(per_pixel), dim3(256), 0, st, r.cfg, m0, mc, F, Fs, o.lambda0, s, table, oc, cfg, cfg_free);
-    HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
-    for (int it = 0; it <= o.n_iter; ++it) {
-      const int last = it == o.n_iter ? 1 : 0;
-      if (int rc = refine_forward(r, rows, params, cols, mat, ws, st)) return rc;
-      hipLaunchKernelGGL(k_tiles_cost, dim3(per_pixel), dim3(256), 0, st, ycol, obs, wts, wper, pmu, ppw, pper, mc, Fl, nb, it, s, oc);
-      hipLaunchKernelGGL(k_series_decide, dim3((unsigned)((tc + 255) / 256)), dim3(256), 0, st, smu, spw, sper, tc, Fs, Fl, it, last,
-                         (const double*)gamma, link, s, oc);
-      hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, ycol, obs, wts, wper, pmu,
-                         ppw, pper, (const double*)cfg, mc, F, Fs, nb, s, oc);
-      if (!last || want_std) {                                      // (the sums of the last point are only for the std)
-        hipLaunchKernelGGL(k_series_augment, dim3((unsigned)(((int64_t)mc * Fl + 255) / 256)), dim3(256), 0, st, mc, F, Fs,
-                           (const double*)gamma, link, s);
-        if (Fs > 0)
-          hipLaunchKernelGGL(k_series_sums, dim3((unsigned)(((int64_t)tc * Ps + 255) / 256)), dim3(256), 0, st, smu, spw, sper, tc, F,
-                             Fs, s, oc);
-        hipLaunchKernelGGL(W == 8 ? k_series_factor<8> : k_series_factor<4>, dim3(groups), dim3(64), lds_f, st, tc, F, Fs, last,
-                           (const double*)gamma, link, s, Xp);
-        if (Fs > 0)
-          hipLaunchKernelGGL(k_series_shared, dim3((unsigned)((tc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)),
-                             dim3(SERIES_STD_THREADS), (size_t)Fs * SERIES_STD_THREADS * 8, st, tc, Fs, last, s, oc.shared_std);
-      }
-      if (!last) {
-        hipLaunchKernelGGL(W == 8 ? k_series_back<8> : k_series_back<4>, dim3(groups), dim3(64), lds_b, st, tc, F, Fs,
-                           (const double*)gamma, link, s, (const double*)Xp);
-        hipLaunchKernelGGL(k_tiles_apply, dim3(per_pixel), dim3(256), 0, st, (const double*)cfg, (const int32_t*)cfg_free, table, mc, F,
-                           Fs, s, oc);
-      } else if (out.local_std) {
-        hipLaunchKernelGGL(k_series_std, dim3((unsigned)((mc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)),
-                           dim3(SERIES_STD_THREADS), lds_s, st, mc, F, Fs, (const double*)gamma, link, s, (const double*)Xp, oc.local_std);
-      }
-      HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(gamma, so.smooth, (size_t)Fl * 8, hipMemcpyHostToDevice, st));
+  return tiles_loop(r, y.x, T, series_start, so.tiles, out, st, [&](const TilesChunk& c, int it, int last) {
+    const int mc = c.mc, tc = c.tc;
+    const unsigned groups = (unsigned)((tc + W - 1) / W);
+    const double* link = rows_at(so.link, c.m0, 1);
+    hipLaunchKernelGGL(k_tiles_cost, dim3(c.per_pixel), dim3(256), 0, st, c.ycol, c.obs, c.wts, c.wper, c.pmu, c.ppw, c.pper, mc, Fl, nb,
+                       it, c.s, c.oc);
+    hipLaunchKernelGGL(k_series_decide, dim3((unsigned)((tc + 255) / 256)), dim3(256), 0, st, c.smu, c.spw, c.sper, tc, Fs, Fl, it, last,
+                       (const double*)gamma, link, c.s, c.oc);
+    hipLaunchKernelGGL(k_tiles_normal, dim3((unsigned)(((int64_t)mc * P + 255) / 256)), dim3(256), 0, st, c.ycol, c.obs, c.wts, c.wper,
+                       c.pmu, c.ppw, c.pper, (const double*)c.cfg, mc, F, Fs, nb, c.s, c.oc);
+    if (!last || want_std) {                                        // (the sums of the last point are only for the std)
+      hipLaunchKernelGGL(k_series_augment, dim3((unsigned)(((int64_t)mc * Fl + 255) / 256)), dim3(256), 0, st, mc, F, Fs,
+                         (const double*)gamma, link, c.s);
+      if (Fs > 0)
+        hipLaunchKernelGGL(k_series_sums, dim3((unsigned)(((int64_t)tc * Ps + 255) / 256)), dim3(256), 0, st, c.smu, c.spw, c.sper, tc,
+                           F, Fs, c.s, c.oc);
+      hipLaunchKernelGGL(W == 8 ? k_series_factor<8> : k_series_factor<4>, dim3(groups), dim3(64), lds_f, st, tc, F, Fs, last,
+                         (const double*)gamma, link, c.s, Xp);
+      if (Fs > 0)
+        hipLaunchKernelGGL(k_series_shared, dim3((unsigned)((tc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)),
+                           dim3(SERIES_STD_THREADS), (size_t)Fs * SERIES_STD_THREADS * 8, st, tc, Fs, last, c.s, c.oc.shared_std);
     }
-    t0 = t1;
-  }
-  return SPART_OK;
+    if (!last) {
+      hipLaunchKernelGGL(W == 8 ? k_series_back<8> : k_series_back<4>, dim3(groups), dim3(64), lds_b, st, tc, F, Fs,
+                         (const double*)gamma, link, c.s, (const double*)Xp);
+      hipLaunchKernelGGL(k_tiles_apply, dim3(c.per_pixel), dim3(256), 0, st, (const double*)c.cfg, (const int32_t*)c.cfg_free, c.table, mc,
+                         F, Fs, c.s, c.oc);
+    } else if (out.local_std) {
+      hipLaunchKernelGGL(k_series_std, dim3((unsigned)((mc + SERIES_STD_THREADS - 1) / SERIES_STD_THREADS)), dim3(SERIES_STD_THREADS),
+                         lds_s, st, mc, F, Fs, (const double*)gamma, link, c.s, (const double*)Xp, c.oc.local_std);
+    }
+  });
 }
 
 size_t spart_series_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int n_shared) {
-  if (!tiles_sizes_ok(ctx, M, F, n_shared) || n_shared >= F) return 0;
-  RefineLayout l;
-  series_layout(ctx->nb, M, F, n_shared, l);
-  return l.total;
+  return tiles_sizes_ok(ctx, M, F, n_shared) && n_shared < F ? series_layout(ctx->nb, M, F, n_shared).total : 0;
 }
 
 // spart_refine_tiles' refusals in its order (series_start under the 256-row rule), then Fl = 0, then smooth; the workspace last
@@ -2072,7 +2102,7 @@ int spart_refine_series(spart_ctx* ctx, int64_t M, const double* const base[SPAR
         return SPART_OK;
       },
       refine_no_check,
-      [&](RefineRun& r) {
+      [&](RefineRun&, size_t& total) {
         if (int rc = tiles_check(who, so.tiles, M, F, S, series_start, "S", "series_start", "series", "rows per series", SERIES_MAXT))
           return rc;
         const int Fl = F - so.tiles.n_shared;
@@ -2081,20 +2111,22 @@ int spart_refine_series(spart_ctx* ctx, int64_t M, const double* const base[SPAR
         for (int b = 0; b < Fl; ++b)
           if (!(so.smooth[b] >= 0.0) || std::isinf(so.smooth[b]))
             return fail(SPART_ERR_INVALID, "%s: smooth[%d] = %g, expected a finite value >= 0", who, b, so.smooth[b]);
-        y = series_layout(ctx->nb, M, F, so.tiles.n_shared, r.l);
+        y = series_layout(ctx->nb, M, F, so.tiles.n_shared);
+        total = y.total;
         return SPART_OK;
       },
-      [&](const RefineRun& r, hipStream_t st) { return series_impl(r, y, so.tiles.n_shared, S, series_start, so, oo, st); });
+      [&](const RefineRun& r, hipStream_t st) { return series_impl(r, y, S, series_start, so, oo, st); });
 }
 
-// ---- spart_sobol (csrc/spart_sobol.h).  Workspace: ONE chunk of forward rows -- the (27, R) table, the three (R, nb)
-// column blocks and the forward call's scratch, R = 64 (F + 2) bcap -- then c_j and the block sums of the nslot sites a chunk
-// can touch ((N / 64) nb Q doubles each).  bcap = min(M G, sobol_chunk_blocks(F)) blocks, G = N / 64: it depends on M only
-// while the whole call is smaller than one chunk.
+// ---- spart_sobol (csrc/spart_sobol.h).  Workspace: ONE chunk of forward rows -- the forward block of R = 64 (F + 2) bcap
+// rows -- then c_j and the block sums of the nslot sites a chunk can touch ((N / 64) nb Q doubles each).
+// bcap = min(M G, sobol_chunk_blocks(F)) blocks, G = N / 64: it depends on M only while the whole call is smaller than one
+// chunk.
 struct SobolLayout {
   int64_t bcap;                 // blocks per chunk
   int nslot;                    // sites whose block sums are kept at once
-  size_t table, cols[3], fwd, cbuf, bs, total;
+  ForwardBlock b;
+  size_t cbuf, bs, total;
 };
 static SobolLayout sobol_layout(int nb, int64_t M, int64_t N, int F) {
   SobolLayout l;
@@ -2103,9 +2135,7 @@ static SobolLayout sobol_layout(int nb, int64_t M, int64_t N, int F) {
   l.nslot = (int)std::min<int64_t>(M, l.bcap / G + 2);            // (bc consecutive blocks touch at most bc / G + 2 sites)
   const size_t rows = (size_t)l.bcap * SOBOL_BLOCK * (size_t)(F + 2);
   Carver c;
-  l.table = c.take((size_t)NPARAM * rows * 8);
-  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
-  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  l.b = forward_block(c, nb, rows, carve_bound_f64((int64_t)rows));
   l.cbuf = c.take((size_t)l.nslot * nb * 8);
   l.bs = c.take((size_t)l.nslot * (size_t)G * (size_t)sobol_nq(F) * nb * 8);
   l.total = c.o;
@@ -2115,39 +2145,25 @@ static SobolLayout sobol_layout(int nb, int64_t M, int64_t N, int F) {
 static bool sobol_n_ok(int64_t N) { return N >= SOBOL_MIN_N && N <= SOBOL_MAX_N && N % SOBOL_BLOCK == 0; }
 
 size_t spart_sobol_workspace_bytes(const spart_ctx* ctx, int64_t M, int64_t N, int F) {
-  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF || !sobol_n_ok(N)) return 0;
-  return sobol_layout(ctx->nb, M, N, F).total;
+  return fit_sizes_ok(ctx, M, F) && sobol_n_ok(N) ? sobol_layout(ctx->nb, M, N, F).total : 0;
 }
 
 // the chunk loop: the table, the forward call, the block sums, then the sites whose last block lies in the chunk
 static int sobol_impl(spart_ctx* ctx, const SobolCfg& cfg, int64_t M, int F, int64_t N, const double* uA, const double* uB,
                       const spart_sobol_opt& o, const SobolOut& out, char* wsp, const SobolLayout& l, hipStream_t st) {
   const int nb = ctx->nb, G = (int)(N / SOBOL_BLOCK), per = SOBOL_BLOCK * (F + 2);
-  const bool srf = o.band_model == 1;
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
-  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  double* table = (double*)(wsp + l.table);
+  const Forward fwd(ctx, wsp, l.b, o.column, o.band_model == 1, o.fast_prelude, o.nlayers);
   double* cbuf = (double*)(wsp + l.cbuf);
   double* bs = (double*)(wsp + l.bs);
   const int64_t B = M * G;
   for (int64_t b0 = 0; b0 < B; b0 += l.bcap) {
     const int bc = (int)std::min<int64_t>(l.bcap, B - b0);
     const int64_t rows = (int64_t)bc * per;
-    hipLaunchKernelGGL(k_sobol_rows, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, F, b0, bc, G, uA, uB, table);
+    hipLaunchKernelGGL(k_sobol_rows, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, F, b0, bc, G, uA, uB, fwd.table);
     HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
-    if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat, wsp + l.fwd,
-                                                  ws, st, !srf))
-      return rc;
-    hipLaunchKernelGGL(k_sobol_blocks, dim3((unsigned)(((int64_t)bc * nb + 3) / 4)), dim3(256), 0, st, (const double*)cols[o.column],
-                       nb, F, b0, bc, G, l.nslot, cbuf, bs);
+    if (int rc = fwd.run(rows, st)) return rc;
+    hipLaunchKernelGGL(k_sobol_blocks, dim3((unsigned)(((int64_t)bc * nb + 3) / 4)), dim3(256), 0, st, fwd.y, nb, F, b0, bc, G, l.nslot,
+                       cbuf, bs);
     const int64_t m0 = b0 / G, m1 = (b0 + bc) / G;                 // sites m0 <= m < m1 end in this chunk
     if (m1 > m0)
       hipLaunchKernelGGL(k_sobol_finish, dim3((unsigned)((nb * F + 63) / 64), (unsigned)(m1 - m0)), dim3(64), 0, st,
@@ -2157,75 +2173,63 @@ static int sobol_impl(spart_ctx* ctx, const SobolCfg& cfg, int64_t M, int F, int
   return SPART_OK;
 }
 
-// spart_refine's checks of F, the four host arrays, the options and the free columns in its order; then band_model, N, M;
-// then, with M > 0, what is NULL; the workspace last
+// spart_refine's checks of F, the four host arrays, the options and the free columns in its order (refine_check_fit on a
+// zeroed spart_refine_opt that carries column and nlayers); then band_model, N, M; then, with M > 0, what is NULL; the
+// workspace last
 int spart_sobol(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols, const double* lo,
                 const double* hi, int64_t N, const double* uA, const double* uB, const spart_sobol_opt* opt,
                 const spart_sobol_out* out, void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "spart_sobol";
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  if (int r = fit_check_head(who, ctx, F, free_cols, lo, hi)) return r;
   spart_sobol_opt o;
   std::memset(&o, 0, sizeof(o));
   if (opt) o = *opt;
-  if (o.column < 0 || o.column > 2) return fail(SPART_ERR_INVALID, "%s: column = %d (0 R_TOC, 1 R_TOA, 2 L_TOA)", who, o.column);
-  if (o.nlayers < 0 || o.nlayers > SPART_MAX_NLAYERS)
-    return fail(SPART_ERR_INVALID, "%s: nlayers = %d (0 = the default 60, else 1 ... %d)", who, o.nlayers, SPART_MAX_NLAYERS);
-  SobolCfg cfg;
-  std::memset(&cfg, 0, sizeof(cfg));
-  for (int f = 0; f < F; ++f) {
-    const int c = free_cols[f];
-    if (c < 0 || c >= SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, SPART_NPARAM - 1);
-    if (cfg.is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
-    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
-      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
-    cfg.is_free[c] = 1;
-    cfg.free_col[f] = c;
-    cfg.lo[f] = lo[f];
-    cfg.hi[f] = hi[f];
-  }
-  if (int rc = refine_check_band_model(who, o.band_model)) return rc;
+  spart_refine_opt ro;
+  std::memset(&ro, 0, sizeof(ro));
+  ro.column = o.column, ro.nlayers = o.nlayers;
+  RefineCfg rc;
+  if (int r = refine_check_fit(who, ro, F, free_cols, lo, hi, rc)) return r;
+  if (int r = refine_check_band_model(who, o.band_model)) return r;
   if (!sobol_n_ok(N))
     return fail(SPART_ERR_INVALID, "%s: N = %lld, expected a multiple of %d in %lld ... %lld", who, (long long)N, SOBOL_BLOCK,
                 (long long)SOBOL_MIN_N, (long long)SOBOL_MAX_N);
   if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
   if (M > 0) {
-    if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
-    if (!out) return fail(SPART_ERR_INVALID, "%s: out is null", who);
-    if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
-    if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+    if (int r = fit_check_given(who, opt, out, base)) return r;
     if (!uA) return fail(SPART_ERR_INVALID, "%s: uA is null", who);
     if (!uB) return fail(SPART_ERR_INVALID, "%s: uB is null", who);
     if (!out->mean && !out->var && !out->S1 && !out->ST && !out->S1_se && !out->ST_se)
       return fail(SPART_ERR_INVALID, "%s: every output is null", who);
   }
-  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (M == 0) return SPART_OK;
-  const SobolLayout l = sobol_layout(ctx->nb, M, N, F);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
-  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
-  const SobolOut so = {out->mean, out->var, out->S1, out->ST, out->S1_se, out->ST_se};
-  return guarded(ctx, who, workspace, l.total, stream,
-                 [&](hipStream_t st) { return sobol_impl(ctx, cfg, M, F, N, uA, uB, o, so, (char*)workspace, l, st); });
+  SobolLayout l;
+  return fit_tail(
+      who, ctx, M, workspace, workspace_bytes, stream,
+      [&](size_t& total) {
+        l = sobol_layout(ctx->nb, M, N, F);
+        total = l.total;
+        return SPART_OK;
+      },
+      [&](hipStream_t st) {
+        const SobolCfg cfg = fit_cfg<SobolCfg>(rc, base, F);
+        const SobolOut so = {out->mean, out->var, out->S1, out->ST, out->S1_se, out->ST_se};
+        return sobol_impl(ctx, cfg, M, F, N, uA, uB, o, so, (char*)workspace, l, st);
+      });
 }
 
-// ---- spart_sample (csrc/spart_sample.h).  Workspace: ONE chunk of Mc = min(M, sample_chunk(W)) observations -- the (27, R)
-// table, the three (R, nb) column blocks and the forward call's scratch, R = Mc W / 2 rows of a half-step -- then the chunk's
-// state and the per-row hand-over between k_sample_table and k_sample_step.
+// ---- spart_sample (csrc/spart_sample.h).  Workspace: ONE chunk of Mc = min(M, sample_chunk(W)) observations -- the forward
+// block of R = Mc W / 2 rows of a half-step -- then the chunk's state and the per-row hand-over between k_sample_table and
+// k_sample_step.
 struct SampleLayout {
   int64_t mcap;                 // observations per chunk
-  size_t table, cols[3], fwd, x, c, x0, S, Q, bx, bc, na, dead, zp, u2, inside, free_col, out, total;
+  ForwardBlock b;
+  size_t x, c, x0, S, Q, bx, bc, na, dead, zp, u2, inside, free_col, out, total;
 };
 static SampleLayout sample_layout(int nb, int64_t M, int F, int W) {
   SampleLayout l;
   l.mcap = std::min<int64_t>(M, sample_chunk(W));
   const size_t mc = (size_t)l.mcap, rows = mc * (size_t)(W / 2);
   Carver c;
-  l.table = c.take((size_t)NPARAM * rows * 8);
-  for (size_t& o : l.cols) o = c.take(rows * (size_t)nb * 8);
-  l.fwd = c.take(carve_bound_f64((int64_t)rows));
+  l.b = forward_block(c, nb, rows, carve_bound_f64((int64_t)rows));
   l.x = c.take(mc * (size_t)W * F * 8);
   l.c = c.take(mc * (size_t)W * 8);
   l.x0 = c.take(mc * F * 8);
@@ -2245,23 +2249,15 @@ static SampleLayout sample_layout(int nb, int64_t M, int F, int W) {
 }
 
 size_t spart_sample_workspace_bytes(const spart_ctx* ctx, int64_t M, int F, int W) {
-  if (!ctx || ctx->nb <= 0 || M <= 0 || M > 2000000000LL || F < 1 || F > REFINE_MAXF || !sample_walkers_ok(W, F)) return 0;
-  return sample_layout(ctx->nb, M, F, W).total;
+  return fit_sizes_ok(ctx, M, F) && sample_walkers_ok(W, F) ? sample_layout(ctx->nb, M, F, W).total : 0;
 }
 
 // the chunk loop: per chunk k_sample_init, then for the start and every step, per half: the table, the forward call, the step
 static int sample_impl(spart_ctx* ctx, const SampleCfg& cfg, int64_t M, int F, const double* obs, const double* weights,
                        const spart_sample_opt& o, const SampleOut& out, char* wsp, const SampleLayout& l, hipStream_t st) {
   const int nb = ctx->nb, W = o.W, H = W / 2;
-  const bool srf = o.band_model == 1;
-  spart_materialize mat;
-  std::memset(&mat, 0, sizeof(mat));
-  mat.prune_unused_bands = 1;
-  mat.fast_prelude = o.fast_prelude;
-  mat.nlayers = o.nlayers;
-  double* cols[3] = {(double*)(wsp + l.cols[0]), (double*)(wsp + l.cols[1]), (double*)(wsp + l.cols[2])};
-  if (srf) (o.column == 0 ? mat.R_TOC_srf : o.column == 1 ? mat.R_TOA_srf : mat.L_TOA_srf) = cols[o.column];
-  double* table = (double*)(wsp + l.table);
+  const Forward fwd(ctx, wsp, l.b, o.column, o.band_model == 1, o.fast_prelude, o.nlayers);
+  double* table = fwd.table;
   const SampleState state = {(double*)(wsp + l.x),  (double*)(wsp + l.c),      (double*)(wsp + l.x0),    (double*)(wsp + l.S),
                              (double*)(wsp + l.Q),  (double*)(wsp + l.bx),     (double*)(wsp + l.bc),    (int64_t*)(wsp + l.na),
                              (int32_t*)(wsp + l.dead), (double*)(wsp + l.zp),  (double*)(wsp + l.u2),    (int32_t*)(wsp + l.inside),
@@ -2278,11 +2274,8 @@ static int sample_impl(spart_ctx* ctx, const SampleCfg& cfg, int64_t M, int F, c
     hipLaunchKernelGGL(k_sample_init, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, W, o.seed, g0,
                        (uint64_t)o.step0, o.rel_init, o.init_radius, o.init, table, state, oc);
     HIP_TRY(hipGetLastError());
-    const double* params[SPART_NPARAM];
-    for (int p = 0; p < SPART_NPARAM; ++p) params[p] = table + (int64_t)p * rows;
-    const Workspace ws = carve(SPART_F64, rows);
     SampleStep a;
-    a.cols = cols[o.column];
+    a.cols = fwd.y;
     a.obs = obs + m0 * nb;
     a.wts = rows_at(weights, m0, nb, o.weights_per_obs);
     a.pmu = rows_at(o.prior_mean, m0, F, o.prior_per_obs);
@@ -2302,9 +2295,7 @@ static int sample_impl(spart_ctx* ctx, const SampleCfg& cfg, int64_t M, int F, c
         hipLaunchKernelGGL(k_sample_table, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, cfg, mc, F, W, h, a.start, o.seed,
                            g0, (uint64_t)(o.step0 + rel), o.a, table, state);
         HIP_TRY(hipGetLastError());
-        if (int rc = run_impl<double, double, double>(ctx, rows, params, nullptr, nullptr, cols[0], cols[1], cols[2], &mat,
-                                                      wsp + l.fwd, ws, st, !srf))
-          return rc;
+        if (int rc = fwd.run(rows, st)) return rc;
         hipLaunchKernelGGL(k_sample_step, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, a);
         HIP_TRY(hipGetLastError());
       }
@@ -2319,9 +2310,7 @@ int spart_sample(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARA
                  const double* hi, const double* obs, const double* weights, const spart_sample_opt* opt, const spart_sample_out* out,
                  void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "spart_sample";
-  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
-  if (F < 1 || F > REFINE_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, REFINE_MAXF);
-  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  if (int r = fit_check_head(who, ctx, F, free_cols, lo, hi)) return r;
   spart_sample_opt o;
   std::memset(&o, 0, sizeof(o));
   if (opt) o = *opt;
@@ -2351,30 +2340,28 @@ int spart_sample(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARA
     return fail(SPART_ERR_INVALID, "%s: step0 = %lld and obs_offset = %lld must be >= 0", who, (long long)o.step0, (long long)o.obs_offset);
   if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
   if (M > 0) {
-    if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
-    if (!out) return fail(SPART_ERR_INVALID, "%s: out is null", who);
-    if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
-    if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+    if (int r = fit_check_given(who, opt, out, base)) return r;
     if (!obs) return fail(SPART_ERR_INVALID, "%s: obs is null", who);
     if (o.weights_per_obs && !weights) return fail(SPART_ERR_INVALID, "%s: weights_per_obs without weights", who);
     if (!out->mean && !out->cov && !out->std && !out->best_x && !out->best_cost && !out->n_accept && !out->status && !out->chain &&
         !out->chain_cost && !out->last && !out->last_cost)
       return fail(SPART_ERR_INVALID, "%s: every output is null", who);
   }
-  if (ctx->nb == 0) return fail(SPART_ERR_NOSENSOR, "%s: context has no sensor", who);
-  if (M == 0) return SPART_OK;
-  const SampleLayout l = sample_layout(ctx->nb, M, F, o.W);
-  if (!workspace || workspace_bytes < l.total)
-    return fail(SPART_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, l.total, workspace_bytes);
-  SampleCfg cfg;
-  std::memset(&cfg, 0, sizeof(cfg));
-  for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p], cfg.is_free[p] = rc.is_free[p];
-  for (int f = 0; f < F; ++f)
-    cfg.free_col[f] = rc.free_col[f], cfg.freebase[f] = base[rc.free_col[f]], cfg.lo[f] = rc.lo[f], cfg.hi[f] = rc.hi[f];
-  const SampleOut so = {out->mean,   out->cov,   out->std,        out->best_x, out->best_cost, out->n_accept,
-                        out->status, out->chain, out->chain_cost, out->last,   out->last_cost};
-  return guarded(ctx, who, workspace, l.total, stream,
-                 [&](hipStream_t st) { return sample_impl(ctx, cfg, M, F, obs, weights, o, so, (char*)workspace, l, st); });
+  SampleLayout l;
+  return fit_tail(
+      who, ctx, M, workspace, workspace_bytes, stream,
+      [&](size_t& total) {
+        l = sample_layout(ctx->nb, M, F, o.W);
+        total = l.total;
+        return SPART_OK;
+      },
+      [&](hipStream_t st) {
+        SampleCfg cfg = fit_cfg<SampleCfg>(rc, base, F);
+        for (int f = 0; f < F; ++f) cfg.freebase[f] = base[rc.free_col[f]];
+        const SampleOut so = {out->mean,   out->cov,   out->std,        out->best_x, out->best_cost, out->n_accept,
+                              out->status, out->chain, out->chain_cost, out->last,   out->last_cost};
+        return sample_impl(ctx, cfg, M, F, obs, weights, o, so, (char*)workspace, l, st);
+      });
 }
 
 int spart_profile_enable(spart_ctx* ctx, int max_calls) {
