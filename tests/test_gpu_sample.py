@@ -228,6 +228,38 @@ def test_engine_and_host_forms_are_the_raw_call(torch_mod, engines, plain):
     assert rc == 0 and same(d["mean"], raw["mean"]) and same(d["last"], raw["last"])
 
 
+@pytest.mark.parametrize("lidf,nlayers", [("newton", None), ("literal", 1), ("literal", 30), ("newton", 30)])
+def test_options_reach_the_forward_model(torch_mod, engines, plain, lidf, nlayers):
+    """fast_prelude and nlayers: the raw call is the definition under the same options and not the default's, both together are
+    neither alone, and Engine.sample / spart_amd.sample hand lidf and nlayers on.  What carries the forward model in these
+    6 steps is the costs (chain_cost, last_cost, best_cost): a walker's position is a function of the random numbers and the
+    accept decisions alone, and no decision of the plain case flips under any of the four options (accepted 191, rejected 41,
+    outside 8 in each, as under the defaults), so chain has the default's bits (measured; the test prints which outputs
+    differ)."""
+    import spart_amd
+    eng = engines[S2]
+    (base, free, lo, hi, obs), kw, default = plain
+    raw = dict(fast_prelude=1 if lidf == "newton" else 0, nlayers=nlayers or 0)
+    ref, got = check_sample(torch_mod, eng, base, free, lo, hi, obs, what=f"plain, lidf {lidf} nlayers {nlayers}", **kw, **raw)
+    moved = [k for k in OUTS if not same(got[k], default[k])]
+    print(f"spart_sample plain, lidf {lidf} nlayers {nlayers}: outputs that differ from the default's: {moved}")
+    assert all(not same(got[k], default[k]) for k in ("chain_cost", "last_cost", "best_cost")), (lidf, nlayers, moved)
+    assert np.array_equal(ref["status"], default["status"]) and (ref["status"] == 0).any()
+    if lidf == "newton" and nlayers == 30:
+        for only in (dict(nlayers=30), dict(fast_prelude=1)):
+            rc, one = sample_call(torch_mod, eng, base, free, lo, hi, obs, **kw, **only)
+            assert rc == 0 and not same(got["chain_cost"], one["chain_cost"]) and not same(got["last_cost"], one["last_cost"]), only
+    names = FREE[3]
+    opts = dict(weights=kw["weights"], prior_mean=kw["prior_mean"], prior_weight=kw["prior_weight"], walkers=8, n_steps=6, burn=2, thin=2,
+                seed=5, chain=True, lidf=lidf, nlayers=nlayers)
+    want = {"mean": "mean", "std": "std", "cov": "cov", "best": "best_x", "best_cost": "best_cost", "status": "status", "last": "last",
+            "last_cost": "last_cost", "chain": "chain", "chain_cost": "chain_cost"}
+    res = eng.sample(torch_mod.as_tensor(base.T.copy(), device=eng.device), obs, names, **opts)
+    host = spart_amd.sample(base.T, obs, S2, names, **opts)
+    for r in ({k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}, host):
+        assert r["names"] == names and all(same(r[k], got[v]) for k, v in want.items()), [k for k, v in want.items() if not same(r[k], got[v])]
+
+
 def test_the_example_runs():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "sample.py"), "120"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

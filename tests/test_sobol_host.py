@@ -180,6 +180,55 @@ def test_the_functions_are_clean_under_address_and_undefined_sanitizers(tmp_path
     assert "WRONG" not in r.stdout and r.stdout.count(" ok") == 3 * 3 * 2 and "Sanitizer" not in r.stderr
 
 
+# ---- the slots of the workspace: sobol_layout's rule, by brute force
+def test_a_chunk_touches_at_most_nslot_sites_with_distinct_slots(lib):
+    """csrc/spart_capi.hip, sobol_layout: "bc consecutive blocks touch at most bc / G + 2 sites", and a site's sums wait in slot
+    m % nslot, nslot = min(M, bcap / G + 2).  Every launch of every call with F = 1 ... 16, G around the chunk's size and M up
+    to three chunks' worth: the sites a launch touches (the one that entered from the launch before among them) are within
+    the bound and have distinct slots; with one slot fewer, two of them share one in the cases listed, the shapes of
+    tests/test_gpu_sobol_edges.py among them.  No GPU and no library but for sobol_chunk_blocks, which ROWS restates."""
+    from helpers.sobol_calls import ROWS, chunk_blocks, chunks_of, layout_of
+    assert ROWS == 1 << 19 and all(lib.sbh_chunk_blocks(F) == chunk_blocks(F) for F in range(1, 17))
+
+    def shared_slot(F, N, M, nslot):
+        return any(last - first + 1 > nslot for _, _, first, last in chunks_of(F, N, M))       # (consecutive m: distinct iff few enough)
+
+    equal, checked = [], 0
+    for F in range(1, 17):
+        cb = chunk_blocks(F)
+        for G in (2, 3, 5, 64, cb - 1, cb, cb + 1, 2 * cb + 1):
+            if not sd.MIN_N <= 64 * G <= sd.MAX_N:
+                continue
+            for M in range(1, 3 * cb // G + 3):
+                _, bcap, nslot = layout_of(F, 64 * G, M)
+                launches = chunks_of(F, 64 * G, M)
+                assert sum(bc for _, bc, _, _ in launches) == M * G and all(0 < bc <= bcap for _, bc, _, _ in launches)
+                for b0, bc, first, last in launches:
+                    touched = last - first + 1
+                    assert touched <= min(M, bc // G + 2) <= nslot, (F, G, M, b0)
+                    assert len({m % nslot for m in range(first, last + 1)}) == touched, (F, G, M, b0)
+                    checked += 1
+                if nslot < M and any(last - first + 1 == nslot for _, _, first, last in launches):
+                    equal.append((F, G, M))
+                    assert shared_slot(F, 64 * G, M, nslot - 1)
+    per_F = {F: sum(1 for e in equal if e[0] == F) for F in range(1, 17)}
+    print(f"{checked} launches checked; nslot < M met with equality in {len(equal)} calls (per F: {per_F}); the smallest M per (F, G):",
+          sorted({(F, G): M for F, G, M in reversed(equal)}.items())[:12], "...")
+    # the bound is met with equality where a launch begins with a site's last block(s) and ends with another's first:
+    # G = 3 at F = 2 (2048 = 3 * 682 + 2) from M = 1366 on, so at test_gpu_sobol_edges' M = 1400; never at G = 2
+    # (2048 is a multiple of 2: bc / G + 1 sites at most)
+    assert (2, 3, 1400) in equal and (2, 3, 1366) in equal and (2, 3, 1365) not in equal and not any(e[:2] == (2, 2) for e in equal)
+    # G > bcap (a site longer than a chunk): two slots, both in use in the launch that ends one site and begins the next
+    assert layout_of(16, 29440, 3) == (460, 455, 2) and (16, 456, 3) in equal and (16, 911, 3) in equal
+    # one slot fewer than the rule's, in the GPU tests' own shapes: two sites of one launch share a slot
+    for F, N, M in ((2, 192, 1400), (16, 29440, 3)):
+        nslot = layout_of(F, N, M)[2]
+        assert nslot < M and not shared_slot(F, N, M, nslot) and shared_slot(F, N, M, nslot - 1), (F, N, M)
+    # ... and not in any call of the suite before them: its calls have nslot = M or one site
+    for F, N, M in ((2, 192, 684), (1, 1 << 18, 1), (3, 192, 3), (16, 128, 1)):
+        assert layout_of(F, N, M)[2] == M
+
+
 # ---- the consequences, on a toy forward model
 NB = 5
 
