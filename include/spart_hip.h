@@ -74,7 +74,8 @@ extern "C" {
  * spart_refine_series and spart_series_workspace_bytes with spart_refine_series_opt, which embeds spart_refine_tiles_opt
  * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise, and
  * spart_sample and spart_sample_workspace_bytes with spart_sample_opt / spart_sample_out.  spart_refine_mix and
- * spart_mix_workspace_bytes with spart_refine_mix_opt, which embeds spart_refine_opt unchanged, and spart_refine_mix_out likewise. */
+ * spart_mix_workspace_bytes with spart_refine_mix_opt, which embeds spart_refine_opt unchanged, and spart_refine_mix_out likewise.
+ * spart_vjp and spart_vjp_workspace_bytes with spart_vjp_opt likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -1085,6 +1086,57 @@ typedef struct spart_products_out {
 } spart_products_out;
 int spart_products(spart_ctx *ctx, int64_t B, const double *const params[SPART_NPARAM], const spart_products_out *out,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* The forward model made DIFFERENTIABLE: the vector-Jacobian product of the sensor columns with respect to up to 16 free
+ * parameters, by bounded central differences, without ever storing a Jacobian -- what torch.autograd needs to put the model
+ * behind a network or under torch.optim (spart_amd.SpartLayer).  base, free_cols, lo, hi are spart_refine's.  gy[c] is the
+ * gradient of the caller's loss with respect to column c (0 R_TOC, 1 R_TOA, 2 L_TOA), (M, nb) float64 on the device, or NULL
+ * for a column the loss does not read.  grad (M, F): dLoss / d free parameter.
+ * Definition (tools/vjp_defined.py is the same text in numpy), per observation m, float64, every written operation one rounded
+ * operation, no FMA contraction, IEEE division:
+ *   point     x_f = clip(base[free_f][m], lo_f, hi_f) (spart_refine's clip: a NaN stays a NaN);  h_f = rel_step * (hi_f - lo_f)
+ *   steps     a_f = x_f + h_f; if a_f > hi_f: a_f = hi_f.   b_f = x_f - h_f; if b_f < lo_f: b_f = lo_f.  The difference is
+ *             central inside the box and one-sided on a bound; rel_step <= 0.5 gives a_f - b_f >= h_f > 0 always (but for the
+ *             rounding of x_f + h_f and x_f - h_f: a step below the spacing of the doubles at x_f is the caller's to avoid)
+ *   rows      2 F rows and no centre row: p_f^+ is base_m with every free column at x and column free_f at a_f, p_f^- the same
+ *             with b_f.  Y^+_(c,f), Y^-_(c,f) (nb,) are column c of those rows, bit for bit what
+ *             spart_run_batch(SPART_F64, prune_unused_bands = 1) returns for them (thermal inputs at their defaults, no rdry_in /
+ *             lidf_in, fast_prelude and nlayers honoured); with band_model 1 the *_srf column instead
+ *   sum       s_f = 0.0; for c = 0, 1, 2 with gy[c] != NULL, in that order, for j ascending: g = gy[c][m, j]; g == 0 skips the
+ *             band (Y may be NaN there); otherwise d = Y^+_(c,f)[j] - Y^-_(c,f)[j] and s_f = s_f + g * d, one multiplication
+ *             and one addition.  grad[m, f] = s_f / (a_f - b_f)
+ *   status    there is none: a NaN parameter or a non-finite g propagates by IEEE into that row's grad and nowhere else
+ * Consequences (a row's column is a pure function of its own 27 parameters).  A row's gradient is the same bits wherever the row
+ * stands in whatever batch or chunk.  A block of zeros for a column is NULL for it, bit for bit.  The gradient is that of the
+ * CLIPPED point: a parameter outside its bounds gets the one-sided slope at the bound (straight through the clip).
+ * Observations go in chunks of 2^19 / (2 F), ONE forward call of 2 F Mc rows per chunk.  spart_vjp_workspace_bytes is 0 exactly
+ * for refused sizes (NULL or sensorless context, M outside 1 ... 2e9, F outside 1 ... 16); with Mc = min(M, 2^19 / (2 F)) and
+ * R = 2 F Mc it is (each term rounded up to 256 bytes)
+ *   8 * 27 R  +  3 * 8 R nb  +  forward scratch of R rows  +  8 Mc F:
+ * one chunk's forward block and its denominators a_f - b_f, constant in M once M >= 2^19 / (2 F).
+ * Everything is queued on `stream`; nothing synchronises.  Refused before anything is launched or written: SPART_ERR_INVALID
+ * for a NULL context; F outside 1 ... 16; NULL free_cols / lo / hi; nlayers; a free column out of range or named twice, bounds
+ * not finite lo < hi (spart_refine's checks in its order); then a NULL opt; then band_model outside 0 / 1; then rel_step
+ * negative, not finite or above 0.5; then a NULL gy, or all three entries NULL; then, with band_model 1, more than one entry
+ * (the SRF forward call writes one column); then a NULL grad; then M < 0 or M > 2e9; then, with M > 0, a NULL base or base column
+ * (the first named).  Then SPART_ERR_NOSENSOR, then (M = 0 launches nothing) SPART_ERR_WORKSPACE.
+ * How (csrc/spart_vjp.h): k_vjp_init writes the table and the denominators, the forward call is the unchanged float64 pruned
+ * path, k_vjp_reduce stages tiles of 16 bands of g (Y^+ - Y^-) through LDS and one lane per (observation, f) adds them in
+ * order into a register: no atomics.  Forward-mode products, second derivatives, gradients with respect to columns that are not
+ * free, to the thermal inputs, rdry_in or lidf_in, and F > 16 are out of scope.  Added WITHOUT a new interface number, by
+ * spart_refine_srf's rule: two symbols, one struct. */
+typedef struct spart_vjp_opt {
+  int32_t band_model;    /* 0 centre columns, 1 SRF-convolved columns */
+  int32_t fast_prelude;  /* as spart_materialize.fast_prelude */
+  int32_t nlayers;       /* as spart_materialize.nlayers, 0 = 60 */
+  double  rel_step;      /* 0 = 1e-3; otherwise finite, in (0, 0.5] */
+} spart_vjp_opt;
+size_t spart_vjp_workspace_bytes(const spart_ctx *ctx, int64_t M, int F);
+int spart_vjp(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM], int F,
+              const int32_t *free_cols /* HOST */, const double *lo, const double *hi /* HOST (F,) */,
+              const double *const gy[3] /* device, each NULL or (M, nb): dLoss/dR_TOC, dR_TOA, dL_TOA */,
+              const spart_vjp_opt *opt, double *grad /* device (M, F) */,
+              void *workspace, size_t workspace_bytes, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -26,6 +26,7 @@
 #include "spart_refine_tiles.h"
 #include "spart_refine_series.h"
 #include "spart_sobol.h"
+#include "spart_vjp.h"
 #include "spart_sample.h"
 #include "spart_products.h"
 
@@ -2213,6 +2214,99 @@ int spart_sobol(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM
         const SobolCfg cfg = fit_cfg<SobolCfg>(rc, base, F);
         const SobolOut so = {out->mean, out->var, out->S1, out->ST, out->S1_se, out->ST_se};
         return sobol_impl(ctx, cfg, M, F, N, uA, uB, o, so, (char*)workspace, l, st);
+      });
+}
+
+// ---- spart_vjp (csrc/spart_vjp.h).  Workspace: ONE chunk of Mc = min(M, vjp_chunk(F)) observations -- the forward block of
+// 2 F Mc rows -- then the chunk's denominators a_f - b_f.  The call's constants travel as k_vjp_init's argument: no kernel
+// after it reads them, so they have no device copy.
+struct VjpLayout {
+  int64_t mcap;                 // observations per chunk
+  ForwardBlock b;
+  size_t den, total;
+};
+static VjpLayout vjp_layout(int nb, int64_t M, int F) {
+  VjpLayout l;
+  l.mcap = std::min<int64_t>(M, vjp_chunk(F));
+  const size_t rows = (size_t)l.mcap * 2 * (size_t)F;
+  Carver c;
+  l.b = forward_block(c, nb, rows, carve_bound_f64((int64_t)rows));
+  l.den = c.take((size_t)l.mcap * F * 8);
+  l.total = c.o;
+  return l;
+}
+
+size_t spart_vjp_workspace_bytes(const spart_ctx* ctx, int64_t M, int F) {
+  return fit_sizes_ok(ctx, M, F) ? vjp_layout(ctx->nb, M, F).total : 0;
+}
+
+// the chunk loop: the table, ONE forward call, the sums
+static int vjp_impl(spart_ctx* ctx, const RefineCfg& cfg, int64_t M, int F, const double* const gy[3], int column,
+                    const spart_vjp_opt& o, double* grad, char* wsp, const VjpLayout& l, hipStream_t st) {
+  const int nb = ctx->nb, W = vjp_group_lds(F);
+  const Forward fwd(ctx, wsp, l.b, column, o.band_model == 1, o.fast_prelude, o.nlayers);
+  double* den = (double*)(wsp + l.den);
+  for (int64_t m0 = 0; m0 < M; m0 += l.mcap) {
+    const int mc = (int)std::min<int64_t>(l.mcap, M - m0);
+    hipLaunchKernelGGL(k_vjp_init, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, st, cfg, m0, mc, F, fwd.table, den);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fwd.run((int64_t)mc * 2 * F, st)) return rc;
+    VjpCols a;
+    for (int c = 0; c < 3; ++c) a.y[c] = fwd.cols[c], a.g[c] = rows_at(gy[c], m0, nb);
+    hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)((mc + W - 1) / W)), dim3(64), vjp_lds_bytes(F, W), st, a, (const double*)den, mc,
+                       F, nb, W, grad + m0 * F);
+    HIP_TRY(hipGetLastError());
+  }
+  return SPART_OK;
+}
+
+// spart_sobol's head (F, the host arrays, nlayers, the free columns and their bounds: refine_check_fit on a zeroed
+// spart_refine_opt that carries nlayers); then opt, band_model, rel_step, gy, grad, M; then, with M > 0, base; the sensor and
+// the workspace last
+int spart_vjp(spart_ctx* ctx, int64_t M, const double* const base[SPART_NPARAM], int F, const int32_t* free_cols, const double* lo,
+              const double* hi, const double* const gy[3], const spart_vjp_opt* opt, double* grad, void* workspace,
+              size_t workspace_bytes, void* stream) {
+  const char* who = "spart_vjp";
+  if (int r = fit_check_head(who, ctx, F, free_cols, lo, hi)) return r;
+  spart_vjp_opt o;
+  std::memset(&o, 0, sizeof(o));
+  if (opt) o = *opt;
+  spart_refine_opt ro;
+  std::memset(&ro, 0, sizeof(ro));
+  ro.nlayers = o.nlayers;
+  RefineCfg cfg;
+  if (int r = refine_check_fit(who, ro, F, free_cols, lo, hi, cfg)) return r;
+  if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
+  if (int r = refine_check_band_model(who, o.band_model)) return r;
+  if (!(o.rel_step >= 0.0) || !(o.rel_step <= VJP_MAX_REL_STEP))
+    return fail(SPART_ERR_INVALID, "%s: rel_step = %g, expected 0 (the default %g) or a finite value in (0, %g]", who, o.rel_step,
+                VJP_REL_STEP, VJP_MAX_REL_STEP);
+  if (!gy) return fail(SPART_ERR_INVALID, "%s: gy is null", who);
+  const int ngy = (gy[0] != nullptr) + (gy[1] != nullptr) + (gy[2] != nullptr);
+  if (ngy == 0) return fail(SPART_ERR_INVALID, "%s: every entry of gy is null", who);
+  if (o.band_model == 1 && ngy != 1)
+    return fail(SPART_ERR_INVALID, "%s: band_model = 1 takes exactly one entry of gy, %d given (one SRF column per forward call)", who,
+                ngy);
+  if (!grad) return fail(SPART_ERR_INVALID, "%s: grad is null", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (M > 0) {
+    if (!base) return fail(SPART_ERR_INVALID, "%s: base is null", who);
+    if (int i = first_null(base, SPART_NPARAM); i < SPART_NPARAM) return fail(SPART_ERR_INVALID, "%s: base[%d] is null", who, i);
+  }
+  const double rel = o.rel_step == 0.0 ? VJP_REL_STEP : o.rel_step;
+  VjpLayout l;
+  return fit_tail(
+      who, ctx, M, workspace, workspace_bytes, stream,
+      [&](size_t& total) {
+        l = vjp_layout(ctx->nb, M, F);
+        total = l.total;
+        return SPART_OK;
+      },
+      [&](hipStream_t st) {
+        for (int p = 0; p < SPART_NPARAM; ++p) cfg.base[p] = base[p];
+        for (int f = 0; f < F; ++f) cfg.freebase[f] = base[cfg.free_col[f]], cfg.h[f] = rel * (cfg.hi[f] - cfg.lo[f]);
+        const int column = gy[0] ? 0 : gy[1] ? 1 : 2;         // (what the SRF band model evaluates: its one entry)
+        return vjp_impl(ctx, cfg, M, F, gy, column, o, grad, (char*)workspace, l, st);
       });
 }
 

@@ -15,6 +15,14 @@ from . import workloads  # noqa: F401
 from .lut import (date_links, generate_lut, invert_lut, jacobian, load_lut, lut_products, lut_to_parquet, noise_weights, posterior,  # noqa: F401
                   products, refine, refine_mix, refine_series, refine_views, refine_tiles, retrieve, retrieve_stream, chain_summary, sample, sobol,
                   sobol_design,
-                  tiles_from_labels, window_tiles)
+                  tiles_from_labels, vjp, window_tiles)
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # spart_amd.SpartLayer is a torch.nn.Module: torch is imported when it is first asked for, not with the package
+    if name == "SpartLayer":
+        from .autograd import SpartLayer
+        return SpartLayer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

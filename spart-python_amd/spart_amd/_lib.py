@@ -98,6 +98,10 @@ class SpartSobolOut(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("mean", "var", "S1", "ST", "S1_se", "ST_se")]
 
 
+class SpartVjpOpt(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("band_model", "fast_prelude", "nlayers")] + [("rel_step", ctypes.c_double)]
+
+
 class SpartSampleOpt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("column", "band_model", "fast_prelude", "nlayers", "weights_per_obs", "prior_per_obs")] + [
         ("prior_mean", vp), ("prior_weight", vp), ("W", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_steps", ctypes.c_int64),
@@ -127,6 +131,7 @@ TILES_MAXG = 4096                                   # pixels per tile of spart_r
 SERIES_MAXT = 256                                   # rows per series of spart_refine_series
 SOBOL_OUTS = tuple(n for n, _ in SpartSobolOut._fields_)             # spart_sobol_out, in its order
 SOBOL_BLOCK, SOBOL_MIN_N, SOBOL_MAX_N = 64, 128, 1 << 20             # spart_sobol: N a multiple of 64 in 128 ... 2^20
+VJP_MAX_REL_STEP = 0.5                              # spart_vjp_opt.rel_step
 SAMPLE_OUTS = tuple(n for n, _ in SpartSampleOut._fields_)           # spart_sample_out, in its order
 SAMPLE_WALKERS, SAMPLE_MAX_STEPS = (8, 16, 32, 64), 1 << 20          # spart_sample_opt.W (and W >= 2 F), n_steps
 
@@ -204,6 +209,8 @@ SIGNATURES = {
                                                      ctypes.POINTER(SpartSobolOut)] + _REFINE_CALL[16:]),
     "spart_sample_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "spart_sample": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartSampleOpt), ctypes.POINTER(SpartSampleOut)] + _REFINE_CALL[16:]),
+    "spart_vjp_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
+    "spart_vjp": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.POINTER(vp), ctypes.POINTER(SpartVjpOpt), vp] + _REFINE_CALL[16:]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

@@ -693,6 +693,59 @@ def sobol_args(params, free, N, bounds, design, seed, column, band_model, lidf):
     return plan, params, M, N, uA, uB
 
 
+def vjp_columns(columns, band_model):
+    """The sensor columns a vjp() call or a SpartLayer is about: names from R_TOC / R_TOA / L_TOA, at least one, each once, and
+    exactly one with band_model "srf" (the SRF forward call writes one column) -> tuple of names, in the caller's order"""
+    if isinstance(columns, str):
+        columns = (columns,)
+    cols = tuple(str(c) for c in columns)
+    unknown = [c for c in cols if c not in _lib.REFINE_COLUMNS]
+    if unknown:
+        raise ValueError(f"columns: unknown column name(s) {unknown}; expected names from {list(_lib.REFINE_COLUMNS)}")
+    if not cols:
+        raise ValueError("columns: 0 names, expected 1 ... 3")
+    twice = sorted({c for c in cols if cols.count(c) > 1})
+    if twice:
+        raise ValueError(f"columns: {twice} named twice")
+    if _band_model(band_model) and len(cols) != 1:
+        raise ValueError(f"band_model='srf' takes one column per call, {len(cols)} given: {list(cols)}")
+    return cols
+
+
+def vjp_rel_step(rel_step):
+    """rel_step of vjp() / SpartLayer: finite, in (0, 0.5] -> float"""
+    if isinstance(rel_step, bool) or not (np.ndim(rel_step) == 0 and np.isfinite(rel_step) and 0 < rel_step <= _lib.VJP_MAX_REL_STEP):
+        raise ValueError(f"rel_step = {rel_step!r}, expected a finite value in (0, {_lib.VJP_MAX_REL_STEP}]")
+    return float(rel_step)
+
+
+def vjp_args(params, grad_outputs, free, bounds, rel_step, lidf, band_model, nb=None):
+    """Every argument check of spart_amd.vjp and Engine.vjp that needs no device: refine_plan on ``free`` / ``bounds``,
+    rel_step in (0, 0.5], the band model's name, lidf, ``grad_outputs`` -- a dict {column name: (M, nb) array or tensor, or
+    None for a column that takes no part}, at least one given, all of one shape (``nb`` given: that nb), one only with
+    band_model "srf" -- and params (a (27, M) block or 27 entries of 1 or M values).
+    -> (plan, params, M, [gy of R_TOC, R_TOA, L_TOA; None where not given]); params as refine_args returns it"""
+    plan = refine_plan(free, bounds, 0, "R_TOC", 1e-3, 1e-2)
+    rel_step = vjp_rel_step(rel_step)
+    if not isinstance(grad_outputs, dict):
+        raise ValueError("grad_outputs: expected a dict {column name: (M, nb) tensor}")
+    given = {k: v for k, v in grad_outputs.items() if v is not None}
+    vjp_columns(tuple(grad_outputs), "centre")
+    if not given:
+        raise ValueError("grad_outputs: every entry is None")
+    vjp_columns(tuple(given), band_model)
+    shapes = {k: tuple(int(n) for n in v.shape) if hasattr(v, "shape") else np.shape(v) for k, v in given.items()}
+    first = next(iter(shapes.values()))
+    for k, s in shapes.items():
+        if len(s) != 2 or s != first or (nb is not None and s[1] != nb):
+            raise ValueError(f"grad_outputs[{k!r}] has shape {s}, expected (M, nb)" + ("" if nb is None else f" = (M, {nb})") +
+                             ("" if s == first else f" like the others, {first}"))
+    M = first[0]
+    params = refine_args(params, np.broadcast_to(np.float64(0.0), first), free, bounds, None, "R_TOC", 0, 1e-3, 1e-2, lidf, None,
+                         None, None, band_model, _plan=plan)[1]
+    return dict(plan, rel_step=rel_step), params, M, [given.get(c) for c in _lib.REFINE_COLUMNS]
+
+
 def sample_args(params, obs, free, bounds, weights, prior, prior_mean, prior_weight, walkers, n_steps, burn, thin, a, temperature,
                 rel_init, init, init_radius, step0, obs_offset, seed, column, band_model, lidf, nb=None):
     """Every argument check of spart_amd.sample and Engine.sample that needs no device: refine_args (refine_plan on ``free`` /
@@ -1972,6 +2025,37 @@ class Engine:
         _lib.check(self.lib, self.ctx, rc)
         res["names"] = list(plan["names"])
         return res
+
+    def vjp(self, params, grad_outputs, free, bounds=None, rel_step=1e-3, lidf="literal", nlayers=None, band_model="centre"):
+        """The vector-Jacobian product of the sensor columns with respect to the ``free`` parameters, on the device in one call
+        (include/spart_hip.h: spart_vjp, which defines every sum; tools/vjp_defined.py is the numpy form): what a backward pass
+        needs, by bounded central differences, with no Jacobian stored.
+        params, free, bounds, lidf, nlayers, band_model : as for refine(); the point is ``params`` with its free columns clipped
+                 to the bounds
+        grad_outputs : {column name: (M, nb) tensor or array}, dLoss / d column for R_TOC / R_TOA / L_TOA; a column that is
+                 missing or None takes no part; band_model "srf" takes one column
+        rel_step : the step is rel_step (hi - lo) to either side, cut at the bounds; in (0, 0.5]
+        -> {"grad": (M, F) float64 device tensor, dLoss / d free parameter, "names": [...]}.  A NaN parameter or gradient makes
+        that row's grad NaN and no other."""
+        plan, params, M, gys = vjp_args(params, grad_outputs, free, bounds, rel_step, lidf, band_model, nb=self.nb or None)
+        srf = _band_model(band_model, self)
+        nl = self._nlayers(nlayers)
+        F = len(plan["names"])
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        cols = self._refine_columns(params, M)
+        gys = [None if g is None else torch.as_tensor(g).to(**f64).contiguous() for g in gys]
+        grad = torch.empty((M, F), **f64)
+        opt = _lib.SpartVjpOpt(band_model=int(srf), fast_prelude=1 if lidf == "newton" else 0, nlayers=nl, rel_step=plan["rel_step"])
+        nbytes = max(int(self.lib.spart_vjp_workspace_bytes(self.ctx, M, F)), 256)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.calls["spart_vjp"] += 1
+        rc = self.lib.spart_vjp(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                _dp(plan["lo"]), _dp(plan["hi"]), self._ptrs(gys), ctypes.byref(opt), grad.data_ptr(), ws.data_ptr(),
+                                nbytes, self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        return {"grad": grad, "names": list(plan["names"])}
 
     def sample(self, params, obs, free, bounds=None, weights=None, prior=None, walkers=None, n_steps=1000, burn=None, thin=1, seed=0,
                init=None, init_radius=None, step0=0, obs_offset=0, column="R_TOC", band_model="centre", chain=False, a=2.0,

@@ -21,7 +21,7 @@ from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, chain_summary, get_engine, knn_prior,  # noqa: F401
                      lut_weights_kind, sample_args,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
-                     refine_mix_args, refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design)
+                     refine_mix_args, refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design, vjp_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -627,6 +627,17 @@ def jacobian(params, sensor, free, bounds=None, column="R_TOC", rel_step=1e-3, l
     eng = get_engine(sensor, device, sensor_info=sensor_info)
     res = eng.posterior(params, None, free, lidf=lidf, nlayers=nlayers, band_model=band_model, _plan=plan, _outputs=("y", "jac"))
     return {"y": res["y"].cpu().numpy(), "jac": res["jac"].cpu().numpy(), "names": res["names"]}
+
+
+def vjp(params, grad_outputs, sensor, free, bounds=None, rel_step=1e-3, lidf="literal", nlayers=None, sensor_info=None, device=None,
+        band_model="centre"):
+    """The host form of Engine.vjp: ``grad_outputs`` {column name: (M, nb) array} -> {"grad": (M, F) numpy array, "names"}.
+    Every argument check that needs no device runs before one is asked for."""
+    params = vjp_args(params, grad_outputs, free, bounds, rel_step, lidf, band_model)[1]
+    Engine._nlayers(nlayers)
+    eng = get_engine(sensor, device, sensor_info=sensor_info)
+    res = eng.vjp(params, grad_outputs, free, bounds=bounds, rel_step=rel_step, lidf=lidf, nlayers=nlayers, band_model=band_model)
+    return {"grad": res["grad"].cpu().numpy(), "names": res["names"]}
 
 
 def refine_views(params, obs, sensor, shared, local=(), bounds=None, weights=None, column="R_TOC", n_iter=10, rel_step=1e-3,

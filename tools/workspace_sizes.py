@@ -1,4 +1,4 @@
-"""The workspace sizes of the refinement family, the tiles, the series, Sobol' and the sampler over a fixed grid of shapes:
+"""The workspace sizes of the refinement family, the tiles, the series, Sobol', the sampler and spart_vjp over a fixed grid of shapes:
 one line per case, `entry  arguments  bytes`.  Two libraries lay their workspaces out alike in total when their outputs are
 equal line for line.
 
@@ -39,6 +39,9 @@ def cases():
         yield "spart_sobol_workspace_bytes", ("M", "N", "F"), (M, N, F)
     for M, F, W in ((1, 1, 8), (16384, 4, 16), (70000, 16, 64)):
         yield "spart_sample_workspace_bytes", ("M", "F", "W"), (M, F, W)
+    for M in MS:
+        for F in FS:
+            yield "spart_vjp_workspace_bytes", ("M", "F"), (M, F)
 
 
 def main():
