@@ -75,7 +75,7 @@ extern "C" {
  * unchanged, likewise.  spart_sobol and spart_sobol_workspace_bytes with spart_sobol_opt / spart_sobol_out likewise, and
  * spart_sample and spart_sample_workspace_bytes with spart_sample_opt / spart_sample_out.  spart_refine_mix and
  * spart_mix_workspace_bytes with spart_refine_mix_opt, which embeds spart_refine_opt unchanged, and spart_refine_mix_out likewise.
- * spart_vjp and spart_vjp_workspace_bytes with spart_vjp_opt likewise. */
+ * spart_vjp and spart_vjp_workspace_bytes with spart_vjp_opt likewise.  spart_refine_leaf with spart_leaf_fit_opt / _out likewise. */
 #define SPART_ABI_VERSION 14
 
 #define SPART_F32 0
@@ -1137,6 +1137,63 @@ int spart_vjp(spart_ctx *ctx, int64_t M, const double *const base[SPART_NPARAM],
               const double *const gy[3] /* device, each NULL or (M, nb): dLoss/dR_TOC, dR_TOA, dL_TOA */,
               const spart_vjp_opt *opt, double *grad /* device (M, F) */,
               void *workspace, size_t workspace_bytes, void *stream);
+
+/* PROSPECT INVERSION: bounded Levenberg-Marquardt fits of up to nine leaf parameters against measured leaf reflectance and / or
+ * transmittance on the 2001-band grid (integrating-sphere spectra of LOPEX / ANGERS-type collections), one fit per leaf.  No
+ * sensor is involved (a context without one serves; there is no SPART_ERR_NOSENSOR case) and no workspace.
+ * leaf[9] is spart_prospect_batch's order (Cab, Cdm, Cw, Cs, Cca, Cant, N, PROT, CBC), each (M,) float64 on the device: the start
+ * rows.  free_cols: F distinct entries of 0 ... 8, 1 <= F <= 9, with bounds lo / hi (host).  obs_refl, obs_tran: dense (M, 2001)
+ * float64 on the device; either may be NULL, not both.  w_refl / w_tran: NULL (weight 1 on every band of that array), or (2001,)
+ * with weights_per_obs 0, or (M, 2001) with 1; only for an observation array that is given.  A weight of exactly 0 skips the
+ * band, and the observation may be NaN there.
+ * Definition (tools/refine_leaf_defined.py is the same text in numpy): spart_refine's text word for word, per leaf m, float64,
+ * every written operation one rounded operation, no FMA contraction, IEEE division and square root, with these substitutions.
+ *   rows, Y   p_0 is the leaf's nine parameters with the free ones at the trial t; p_f is p_0 with free[f-1] moved by s_f h_f
+ *             (h_f = rel_step (hi_f - lo_f); s_f = +1 if t_f + h_f <= hi_f else -1).  Y_0 ... Y_F are the (refl, tran) spectra
+ *             of those rows: leaf_band<double> (csrc/spart_math.h) of the row's leaf constants, which are formed exactly as
+ *             the prelude's PRE_LEAF part forms them (the PROSPECT-PRO rule, 1 / N, c / N, N - 1)
+ *   band sums every sum over bands -- the trial cost, each A_ab, each g_a, the sums inside std's A -- is 64 lane partials plus
+ *             a fixed join.  Partial p_l starts at 0.0 and takes the bands i = l, l + 64, ... < 2001 in ascending order; at
+ *             each band the reflectance term first, then the transmittance term; a term is skipped if its array is absent or
+ *             its weight is 0.  The terms: c = c + (w d) d with d = Y_0 - obs;  A_ab = A_ab + (w J_a) J_b (a >= b);
+ *             g_a = g_a + (w J_a) r with r = Y_0 - obs and J_f = (Y_f - Y_0) / (s_f h_f).
+ *             Join: for d = 32, 16, 8, 4, 2, 1: p_l = p_l + p_(l+d) for l < d; the sum is p_0.
+ *             The prior's terms (c + (p e) e; A_aa + p_a; g_a + p_a e_a; e = t - mu, a weight of 0 skipped) are added after
+ *             the join, in ascending order
+ *   the rest  is spart_refine's: x = t = clip(start); n_iter + 1 evaluations, no early exit; the trial is accepted when
+ *             c_t < c; lambda / 10 on an accept and * 10 on a reject within [1e-12, 1e12]; D_a = A_aa if A_aa > 0 else 1;
+ *             (A + lambda diag D) delta = -g by Cholesky, a failed factorisation or a non-finite delta gives delta = 0;
+ *             t = clip(x + delta); cost <= cost0; std from the undamped A of the last accepted point (NaN when its
+ *             factorisation fails).  A dead leaf -- a negative, NaN or infinite weight on any band of a given weights array or in
+ *             its prior, or a start cost not < +inf -- has n_accept = -1, std NaN, x the clipped start and cost = cost0
+ *   y         y_refl, y_tran are the spectra at the returned x from one closing pass; no claim is made that they equal the
+ *             in-loop Y_0 bit for bit
+ * A leaf's outputs depend on nothing but its own inputs: the same bits at any position of any batch.
+ * Everything is queued on `stream`; nothing synchronises; M = 0 launches nothing.  Refused before anything is launched or
+ * written, each SPART_ERR_INVALID, in this order: a NULL ctx; F outside 1 ... 9; NULL free_cols, lo or hi; a free column outside
+ * 0 ... 8 or named twice; bounds not finite with lo < hi; a NULL opt; n_iter outside 0 ... 100; rel_step or lambda0 negative or
+ * not finite; weights_per_obs outside 0 / 1; exactly one of prior_mean / prior_weight NULL; prior_per_obs outside 0 / 1; both
+ * observation arrays NULL; a weights array for a NULL observation array; a NULL out, out->x or out->cost; M < 0 or M > 2e9;
+ * with M > 0 a NULL leaf or leaf column (the first is named).
+ * How (csrc/spart_refine_leaf.h): k_refine_leaf<F>, one wave per leaf with its lanes along the bands, the leaf model and the
+ * Levenberg-Marquardt step fused, all n_iter + 1 evaluations in one launch, no spectra in memory.  Fitting BSM or SAILH stage
+ * spectra, float32, the thermal inputs, kChlrel as an observation and band-correlated noise are out of scope.  Added WITHOUT a
+ * new interface number, by spart_refine_srf's rule: one symbol, two structs. */
+typedef struct spart_leaf_fit_opt {
+  int32_t n_iter;            /* 0 ... 100 */
+  int32_t weights_per_obs;   /* 0: each weights array NULL or (2001,); 1: (M, 2001) */
+  double  rel_step;          /* 0 = 1e-3 */
+  double  lambda0;           /* 0 = 1e-2 */
+  int32_t prior_per_obs;     /* 0: (F,), 1: (M, F) */
+  const double *prior_mean, *prior_weight;   /* device; both NULL = no prior */
+} spart_leaf_fit_opt;
+typedef struct spart_leaf_fit_out {          /* device; x and cost required, the rest optional */
+  double *x, *cost, *cost0, *std; int32_t *n_accept; double *y_refl, *y_tran;   /* (M,F) (M,) (M,) (M,F) (M,) (M,2001) (M,2001) */
+} spart_leaf_fit_out;
+int spart_refine_leaf(spart_ctx *ctx, int64_t M, const double *const leaf[9], int F, const int32_t *free_cols /* HOST */,
+                      const double *lo, const double *hi /* HOST (F,) */, const double *obs_refl, const double *obs_tran,
+                      const double *w_refl, const double *w_tran, const spart_leaf_fit_opt *opt,
+                      const spart_leaf_fit_out *out, void *stream);
 
 /* Measurement aid (bench.py): when enabled, spart_run_batch brackets each of its kernels with HIP events recorded on
  * the stream the kernel runs on, for up to max_calls calls (max_calls = 0 disables).  spart_profile_read_stages waits for

@@ -20,7 +20,7 @@ SRC = os.path.join(CSRC, "spart_capi.hip")
 SOURCES = [SRC, os.path.join(CSRC, "spart_bands_f32.hip")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("spart_kernels.h", "spart_math.h", "spart_e3_coeffs.h", "spart_f64_tables.h",
                                                   "spart_bands_f32.h", "spart_lut.h", "spart_refine.h", "spart_refine_views.h", "spart_refine_mix.h",
-                                                  "spart_refine_posterior.h", "spart_refine_tiles.h", "spart_refine_series.h", "spart_products.h", "spart_sobol.h", "spart_sample.h", "spart_vjp.h")] + [os.path.join(HERE, "..", "include", "spart_hip.h")]
+                                                  "spart_refine_posterior.h", "spart_refine_tiles.h", "spart_refine_series.h", "spart_products.h", "spart_sobol.h", "spart_sample.h", "spart_vjp.h", "spart_refine_leaf.h")] + [os.path.join(HERE, "..", "include", "spart_hip.h")]
 OUT = os.path.join(HERE, "libspart_hip.so")
 # -fno-slp-vectorize: hipcc's SLP pass packs independent fp32 ops into v_pk_mul/v_pk_fma, which issue at
 # half rate on gfx950 and block FMA contraction; the VALU-bound band kernel is 12 % faster without it

@@ -29,6 +29,7 @@
 #include "spart_vjp.h"
 #include "spart_sample.h"
 #include "spart_products.h"
+#include "spart_refine_leaf.h"
 
 using namespace spart;
 
@@ -1698,6 +1699,14 @@ static std::vector<int> srf_deal(const std::vector<int>& start, int nb) {
 // tag + id: build.py finds the id in the file's bytes (binary_id), spart_build_id() returns the part after the tag
 static const char k_build_id[] = "SPART_BUILD_ID:" SPART_BUILD_ID;
 
+// ---- spart_refine_leaf (csrc/spart_refine_leaf.h): one launch, no workspace
+template <int F> static void launch_refine_leaf(int F_, unsigned blocks, hipStream_t st, const double* tab, const LeafFitArgs& a, int64_t M) {
+  if constexpr (F <= LEAF_MAXF) {
+    if (F_ == F) hipLaunchKernelGGL((k_refine_leaf<F>), dim3(blocks), dim3(LEAF_LANES), 0, st, tab, a, M);
+    else launch_refine_leaf<F + 1>(F_, blocks, st, tab, a, M);
+  }
+}
+
 extern "C" {
 
 const char* spart_build_id(void) { return k_build_id + 15; }
@@ -2923,6 +2932,65 @@ int spart_lut_summarise(spart_ctx* ctx, int64_t B, int P, const double* params, 
   if (!params || !idx || (!mean && !median && !std && !count)) return fail(SPART_ERR_INVALID, "%s: null argument", who);
   return guarded(ctx, who, nullptr, 0, stream,
                  [&](hipStream_t st) { return launch_lut_summarise(B, P, params, M, k, idx, mean, median, std, count, st); });
+}
+
+int spart_refine_leaf(spart_ctx* ctx, int64_t M, const double* const leaf[9], int F, const int32_t* free_cols, const double* lo,
+                      const double* hi, const double* obs_refl, const double* obs_tran, const double* w_refl, const double* w_tran,
+                      const spart_leaf_fit_opt* opt, const spart_leaf_fit_out* out, void* stream) {
+  const char* who = "spart_refine_leaf";
+  if (!ctx) return fail(SPART_ERR_INVALID, "%s: null context", who);
+  if (F < 1 || F > LEAF_MAXF) return fail(SPART_ERR_INVALID, "%s: F = %d, expected 1 <= F <= %d", who, F, LEAF_MAXF);
+  if (!free_cols || !lo || !hi) return fail(SPART_ERR_INVALID, "%s: null argument (free_cols, lo and hi are required)", who);
+  LeafFitArgs a;
+  std::memset(&a, 0, sizeof(a));
+  bool is_free[LEAF_NPAR] = {false};
+  for (int f = 0; f < F; ++f) {
+    const int c = free_cols[f];
+    if (c < 0 || c >= LEAF_NPAR) return fail(SPART_ERR_INVALID, "%s: free_cols[%d] = %d, expected 0 ... %d", who, f, c, LEAF_NPAR - 1);
+    if (is_free[c]) return fail(SPART_ERR_INVALID, "%s: column %d is free twice", who, c);
+    is_free[c] = true;
+    a.free_col[f] = c;
+  }
+  for (int f = 0; f < F; ++f) {
+    if (!std::isfinite(lo[f]) || !std::isfinite(hi[f]) || !(lo[f] < hi[f]))
+      return fail(SPART_ERR_INVALID, "%s: bounds of free_cols[%d]: finite lo < hi expected", who, f);
+    a.lo[f] = lo[f];
+    a.hi[f] = hi[f];
+  }
+  if (!opt) return fail(SPART_ERR_INVALID, "%s: opt is null", who);
+  if (opt->n_iter < 0 || opt->n_iter > REFINE_MAX_ITER)
+    return fail(SPART_ERR_INVALID, "%s: n_iter = %d, expected 0 ... %d", who, opt->n_iter, REFINE_MAX_ITER);
+  if (!(opt->rel_step >= 0.0) || !(opt->lambda0 >= 0.0) || std::isinf(opt->rel_step) || std::isinf(opt->lambda0))
+    return fail(SPART_ERR_INVALID, "%s: rel_step and lambda0 must be finite and >= 0 (0 = the default)", who);
+  if (opt->weights_per_obs != 0 && opt->weights_per_obs != 1)
+    return fail(SPART_ERR_INVALID, "%s: weights_per_obs = %d (0: one row for all, 1: one row per leaf)", who, opt->weights_per_obs);
+  if (!opt->prior_mean != !opt->prior_weight)
+    return fail(SPART_ERR_INVALID, "%s: prior_mean and prior_weight come together (both NULL = no prior)", who);
+  if (opt->prior_per_obs != 0 && opt->prior_per_obs != 1)
+    return fail(SPART_ERR_INVALID, "%s: prior_per_obs = %d (0: one row for all, 1: one row per leaf)", who, opt->prior_per_obs);
+  if (!obs_refl && !obs_tran) return fail(SPART_ERR_INVALID, "%s: obs_refl and obs_tran are both null", who);
+  if ((w_refl && !obs_refl) || (w_tran && !obs_tran))
+    return fail(SPART_ERR_INVALID, "%s: weights given for an observation array that is null", who);
+  if (!out || !out->x || !out->cost) return fail(SPART_ERR_INVALID, "%s: out, out->x and out->cost are required", who);
+  if (M < 0 || M > 2000000000LL) return fail(SPART_ERR_INVALID, "%s: M = %lld, expected 0 <= M <= 2e9", who, (long long)M);
+  if (M == 0) return SPART_OK;
+  if (!leaf) return fail(SPART_ERR_INVALID, "%s: null leaf", who);
+  if (int i = first_null(leaf, LEAF_NPAR); i < LEAF_NPAR) return fail(SPART_ERR_INVALID, "%s: leaf[%d] is null", who, i);
+  const double rel = opt->rel_step == 0.0 ? 1e-3 : opt->rel_step;
+  for (int k = 0; k < LEAF_NPAR; ++k) a.leaf[k] = leaf[k];
+  for (int f = 0; f < F; ++f) a.h[f] = rel * (a.hi[f] - a.lo[f]);
+  a.n_iter = opt->n_iter, a.wper = opt->weights_per_obs, a.pper = opt->prior_per_obs;
+  a.lambda0 = opt->lambda0 == 0.0 ? 1e-2 : opt->lambda0;
+  a.obs_r = obs_refl, a.obs_t = obs_tran, a.w_r = w_refl, a.w_t = w_tran;
+  a.pmu = opt->prior_mean, a.ppw = opt->prior_weight;
+  a.x = out->x, a.cost = out->cost, a.cost0 = out->cost0, a.sdev = out->std, a.n_accept = out->n_accept;
+  a.y_r = out->y_refl, a.y_t = out->y_tran;
+  return guarded(ctx, who, nullptr, 0, stream, [&](hipStream_t st) {
+    const unsigned blocks = (unsigned)std::min<int64_t>(M, LEAF_MAX_BLOCKS);
+    launch_refine_leaf<1>(F, blocks, st, (const double*)ctx->tabD, a, M);
+    HIP_TRY(hipGetLastError());
+    return SPART_OK;
+  });
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ from .srf import align_srf, check_srf  # noqa: F401
 from .tables import SENSORS  # noqa: F401
 from . import workloads  # noqa: F401
 from .lut import (date_links, generate_lut, invert_lut, jacobian, load_lut, lut_products, lut_to_parquet, noise_weights, posterior,  # noqa: F401
-                  products, refine, refine_mix, refine_series, refine_views, refine_tiles, retrieve, retrieve_stream, chain_summary, sample, sobol,
+                  products, refine, refine_leaf, refine_mix, refine_series, refine_views, refine_tiles, retrieve, retrieve_stream, chain_summary, sample, sobol,
                   sobol_design,
                   tiles_from_labels, vjp, window_tiles)
 

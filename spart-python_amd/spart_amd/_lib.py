@@ -102,6 +102,15 @@ class SpartVjpOpt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("band_model", "fast_prelude", "nlayers")] + [("rel_step", ctypes.c_double)]
 
 
+class SpartLeafFitOpt(ctypes.Structure):
+    _fields_ = [("n_iter", ctypes.c_int32), ("weights_per_obs", ctypes.c_int32), ("rel_step", ctypes.c_double),
+                ("lambda0", ctypes.c_double), ("prior_per_obs", ctypes.c_int32), ("prior_mean", vp), ("prior_weight", vp)]
+
+
+class SpartLeafFitOut(ctypes.Structure):
+    _fields_ = [(n, vp) for n in ("x", "cost", "cost0", "std", "n_accept", "y_refl", "y_tran")]
+
+
 class SpartSampleOpt(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("column", "band_model", "fast_prelude", "nlayers", "weights_per_obs", "prior_per_obs")] + [
         ("prior_mean", vp), ("prior_weight", vp), ("W", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_steps", ctypes.c_int64),
@@ -132,6 +141,8 @@ SERIES_MAXT = 256                                   # rows per series of spart_r
 SOBOL_OUTS = tuple(n for n, _ in SpartSobolOut._fields_)             # spart_sobol_out, in its order
 SOBOL_BLOCK, SOBOL_MIN_N, SOBOL_MAX_N = 64, 128, 1 << 20             # spart_sobol: N a multiple of 64 in 128 ... 2^20
 VJP_MAX_REL_STEP = 0.5                              # spart_vjp_opt.rel_step
+LEAF_NPAR, LEAF_MAXF = 9, 9                          # spart_refine_leaf: leaf[9], 1 <= F <= 9
+LEAF_FIT_OUTS = tuple(n for n, _ in SpartLeafFitOut._fields_)        # spart_leaf_fit_out, in its order
 SAMPLE_OUTS = tuple(n for n, _ in SpartSampleOut._fields_)           # spart_sample_out, in its order
 SAMPLE_WALKERS, SAMPLE_MAX_STEPS = (8, 16, 32, 64), 1 << 20          # spart_sample_opt.W (and W >= 2 F), n_steps
 
@@ -211,6 +222,8 @@ SIGNATURES = {
     "spart_sample": (ctypes.c_int, _REFINE_CALL[:9] + [ctypes.POINTER(SpartSampleOpt), ctypes.POINTER(SpartSampleOut)] + _REFINE_CALL[16:]),
     "spart_vjp_workspace_bytes": (ctypes.c_size_t, [vp, ctypes.c_int64, ctypes.c_int]),
     "spart_vjp": (ctypes.c_int, _REFINE_CALL[:7] + [ctypes.POINTER(vp), ctypes.POINTER(SpartVjpOpt), vp] + _REFINE_CALL[16:]),
+    "spart_refine_leaf": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), c_dp, c_dp,
+                                         vp, vp, vp, vp, ctypes.POINTER(SpartLeafFitOpt), ctypes.POINTER(SpartLeafFitOut), vp]),
     "spart_profile_enable": (ctypes.c_int, [vp, ctypes.c_int]),
     "spart_profile_read": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),
     "spart_profile_read_stages": (ctypes.c_int, [vp, c_dp, ctypes.POINTER(ctypes.c_int)]),

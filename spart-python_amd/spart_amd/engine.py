@@ -286,6 +286,67 @@ def refine_args(params, obs, free, bounds, weights, column, n_iter, rel_step, la
                                                    None if plan.get("prior") is None else prior_arrays(plan["prior"], M))
 
 
+LEAF_NAMES = tuple(workloads.PARAM_NAMES[:_lib.LEAF_NPAR])      # spart_refine_leaf's leaf[9], spart_prospect_batch's order
+
+
+def refine_leaf_args(leaf, refl, tran, free, bounds, weights_refl, weights_tran, n_iter, rel_step, lambda0, prior, prior_mean,
+                     prior_weight):
+    """Every argument check of spart_amd.refine_leaf and Engine.refine_leaf that needs no device: prior exclusivity; ``free``
+    1 ... 9 distinct names of LEAF_NAMES with refine_plan's checks of bounds, n_iter, rel_step, lambda0 and the prior; refl and
+    tran (M, 2001), at least one of them; weights only for a given array, (2001,) or (M, 2001); leaf a (9, M) block or nine
+    columns of 1 or M values; the prior's shapes.
+    -> (plan, leaf, M, weights per observation 0 / 1, prior_mean, prior_weight, prior per observation 0 / 1); ``leaf`` comes
+    back as the 2-D tensor it was, else as a list of nine columns; a plan's prior comes back as its prior_arrays."""
+    import torch
+    ready = prior_mean is not None or prior_weight is not None
+    if prior is not None and ready:
+        raise ValueError("prior and prior_mean / prior_weight exclude each other")
+    names = [str(n) for n in free]
+    stray = [n for n in names if n not in LEAF_NAMES]
+    if stray:
+        raise ValueError(f"free: {stray} are no leaf parameters; expected names from {list(LEAF_NAMES)}")
+    if not 1 <= len(names) <= _lib.LEAF_MAXF:
+        raise ValueError(f"free: {len(names)} names, expected 1 ... {_lib.LEAF_MAXF}")
+    plan = refine_plan(names, bounds, n_iter, _lib.REFINE_COLUMNS[0], rel_step, lambda0, prior=prior)
+    if refl is None and tran is None:
+        raise ValueError("refl and tran are both None: at least one spectrum per leaf is needed")
+    shapes = {k: tuple(int(n) for n in np.shape(v)) for k, v in (("refl", refl), ("tran", tran)) if v is not None}
+    for k, sh in shapes.items():
+        if len(sh) != 2 or sh[1] != _lib.NWL:
+            raise ValueError(f"{k} has shape {sh}, expected (M, {_lib.NWL})")
+    if len({sh[0] for sh in shapes.values()}) != 1:
+        raise ValueError(f"refl {shapes['refl']} and tran {shapes['tran']} differ in their number of leaves")
+    M = next(iter(shapes.values()))[0]
+    wper = 0
+    for k, w, obs in (("weights_refl", weights_refl, refl), ("weights_tran", weights_tran, tran)):
+        if w is None:
+            continue
+        if obs is None:
+            raise ValueError(f"{k} given without its spectra")
+        if lut_weights_kind(np.shape(w), M, _lib.NWL) == "per_observation":
+            wper = 1
+    if not isinstance(leaf, (list, tuple)):
+        if not torch.is_tensor(leaf):
+            leaf = np.asarray(leaf, dtype=np.float64)
+        if len(leaf.shape) != 2 or leaf.shape[0] != _lib.LEAF_NPAR:
+            raise ValueError(f"leaf must be ({_lib.LEAF_NPAR}, M) or a list of {_lib.LEAF_NPAR} columns, got shape {tuple(leaf.shape)}")
+        counts = [int(leaf.shape[1])]
+        if not torch.is_tensor(leaf):
+            leaf = list(leaf)
+    else:
+        if len(leaf) != _lib.LEAF_NPAR:
+            raise ValueError(f"leaf must have {_lib.LEAF_NPAR} entries, got {len(leaf)}")
+        if any(c is None for c in leaf):
+            raise ValueError("leaf: no entry may be None")
+        leaf = list(leaf)
+        counts = [math.prod(np.shape(c)) for c in leaf]
+    for n in counts:
+        if n not in (1, M):
+            raise ValueError(f"a leaf column of {n} values does not broadcast to the {M} rows of the spectra")
+    return (plan, leaf, M, wper) + _refine_prior(prior_mean, prior_weight, M, len(names),
+                                                 None if plan.get("prior") is None else prior_arrays(plan["prior"], M))
+
+
 def _views_prior(names, Fs, V, prior):
     """refine_views' prior: {name: (mean, sigma)} -> (mean, weight) per UNKNOWN, (n,) or -- when any value has a pixel axis --
     (M, n), with M read from the values.  A shared name takes a scalar or (M,); a local name a scalar, (V,) or (M, V)."""
@@ -1760,6 +1821,60 @@ class Engine:
             post = self.posterior(fitted, o, free, weights=w, lidf=lidf, nlayers=nlayers, prior_mean=prior_mean,
                                   prior_weight=prior_weight, band_model=band_model, _plan=dict(plan, prior=None))
             res.update({k: post[k] for k in ("cov", "corr", "ak", "dfs")})
+        return res
+
+    def refine_leaf(self, leaf, refl=None, tran=None, free=("Cab", "Cw", "Cdm", "N"), bounds=None, weights_refl=None,
+                    weights_tran=None, n_iter=20, rel_step=1e-3, lambda0=1e-2, prior=None, prior_mean=None, prior_weight=None,
+                    spectra=False):
+        """PROSPECT inversion: bounded Levenberg-Marquardt fits of the ``free`` leaf parameters of every start row against
+        its measured leaf reflectance and / or transmittance on the 400 ... 2400 nm grid, on the device in ONE launch
+        (include/spart_hip.h: spart_refine_leaf, which defines every sum and solve; tools/refine_leaf_defined.py is the numpy
+        form).  No sensor is involved: any engine serves.
+        leaf : the start rows, a (9, M) float64 tensor or a list of nine scalars / arrays (each 1 or M values), in LEAF_NAMES
+               order (Cab, Cdm, Cw, Cs, Cca, Cant, N, PROT, CBC); the parameters not in ``free`` stay at these values
+        refl, tran : (M, 2001) measured spectra; either may be None (reflectance-only fits are common), not both
+        free : names from LEAF_NAMES (1 ... 9); bounds : {name: (lo, hi)}, the default is workloads.RANGES[name]
+        weights_refl, weights_tran : None (weight 1), (2001,) or (M, 2001), only for spectra that are given; a weight of exactly
+               0 skips the band (the measurement may be NaN there); 1 / sigma^2 makes ``std`` the linearised 1-sigma
+        n_iter : proposals (0 ... 100), n_iter + 1 evaluations of F + 1 leaves each; there is no early exit
+        prior, prior_mean, prior_weight : as for refine()
+        -> dict of device tensors x (M, F), std (M, F), cost, cost0 (M,), n_accept (M,) int32 (-1: the start could not be
+        evaluated, x is then the clipped start) and ``names``; with ``spectra`` also y_refl, y_tran (M, 2001), the model at x."""
+        plan, leaf, M, wper, prior_mean, prior_weight, per_obs = refine_leaf_args(
+            leaf, refl, tran, free, bounds, weights_refl, weights_tran, n_iter, rel_step, lambda0, prior, prior_mean, prior_weight)
+        # ---- the device from here on
+        torch = self.torch
+        f64 = dict(dtype=torch.float64, device=self.device)
+        F = len(plan["names"])
+        if torch.is_tensor(leaf):
+            L = leaf.to(**f64)
+            cols = list(L.expand(_lib.LEAF_NPAR, M).contiguous()) if M else list(L)
+        else:
+            cols = self.columns(leaf, M)[0]
+
+        def dense(v, rows):
+            if v is None:
+                return None
+            v = torch.as_tensor(v).to(**f64)
+            return (v.expand(M, _lib.NWL) if rows and v.dim() == 1 else v).contiguous()
+        obs = [dense(refl, False), dense(tran, False)]
+        wts = [dense(weights_refl, bool(wper)), dense(weights_tran, bool(wper))]
+        opt = _lib.SpartLeafFitOpt(n_iter=plan["n_iter"], weights_per_obs=wper, rel_step=plan["rel_step"], lambda0=plan["lambda0"])
+        if prior_mean is not None:
+            pm, pw = (torch.as_tensor(v).to(**f64).contiguous() for v in (prior_mean, prior_weight))
+            opt.prior_per_obs, opt.prior_mean, opt.prior_weight = per_obs, pm.data_ptr(), pw.data_ptr()
+        shapes = {"x": (M, F), "cost": (M,), "cost0": (M,), "std": (M, F), "n_accept": (M,)}
+        if spectra:
+            shapes.update(y_refl=(M, _lib.NWL), y_tran=(M, _lib.NWL))
+        res = {k: torch.empty(sh, dtype=torch.int32 if k == "n_accept" else torch.float64, device=self.device)
+               for k, sh in shapes.items()}
+        out = _lib.SpartLeafFitOut(**{k: res[k].data_ptr() if k in res else None for k in _lib.LEAF_FIT_OUTS})
+        self.calls["spart_refine_leaf"] += 1
+        ptr = [None if t is None else t.data_ptr() for t in obs + wts]
+        rc = self.lib.spart_refine_leaf(self.ctx, M, self._ptrs(cols), F, plan["cols"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        _dp(plan["lo"]), _dp(plan["hi"]), *ptr, ctypes.byref(opt), ctypes.byref(out), self._stream())
+        _lib.check(self.lib, self.ctx, rc)
+        res["names"] = list(plan["names"])
         return res
 
     def posterior(self, params, obs, free, bounds=None, weights=None, column="R_TOC", rel_step=1e-3, lidf="literal", nlayers=None,

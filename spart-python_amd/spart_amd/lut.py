@@ -21,7 +21,7 @@ from . import _lib, workloads
 from .engine import (BAND_MODELS, DTYPES, PRODUCT_NAMES, _SRF_COLUMNS, Engine, _band_model, chain_summary, get_engine, knn_prior,  # noqa: F401
                      lut_weights_kind, sample_args,
                      params_rows, prior_arrays, product_names, products_columns, quantile_levels, refine_args, refine_plan,
-                     refine_mix_args, refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design, vjp_args)
+                     refine_leaf_args, refine_mix_args, refine_series_args, refine_tiles_args, refine_views_args, sobol_args, sobol_design, vjp_args)
 
 COLUMNS = ("R_TOC", "R_TOA", "L_TOA")
 LUT_MAX_K = 256                    # the k of spart_lut_topk / spart_lut_summarise: 1 ... 256
@@ -566,6 +566,25 @@ def refine(params, obs, sensor, free, bounds=None, weights=None, column="R_TOC",
     eng = get_engine(sensor, device, sensor_info=sensor_info)
     res = eng.refine(params, np.asarray(obs, dtype=np.float64), free, weights=weights, lidf=lidf, nlayers=nlayers,
                      prior_mean=prior_mean, prior_weight=prior_weight, band_model=band_model, _plan=plan)
+    return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
+
+
+def refine_leaf(leaf, refl=None, tran=None, free=("Cab", "Cw", "Cdm", "N"), bounds=None, weights_refl=None, weights_tran=None,
+                n_iter=20, rel_step=1e-3, lambda0=1e-2, prior=None, prior_mean=None, prior_weight=None, spectra=False, device=None):
+    """The host form of Engine.refine_leaf (PROSPECT inversion of measured leaf spectra): numpy in and out.  ``leaf``: the
+    start rows, a (9, M) array, a list of nine scalars / arrays, or a LeafBiology whose fields are scalars or arrays; ``refl``,
+    ``tran`` (M, 2001), either may be None; everything else as for Engine.refine_leaf.  No sensor is involved.
+    -> dict of numpy arrays x, std, cost, cost0, n_accept (and y_refl, y_tran with ``spectra``) and the list ``names``.  Every
+    argument check that needs no device runs before one is asked for."""
+    if hasattr(leaf, "columns") and callable(leaf.columns):
+        leaf = [np.asarray(c, dtype=np.float64) for c in leaf.columns()]
+    plan, leaf = refine_leaf_args(leaf, refl, tran, free, bounds, weights_refl, weights_tran, n_iter, rel_step, lambda0, prior,
+                                  prior_mean, prior_weight)[:2]
+    eng = get_engine(None, device)
+    host = lambda v: None if v is None else np.asarray(v, dtype=np.float64)      # noqa: E731
+    res = eng.refine_leaf(leaf, host(refl), host(tran), free, bounds=bounds, weights_refl=weights_refl, weights_tran=weights_tran,
+                          n_iter=n_iter, rel_step=rel_step, lambda0=lambda0, prior=prior, prior_mean=prior_mean,
+                          prior_weight=prior_weight, spectra=spectra)
     return {k: (v if k == "names" else v.cpu().numpy()) for k, v in res.items()}
 
 
